@@ -2,6 +2,8 @@
 """bench.py -- header_range_256 hot path on MI355X (contract: see the task brief / DESIGN.md section 7).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR               (also write what the last timed step returned, DIR/*.npy)
+  python bench.py ... --full                           (also everything beyond the headline, see below)
 
 One "step" = one pass of the implemented hot path over one synthetic header_range_256 input
 resident in HBM (a 256-header P15k chain + its STARK trace): see `config.stages` in the JSON
@@ -12,9 +14,12 @@ fixed-size result blobs, outside the per-step work but inside the timed region. 
 proofs are in flight per GPU (`--inflight`): K steps are K complete proofs, handed to four worker
 contexts from one queue, so one proof's small-kernel tail overlaps another's bulk kernels.
 
-The JSON line carries `roofline` (NTT kernel: algorithmic bytes 16*n*c per transform over
-its HIP-event time on the ctx stream) and `cpu_baseline` (the C oracle, kind "port", timed on
-a bounded sample on this host).  The oracle is used ONLY for that baseline leg.
+A plain run sets up, warms up, times the K steps and prints the line.  With `--full` it then
+also checks the result (the product's verifier on the blob; every gathered blob at N > 1) and
+adds `latency_ms`, `gathered_blobs`, `roofline` (NTT kernel: algorithmic bytes 16*n*c per
+transform over its HIP-event time on the ctx stream), `roofline_poseidon`, `pmax` and
+`cpu_baseline` (the C oracle, kind "port", timed on a bounded sample on this host).  The oracle
+is used ONLY for that baseline leg.
 """
 import argparse
 import json
@@ -266,6 +271,27 @@ def cpu_baseline(vx, ctx):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out_bytes, words):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as float64 .npy files that hold it exactly:
+    public_outputs.npy = the output bytes, proof_words.npy = the proof's 64-bit words as (low 32 bits, high 32 bits) rows.  A proof
+    over the size limit is written as a fixed sample of its words (seed 0), their positions in proof_word_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "public_outputs.npy"), np.frombuffer(out_bytes, dtype=np.uint8).astype(np.float64))
+    w = np.ascontiguousarray(words).view(np.uint64).reshape(-1)
+    max_words = (DUMP_LIMIT_BYTES - 8 * len(out_bytes)) // 24  # 16 B per word, 8 B per index if sampled
+    ipath = os.path.join(path, "proof_word_index.npy")
+    if w.size > max_words:
+        idx = np.sort(np.random.default_rng(0).choice(w.size, max_words, replace=False))
+        np.save(ipath, idx.astype(np.float64))
+        w = w[idx]
+    elif os.path.exists(ipath):  # left by an earlier run into the same DIR
+        os.remove(ipath)
+    np.save(os.path.join(path, "proof_words.npy"), np.stack([w & np.uint64(0xFFFFFFFF), w >> np.uint64(32)], axis=1).astype(np.float64))
+
+
 def sharded_proof_bench(args, vx, ctx, wl, dist, rank, world, local_rank, barrier):
     """--shard-proof S: K steps = K proofs, each proven by ALL ranks together (table t of the proof on rank t mod world); strong scaling."""
     S = args.shard_proof
@@ -293,10 +319,13 @@ def sharded_proof_bench(args, vx, ctx, wl, dist, rank, world, local_rank, barrie
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
-        assert out96 == ch.expected_outputs(N_HEADERS)
-        vx.lib.header_range_verify(blob, N_HEADERS, ch.trusted_block, ch.trusted_hash, ch.target_block, out96, wl.cfg,
-                                   authority_set_hash=wl.just.sh.tobytes() if wl.just is not None else None,
-                                   authority_set_id=wl.just.struct.authority_set_id if wl.just is not None else 0)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out96, blob)
+        if args.full:
+            assert out96 == ch.expected_outputs(N_HEADERS)
+            vx.lib.header_range_verify(blob, N_HEADERS, ch.trusted_block, ch.trusted_hash, ch.target_block, out96, wl.cfg,
+                                       authority_set_hash=wl.just.sh.tobytes() if wl.just is not None else None,
+                                       authority_set_id=wl.just.struct.authority_set_id if wl.just is not None else 0)
         emit({
             "metric": f"header_range_{N_HEADERS} proofs/sec, ONE proof sharded over the GPUs", "value": round(args.steps / elapsed, 4), "unit": "proofs/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "strong",
@@ -305,7 +334,7 @@ def sharded_proof_bench(args, vx, ctx, wl, dist, rank, world, local_rank, barrie
                                    f"{S + 4} (segments, Merkle, commitment, Ed25519, SHA-512) proven by rank t mod {world}; one all-reduce of the trace caps per proof, "
                                    "partial blobs gathered and merged on rank 0", "map_segments": S, "blob_bytes": int(blob.size * 8),
                        "exchange": f"torch.distributed all_reduce ({dist.get_backend()})" if dist else "none (1 rank)"},
-            "verified": True})
+            "verified": bool(args.full)})
     ctx.close()
     if dist:
         dist.destroy_process_group()
@@ -395,6 +424,11 @@ def main():
                          "spread over the ranks (SURVEY 8 f2); the ranks exchange their trace caps once per proof and rank 0 merges the partial blobs. "
                          "Not the headline metric (that is one proof per rank, weak scaling)")
     ap.add_argument("--dry-launch", action="store_true", help="rehearse the multi-rank launch on CPU (gloo), no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also verify the result and measure latency, the NTT and Poseidon rooflines, the Pmax rate and the CPU "
+                         "baseline (off by default: a plain run prints the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one returned (rank 0): DIR/public_outputs.npy, DIR/proof_words.npy (float64, exact)")
     args = ap.parse_args()
     global N_HEADERS, PROFILE
     N_HEADERS, PROFILE = args.headers, args.profile
@@ -520,79 +554,81 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     if rank == 0:
-        gathered_ok = None
-        if gathered is not None:
-            assert len(gathered) == world and all(g.size == blob.size for g in gathered)
-            if args.circuit == "header_range":
-                # (outside the timed region) every rank's blob is a proof of THAT rank's input: rank r proved the chain of seed + r
-                import hashlib
-
-                digests = set()
-                for r, g in enumerate(gathered):
-                    ch_r = wl.chain if r == rank else vx.synth.Chain(N_HEADERS, profile=PROFILE, seed=vx.synth.CHAIN_SEED + r)
-                    words = np.ascontiguousarray(g).view(np.uint64)
-                    out_r = words[4:16].tobytes()
-                    assert out_r == ch_r.expected_outputs(N_HEADERS), f"rank {r}: public outputs differ from the native mirror"
-                    vx.lib.header_range_verify(words, N_HEADERS, ch_r.trusted_block, ch_r.trusted_hash, ch_r.target_block, out_r, wl.cfg,
-                                               authority_set_hash=wl.just.sh.tobytes() if wl.just is not None else None,
-                                               authority_set_id=wl.just.struct.authority_set_id if wl.just is not None else 0)
-                    digests.add(hashlib.sha256(words.tobytes()).hexdigest())
-                assert len(digests) == world, "ranks proved the same input"
-                gathered_ok = {"verified": world, "distinct": len(digests)}
-        wl.check(res)
-        roof = ntt_roofline(ctx)
-        # single-proof latency: a few steps with ONE proof in flight (value above is throughput with `inflight` in flight)
-        t1 = time.perf_counter()
-        for _ in range(2):
-            wl.step()
-        ctx.sync()
-        latency_ms = 1e3 * (time.perf_counter() - t1) / 2
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res[0], res[1])
         LOG_ROWS = None
         if args.circuit == "header_range":
             comps = sum((int(z) + 127) // 128 for z in wl.chain.sizes)
             LOG_ROWS = max(16, (16 * comps - 1).bit_length())  # 16 rows per compression, padded to a power of two
-        pose = poseidon_roofline(ctx, vx, LOG_ROWS + 1) if args.circuit == "header_range" else None
-        pmax = None
-        if args.circuit == "header_range" and PROFILE == "P15k" and N_HEADERS == 256 and not args.no_pmax and world == 1:
-            # the reference circuit's fixed capacity: every header padded to MAX_HEADER_SIZE (circuits/consts.rs:9-16, 71,680 compressions):
-            # the same step on a Pmax chain, two proofs in flight, after (outside) the timed region.  A Pmax proof holds 4x the
-            # memory of a P15k one: the P15k inputs and the pools of the other contexts are given back first
-            k = min(2, inflight)
-            for w in wls:
-                w.free()
-            for c in ctxs[k:]:
-                c.close()
-            pw = [Workload(vx, ctxs[i], seed_offset=rank, profile="Pmax") for i in range(k)]
-            for w in pw:  # warm-up: pool blocks of the larger shapes
-                w.step()
+        gathered_ok = roof = latency_ms = pose = pmax = None
+        if args.full:  # everything below the headline: checks, latency, rooflines, Pmax (the CPU baseline follows the line)
+            if gathered is not None:
+                assert len(gathered) == world and all(g.size == blob.size for g in gathered)
+                if args.circuit == "header_range":
+                    # (outside the timed region) every rank's blob is a proof of THAT rank's input: rank r proved the chain of seed + r
+                    import hashlib
 
-            def two(w):
-                w.step()
-                w.step()
+                    digests = set()
+                    for r, g in enumerate(gathered):
+                        ch_r = wl.chain if r == rank else vx.synth.Chain(N_HEADERS, profile=PROFILE, seed=vx.synth.CHAIN_SEED + r)
+                        words = np.ascontiguousarray(g).view(np.uint64)
+                        out_r = words[4:16].tobytes()
+                        assert out_r == ch_r.expected_outputs(N_HEADERS), f"rank {r}: public outputs differ from the native mirror"
+                        vx.lib.header_range_verify(words, N_HEADERS, ch_r.trusted_block, ch_r.trusted_hash, ch_r.target_block, out_r, wl.cfg,
+                                                   authority_set_hash=wl.just.sh.tobytes() if wl.just is not None else None,
+                                                   authority_set_id=wl.just.struct.authority_set_id if wl.just is not None else 0)
+                        digests.add(hashlib.sha256(words.tobytes()).hexdigest())
+                    assert len(digests) == world, "ranks proved the same input"
+                    gathered_ok = {"verified": world, "distinct": len(digests)}
+            wl.check(res)
+            roof = ntt_roofline(ctx)
+            # single-proof latency: a few steps with ONE proof in flight (value above is throughput with `inflight` in flight)
+            t1 = time.perf_counter()
+            for _ in range(2):
+                wl.step()
+            ctx.sync()
+            latency_ms = 1e3 * (time.perf_counter() - t1) / 2
+            pose = poseidon_roofline(ctx, vx, LOG_ROWS + 1) if args.circuit == "header_range" else None
+            if args.circuit == "header_range" and PROFILE == "P15k" and N_HEADERS == 256 and not args.no_pmax and world == 1:
+                # the reference circuit's fixed capacity: every header padded to MAX_HEADER_SIZE (circuits/consts.rs:9-16, 71,680 compressions):
+                # the same step on a Pmax chain, two proofs in flight, after (outside) the timed region.  A Pmax proof holds 4x the
+                # memory of a P15k one: the P15k inputs and the pools of the other contexts are given back first
+                k = min(2, inflight)
+                for w in wls:
+                    w.free()
+                for c in ctxs[k:]:
+                    c.close()
+                pw = [Workload(vx, ctxs[i], seed_offset=rank, profile="Pmax") for i in range(k)]
+                for w in pw:  # warm-up: pool blocks of the larger shapes
+                    w.step()
 
-            for c in ctxs[:k]:
-                c.sync()
-            t2 = time.perf_counter()
-            ths = [threading.Thread(target=two, args=(w,)) for w in pw]
-            for t_ in ths:
-                t_.start()
-            for t_ in ths:
-                t_.join()
-            for c in ctxs[:k]:
-                c.sync()
-            dt = time.perf_counter() - t2
-            res_p = pw[0].step()
-            assert res_p[0] == pw[0].chain.expected_outputs(N_HEADERS), "Pmax public outputs differ from the native mirror"
-            pmax = {"value": round(2 * k / dt, 4), "unit": "proofs/s", "ms_per_step": round(1e3 * dt / (2 * k), 2), "inflight": k, "steps": 2 * k,
-                    "workload": f"header_range_{N_HEADERS} with every header MAX_HEADER_SIZE = 35,840 B (Pmax): 71,680 Blake2b compressions, hash-chain table 2^21 rows -- "
-                                "what the reference circuit always pays for (circuits/consts.rs:9-16); the P15k headline is NOT the circuit's worst case"}
-            for w in pw:
-                w.free()
+                def two(w):
+                    w.step()
+                    w.step()
+
+                for c in ctxs[:k]:
+                    c.sync()
+                t2 = time.perf_counter()
+                ths = [threading.Thread(target=two, args=(w,)) for w in pw]
+                for t_ in ths:
+                    t_.start()
+                for t_ in ths:
+                    t_.join()
+                for c in ctxs[:k]:
+                    c.sync()
+                dt = time.perf_counter() - t2
+                res_p = pw[0].step()
+                assert res_p[0] == pw[0].chain.expected_outputs(N_HEADERS), "Pmax public outputs differ from the native mirror"
+                pmax = {"value": round(2 * k / dt, 4), "unit": "proofs/s", "ms_per_step": round(1e3 * dt / (2 * k), 2), "inflight": k, "steps": 2 * k,
+                        "workload": f"header_range_{N_HEADERS} with every header MAX_HEADER_SIZE = 35,840 B (Pmax): 71,680 Blake2b compressions, hash-chain table 2^21 rows -- "
+                                    "what the reference circuit always pays for (circuits/consts.rs:9-16); the P15k headline is NOT the circuit's worst case"}
+                for w in pw:
+                    w.free()
         line = {
             "metric": f"header_range_{N_HEADERS} proofs/sec", "value": round(world * args.steps / elapsed, 4), "unit": "proofs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64 (Goldilocks) / u8 (hashes)",
-            "data": "synthetic", "inflight_per_gpu": inflight, "latency_ms": round(latency_ms, 2), "gather": gather_kind, "gathered_blobs": gathered_ok,
+            "data": "synthetic", "inflight_per_gpu": inflight, "gather": gather_kind,
             "proof_scope": "every statement of HeaderRangeCircuit is inside a STARK: all 96 public output bytes (Blake2b header-chain table + SHA-256 Merkle table "
                            "of the state / data roots), the authority-set commitment, and the justification -- floor(2n/3)+1 = 201 Ed25519 signatures over the precommit of "
                            "the target header (curve table + SHA-512 table), bound to the committed keys; five tables on one logUp bus under shared challenges. "
@@ -618,12 +654,13 @@ def main():
                            "Sha512Air witness + STARK: H = SHA-512(R || A || precommit) for the same 201 signatures, exchanged with EdAir over the bus"],
                 "missing": ["recursive aggregation of the five STARKs into one succinct proof (f4)"],
             },
-            "roofline": roof,
         }
-        if pmax:
-            line["pmax"] = pmax
-        if args.circuit == "header_range":
-            line["roofline_poseidon"] = pose
+        if args.full:
+            line.update({"latency_ms": round(latency_ms, 2), "gathered_blobs": gathered_ok, "roofline": roof})
+            if pmax:
+                line["pmax"] = pmax
+            if args.circuit == "header_range":
+                line["roofline_poseidon"] = pose
         if args.circuit == "header_range":
             # SURVEY 8d "whole proof" figure: compulsory (algorithmic) bytes of every streaming stage of the BlakeChainAir
             # proof over the time of a step -- trace written 8nc, LDE 8nc(1+2^r), leaf hashing 8Nc, quotient 16Nc,
@@ -646,7 +683,7 @@ def main():
                            "the justification by the current set in-proof: EdAir (201 signatures, 2^16 x 1527) + Sha512Air (2^15 x 805) on one logUp bus with the current set's commitment"],
                 "missing": ["recursive aggregation of the six STARKs into one proof"],
             }
-        elif not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N = 1 only
+        elif args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N = 1 only
             line["cpu_baseline"] = cpu_baseline(vx, ctx)
         emit(line)
     if comm:

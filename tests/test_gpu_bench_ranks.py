@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_prove_distinct_inputs_and_gather():
     env = dict(os.environ, VX_BENCH_BACKEND="gloo", VX_BENCH_DEVICE="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--inflight", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--inflight", "2", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -36,7 +36,7 @@ def test_one_proof_sharded_over_two_ranks():
     caps once per proof, rank 0 gathers and merges the partial blobs and the product verifier accepts the result."""
     env = dict(os.environ, VX_BENCH_BACKEND="gloo", VX_BENCH_DEVICE="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--shard-proof", "4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--shard-proof", "4", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -22,6 +22,6 @@ cd /tmp && export TMPDIR=/tmp
 for v in 0 1; do $R/build_ab/poseidon_rate_$v; done | tee $O/ab_poseidon_fp64_micro.txt
 for v in 0 1; do
   export VX_LIB_PATH=$R/0-kno-vectorx_amd/libvx_pfp$v.so
-  python3 $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-pmax > $O/ab_pfp_$v.json 2>/dev/null
+  python3 $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-pmax > $O/ab_pfp_$v.json 2>/dev/null
   python3 -c "import json; d=json.loads([l for l in open('$O/ab_pfp_$v.json') if l.startswith('{')][-1]); print('fp64=$v: proofs/s', d['value'], 'latency', d['latency_ms'], 'poseidon', d['roofline_poseidon']['achieved'], d['roofline_poseidon']['unit'])"
 done | tee $O/ab_poseidon_fp64_bench.txt

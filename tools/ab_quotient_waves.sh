@@ -8,6 +8,6 @@ for w in 4 3 2; do
   rocprofv3 --kernel-trace --stats -d $O/abqw_$w -o p -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --inflight 1 > $O/abqw_$w.log 2>&1
   python3 $R/tools/rocpd_timeline.py $O/abqw_$w | grep -E "one proof|k_quotient" > $O/abqw_$w.txt
   echo "== waves $w"; cat $O/abqw_$w.txt
-  python3 $R/bench.py --steps 9 --warmup 3 --no-cpu-baseline > $O/abqw_${w}_bench.json 2>/dev/null
+  python3 $R/bench.py --full --steps 9 --warmup 3 --no-cpu-baseline > $O/abqw_${w}_bench.json 2>/dev/null
   python3 -c "import json,sys; d=json.loads([l for l in open('$O/abqw_${w}_bench.json') if l.startswith('{')][-1]); print('throughput', d['value'], 'latency', d['latency_ms'])"
 done

@@ -4,6 +4,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_ntt_stats -o p -- python3 $R/tools/ntt_stats_run.py > $O/r02_ntt_stats.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_bench_stats -o p -- python3 $R/bench.py --no-cpu-baseline > $O/r02_bench_stats.json 2> $O/r02_bench_stats.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r02_bench_stats -o p -- python3 $R/bench.py --full --no-cpu-baseline > $O/r02_bench_stats.json 2> $O/r02_bench_stats.log
 find $O/r02_ntt_stats $O/r02_bench_stats -name "*stats*.csv" | head
 echo done
