@@ -20,7 +20,8 @@
 // num_challenges alphas; transition constraints are multiplied by z_last = x - w^-1,
 // first/last-row constraints by the Lagrange basis polynomial of that row.  Constraints
 // pushed with `constraint()` must hold on EVERY row including the wrap-around pair
-// (last, first): the total degree bound is 3 (quotient_degree_factor 2, rate_bits 1).
+// (last, first): the total degree bound is 3 (quotient_degree_factor 2: two
+// chunks of n coefficients per challenge, whatever the rate_bits).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -817,7 +817,10 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     VX_TRY(quotient_eval_dev(ctx, air, L, r, trace_lde, alphas, public_inputs, n_public, chal, apub, qv, mem));
     // values on the coset -> coefficients (coset_ifft), split into Q chunks of n, commit (from_coeffs)
     VX_TRY(vx_ntt_dev(ctx, qv, LN, 2, N, 1, g, VX_ORDER_NATURAL));
-    // chunk j of challenge k = qv[k*N + j*n .. +n): already contiguous as 2*Q columns of n coefficients
+    // chunk j of challenge k = qv[k*N + j*n .. +n) (the coefficients from Q*n on are zero for a valid trace).  At rate_bits 1
+    // (N = Q*n) they are already 2*Q contiguous columns of n coefficients; above it challenge 1's chunks move down to
+    // qv[Q*n .. 2*Q*n), which does not overlap qv[N .. N + Q*n) since N >= 2*Q*n.
+    if (N != (size_t)Q * n) VX_HIP(hipMemcpyAsync(qv + (size_t)Q * n, qv + N, (size_t)Q * n * 8, hipMemcpyDeviceToDevice, ctx->stream));
     uint64_t* quot_lde = mem.alloc(N * nq);
     VX_CHECK(quot_lde, "stark prove: out of device memory (quotient LDE)");
     VX_TRY(vx_lde_dev(ctx, qv, L, nq, r, g, VX_LDE_SRC_COEFFS, quot_lde, nullptr));

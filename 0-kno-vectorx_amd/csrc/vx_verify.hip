@@ -263,7 +263,7 @@ int32_t vx_air_register(const vx_air_program* in, int* air_id, char* err, size_t
             case VX_AIRP_ASSERT_LAST: {
                 AIRP_NEED(i.d == 0 && i.b == 0 && src(i.a), "air program: instruction %u asserts a register that was never written (or out of range)", pc);
                 const int lim = i.op == VX_AIRP_ASSERT ? 3 : 2;
-                AIRP_NEED(deg[i.a] <= lim, "air program: instruction %u asserts an expression of degree %d (limit %d at rate_bits 1)", pc, deg[i.a], lim);
+                AIRP_NEED(deg[i.a] <= lim, "air program: instruction %u asserts an expression of degree %d (limit %d: two quotient chunks per challenge)", pc, deg[i.a], lim);
                 ++pg->n_constraints;
                 break;
             }

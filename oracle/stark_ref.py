@@ -538,8 +538,8 @@ def prove(air, trace, public_inputs, cfg=None, chal_hook=None):
     perm = bitrev_perm(LN)
     lde_nat = leaves_t_all[perm].T.copy()  # [c][N], lde_nat[:, i] = values at g*w_N^i
     qvals = quotient_values(air, lde_nat, pub, alphas, L, r, chal, aux_pub)
-    qcoef = O.ntt(qvals, inverse=True, shift=G)  # coset_ifft
-    chunks = qcoef.reshape(nq, n)  # flat_map(|q| q.chunks(degree))
+    qcoef = O.ntt(qvals, inverse=True, shift=G)  # coset_ifft: [2][N], degree < 2n (coefficients 2n.. are zero for a valid trace)
+    chunks = qcoef[:, : 2 * n].reshape(nq, n)  # flat_map(|q| q.chunks(degree)), quotient_degree_factor 2
     leaves_q = O.lde_from_coeffs(chunks, r, G)
     tree_q = O.MerkleTree(leaves_q, cap_h)
     proof += [int(x) for x in tree_q.cap.reshape(-1)]

@@ -19,6 +19,16 @@ def oracle_air(air_id, b):
 
 @pytest.mark.parametrize("name,log_n", [("fib", 6), ("mix", 7)])
 def test_restated_airs_give_the_compiled_airs_proofs(vx, oracle, name, log_n):
+    restated_proof_is_the_compiled_proof(vx, name, log_n, CFG)
+
+
+@pytest.mark.parametrize("name,log_n", [("fib", 6), ("mix", 7)])
+def test_restated_airs_give_the_compiled_airs_proofs_at_rate_3(vx, oracle, name, log_n):
+    """The reference's outer config (rate_bits 3, 28 queries): the host interpreter evaluates at zeta whatever the rate."""
+    restated_proof_is_the_compiled_proof(vx, name, log_n, dict(S.DEFAULT_CFG, rate_bits=3, num_queries=28, pow_bits=8))
+
+
+def restated_proof_is_the_compiled_proof(vx, name, log_n, cfg):
     ap = vx.air_program
     base, b = (S.FibAir, AP.fib_builder(ap)) if name == "fib" else (S.MixAir, AP.mix_builder(ap))
     air_id = b.register()
@@ -27,13 +37,13 @@ def test_restated_airs_give_the_compiled_airs_proofs(vx, oracle, name, log_n):
     trace, pub = base.trace(log_n)
     assert S.check_trace(air, trace, pub) is None
     S.register_air(air)
-    got, want = S.prove(air, trace, pub, CFG), S.prove(base, trace, pub, CFG)
+    got, want = S.prove(air, trace, pub, cfg), S.prove(base, trace, pub, cfg)
     assert got[1] == air_id and want[1] == base.ID
     assert (np.delete(got, 1) == np.delete(want, 1)).all()
-    pcfg = vx.lib.default_stark_config(num_queries=CFG["num_queries"])
+    pcfg = vx.lib.default_stark_config(**cfg)
     # the product's host interpreter (at zeta, in the extension field) accepts it under the program's id ...
     vx.lib.stark_verify(got, pcfg, expect_air=air_id, expect_public=pub)
-    S.verify(got, CFG, expect_air=air_id, expect_public=pub)
+    S.verify(got, cfg, expect_air=air_id, expect_public=pub)
     for w in (12, len(got) // 2, len(got) - 4):
         bad = got.copy()
         bad[w] ^= np.uint64(1)

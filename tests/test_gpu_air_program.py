@@ -70,6 +70,24 @@ def test_quotient_values_of_a_program(ctx, vx, oracle):
     assert (got == S.quotient_values(S.MixAir, lde_nat, [int(x) % P for x in pub], alphas, log_n, r)).all()
 
 
+@pytest.mark.parametrize("name,log_n,r", [("mix", 6, 2), ("mix", 7, 3), ("cube", 7, 2), ("cube", 8, 3)])
+def test_quotient_values_of_a_program_high_rate(ctx, vx, oracle, name, log_n, r):
+    """The interpreter (k_quotient_prog) at rate_bits 2 and 3: the row after x is 2^r LDE points on, the periodic columns are
+    2^r times longer; the values equal the reference's (and, for the restated MixAir, the compiled kernel's)."""
+    b = AP.mix_builder(vx.air_program) if name == "mix" else AP.cube_builder(vx.air_program)
+    air_id = b.register()
+    air = S.MixAir if name == "mix" else oracle_air(air_id, b)
+    trace, pub = S.MixAir.trace(log_n) if name == "mix" else AP.cube_trace(log_n)
+    leaves, _ = oracle.lde_from_values(trace, r, 7)
+    lde_nat = np.ascontiguousarray(leaves[S.bitrev_perm(log_n + r)].T)
+    alphas = [0x123456789ABCDEF % P, 0xFEDCBA987654321 % P]
+    buf = ctx.from_host(lde_nat)
+    got = ctx.quotient_eval(air_id, r, buf, log_n, alphas, pub)
+    if name == "mix":
+        assert (got == ctx.quotient_eval(S.MixAir.ID, r, buf, log_n, alphas, pub)).all()
+    assert (got == S.quotient_values(air, lde_nat, [int(x) % P for x in pub], alphas, log_n, r)).all()
+
+
 def test_large_program_trace_and_other_configs(ctx, vx, oracle):
     b = AP.cube_builder(vx.air_program)
     air_id = b.register()
@@ -79,7 +97,8 @@ def test_large_program_trace_and_other_configs(ctx, vx, oracle):
     vx.lib.stark_verify(proof, expect_air=air_id, expect_public=pub)
     S.verify(proof, expect_air=air_id, expect_public=pub)
     trace, pub = AP.cube_trace(9)
-    for over in (dict(num_queries=10, pow_bits=8), dict(cap_height=0, num_queries=5), dict(arity_bits=2, final_poly_bits=0, num_queries=3, pow_bits=0)):
+    for over in (dict(num_queries=10, pow_bits=8), dict(cap_height=0, num_queries=5), dict(arity_bits=2, final_poly_bits=0, num_queries=3, pow_bits=0),
+                 dict(rate_bits=3, num_queries=28)):
         got = ctx.stark_prove(air_id, ctx.from_host(trace), 9, pub, ctx.stark_config(**over))
         assert (got == S.prove(air, trace, pub, dict(S.DEFAULT_CFG, **over))).all(), over
 

@@ -206,6 +206,35 @@ def test_header_range_prove_end_to_end(ctx, vx, oracle):
     assert e.value.code == -5
 
 
+def test_header_range_at_the_outer_rate(ctx, vx, oracle):
+    """The whole header_range path at the reference's outer config (rate_bits 3, 28 queries): five tables on one bus, each a 2^3
+    blowup (the hash chain's 2^16 rows -> 2^19 LDE points).  The reference verifier accepts every table and the bus balances; the
+    product's verifier accepts the blob under that config, and refuses it under the default config, under rate_bits 1 with the
+    same queries, and with one word flipped."""
+    ch = vx.synth.Chain(16, profile="Ptiny", stride=512)
+    cfg, ocfg = ctx.stark_config(rate_bits=3, num_queries=28), dict(S.DEFAULT_CFG, rate_bits=3, num_queries=28)
+    just = vx.lib.PackedJustification(vx.synth.Justification(ch.target_block, ch.target_hash, n_auth=9, n_signed=7), 12)
+    out96, blob = ctx.header_range_prove(ctx.from_host(ch.headers), 512, ch.sizes, 16, ch.trusted_block, ch.trusted_hash, ch.target_block, cfg, just=just)
+    assert out96 == ch.expected_outputs(16)
+    parts = vx.lib.split_blob(blob)
+    assert all(p.size and int(p[5]) == 3 for p in parts)
+    oracle_verify_blob(vx, blob, ocfg, 16)
+    sid, sh = just.struct.authority_set_id, just.sh.tobytes()
+
+    def check(b, c):
+        vx.lib.header_range_verify(b, 16, ch.trusted_block, ch.trusted_hash, ch.target_block, out96, c, authority_set_hash=sh, authority_set_id=sid)
+
+    check(blob, cfg)
+    for other in (ctx.stark_config(), ctx.stark_config(num_queries=28), ctx.stark_config(rate_bits=2, num_queries=28)):
+        with pytest.raises(vx.VxError):
+            check(blob, other)
+    for w in (len(blob) // 3, len(blob) // 2, len(blob) - 5):
+        bad = blob.copy()
+        bad[w] ^= np.uint64(1)
+        with pytest.raises(vx.VxError):
+            check(bad, cfg)
+
+
 def test_merkle_roots_are_bound_by_the_proof(ctx, vx, oracle):
     """all 96 output bytes are proven.  The two Merkle roots are public inputs of the Merkle table, whose
     leaves come over the bus from the header bytes the hash-chain table hashed: a blob claiming any other state / data

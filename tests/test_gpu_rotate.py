@@ -130,6 +130,28 @@ def test_rotate_prove_small(ctx, vx):
     hb.free()
 
 
+def test_rotate_at_the_outer_rate(ctx, vx):
+    """The small rotation of test_rotate_prove_small at rate_bits 3 with 28 queries: six tables on two buses, accepted by the
+    product's verifier under that config; refused under the default config, under rate_bits 1 with the same queries, and with one
+    word flipped."""
+    cfg = ctx.stark_config(rate_bits=3, num_queries=28)
+    e = vx.synth.EpochEndHeader(140000, 5)
+    sj = vx.synth.Justification(140000, e.hash, n_auth=7, n_signed=5, set_id=3)
+    just = vx.lib.PackedJustification(sj, 12)
+    out32, blob = ctx.rotate_prove(ctx.from_host(e.padded), e.size, 140000, 5, e.start_position, e.new_pubkeys, just, cfg)
+    assert out32 == e.new_authority_set_hash
+    assert all(int(p[5]) == 3 for p in vx.lib.split_rotate_blob(blob))
+    vx.lib.rotate_verify(blob, 3, sj.authority_set_hash, out32, cfg)
+    for other in (ctx.stark_config(), ctx.stark_config(num_queries=28)):
+        with pytest.raises(vx.VxError):
+            vx.lib.rotate_verify(blob, 3, sj.authority_set_hash, out32, other)
+    for w in (28 + int(blob[16]) // 2, len(blob) // 2, len(blob) - 7):
+        bad = blob.copy()
+        bad[w] ^= np.uint64(1)
+        with pytest.raises(vx.VxError):
+            vx.lib.rotate_verify(bad, 3, sj.authority_set_hash, out32, cfg)
+
+
 @pytest.mark.parametrize("n_new,size,logs_before", [(1, None, 0), (70, 35840, 2)])
 def test_rotate_edges(ctx, vx, n_new, size, logs_before):
     """One new authority (1-byte compact count, the log right behind the fixed fields) and a header of exactly MAX_HEADER_SIZE

@@ -50,3 +50,82 @@ def test_lookup_air_auxiliary_round(oracle):
     for air, L in ((S.FibAir, 6), (S.MixAir, 6)):
         t_, p_ = air.trace(L)
         assert S.check_trace(air, t_, p_) is None
+
+
+# rate_bits 2 and 3: the coset has N = n 2^r points, the quotient 2n coefficients per challenge (the reference's outer
+# Plonky2 config runs at rate_bits 3 with 28 queries)
+HI_RATE = [(S.FibAir, 6), (S.MixAir, 7), (S.LookupAir, 8)]
+
+
+def rate_cfg(r):
+    return dict(S.DEFAULT_CFG, rate_bits=r, num_queries=28, pow_bits=8)
+
+
+@pytest.mark.parametrize("r", [2, 3])
+@pytest.mark.parametrize("air,log_n", HI_RATE)
+def test_prove_verify_roundtrip_high_rate(oracle, air, log_n, r):
+    cfg = rate_cfg(r)
+    trace, pub = air.trace(log_n)
+    proof = S.prove(air, trace, pub, cfg)
+    assert int(proof[5]) == r
+    info = S.verify(proof, cfg, expect_air=air.ID, expect_public=pub)
+    assert info["degree_bits"] == log_n
+    for w in (12, 40, len(proof) // 2, len(proof) - 3):
+        bad = proof.copy()
+        bad[w] ^= np.uint64(1)
+        with pytest.raises(S.VerifyError):
+            S.verify(bad, cfg)
+    with pytest.raises(S.VerifyError):
+        S.verify(proof[:-1], cfg)
+    with pytest.raises(S.VerifyError):
+        S.verify(proof, cfg, expect_public=[p + 1 for p in pub] or [1])
+    for other in (dict(cfg, rate_bits=1), dict(cfg, rate_bits=5 - r)):
+        with pytest.raises(S.VerifyError, match="config mismatch"):
+            S.verify(proof, other)
+
+
+def quotient_coeffs(air, trace, pub, r, alphas, chal=None):
+    """The prover's step 2 on its own: quotient values on the size-n 2^r coset -> coset_ifft coefficients [2][N]."""
+    log_n = trace.shape[1].bit_length() - 1
+    aux_pub = None
+    if chal is not None:
+        aux, aux_pub = air.gen_aux(trace, chal)
+        trace = np.concatenate([trace, aux])
+    leaves, _ = S.O.lde_from_values(trace, r, S.G)
+    lde_nat = leaves[S.bitrev_perm(log_n + r)].T.copy()
+    qv = S.quotient_values(air, lde_nat, [int(x) % S.P for x in pub], alphas, log_n, r, chal, aux_pub)
+    return S.O.ntt(qv, inverse=True, shift=S.G)
+
+
+@pytest.mark.parametrize("r", [1, 2, 3])
+@pytest.mark.parametrize("air,log_n", HI_RATE)
+def test_quotient_degree_is_below_2n(oracle, air, log_n, r):
+    """For an honest trace every coefficient of the quotient from 2n on is exactly zero: what lets both provers commit only the
+    first 2n (two chunks of n) per challenge at any rate.  A violating trace leaves non-zero coefficients up there at r >= 2."""
+    n = 1 << log_n
+    alphas = [0x0123456789ABCDEF % S.P, 0xFEDCBA9876543210 % S.P]
+    chal = [3, 5, 7, 11] if getattr(air, "AUX", 0) else None
+    trace, pub = air.trace(log_n)
+    qc = quotient_coeffs(air, trace, pub, r, alphas, chal)
+    assert qc.shape == (2, n << r)
+    assert not qc[:, 2 * n:].any()
+    assert qc[:, n:2 * n].any() == (air is not S.FibAir)  # constraints of degree 3 fill the second chunk (FibAir's are of degree 2)
+    if r >= 2:
+        bad = trace.copy()
+        bad[1, n // 3] ^= np.uint64(1)
+        assert quotient_coeffs(air, bad, pub, r, alphas, chal)[:, 2 * n:].any()
+
+
+def test_violating_trace_is_rejected_at_rate_3(oracle):
+    cfg = rate_cfg(3)
+    trace, pub = S.MixAir.trace(7)
+    trace[1, 10] ^= np.uint64(1)
+    with pytest.raises(S.VerifyError, match="constraint identity"):
+        S.verify(S.prove(S.MixAir, trace, pub, cfg), cfg)
+    trace, pub = S.FibAir.trace(6)
+    with pytest.raises(S.VerifyError, match="constraint identity"):
+        S.verify(S.prove(S.FibAir, trace, [pub[0], pub[1], pub[2] + 1], cfg), cfg)
+    tr, pub = S.LookupAir.trace(8)
+    tr[6, 3] += np.uint64(1)  # a multiplicity one too high: the running sum does not close
+    with pytest.raises(S.VerifyError):
+        S.verify(S.prove(S.LookupAir, tr, pub, cfg), cfg)

@@ -30,6 +30,39 @@ def test_accepts_reference_proofs_and_rejects_tampering(vx, oracle, air, log_n):
         vx.lib.stark_verify(proof, vx.lib.default_stark_config(num_queries=83))
 
 
+
+@pytest.mark.parametrize("r", [2, 3])
+@pytest.mark.parametrize("air,log_n", [(S.FibAir, 6), (S.MixAir, 7), (S.LookupAir, 8)])
+def test_accepts_reference_proofs_at_high_rate(vx, oracle, air, log_n, r):
+    """rate_bits 2 and 3 (the reference's outer config: rate_bits 3, 28 queries): the host verifier accepts the reference prover's
+    proofs under their config, rejects tampering, and rejects the same proof under any other rate."""
+    cfg = dict(S.DEFAULT_CFG, rate_bits=r, num_queries=28, pow_bits=8)
+    pcfg = vx.lib.default_stark_config(rate_bits=r, num_queries=28, pow_bits=8)
+    trace, pub = air.trace(log_n)
+    proof = S.prove(air, trace, pub, cfg)
+    vx.lib.stark_verify(proof, pcfg, expect_air=air.ID, expect_public=pub)
+    for w in (11, 40, len(proof) // 3, len(proof) // 2, len(proof) - 3):
+        bad = proof.copy()
+        bad[w] ^= np.uint64(1)
+        with pytest.raises(vx.VxError):
+            vx.lib.stark_verify(bad, pcfg)
+    with pytest.raises(vx.VxError):
+        vx.lib.stark_verify(proof[:-1], pcfg)
+    for other in (1, 5 - r):
+        with pytest.raises(vx.VxError, match="config mismatch"):
+            vx.lib.stark_verify(proof, vx.lib.default_stark_config(rate_bits=other, num_queries=28, pow_bits=8))
+    # the header claims rate 1 (so the config check passes): the Merkle paths and the FRI plan no longer fit
+    forged = proof.copy()
+    forged[5] = 1
+    with pytest.raises(vx.VxError):
+        vx.lib.stark_verify(forged, vx.lib.default_stark_config(num_queries=28, pow_bits=8))
+    # a trace that violates the AIR in one cell: the prover still emits a proof, the verifier refuses it
+    bad_trace = trace.copy()
+    bad_trace[1, 10] ^= np.uint64(1)
+    with pytest.raises(vx.VxError):
+        vx.lib.stark_verify(S.prove(air, bad_trace, pub, cfg), pcfg)
+
+
 def test_blake_chain_proof(vx, blake_proof):
     """The product's host verifier (the AIR as compiled into libvxprove, evaluated at zeta) accepts the reference
     prover's BlakeChainAir proof -- auxiliary round, 2^16-row periodic tables and all -- and rejects tampering."""
