@@ -1,10 +1,12 @@
-// Host-side plumbing shared by the circuit provers (vx_header_range_prove, vx_rotate_prove): the tables of one statement
+// Host-side plumbing shared by the circuit provers (vx_header_range_prove in vx_header_range.hip, vx_rotate_prove in
+// vx_rotate.hip), implemented in vx_bus.hip: the tables of one statement
 // sit on ONE logUp bus and must use the same lookup challenges, drawn after every trace is committed.  Each table is proven
 // from its own host thread on its own context; the provers stop after their trace caps (vx_chal_hook) and MEET: every one
 // deposits its public inputs + cap, waits for all the others and derives the challenges from the transcript of all
 // (public inputs, cap) pairs in table order.
 #pragma once
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -42,7 +44,7 @@ struct BusParty {
     int who;
 };
 int32_t vx_bus_hook(void* party, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal);
-// one table of the statement, proven from its own host thread on its own context
+// one table of the statement, proven on its own context (all but the caller's own table from a host thread of their own)
 struct TableJob {
     vx_ctx* c = nullptr;
     std::thread th;
@@ -50,6 +52,30 @@ struct TableJob {
     std::vector<uint64_t> proof;
     size_t len = 0;
 };
+// Proves one table into j.proof / j.len: proof bound -> size j.proof -> allocate the n_cols << log_n trace on `c` -> gen ->
+// vx_stark_prove_impl with the party's hook -> free the trace.  gen(c, trace, pub) writes the trace and the n_pub public
+// inputs and may refuse the statement (vx_fail on `c`); nothing is proven then.
+using TableGen = std::function<int32_t(vx_ctx* c, vx_buf* trace, uint64_t* pub)>;
+int32_t run_table(vx_ctx* c, TableJob& j, int air_id, int log_n, size_t n_cols, size_t n_pub, const vx_stark_config* cfg, const vx_chal_hook* hook, int consume_trace,
+                  const TableGen& gen);
+// the bound -> size -> prove part alone, for a table whose trace exists before its prover starts (rotate's epoch-end table)
+int32_t prove_table(vx_ctx* c, TableJob& j, int air_id, int log_n, const vx_stark_config* cfg, const vx_chal_hook* hook, int consume_trace, vx_buf* trace, const uint64_t* pub,
+                    size_t n_pub);
+// Runs j.rc = fn(j.c, j) on a host thread of its own; a table that fails tells the rendezvous (rv.fail(who)) so that the other
+// provers are not left waiting at their hooks -- also when the thread cannot be created, which returns false.  `j`, `rv` and
+// whatever `fn` refers to must outlive the join: declare a TableJoin after them.
+bool start_table(TableJob& j, BusMeet& rv, int who, std::function<int32_t(vx_ctx*, TableJob&)> fn);
+// joins the threads of its jobs, at the latest when it goes out of scope (every exit path waits for the threads)
+struct TableJoin {
+    std::vector<TableJob*> jobs;
+    void join() {
+        for (TableJob* j : jobs)
+            if (j->th.joinable()) j->th.join();
+    }
+    ~TableJoin() { join(); }
+};
+// out[0 .. n): the chain of side contexts behind `ctx` (every table is proven on a context of its own); fails with `msg`
+int32_t side_contexts(vx_ctx* ctx, size_t n, vx_ctx** out, const char* msg);
 
 // The three tables of a justification -- authority-set commitment (ShaChainAir, sends the chosen signers' keys), Ed25519
 // (EdAir) and SHA-512 (Sha512Air) -- as parties first, first + 1, first + 2 of `rv`.  The prover verifies exactly

@@ -5,13 +5,15 @@
 // new set's commitment is proved (second SHA-256 chain STARK) and returned as the 32 output bytes.  Two logUp buses:
 //   A  current-set commitment -> Ed25519 <-> SHA-512                 (the justification, vx_bus.h)
 //   B  Blake2b header hash -> EpochEndAir -> new-set commitment     (the header bytes of the log ARE the committed keys)
+// Every table goes through the runner / starter / join of vx_bus.h (vx_bus.hip) and is sized by vx_table_shapes.h; the verifier
+// is vx_rotate_verify in vx_verify.hip.
 #include <cstdio>
 #include <cstring>
 #include <thread>
 #include <vector>
 
 #include "vx_bus.h"
-#include "vx_internal.h"
+#include "vx_table_shapes.h"
 
 namespace {
 
@@ -69,18 +71,6 @@ __global__ __launch_bounds__(64) void k_epoch_end_check(const uint8_t* __restric
     if (t + 1 == num_authorities && (v[40] | v[41] | v[42] | v[43]) != 0) return fail(EE_DELAY, t);  // :267-274
 }
 
-int sha_rows_log(size_t n_keys) {
-    int log_n = 6;
-    while (((size_t)1 << log_n) < 64 * (2 * n_keys - 1)) ++log_n;
-    return log_n;
-}
-int blake_rows_log(size_t chunks) {
-    int log_n = 16;  // one copy of the 2^16-row XOR tables (BlakeChainAir)
-    while (((size_t)1 << log_n) < 16 * chunks) ++log_n;
-    return log_n;
-}
-
-
 }  // namespace
 
 extern "C" {
@@ -115,10 +105,10 @@ int32_t vx_verify_epoch_end_header(vx_ctx* ctx, const vx_buf* header, uint32_t n
 int32_t vx_rotate_proof_bound(const vx_stark_config* cfg, size_t n_chunks, size_t n_cur_authorities, size_t n_new_authorities, size_t* n_words) {
     if (!cfg || !n_words || n_chunks == 0 || n_cur_authorities == 0 || n_new_authorities == 0) return VX_ERR_ARG;
     size_t w1 = 0, w2 = 0, w3 = 0, w4 = 0;
-    int32_t rc = vx_stark_proof_bound(VX_AIR_BLAKE_CHAIN, cfg, blake_rows_log(n_chunks), &w1);
+    int32_t rc = vx_stark_proof_bound(VX_AIR_BLAKE_CHAIN, cfg, blake_log_n(n_chunks), &w1);
     if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_EPOCH_END, cfg, VX_EPOCH_END_LOG_ROWS, &w4);
     if (rc == VX_OK) w2 = vx_justification_proof_bound(cfg, n_cur_authorities, &rc);  // commitment of the current set + Ed25519 + SHA-512
-    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_SHA_CHAIN, cfg, sha_rows_log(n_new_authorities), &w3);
+    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_SHA_CHAIN, cfg, sha_log_n(n_new_authorities), &w3);
     *n_words = VX_ROT_HDR + w1 + w2 + w3 + w4;
     return rc;
 }
@@ -160,11 +150,7 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     JustificationTables jt;
     TableJob epoch, newset;
     vx_ctx* side[5];
-    {
-        vx_ctx* c = ctx;
-        for (int t = 0; t < 5; ++t) side[t] = c = c ? vx_side_ctx(c) : nullptr;
-        VX_CHECK(c, "rotate: no side context for every table");
-    }
+    VX_TRY(side_contexts(ctx, 5, side, "rotate: no side context for every table"));
     epoch.c = side[3], newset.c = side[4];
     // the epoch-end trace (512 rows) is written from this thread: its prefix gives the byte window the Blake2b table sends
     vx_buf* et = nullptr;
@@ -185,100 +171,54 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     if (start_position + 1 < 72 || (uint64_t)start_position + 1 + wlen > header_size)  // (the hash covers header_size bytes; 72 = parent hash + number + state root)
         return vx_fail(ctx, VX_ERR_STATEMENT, "rotate: the log at %u..%llu lies outside the hashed digest bytes of the %u-byte header", start_position + 1,
                        (unsigned long long)start_position + 1 + wlen, header_size);
-    struct Joiner {  // every exit path waits for the threads
-        JustificationTables& j;
-        TableJob &a, &b;
-        ~Joiner() {
-            for (int t = 0; t < 3; ++t)
-                if (j.job[t].th.joinable()) j.job[t].th.join();
-            if (a.th.joinable()) a.th.join();
-            if (b.th.joinable()) b.th.join();
-        }
-    } joiner{jt, epoch, newset};
+    TableJob hash;
+    hash.c = ctx;
+    auto prove_epoch = [&](vx_ctx* c, TableJob& j) -> int32_t {
+        return prove_table(c, j, VX_AIR_EPOCH_END, VX_EPOCH_END_LOG_ROWS, cfg, &hb[1], /*consume_trace=*/0, et, epub, 10);
+    };
+    auto prove_newset = [&](vx_ctx* c, TableJob& j) -> int32_t {  // the output (rotate.rs:317-320): receives every key from the epoch-end table
+        const int sl = sha_log_n(num_authorities);
+        return run_table(c, j, VX_AIR_SHA_CHAIN, sl, VX_SHA_AIR_COLS, 10, cfg, &hb[2], /*consume_trace=*/0, [&](vx_ctx* c, vx_buf* st, uint64_t* spub) {
+            return vx_sha_chain_trace_dev(c, new_pubkeys, num_authorities, nullptr, 2, sl, st->d, spub, new_commit);
+        });
+    };
+    TableJoin threads{{&jt.job[0], &jt.job[1], &jt.job[2], &epoch, &newset}};  // every exit path waits for the threads
     {
         const int32_t rs = vx_justification_tables_start(side, just, cfg, &rv, 0, nullptr, nullptr, &jt);
         if (rs != VX_OK) return vx_fail(ctx, rs, "rotate: no host thread for the justification tables");
     }
-    auto prove_epoch = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        size_t bound = 0;
-        VX_TRY(vx_stark_proof_bound(VX_AIR_EPOCH_END, cfg, VX_EPOCH_END_LOG_ROWS, &bound));
-        j.proof.resize(bound);
-        return vx_stark_prove_impl(c, VX_AIR_EPOCH_END, cfg, et->d, et->n, /*consume_trace=*/0, VX_EPOCH_END_LOG_ROWS, epub, 10, j.proof.data(), j.proof.size(), &j.len, &hb[1]);
-    };
-    auto prove_newset = [&](vx_ctx* c, TableJob& j) -> int32_t {  // the output (rotate.rs:317-320): receives every key from the epoch-end table
-        const int sl = sha_rows_log(num_authorities);
-        size_t bound = 0;
-        VX_TRY(vx_stark_proof_bound(VX_AIR_SHA_CHAIN, cfg, sl, &bound));
-        j.proof.resize(bound);
-        vx_buf* st = nullptr;
-        VX_TRY(vx_alloc(c, ((size_t)VX_SHA_AIR_COLS) << sl, &st));
-        uint64_t spub[10];
-        int32_t r = vx_sha_chain_trace_dev(c, new_pubkeys, num_authorities, nullptr, 2, sl, st->d, spub, new_commit);
-        if (r == VX_OK) r = vx_stark_prove_impl(c, VX_AIR_SHA_CHAIN, cfg, st->d, st->n, /*consume_trace=*/0, sl, spub, 10, j.proof.data(), j.proof.size(), &j.len, &hb[2]);
-        (void)vx_free(c, st);
-        return r;
-    };
+    // (the tables of bus B name themselves when they fail; BusMeet::fail looks at the party only when an exchange is set, which
+    // this circuit never does, so that is the plain rvb.fail())
     int32_t rc = VX_OK;
-    try {
-        epoch.th = std::thread([&] {
-            (void)hipSetDevice(epoch.c->device);
-            epoch.rc = prove_epoch(epoch.c, epoch);
-            if (epoch.rc != VX_OK) rvb.fail();  // do not leave the other provers waiting at their hooks
-        });
-        newset.th = std::thread([&] {
-            (void)hipSetDevice(newset.c->device);
-            newset.rc = prove_newset(newset.c, newset);
-            if (newset.rc != VX_OK) rvb.fail();
-        });
-    } catch (...) {
-        rvb.fail();
+    if (!start_table(epoch, rvb, 1, prove_epoch) || !start_table(newset, rvb, 2, prove_newset))
         rc = vx_fail(ctx, VX_ERR_DEVICE, "rotate: no host thread for the epoch-end tables");
-    }
     // 2. header hash = Blake2b-256 of the first header_size bytes (rotate.rs:293); the trace of its compressions
     //    is the witness of the hash STARK (one-header chain anchored at the header's own parent hash)
-    const size_t chunks = (header_size + 127) / 128;
-    const int bl = blake_rows_log(chunks);
-    vx_buf* trace = nullptr;
-    if (rc == VX_OK) rc = vx_alloc(ctx, ((size_t)VX_BLAKE_AIR_COLS) << bl, &trace);
-    uint64_t pub[20];
-    if (rc == VX_OK) rc = vx_blake_chain_trace(ctx, header, MAX_HEADER_SIZE, &header_size, 1, parent, epoch_end_block_number, 0, start_position + 1, wlen, bl, trace, pub, header_hash);
-    // 3. justification by the current set over (epoch_end_block_number, header hash) (rotate.rs:297-302), natively
+    const int bl = blake_log_n((header_size + 127) / 128);
     if (rc == VX_OK)
-        rc = vx_verify_simple_justification(ctx, epoch_end_block_number, header_hash, just->authority_set_id, just->authority_set_hash,
-                                            just->precommit, just->pubkeys, just->signatures, just->validator_signed, just->num_authorities,
-                                            just->max_authorities);
-    size_t len[3] = {0, 0, 0};
-    int32_t rc_room = VX_OK;
-    auto room = [&](size_t off) { return rc_room == VX_OK && proof_out && proof_cap > off; };
-    if (rc == VX_OK) {
-        rc = vx_stark_prove_impl(ctx, VX_AIR_BLAKE_CHAIN, cfg, trace->d, trace->n, 1, bl, pub, 20, room(VX_ROT_HDR) ? proof_out + VX_ROT_HDR : nullptr,
-                                 room(VX_ROT_HDR) ? proof_cap - VX_ROT_HDR : 0, &len[0], &hb[0]);
-        if (rc == VX_ERR_BUFSZ) rc_room = rc, rc = VX_OK;
-    }
-    if (rc != VX_OK) rvb.fail();
-    if (trace) (void)vx_free(ctx, trace);
+        rc = run_table(ctx, hash, VX_AIR_BLAKE_CHAIN, bl, VX_BLAKE_AIR_COLS, 20, cfg, &hb[0], /*consume_trace=*/1, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+            VX_TRY(vx_blake_chain_trace(c, header, MAX_HEADER_SIZE, &header_size, 1, parent, epoch_end_block_number, 0, start_position + 1, wlen, bl, trace, pub, header_hash));
+            // 3. justification by the current set over (epoch_end_block_number, header hash) (rotate.rs:297-302), natively
+            return vx_verify_simple_justification(c, epoch_end_block_number, header_hash, just->authority_set_id, just->authority_set_hash, just->precommit, just->pubkeys,
+                                                  just->signatures, just->validator_signed, just->num_authorities, just->max_authorities);
+        });
+    if (rc != VX_OK) rvb.fail(0);
     // 4. collect the side tables
-    if (epoch.th.joinable()) epoch.th.join();
-    if (newset.th.joinable()) newset.th.join();
+    threads.join();
     const int32_t rc_just = vx_justification_tables_join(ctx, &jt);
     if (rc == VX_OK && rc_just != VX_OK) rc = rc_just;
     for (TableJob* j : {&epoch, &newset})
         if (rc == VX_OK && j->rc != VX_OK) rc = vx_fail(ctx, j->rc, "rotate: %s", vx_last_error(j->c)[0] ? vx_last_error(j->c) : "an epoch-end table failed");
-    len[1] = jt.job[0].len, len[2] = newset.len;
-    const size_t len_ed = jt.job[1].len, len_h = jt.job[2].len, len_ep = epoch.len, total = VX_ROT_HDR + len[0] + len[1] + len[2] + len_ed + len_h + len_ep;
-    if (rc == VX_OK && rc_room == VX_OK && proof_out && proof_cap >= total) {
-        size_t off = VX_ROT_HDR + len[0];
-        memcpy(proof_out + off, jt.job[0].proof.data(), len[1] * 8), off += len[1];
-        memcpy(proof_out + off, newset.proof.data(), len[2] * 8), off += len[2];
-        memcpy(proof_out + off, jt.job[1].proof.data(), len_ed * 8), off += len_ed;
-        memcpy(proof_out + off, jt.job[2].proof.data(), len_h * 8), off += len_h;
-        memcpy(proof_out + off, epoch.proof.data(), len_ep * 8);
-    }
     if (rc != VX_OK) return rc;
+    // blob order: header hash, current-set commitment, new-set commitment, Ed25519, SHA-512, epoch end
+    const TableJob* order[6] = {&hash, &jt.job[0], &newset, &jt.job[1], &jt.job[2], &epoch};
+    size_t total = VX_ROT_HDR;
+    for (const TableJob* j : order) total += j->len;
     *proof_len = total;
     memcpy(out32, new_commit, 32);
-    if (rc_room != VX_OK || !proof_out || proof_cap < *proof_len)
-        return vx_fail(ctx, VX_ERR_BUFSZ, "rotate: proof needs %zu words, buffer has %zu", *proof_len, proof_cap);
+    if (!proof_out || proof_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "rotate: proof needs %zu words, buffer has %zu", total, proof_cap);
+    size_t off = VX_ROT_HDR;
+    for (const TableJob* j : order) memcpy(proof_out + off, j->proof.data(), j->len * 8), off += j->len;
     proof_out[0] = VX_ROT_MAGIC;
     proof_out[1] = just->authority_set_id;
     proof_out[2] = epoch_end_block_number;
@@ -286,17 +226,17 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     memcpy(proof_out + 4, header_hash, 32);
     memcpy(proof_out + 8, just->authority_set_hash, 32);
     memcpy(proof_out + 12, new_commit, 32);
-    proof_out[16] = len[0];
-    proof_out[17] = len[1];
-    proof_out[18] = len[2];
-    proof_out[19] = len_ed;
+    proof_out[16] = hash.len;
+    proof_out[17] = jt.job[0].len;
+    proof_out[18] = newset.len;
+    proof_out[19] = jt.job[1].len;
     memcpy(proof_out + 20, parent, 32);
-    proof_out[24] = len_h;
+    proof_out[24] = jt.job[2].len;
     uint64_t round = 0;
     memcpy(&round, just->precommit + 37, 8);  // 0x01 || hash 32 || block 4 || round 8 || set id 8 (decoder.rs:159-200)
     proof_out[25] = round;
     proof_out[26] = start_position;
-    proof_out[27] = len_ep;
+    proof_out[27] = epoch.len;
     return VX_OK;
 }
 

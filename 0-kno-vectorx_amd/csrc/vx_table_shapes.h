@@ -1,0 +1,37 @@
+// Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers
+// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip) and the host verifier (vx_verify.hip): that both sides size a table
+// the same way is a soundness condition.  Host-only inline functions, no device code.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "vx_internal.h"
+
+// BlakeChainAir (hash chain / header hash): 16 rows per compression, at least one copy of the 2^16-row XOR tables
+// (blk::TABLE_LOG in air_blake.cuh; vx_verify.hip sees both and asserts that they agree)
+constexpr int VX_BLAKE_TABLE_LOG = 16;
+static inline int blake_log_n(size_t chunks) {
+    int log_n = VX_BLAKE_TABLE_LOG;
+    while (((size_t)1 << log_n) < 16 * chunks) ++log_n;
+    return log_n;
+}
+// ShaChainAir (authority-set commitment): 64 rows per SHA-256 compression, 2n - 1 compressions for n keys
+static inline int sha_log_n(size_t n_keys) {
+    int log_n = 6;
+    while (((size_t)1 << log_n) < 64 * (2 * n_keys - 1)) ++log_n;
+    return log_n;
+}
+// ShaTreeAir (the two Merkle trees): one AIR per supported max_headers (0 = none), 256 rows per leaf
+static inline int tree_air_id(uint32_t max_headers) { return max_headers == 256 ? 7 : max_headers == 512 ? 8 : max_headers == 16 ? 9 : 0; }
+static inline int tree_log_n(uint32_t max_headers) {
+    int l = 8;
+    while ((1u << (l - 8)) < max_headers) ++l;
+    return l;
+}
+// the EdDSA tables by the number of signatures they verify: 256 rows per signature (one slot stays idle) / 164 rows per hash.
+// The prover needs floor(2n/3) + 1 of the n authorities (justification.rs:164-186), so it verifies exactly that many.
+static inline size_t sig_quorum(size_t n_auth) { return 2 * n_auth / 3 + 1; }
+static inline int ed_log_n(size_t n_sig) { return n_sig <= 255 ? 16 : 17; }
+static inline int ed_air_id(size_t n_sig) { return n_sig <= 255 ? VX_AIR_ED25519_16 : VX_AIR_ED25519; }
+static inline int s512_log_n(size_t n_sig) { return n_sig <= 6 ? 10 : n_sig <= 204 ? 15 : 16; }
+static inline int s512_air_id(size_t n_sig) { return n_sig <= 6 ? VX_AIR_SHA512_10 : n_sig <= 204 ? VX_AIR_SHA512_15 : VX_AIR_SHA512; }

@@ -23,6 +23,9 @@
 #include "glh_poseidon.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
+#include "vx_table_shapes.h"
+
+static_assert(VX_BLAKE_TABLE_LOG == blk::TABLE_LOG, "vx_table_shapes.h and air_blake.cuh disagree on the rows of the XOR lookup tables");
 
 namespace {
 inline void v_poseidon(uint64_t* s) { glh::poseidon(s); }
@@ -591,6 +594,43 @@ void vx_shared_challenges_host(const uint64_t* const* pubs, const size_t* n_pubs
     v_shared_challenges_n(pubs, n_pubs, caps, k, cap_words, out, n_out);
 }
 
+// One table of a bus group: its serialised proof, what peek_tables reads from it (public inputs, trace cap), and what the
+// request implies for it (AIR id, public inputs).
+struct BusTable {
+    const uint64_t* proof;
+    size_t len;
+    const uint64_t *pub = nullptr, *cap = nullptr;
+    size_t n_pub = 0;
+    int air = 0;
+    const uint64_t* want = nullptr;
+    size_t n_want = 0;
+};
+static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!vx_stark_proof_peek(t[i].proof, t[i].len, cfg->cap_height, &t[i].pub, &t[i].n_pub, &t[i].cap)) return false;
+    return true;
+}
+// The tables of one logUp bus, in bus order (the order of the shared-challenge transcript): the lookup challenges every proof must
+// have used are a transcript of all (public inputs, trace cap) pairs; every table is verified under them against its expected
+// AIR and public inputs; and the bus must close -- a table publishes its total / rows.
+static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, size_t n, const char* unbalanced, char* err, size_t errlen) {
+    std::vector<const uint64_t*> pubs(n), caps(n);
+    std::vector<size_t> n_pubs(n);
+    for (size_t i = 0; i < n; ++i) pubs[i] = t[i].pub, n_pubs[i] = t[i].n_pub, caps[i] = t[i].cap;
+    uint64_t chal[4];
+    v_shared_challenges_n(pubs.data(), n_pubs.data(), caps.data(), n, (size_t)4 << cfg->cap_height, chal, 4);
+    uint64_t bus[2] = {0, 0};
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t* apub = nullptr;
+        int L = 0;
+        const int32_t rc = vx_stark_verify_ext(cfg, t[i].proof, t[i].len, t[i].air, t[i].want, t[i].n_want, chal, &apub, &L, err, errlen);
+        if (rc != VX_OK) return rc;
+        for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
+    }
+    NEED(bus[0] == 0 && bus[1] == 0, "%s", unbalanced);
+    return VX_OK;
+}
+
 // Expected public inputs and AIR ids of the three justification tables (vx_bus.h).
 int32_t vx_justification_expect(const uint64_t* ppub_chain, size_t n_chain, const uint64_t* ppub_ed, size_t n_ed, size_t n_s512, const uint8_t authority_set_hash[32],
                                 uint64_t authority_set_id, const uint8_t block_hash[32], uint32_t block_number, uint64_t round, uint64_t spub[10], uint64_t epub[2],
@@ -598,17 +638,14 @@ int32_t vx_justification_expect(const uint64_t* ppub_chain, size_t n_chain, cons
     NEED(n_chain == 10 && n_ed == 2 && n_s512 == 15, "justification proofs have the wrong number of public inputs");
     // the request's authority_set_hash must be the proven commitment; the number of authorities it binds and the number of verified
     // signatures are read from the proofs: signed * 3 > authorities * 2 (justification.rs:164-186)
-    for (int j = 0; j < 8; ++j)
-        spub[j] = ((uint64_t)authority_set_hash[4 * j] << 24) | ((uint64_t)authority_set_hash[4 * j + 1] << 16) | ((uint64_t)authority_set_hash[4 * j + 2] << 8) |
-                  authority_set_hash[4 * j + 3];
+    be_limbs(authority_set_hash, spub);
     const uint64_t n_auth = ppub_chain[8], n_signed = ppub_ed[0];
     NEED(n_auth >= 1 && n_auth <= 512 && n_signed <= n_auth, "implausible authority counts");
     NEED(n_signed * 3 > n_auth * 2, "fewer than 2/3 of the authority set signed (%llu of %llu)", (unsigned long long)n_signed, (unsigned long long)n_auth);
     spub[8] = n_auth, spub[9] = 1;
     epub[0] = n_signed, epub[1] = 1;
     air[0] = VX_AIR_SHA_CHAIN;
-    air[1] = n_signed <= 255 ? VX_AIR_ED25519_16 : VX_AIR_ED25519;  // the tables are sized by the number of signatures they verify
-    air[2] = n_signed <= 6 ? VX_AIR_SHA512_10 : n_signed <= 204 ? VX_AIR_SHA512_15 : VX_AIR_SHA512;
+    air[1] = ed_air_id(n_signed), air[2] = s512_air_id(n_signed);  // the tables are sized by the number of signatures they verify
     // the signed message: the precommit for (block hash, block number, round, set id) -- decoder.rs:159-200
     uint8_t msg[64];
     memset(msg, 0, sizeof msg);
@@ -656,17 +693,16 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     NEED(justified ? (plen[S + 2] > 0 && plen[S + 3] > 0) : (plen[S + 2] == 0 && plen[S + 3] == 0), "blob carries part of a justification");
     NEED(!authority_set_hash || justified, "blob carries no authority-set commitment proof");
     NEED(!justified || authority_set_hash, "blob carries a justification: the request's authority_set_hash is needed to check it");
-    const int tree_id = max_headers == 256 ? 7 : max_headers == 512 ? 8 : max_headers == 16 ? 9 : 0;
+    const int tree_id = tree_air_id(max_headers);
     NEED(tree_id, "max_headers %u has no Merkle AIR", max_headers);
     // bus order (the order of the shared-challenge transcript): segments, Merkle, commitment, Ed25519, SHA-512
     const size_t n_tab = (size_t)S + (justified ? 4 : 1);
-    std::vector<const uint64_t*> proof(n_tab), ppub(n_tab), pcap(n_tab);
-    std::vector<size_t> pl(n_tab), npub(n_tab);
+    std::vector<BusTable> tab(n_tab);
     for (size_t t = 0; t < n_tab; ++t) {
         const size_t b = t < S ? t : (t == S ? S + 1 : (t == S + 1 ? S : t));  // bus index -> blob index
-        proof[t] = blob + off[b], pl[t] = plen[b];
-        NEED(vx_stark_proof_peek(proof[t], pl[t], cfg->cap_height, &ppub[t], &npub[t], &pcap[t]), "proofs are too short to hold a trace cap");
+        tab[t].proof = blob + off[b], tab[t].len = plen[b];
     }
+    NEED(peek_tables(cfg, tab.data(), n_tab), "proofs are too short to hold a trace cap");
     // public inputs of every table, rebuilt from the request and the claimed outputs.  The hash a segment ends with is read from
     // its own proof and must be the hash the next segment starts from (the reference's reduce step, subchain_verification.rs:
     // 247-257): the first starts at trusted_header_hash / trusted_block + 1, the last ends at target_header_hash / target_block,
@@ -676,17 +712,17 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     uint64_t next_first = (uint64_t)trusted_block + 1;
     for (size_t s = 0; s < S; ++s) {
         uint64_t* pub = spubs.data() + 20 * s;
-        NEED(npub[s] == 20, "a hash-chain segment has %zu public inputs", npub[s]);
+        NEED(tab[s].n_pub == 20, "a hash-chain segment has %zu public inputs", tab[s].n_pub);
         for (int j = 0; j < 8; ++j) {
             uint32_t a;
             memcpy(&a, trusted_hash + 4 * j, 4);
-            pub[j] = s == 0 ? a : ppub[s - 1][8 + j];                        // starts where the previous segment ended
+            pub[j] = s == 0 ? a : tab[s - 1].pub[8 + j];                      // starts where the previous segment ended
             uint32_t b;
             memcpy(&b, out96 + 4 * j, 4);                                     // target_header_hash = first 32 output bytes
-            pub[8 + j] = s + 1 == S ? b : ppub[s][8 + j];                     // an inner boundary: the segment's own claim, bound by the next one
+            pub[8 + j] = s + 1 == S ? b : tab[s].pub[8 + j];                  // an inner boundary: the segment's own claim, bound by the next one
             NEED(pub[8 + j] >> 32 == 0, "a segment hash limb is out of range");
         }
-        const uint64_t last = s + 1 == S ? target_block : ppub[s][17];
+        const uint64_t last = s + 1 == S ? target_block : tab[s].pub[17];
         NEED(last >= next_first && last <= target_block, "the block numbers of the map segments do not run on");
         pub[16] = next_first, pub[17] = last;
         pub[18] = (uint64_t)trusted_block + 1;  // the block of Merkle leaf 0
@@ -694,72 +730,50 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
         next_first = last + 1;
     }
     NEED(next_first == (uint64_t)target_block + 1, "the map segments do not cover the block range");
-    for (int j = 0; j < 16; ++j)  // state_root_merkle_root || data_root_merkle_root as big-endian words
-        tpub[j] = ((uint64_t)out96[32 + 4 * j] << 24) | ((uint64_t)out96[33 + 4 * j] << 16) | ((uint64_t)out96[34 + 4 * j] << 8) | out96[35 + 4 * j];
+    be_limbs(out96 + 32, tpub), be_limbs(out96 + 64, tpub + 8);  // state_root_merkle_root || data_root_merkle_root as big-endian words
     tpub[16] = (uint64_t)target_block - trusted_block;  // the number of headers = of enabled leaves: the Merkle table MUST take every header's roots from the bus
     NEED(tpub[16] <= max_headers, "the block range exceeds max_headers");
-    std::vector<int> air(n_tab, VX_AIR_BLAKE_CHAIN);
-    std::vector<const uint64_t*> want(n_tab);
-    std::vector<size_t> n_want(n_tab, 20);
-    for (size_t s = 0; s < S; ++s) want[s] = spubs.data() + 20 * s;
-    air[S] = tree_id, want[S] = tpub, n_want[S] = 17;
+    for (size_t s = 0; s < S; ++s) tab[s].air = VX_AIR_BLAKE_CHAIN, tab[s].want = spubs.data() + 20 * s, tab[s].n_want = 20;
+    tab[S].air = tree_id, tab[S].want = tpub, tab[S].n_want = 17;
     if (justified) {
         int jair[3];
-        const int32_t rc = vx_justification_expect(ppub[S + 1], npub[S + 1], ppub[S + 2], npub[S + 2], npub[S + 3], authority_set_hash, authority_set_id, out96, target_block, blob[21], cpub, epub,
-                                                   hpub, jair, err, errlen);
+        const int32_t rc = vx_justification_expect(tab[S + 1].pub, tab[S + 1].n_pub, tab[S + 2].pub, tab[S + 2].n_pub, tab[S + 3].n_pub, authority_set_hash, authority_set_id, out96,
+                                                   target_block, blob[21], cpub, epub, hpub, jair, err, errlen);
         if (rc != VX_OK) return rc;
-        air[S + 1] = jair[0], air[S + 2] = jair[1], air[S + 3] = jair[2];
-        want[S + 1] = cpub, want[S + 2] = epub, want[S + 3] = hpub;
-        n_want[S + 1] = 10, n_want[S + 2] = 2, n_want[S + 3] = 15;
-    }
-    // the lookup challenges every proof must have used: a transcript of all public inputs and trace caps
-    uint64_t chal[4];
-    v_shared_challenges_n(ppub.data(), npub.data(), pcap.data(), n_tab, (size_t)4 << cfg->cap_height, chal, 4);
-    uint64_t bus[2] = {0, 0};
-    for (size_t t = 0; t < n_tab; ++t) {
-        const uint64_t* apub = nullptr;
-        int L = 0;
-        const int32_t rc = vx_stark_verify_ext(cfg, proof[t], pl[t], air[t], want[t], n_want[t], chal, &apub, &L, err, errlen);
-        if (rc != VX_OK) return rc;
-        for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));  // a table publishes its total / rows
+        const uint64_t* jwant[3] = {cpub, epub, hpub};
+        const size_t jn[3] = {10, 2, 15};
+        for (int q = 0; q < 3; ++q) tab[S + 1 + q].air = jair[q], tab[S + 1 + q].want = jwant[q], tab[S + 1 + q].n_want = jn[q];
     }
     // the bus closes: state roots and data roots of the hashed headers = the leaves of the Merkle trees; the keys of the signed
     // authorities = the keys the signatures verify under; R || A and H between the curve table and the SHA-512 table
-    NEED(bus[0] == 0 && bus[1] == 0, "the lookup bus between the tables does not balance");
-    return VX_OK;
+    return verify_bus_group(cfg, tab.data(), n_tab, "the lookup bus between the tables does not balance", err, errlen);
 }
 
-// RotateCircuit verify (the prover is vx_rotate.hip; every host verifier lives in this file, which holds no GPU code): the blob must
-// be for this (authority_set_id, authority_set_hash) request and claim out32; then its six STARKs are verified in their two
-// shared-challenge groups against the public inputs those values imply, and both buses must balance.
+// RotateCircuit verify (the provers are vx_rotate.hip and, for the verifier above, vx_header_range.hip; every host verifier lives
+// in this file, which holds no GPU code): the blob must be for this (authority_set_id, authority_set_hash) request and claim out32;
+// then its six STARKs are verified in their two shared-challenge groups against the public inputs those values imply, and both
+// buses must balance.
 int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint64_t authority_set_id,
                          const uint8_t authority_set_hash[32], const uint8_t out32[32], char* err, size_t errlen) {
     if (!cfg || !blob || !authority_set_hash || !out32) return VX_ERR_ARG;
-    auto bad = [&](const char* why) {
-        if (err && errlen) snprintf(err, errlen, "%s", why);
-        return (int32_t)VX_ERR_STATEMENT;
-    };
-    if (len <= VX_ROT_HDR || blob[0] != VX_ROT_MAGIC) return bad("bad rotate blob");
-    if (blob[1] != authority_set_id || memcmp(blob + 8, authority_set_hash, 32) != 0) return bad("blob is for a different request");
-    if (memcmp(blob + 12, out32, 32) != 0) return bad("public output differs from the blob");
+    NEED(len > VX_ROT_HDR && blob[0] == VX_ROT_MAGIC, "bad rotate blob");
+    NEED(blob[1] == authority_set_id && memcmp(blob + 8, authority_set_hash, 32) == 0, "blob is for a different request");
+    NEED(memcmp(blob + 12, out32, 32) == 0, "public output differs from the blob");
     const size_t l0 = blob[16], l1 = blob[17], l2 = blob[18], l3 = blob[19], l4 = blob[24], l5 = blob[27];
-    if (l0 > len || l1 > len || l2 > len || l3 > len || l4 > len || l5 > len || VX_ROT_HDR + l0 + l1 + l2 + l3 + l4 + l5 != len) return bad("blob lengths are inconsistent");
-    if (blob[2] >> 32 || blob[26] >= VX_MAX_HEADER_SIZE || blob[3] == 0 || blob[3] > 510) return bad("block number, start position or authority count out of range");
+    NEED(l0 <= len && l1 <= len && l2 <= len && l3 <= len && l4 <= len && l5 <= len && VX_ROT_HDR + l0 + l1 + l2 + l3 + l4 + l5 == len, "blob lengths are inconsistent");
+    NEED(!(blob[2] >> 32) && blob[26] < VX_MAX_HEADER_SIZE && blob[3] != 0 && blob[3] <= 510, "block number, start position or authority count out of range");
     const uint64_t* p0 = blob + VX_ROT_HDR;
-    int32_t rc;
     // Bus B: the Blake2b table (a chain of exactly one header, numbered epoch_end_block, hashing to the blob's header hash; the anchor
     // is the parent hash the header itself carries -- free in this statement) sends the bytes from start_position + 1 on; the
     // epoch-end table reads the ScheduledChange log of blob[3] authorities there and sends its keys; the new set's commitment table
     // receives every key and hashes to out32.
     {
-        const uint64_t* proof[3] = {p0, p0 + l0 + l1 + l2 + l3 + l4, p0 + l0 + l1};
-        const size_t pl[3] = {l0, l5, l2};
-        const int air[3] = {VX_AIR_BLAKE_CHAIN, VX_AIR_EPOCH_END, VX_AIR_SHA_CHAIN};
-        const uint64_t *ppub[3], *pcap[3];
-        size_t npub[3];
-        for (int t = 0; t < 3; ++t)
-            if (!vx_stark_proof_peek(proof[t], pl[t], cfg->cap_height, &ppub[t], &npub[t], &pcap[t])) return bad("epoch-end proofs are too short to hold a trace cap");
         uint64_t bpub[20], epub[10], spub[10];
+        BusTable tab[3] = {{p0, l0}, {p0 + l0 + l1 + l2 + l3 + l4, l5}, {p0 + l0 + l1, l2}};
+        tab[0].air = VX_AIR_BLAKE_CHAIN, tab[0].want = bpub, tab[0].n_want = 20;
+        tab[1].air = VX_AIR_EPOCH_END, tab[1].want = epub, tab[1].n_want = 10;
+        tab[2].air = VX_AIR_SHA_CHAIN, tab[2].want = spub, tab[2].n_want = 10;
+        NEED(peek_tables(cfg, tab, 3), "epoch-end proofs are too short to hold a trace cap");
         for (int j = 0; j < 8; ++j) {
             uint32_t a, b;
             memcpy(&a, (const uint8_t*)(blob + 20) + 4 * j, 4);
@@ -770,62 +784,35 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
         bpub[16] = bpub[17] = blob[2];
         bpub[18] = blob[26] + 1, bpub[19] = 2;  // window mode: the bytes behind start_position
         // the byte lengths of the log's two compact ints are the prover's to state (one-hot); the table's constraints tie them to the bytes
-        if (npub[1] != 10) return bad("epoch-end proof is malformed");
+        NEED(tab[1].n_pub == 10, "epoch-end proof is malformed");
         epub[0] = blob[3], epub[1] = 1;
         for (int g = 0; g < 2; ++g) {
             uint64_t sum = 0;
             for (int a = 0; a < 4; ++a) {
-                const uint64_t f = ppub[1][2 + 4 * g + a];
-                if (f > 1) return bad("epoch-end proof: length flags are not one-hot");
+                const uint64_t f = tab[1].pub[2 + 4 * g + a];
+                NEED(f <= 1, "epoch-end proof: length flags are not one-hot");
                 epub[2 + 4 * g + a] = f, sum += f;
             }
-            if (sum != 1) return bad("epoch-end proof: length flags are not one-hot");
+            NEED(sum == 1, "epoch-end proof: length flags are not one-hot");
         }
         be_limbs(out32, spub);
         spub[8] = blob[3], spub[9] = 2;  // receives every key
-        uint64_t chal[4];
-        vx_shared_challenges_host(ppub, npub, pcap, 3, (size_t)4 << cfg->cap_height, chal, 4);
-        const uint64_t* want[3] = {bpub, epub, spub};
-        const size_t n_want[3] = {20, 10, 10};
-        uint64_t bus[2] = {0, 0};
-        for (int t = 0; t < 3; ++t) {
-            const uint64_t* apub = nullptr;
-            int L = 0;
-            rc = vx_stark_verify_ext(cfg, proof[t], pl[t], air[t], want[t], n_want[t], chal, &apub, &L, err, errlen);
-            if (rc != VX_OK) return rc;
-            for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
-        }
-        if (bus[0] || bus[1]) return bad("the lookup bus between the header hash, the epoch-end table and the new set does not balance");
+        const int32_t rc = verify_bus_group(cfg, tab, 3, "the lookup bus between the header hash, the epoch-end table and the new set does not balance", err, errlen);
+        if (rc != VX_OK) return rc;
     }
     // the justification by the current set: commitment, Ed25519 and SHA-512 tables under shared lookup challenges; the signed
     // message is the precommit for (the proven header hash, the block number, the round, the request's set id)
-    {
-        const uint64_t* proof[3] = {p0 + l0, p0 + l0 + l1 + l2, p0 + l0 + l1 + l2 + l3};
-        const size_t pl[3] = {l1, l3, l4};
-        const uint64_t *ppub[3], *pcap[3];
-        size_t npub[3];
-        for (int t = 0; t < 3; ++t)
-            if (!vx_stark_proof_peek(proof[t], pl[t], cfg->cap_height, &ppub[t], &npub[t], &pcap[t])) return bad("justification proofs are too short to hold a trace cap");
-        uint64_t spub[10], epub[2], hpub[15];
-        int air[3];
-        rc = vx_justification_expect(ppub[0], npub[0], ppub[1], npub[1], npub[2], authority_set_hash, authority_set_id, (const uint8_t*)(blob + 4), (uint32_t)blob[2], blob[25],
-                                     spub, epub, hpub, air, err, errlen);
-        if (rc != VX_OK) return rc;
-        uint64_t chal[4];
-        vx_shared_challenges_host(ppub, npub, pcap, 3, (size_t)4 << cfg->cap_height, chal, 4);
-        const uint64_t* want[3] = {spub, epub, hpub};
-        const size_t n_want[3] = {10, 2, 15};
-        uint64_t bus[2] = {0, 0};
-        for (int t = 0; t < 3; ++t) {
-            const uint64_t* apub = nullptr;
-            int L = 0;
-            rc = vx_stark_verify_ext(cfg, proof[t], pl[t], air[t], want[t], n_want[t], chal, &apub, &L, err, errlen);
-            if (rc != VX_OK) return rc;
-            for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
-        }
-        if (bus[0] || bus[1]) return bad("the lookup bus between the justification tables does not balance");
-    }
-    return VX_OK;
+    uint64_t spub[10], epub[2], hpub[15];
+    int air[3];
+    BusTable tab[3] = {{p0 + l0, l1}, {p0 + l0 + l1 + l2, l3}, {p0 + l0 + l1 + l2 + l3, l4}};
+    NEED(peek_tables(cfg, tab, 3), "justification proofs are too short to hold a trace cap");
+    const int32_t rc = vx_justification_expect(tab[0].pub, tab[0].n_pub, tab[1].pub, tab[1].n_pub, tab[2].n_pub, authority_set_hash, authority_set_id, (const uint8_t*)(blob + 4),
+                                               (uint32_t)blob[2], blob[25], spub, epub, hpub, air, err, errlen);
+    if (rc != VX_OK) return rc;
+    tab[0].air = air[0], tab[0].want = spub, tab[0].n_want = 10;
+    tab[1].air = air[1], tab[1].want = epub, tab[1].n_want = 2;
+    tab[2].air = air[2], tab[2].want = hpub, tab[2].n_want = 15;
+    return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen);
 }
 
 }
