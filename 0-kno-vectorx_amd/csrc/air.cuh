@@ -27,10 +27,15 @@
 #include <stdint.h>
 
 #include <type_traits>
+#include <vector>
 
+#include "air_bus.cuh"
 #include "gl.cuh"
 
-#define VX_HD __host__ __device__ __forceinline__
+// the witness generator of an AIR's auxiliary round: trace + challenges -> auxiliary columns [AUX][n] (+ 2*AUXPUB published words, host).
+// Every AIR names its own as `gen_aux` (nullptr exactly when AUX = 0); the registry (air_list.h) reads it from the type.
+struct vx_ctx;
+typedef int32_t (*gen_aux_fn)(vx_ctx*, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
 
 // Device base-field element, R LDE points per lane (rows i, i + 256, ... of the block's tile).  R > 1 gives every
 // load R independent streams per lane (the kernel is bound by load latency -- each column lives in its own pages --
@@ -242,6 +247,8 @@ struct RowViewN {  // column-major LDE, rows i[0..R) of it
 struct FibAir {
     static constexpr int ID = 1, COLS = 2, PUB = 3, PERIODIC = 0, PERIOD_LOG = 0, QUOT_ROWS_PER_LANE = 1, AUX = 0, CHAL = 0, AUXPUB = 0, EXACT_LOG = 0;
     static constexpr int plog(int) { return 0; }
+    static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
+    static constexpr gen_aux_fn gen_aux = nullptr;
     template <class F, class Row, class C>
     VX_HD static void eval(const Row& loc, const Row& nxt, const F*, const F* pub, const F*, const F*, C& c) {
         c.first_row(loc[0] - pub[0]);
@@ -260,6 +267,8 @@ struct FibAir {
 struct MixAir {
     static constexpr int ID = 2, COLS = 4, PUB = 2, PERIODIC = 2, PERIOD_LOG = 2, QUOT_ROWS_PER_LANE = 2, AUX = 0, CHAL = 0, AUXPUB = 0, EXACT_LOG = 0;
     static constexpr int plog(int) { return 2; }
+    static void periodic_values(std::vector<uint64_t>& v) { v = {0, 0, 0, 1, 3, 5, 7, 11}; }
+    static constexpr gen_aux_fn gen_aux = nullptr;
     template <class F, class Row, class C>
     VX_HD static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F*, const F*, C& c) {
         F a = loc[0], b = loc[1], cc = loc[2], d = loc[3];
@@ -281,11 +290,15 @@ struct MixAir {
 struct LookupAir {
     static constexpr int ID = 5, COLS = 7, PUB = 0, PERIODIC = 3, PERIOD_LOG = 8, QUOT_ROWS_PER_LANE = 1, AUX = 6, CHAL = 4, AUXPUB = 0, EXACT_LOG = 0;
     static constexpr int plog(int) { return 8; }
+    static void periodic_values(std::vector<uint64_t>& v) {
+        v.resize(3 * 256);
+        for (int i = 0; i < 256; ++i) v[i] = i & 15, v[256 + i] = i >> 4, v[512 + i] = (i & 15) ^ (i >> 4);
+    }
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     template <class F, class Row, class C>
     VX_HD static void eval(const Row& loc, const Row& nxt, const F* per, const F*, const F* chal, const F*, C& c) {
-        const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma;
-        auto fp = [&](const F& a, const F& b, const F& cc) { return beta + a + gamma * b + g2 * cc; };
-        const X2<F> d0 = fp(loc[0], loc[1], loc[2]), d1 = fp(loc[3], loc[4], loc[5]), dt = fp(per[0], per[1], per[2]);
+        const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
+        const X2<F> d0 = bus.xor_row(loc[0], loc[1], loc[2]), d1 = bus.xor_row(loc[3], loc[4], loc[5]), dt = bus.xor_row(per[0], per[1], per[2]);
         const X2<F> h{loc[7], loc[8]}, ht{loc[9], loc[10]}, z{loc[11], loc[12]}, zn{nxt[11], nxt[12]};
         c.constraint_x2(h * d0 * d1 - d0 - d1);
         c.constraint_x2(ht * dt - loc[6]);

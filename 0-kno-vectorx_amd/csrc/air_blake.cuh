@@ -21,6 +21,7 @@
 // Constraint ORDER is protocol: oracle/blake_air.py restates it independently.
 #pragma once
 #include <type_traits>
+#include <vector>
 
 #include "air.cuh"
 #include "blake_tables.h"
@@ -35,8 +36,6 @@ constexpr int TB0 = 680, IB0 = 712, MK0 = 720, CNT = 728, M1 = 729, M2 = 730, SZ
 constexpr int MDF0 = 740, MDF1 = 741, MDF3 = 742, KOF = 743, TR = 744, COLS = 745;
 // helper elements: 128 of the G functions, 4 message-byte range checks, 4 root byte sends, the table helper, the running sum
 constexpr int N_HELP = 138, HM0 = 128, HB0 = 132, HT = 136, ZZ = 137, AUX = 2 * N_HELP, TABLE_LOG = 16;
-// bus tuples are (t0, t1, t2, t3, tag): fingerprint t0 + g t1 + g^2 t2 + g^3 t3 + g^4 tag
-constexpr int TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3;
 VX_HD constexpr int GC(int k, int slot, int j) { return (k * 9 + slot) * 8 + j; }
 VX_HD constexpr int CAR(int k, int q) { return CAR0 + 4 * k + q; }
 VX_HD constexpr int MS(int s, int h) { return MS0 + 2 * s + h; }
@@ -91,6 +90,15 @@ VX_HD F limb4(const F& b0, const F& b1, const F& b2, const F& b3) {
 struct BlakeAir {
     static constexpr int ID = 6, COLS = blk::COLS, PUB = 20, PERIODIC = 20, PERIOD_LOG = 16, QUOT_ROWS_PER_LANE = VX_BLAKE_QR, AUX = blk::AUX, CHAL = 4, AUXPUB = 1, EXACT_LOG = 0;
     static constexpr int plog(int q) { return q < 16 ? 4 : 16; }
+    static void periodic_values(std::vector<uint64_t>& v) {
+        v.assign(16 * 16 + 4 * 65536, 0);
+        for (int k = 0; k < 16; ++k) v[k * 16 + k] = 1;  // sel_k: one-hot on row k of every 16-row block
+        for (uint64_t i = 0; i < 65536; ++i) {           // the XOR tables: row i = (a = i & 255, b = i >> 8)
+            const uint64_t a = i & 255, b = i >> 8;
+            v[256 + i] = a, v[256 + 65536 + i] = b, v[256 + 2 * 65536 + i] = (a ^ b) & 127, v[256 + 3 * 65536 + i] = (a ^ b) >> 7;
+        }
+    }
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
 
     template <class F, class Row, class C>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, C& c) {
@@ -365,15 +373,15 @@ struct BlakeAir {
         c.last_row(loc[NUM] - pub[17]);
         // ---- 10. lookups (logUp): helpers live in the next row, the table side in the local row, Z closes cyclically
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g3 = g2 * gamma, g4 = g2 * g2;
-            const X2<F> bt2 = beta + g4;  // table-2 tuples carry the tag gamma^4
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
+            const X2<F> bt2 = bus.t2_base();  // table-2 tuples carry the tag gamma^4
             const F m3 = g_on + sel[12] + sel[13];
             // denominator beta + fingerprint of lookup i (a byte position) of group grp of G number k
             auto denom = [&](int k, int grp, int i) -> X2<F> {
-                if (grp == 0) return beta + in_byte(k, 3, i) + gamma * nxt[GC(k, S_A1, i)] + g2 * nxt[GC(k, S_D1, (i + 4) & 7)];
-                if (grp == 1) return beta + in_byte(k, 1, i) + gamma * nxt[GC(k, S_C1, i)] + g2 * nxt[GC(k, S_B1, (i + 5) & 7)];
-                if (grp == 2) return beta + nxt[GC(k, S_D1, i)] + gamma * nxt[GC(k, S_A2, i)] + g2 * nxt[GC(k, S_D2, (i + 6) & 7)];
-                return bt2 + nxt[GC(k, S_B1, i)] + gamma * nxt[GC(k, S_C2, i)] + g2 * nxt[GC(k, S_L, i)] + g3 * nxt[GC(k, S_T, i)];
+                if (grp == 0) return bus.xor_row(in_byte(k, 3, i), nxt[GC(k, S_A1, i)], nxt[GC(k, S_D1, (i + 4) & 7)]);
+                if (grp == 1) return bus.xor_row(in_byte(k, 1, i), nxt[GC(k, S_C1, i)], nxt[GC(k, S_B1, (i + 5) & 7)]);
+                if (grp == 2) return bus.xor_row(nxt[GC(k, S_D1, i)], nxt[GC(k, S_A2, i)], nxt[GC(k, S_D2, (i + 6) & 7)]);
+                return bus.t2_row(bt2, nxt[GC(k, S_B1, i)], nxt[GC(k, S_C2, i)], nxt[GC(k, S_L, i)], nxt[GC(k, S_T, i)]);
             };
             X2<F> hsum{F::from(0), F::from(0)};
 #pragma unroll 1
@@ -393,7 +401,7 @@ struct BlakeAir {
             for (int pair = 0; pair < 4; ++pair) {
                 const int e = HM0 + pair;
                 const F b0 = nxt[MB0 + 2 * pair], b1 = nxt[MB0 + 2 * pair + 1];
-                const X2<F> du = beta + b0 + g2 * b0, dv = beta + b1 + g2 * b1;
+                const X2<F> du = bus.xor_row(b0, bus::None{}, b0), dv = bus.xor_row(b1, bus::None{}, b1);
                 const X2<F> h{nxt[AX(e, 0)], nxt[AX(e, 1)]};
                 c.constraint_x2(h * du * dv - (du + dv));
                 hsum = hsum + h;
@@ -408,20 +416,20 @@ struct BlakeAir {
                 const F is1 = pub[19] * (two - pub[19]);  // [mode = 1]
                 const F leaf = nxt[NUM] - (pub[16] + is1 * (pub[18] - pub[16])), bus_on = pub[19] * (F::from(3) - pub[19]) * F::from(0x7FFFFFFF80000001ULL);  // m (3 - m) / 2: 0 = a stand-alone proof
                 const F pos0 = nxt[T] - nxt[INC] + r8n - nxt[KOF];
-                const X2<F> base = beta + leaf + g3 * nxt[TR] + g4 * F::from(TAG_BYTE);
+                const X2<F> base = bus.byte_base(leaf, nxt[TR]);
                 const F live = nxt[ACT] * bus_on;  // an inactive (padding / junk) message shares its block number with the last real header: it must not send
 #pragma unroll 1
                 for (int pair = 0; pair < 4; ++pair) {
                     const int e = HB0 + pair, b0 = 2 * pair, b1 = b0 + 1;
-                    const X2<F> du = base + gamma * (pos0 + F::from(b0)) + g2 * nxt[MB0 + b0], dv = base + gamma * (pos0 + F::from(b1)) + g2 * nxt[MB0 + b1];
+                    const X2<F> du = bus.byte(base, pos0 + F::from(b0), nxt[MB0 + b0]), dv = bus.byte(base, pos0 + F::from(b1), nxt[MB0 + b1]);
                     const X2<F> h{nxt[AX(e, 0)], nxt[AX(e, 1)]};
                     c.constraint_x2(h * du * dv - dv * (nxt[E0 + b0] * live) - du * (nxt[E0 + b1] * live));
                     hsum = hsum + h;
                 }
             }
             const F ta = per[16], tb_ = per[17], tl = per[18], tt = per[19];
-            const X2<F> dt1 = beta + ta + gamma * tb_ + g2 * (tl + tt * F::from(128));
-            const X2<F> dt2 = bt2 + ta + gamma * tb_ + g2 * tl + g3 * tt;
+            const X2<F> dt1 = bus.xor_row(ta, tb_, tl + tt * F::from(128));
+            const X2<F> dt2 = bus.t2_row(bt2, ta, tb_, tl, tt);
             const X2<F> ht{loc[AX(HT, 0)], loc[AX(HT, 1)]};
             c.constraint_x2(ht * dt1 * dt2 - dt2 * loc[M1] - dt1 * loc[M2]);
             const X2<F> z{loc[AX(ZZ, 0)], loc[AX(ZZ, 1)]}, zn{nxt[AX(ZZ, 0)], nxt[AX(ZZ, 1)]};

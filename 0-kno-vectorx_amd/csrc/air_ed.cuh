@@ -24,7 +24,6 @@ constexpr int NG = 14, CELLS = NG * 48;
 constexpr int XA0 = 672, YA0 = 688, NT0 = 704, X30 = 720, Y30 = 736, BT0 = 752, HR0 = 768, SEL0 = 784;
 constexpr int BS = 832, BH = 833, LAH = 834, SG = 835, CNT = 836, MULT = 837, AIDX = 838, COLS = 839;
 constexpr int N_RANGE = CELLS / 2, N_BUS = 6, HB0 = N_RANGE, HT = N_RANGE + N_BUS, ZZ = HT + 1, N_HELP = ZZ + 1, AUX = 2 * N_HELP;
-constexpr int TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7;
 enum { P_S0N, P_S1N, P_STN, P_FINN, P_KEEP, P_STEP, P_LST, P_R0, P_R1, P_R255, P_LE0, P_SLOT = 26, P_T = 27, N_PERIODIC = 28 };
 VX_HD constexpr int C(int g, int k) { return g * 48 + k; }
 VX_HD constexpr int RL(int g, int k) { return g * 48 + 16 + k; }
@@ -75,11 +74,14 @@ __host__ __device__ __attribute__((noinline)) void fold16(const F* a, const F* b
 }
 }  // namespace edc
 
+int32_t vx_ed_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_ed_air.hip
+
 template <int LOGN, int ID_>
 struct EdAirT {
     static constexpr int ID = ID_, COLS = edc::COLS, PUB = 2, PERIODIC = edc::N_PERIODIC, PERIOD_LOG = LOGN, QUOT_ROWS_PER_LANE = 1, AUX = edc::AUX, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int plog(int q) { return q < edc::P_SLOT ? 8 : (q == edc::P_SLOT ? LOGN : 16); }
 
+    static constexpr gen_aux_fn gen_aux = vx_ed_air_gen_aux;
     static void periodic_values(std::vector<uint64_t>& v) {
         using namespace edc;
         const size_t n = (size_t)1 << LOGN;
@@ -347,13 +349,13 @@ struct EdAirT {
         c.last_row(loc[CNT] - pub[0]);
         // ---- 8. lookups of the local row: 672 range checks, 6 bus lookups, the table, the running sum
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g3 = g2 * gamma, g4 = g2 * g2;
-            const X2<F> br = beta + g4 * F::from(TAG_R16);
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
+            const X2<F> br = bus.r16_base();
             X2<F> hsum{zero, zero};
 #pragma unroll 1
             for (int e = 0; e < N_RANGE; ++e) {
                 const X2<F> h{loc[AX(e, 0)], loc[AX(e, 1)]};
-                const X2<F> du = br + loc[2 * e], dv = br + loc[2 * e + 1];
+                const X2<F> du = bus.r16(br, loc[2 * e]), dv = bus.r16(br, loc[2 * e + 1]);
                 c.constraint_x2(h * du * dv - du - dv);
                 hsum = hsum + h;
             }
@@ -370,13 +372,15 @@ struct EdAirT {
             auto p3 = [&](auto&& f, int i) -> F { return f(i) + f(i + 1) * k16 + f(i + 2) * k32; };
             auto p2 = [&](auto&& f, int i) -> F { return f(i) + f(i + 1) * k16; };
             const F slot8 = per[P_SLOT] * F::from(8);
+            // a row is one of up to three kinds at once, picked by its selectors: the slots and the tag are the selector-weighted
+            // sums of bus.key / bus.ed_msg / bus.ed_digest messages
 #pragma unroll 1
             for (int b = 0; b < 4; ++b) {
                 const F m = on * (zero - r0 - r1);
-                const F tag = r0 * F::from(TAG_KEY) + r1 * F::from(TAG_EDH);
+                const F tag = r0 * F::from(bus::TAG_KEY) + r1 * F::from(bus::TAG_EDH);
                 const F t0 = r0 * (loc[AIDX] * F::from(4) + F::from((uint64_t)b)) + r1 * (slot8 + F::from((uint64_t)b));
                 const F u1 = r0 * p2(enc_a, 4 * b) + r1 * dh(3 * b), u2 = r0 * p2(enc_a, 4 * b + 2) + r1 * dh(3 * b + 1), u3 = r1 * dh(3 * b + 2);
-                const X2<F> d = beta + t0 + gamma * u1 + g2 * u2 + g3 * u3 + g4 * tag;
+                const X2<F> d = bus.denom(bus.beta, t0, u1, u2, u3, tag);
                 const X2<F> h{loc[AX(HB0 + b, 0)], loc[AX(HB0 + b, 1)]};
                 c.constraint_x2(h * d - m);
                 hsum = hsum + h;
@@ -384,18 +388,18 @@ struct EdAirT {
 #pragma unroll 1
             for (int b = 4; b < 6; ++b) {
                 const F m = on * (r0 + r255 - r1);
-                const F tag = (r0 + r255) * F::from(TAG_EDMSG) + r1 * F::from(TAG_EDH);
+                const F tag = (r0 + r255) * F::from(bus::TAG_EDMSG) + r1 * F::from(bus::TAG_EDH);
                 const F t0 = r0 * (slot4 + F::from((uint64_t)(b - 2))) + r255 * (slot4 + F::from((uint64_t)(b - 4))) + r1 * (slot8 + F::from((uint64_t)b));
                 const int o = 8 * (b - 4);
                 const F u1 = r0 * p3(enc_a, o) + r255 * p3(enc_r, o) + r1 * dh(3 * b), u2 = r0 * p3(enc_a, o + 3) + r255 * p3(enc_r, o + 3) + r1 * dh(3 * b + 1);
                 const F u3 = r0 * p2(enc_a, o + 6) + r255 * p2(enc_r, o + 6) + r1 * dh(3 * b + 2);
-                const X2<F> d = beta + t0 + gamma * u1 + g2 * u2 + g3 * u3 + g4 * tag;
+                const X2<F> d = bus.denom(bus.beta, t0, u1, u2, u3, tag);
                 const X2<F> h{loc[AX(HB0 + b, 0)], loc[AX(HB0 + b, 1)]};
                 c.constraint_x2(h * d - m);
                 hsum = hsum + h;
             }
             const X2<F> ht{loc[AX(HT, 0)], loc[AX(HT, 1)]};
-            c.constraint_x2(ht * (br + per[P_T]) - loc[MULT]);
+            c.constraint_x2(ht * bus.r16(br, per[P_T]) - loc[MULT]);
             const X2<F> z{loc[AX(ZZ, 0)], loc[AX(ZZ, 1)]}, zn{nxt[AX(ZZ, 0)], nxt[AX(ZZ, 1)]};
             c.constraint_x2(zn - z - hsum + ht + X2<F>{apub[0], apub[1]});
         }

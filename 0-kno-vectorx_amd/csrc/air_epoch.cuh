@@ -12,8 +12,6 @@
 #include <vector>
 
 #include "air.cuh"
-#include "air_blake.cuh"
-#include "air_ed.cuh"
 
 namespace epo {
 constexpr int LOG_N = 9, NB = 44, V = 44, DL = 45, Q0 = 46, COLS = 52, N_HELP = 23, AUX = 2 * N_HELP;
@@ -23,6 +21,7 @@ VX_HD constexpr int len_of(int a) { return a == 0 ? 1 : a == 1 ? 2 : a == 2 ? 4 
 struct EpochEndAir {
     static constexpr int ID = 15, COLS = epo::COLS, PUB = 10, PERIODIC = 2, PERIOD_LOG = epo::LOG_N, QUOT_ROWS_PER_LANE = 1, AUX = epo::AUX, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int plog(int) { return epo::LOG_N; }
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) {
         const size_t n = (size_t)1 << epo::LOG_N;
         v.assign(2 * n, 0);
@@ -91,12 +90,12 @@ struct EpochEndAir {
         }
         // ---- 4. the bus: 40 byte receives, 4 key sends, two lookups per helper
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g3 = g2 * gamma, g4 = g2 * g2;
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
             F l1len = zero, l2len = zero;
 #pragma unroll 1
             for (int a = 0; a < 4; ++a) l1len = l1len + l1[a] * F::from((uint64_t)len_of(a)), l2len = l2len + l2[a] * F::from((uint64_t)len_of(a));
             const F plen = l1len + l2len + F::from(6), kbase = (one - r0) * plen + rec * F::from(40);
-            const X2<F> bbase = beta + g3 + g4 * F::from(blk::TAG_BYTE);  // (0, k, byte, tree 1)
+            const X2<F> bbase = bus.byte_base(bus::None{}, bus::K<1>{});  // (0, k, byte, tree 1)
             auto m_byte = [&](int j) -> F {
                 F pm = zero;  // [j < P] on the prefix row
 #pragma unroll 1
@@ -108,11 +107,11 @@ struct EpochEndAir {
                 if (j < 4) m = m + dl;
                 return zero - m * on;
             };
-            auto d_byte = [&](int j) -> X2<F> { return bbase + gamma * (kbase + F::from((uint64_t)j)) + g2 * loc[j]; };
+            auto d_byte = [&](int j) -> X2<F> { return bus.byte(bbase, kbase + F::from((uint64_t)j), loc[j]); };
             auto d_key = [&](int q) -> X2<F> {
                 const F la = loc[8 * q] + loc[8 * q + 1] * k8 + (loc[8 * q + 2] + loc[8 * q + 3] * k8) * k16;
                 const F lb = loc[8 * q + 4] + loc[8 * q + 5] * k8 + (loc[8 * q + 6] + loc[8 * q + 7] * k8) * k16;
-                return beta + (rec * F::from(4) + F::from((uint64_t)q)) + gamma * la + g2 * lb + g4 * F::from(edc::TAG_KEY);
+                return bus.key(rec * F::from(4) + F::from((uint64_t)q), la, lb);
             };
             X2<F> hsum{zero, zero};
 #pragma unroll 1

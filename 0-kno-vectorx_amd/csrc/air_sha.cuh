@@ -29,7 +29,7 @@ constexpr int W0B = 258, W1B = 290, W14B = 322, WV0 = 354, WV15 = 366;
 constexpr int SV = 367;  // sigma0(W[1]) + sigma1(W[14]), a value below 2^33
 constexpr int CE0 = 368, CA0 = 371, CW0 = 374, FFV0 = 376, FFC0 = 384, HIN0 = 392, DG0 = 400;
 constexpr int T_FIRST = 408, T_DATA = 409, T_PAD = 410, T_IDLE = 411, COLS = 412;  // COLS: the compression layout every SHA-256 table shares
-constexpr int SGC = 412, KC = 413, CHAIN_COLS = 414, TAG_KEY = 5;                    // ShaChainAir only
+constexpr int SGC = 412, KC = 413, CHAIN_COLS = 414;                   // ShaChainAir only
 VX_HD constexpr int WV(int p) { return p == 15 ? WV15 : WV0 + p - 2; }  // value column of window position p (2..13, 15)
 VX_HD constexpr int st_bits(int wd) { return wd == 0 ? A_ : wd == 1 ? B_ : wd == 2 ? C_ : wd == 4 ? E_ : wd == 5 ? F_ : wd == 6 ? G_ : -1; }
 #define SHC_IV_INIT {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19}
@@ -172,6 +172,7 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
 struct ShaAir {
     static constexpr int ID = 4, COLS = shc::CHAIN_COLS, PUB = 10, PERIODIC = 7, PERIOD_LOG = 6, QUOT_ROWS_PER_LANE = 1, AUX = 4, CHAL = 4, AUXPUB = 1, EXACT_LOG = 0;
     static constexpr int plog(int) { return 6; }
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) {
         v.assign(7 * 64, 0);
         v[0] = 1;                                      // sel_0
@@ -240,7 +241,7 @@ struct ShaAir {
         c.last_row(kc - pub[8]);
         // ---- 12. the bus: signed keys go to EdAir
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g4 = g2 * g2;
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
             const F k8 = F::from(256), k16 = F::from(65536);
             auto limbs = [&](int col0) -> F {  // bytes b0 b1 b2 b3 of the big-endian word: (b0 + 256 b1) + 2^16 (b2 + 256 b3)
                 return val(loc, col0 + 24, 8) + val(loc, col0 + 16, 8) * k8 + (val(loc, col0 + 8, 8) + val(loc, col0, 8) * k8) * k16;
@@ -248,7 +249,7 @@ struct ShaAir {
             // public input 9 = bus mode: 0 nothing, 1 SEND the flagged keys (to EdAir), 2 RECEIVE every key (from the epoch-end table)
             const F mode = pub[9], inv2 = F::from(0x7FFFFFFF80000001ULL), on = mode * (F::from(3) - mode) * inv2, rcv = mode * (mode - one) * inv2;
             const F m = on * (per[4] * loc[T_FIRST] + per[5] * tdata) * (sgc * (one - rcv) - rcv);
-            const X2<F> d = beta + ((kc - one) * F::from(4) + per[6]) + gamma * limbs(W0B) + g2 * limbs(W1B) + g4 * F::from(TAG_KEY);
+            const X2<F> d = bus.key((kc - one) * F::from(4) + per[6], limbs(W0B), limbs(W1B));
             const X2<F> h{loc[CHAIN_COLS], loc[CHAIN_COLS + 1]}, z{loc[CHAIN_COLS + 2], loc[CHAIN_COLS + 3]}, zn{nxt[CHAIN_COLS + 2], nxt[CHAIN_COLS + 3]};
             c.constraint_x2(h * d - m);
             c.constraint_x2(zn - z - h + X2<F>{apub[0], apub[1]});

@@ -16,7 +16,6 @@
 #include <vector>
 
 #include "air.cuh"
-#include "air_ed.cuh"
 #include "ed25519_constants.h"
 
 namespace s5 {
@@ -41,10 +40,13 @@ VX_HD uint64_t iv(int i) { return IV_H[i]; }
 VX_HD constexpr uint64_t pad2(int p) { return p == 15 ? 8 * (64 + MSG_LEN) : 0; }  // block 2 of a 117-byte message
 }  // namespace s5
 
+int32_t vx_sha512_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_sha512_air.hip
+
 template <int LOGN, int ID_>
 struct Sha512AirT {
     static constexpr int ID = ID_, COLS = s5::COLS, PUB = 15, PERIODIC = s5::N_PERIODIC, PERIOD_LOG = LOGN, QUOT_ROWS_PER_LANE = 1, AUX = 4, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int plog(int) { return LOGN; }
+    static constexpr gen_aux_fn gen_aux = vx_sha512_air_gen_aux;
     static constexpr size_t max_slots() { return ((size_t)1 << LOGN) / s5::SLOT_ROWS; }
 
     static void periodic_values(std::vector<uint64_t>& v) {
@@ -236,7 +238,7 @@ struct Sha512AirT {
         // ---- 10. the bus: receive rows take 8 limbs of the words at window positions 0 and 1 (limb j of a word = bytes 2j, 2j+1
         // of its big-endian byte string, little-endian); send row j gives the feed-forward halves 3j, 3j+1, 3j+2
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g3 = g2 * gamma, g4 = g2 * g2;
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
             const F k8 = F::from(256), k16 = F::from(65536), k32 = F::from(1ULL << 32), rcv = per[P_RCV];
             auto limb = [&](int q) -> F {  // q = 0..7: limbs of W0 then W1
                 const int col0 = (q < 4 ? W0B : W1B), j = q & 3;
@@ -252,8 +254,9 @@ struct Sha512AirT {
 #pragma unroll 1
             for (int j = 0; j < 6; ++j) snd = snd + per[P_SD0 + j];
             const F m = loc[SGF] * pub[14] * (snd - rcv);
-            const F tag = snd * F::from(edc::TAG_EDH) + rcv * F::from(edc::TAG_EDMSG);
-            const X2<F> d = beta + per[P_T0] + gamma * t[0] + g2 * t[1] + g3 * t[2] + g4 * tag;
+            // a send row carries a bus.ed_digest message, a receive row a bus.ed_msg one: slots and tag are the selector-weighted sums
+            const F tag = snd * F::from(bus::TAG_EDH) + rcv * F::from(bus::TAG_EDMSG);
+            const X2<F> d = bus.denom(bus.beta, per[P_T0], t[0], t[1], t[2], tag);
             const X2<F> h{loc[COLS], loc[COLS + 1]}, z{loc[COLS + 2], loc[COLS + 3]}, zn{nxt[COLS + 2], nxt[COLS + 3]};
             c.constraint_x2(h * d - m);
             c.constraint_x2(zn - z - h + X2<F>{apub[0], apub[1]});

@@ -20,7 +20,6 @@
 #pragma once
 #include <vector>
 
-#include "air_blake.cuh"
 #include "air_sha.cuh"
 
 namespace sht {
@@ -30,12 +29,18 @@ constexpr int ENL = shc::DG0, ENR = shc::DG0 + 1, CNT = shc::DG0 + 2, COLS = shc
 enum { P_SEL0, P_SEL63, P_SCHED, P_K, P_DATA, P_TREE, P_PWA, P_PBL, P_PBR, P_CID, P_JJ, P_PS, P_ROOT, P_GID, P_NB, P_BB, P_LASTN };
 }  // namespace sht
 
+// auxiliary columns of a tree of N leaves (vx_sha_air.hip); the table must have 256 N rows
+int32_t vx_sha_tree_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, size_t N, const uint64_t* chal, uint64_t* aux, uint64_t* aux_pub);
+
 template <int LOGN, int ID_>
 struct ShaTreeAirT {
     static constexpr int ID = ID_, COLS = sht::COLS, PUB = 17, PERIODIC = sht::N_PERIODIC, PERIOD_LOG = 8 + LOGN, QUOT_ROWS_PER_LANE = 1, AUX = sht::AUX, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int TREE_SIZE = 1 << LOGN;
     static constexpr int plog(int q) { return q < 4 ? 6 : (q == 4 ? 7 : 8 + LOGN); }  // 4 x 64, 128, then 12 full-period columns
 
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
+        return vx_sha_tree_gen_aux(ctx, trace, log_n, TREE_SIZE, chal, aux, aux_pub);
+    }
     // one period of every periodic column, back to back (host)
     static void periodic_values(std::vector<uint64_t>& v) {
         using namespace sht;
@@ -106,9 +111,9 @@ struct ShaTreeAirT {
         }
         // ---- 9. the bus (logUp): 13 lookups in 7 helper elements of the local row, cyclic running sum
         {
-            const X2<F> beta{chal[0], chal[1]}, gamma{chal[2], chal[3]}, g2 = gamma * gamma, g3 = g2 * gamma, g4 = g2 * g2;
+            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
             const F en_l = loc[ENL], en_r = loc[ENR], zero = F::from(0);
-            const X2<F> tag_w = g4 * F::from(blk::TAG_WORD), tag_b = g4 * F::from(blk::TAG_BYTE);
+            const X2<F> bword = bus.word_base(), bbyte = bus.byte_base(per[P_CID], per[P_TREE]);
             // lookup q: 0 = word receive, 1..4 = byte receives, 5..12 = digest sends
             auto mult = [&](int q) -> F {
                 if (q == 0) return zero - per[P_PWA];
@@ -116,9 +121,9 @@ struct ShaTreeAirT {
                 return per[P_PS];
             };
             auto denom = [&](int q) -> X2<F> {
-                if (q == 0) return beta + per[P_TREE] + gamma * per[P_CID] + g2 * per[P_JJ] + g3 * w0 + tag_w;
-                if (q <= 4) return beta + per[P_CID] + gamma * (per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1))) + g2 * val(loc, W0B + 24 - 8 * (q - 1), 8) + g3 * per[P_TREE] + tag_b;
-                return beta + per[P_TREE] + gamma * per[P_GID] + g2 * F::from((uint64_t)(q - 5)) + g3 * loc[FFV0 + q - 5] + tag_w;
+                if (q == 0) return bus.word(bword, per[P_TREE], per[P_CID], per[P_JJ], w0);
+                if (q <= 4) return bus.byte(bbyte, per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1)), val(loc, W0B + 24 - 8 * (q - 1), 8));
+                return bus.word(bword, per[P_TREE], per[P_GID], F::from((uint64_t)(q - 5)), loc[FFV0 + q - 5]);
             };
             X2<F> hsum{zero, zero};
 #pragma unroll 1

@@ -13,6 +13,7 @@
 
 #define GL_P 0xFFFFFFFF00000001ULL
 #define GL_EPS 0xFFFFFFFFULL
+#define VX_HD __host__ __device__ __forceinline__
 
 struct gl2 {
     uint64_t a, b;  // a + b X
@@ -199,6 +200,11 @@ __device__ __forceinline__ gl2 gl2_mul(gl2 x, gl2 y) {
     return {gl_add(gl_mul(x.a, y.a), gl_mul_small(bb, 7)), gl_add(gl_mul(x.a, y.b), gl_mul(x.b, y.a))};
 }
 __device__ __forceinline__ gl2 gl2_scale(gl2 x, uint64_t s) { return {gl_mul(x.a, s), gl_mul(x.b, s)}; }
+// the operators X2<F> has (air.cuh), so that one template serves a constraint's X2<F> and a witness kernel's gl2 (air_bus.cuh)
+__device__ __forceinline__ gl2 operator+(gl2 x, gl2 y) { return gl2_add(x, y); }
+__device__ __forceinline__ gl2 operator+(gl2 x, uint64_t y) { return {gl_add(x.a, y), x.b}; }
+__device__ __forceinline__ gl2 operator*(gl2 x, gl2 y) { return gl2_mul(x, y); }
+__device__ __forceinline__ gl2 operator*(gl2 x, uint64_t s) { return gl2_scale(x, s); }
 __device__ __forceinline__ gl2 gl2_inv(gl2 x) {
     uint64_t n = gl_sub(gl_sqr(x.a), gl_mul_small(gl_sqr(x.b), 7));
     uint64_t ni = gl_inv(n);

@@ -328,14 +328,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_AUX_WAVE
     const size_t ip = (i + n - 1) & (n - 1);
     const int rl = (int)(ip & 15);  // row index (mod 16) of the LOCAL row: selectors are taken there
     const bool g_on = rl <= 11, m3 = rl <= 13;
-    const gl2 beta = a.beta, gamma = a.gamma, g2 = gl2_mul(gamma, gamma);
+    const bus::Bus<gl2> bus(a.beta.a, a.beta.b, a.gamma.a, a.gamma.b);
     auto N = [&](int col) -> uint64_t { return a.tr[(size_t)col * n + i]; };
     auto L = [&](int col) -> uint64_t { return a.tr[(size_t)col * n + ip]; };
-    auto fp1 = [&](uint64_t x, uint64_t y, uint64_t z) -> gl2 {
-        gl2 d = gl2_add(beta, gl2_add(gl2_scale(gamma, y), gl2_scale(g2, z)));
-        d.a = gl_add(d.a, x);
-        return d;
-    };
     auto store = [&](int e, gl2 h) {
         a.aux[(size_t)(2 * e) * n + i] = h.a;
         a.aux[(size_t)(2 * e + 1) * n + i] = h.b;
@@ -360,7 +355,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_AUX_WAVE
     };
     if (unit < 8) {
         const int k = unit;
-        const gl2 g3 = gl2_mul(g2, gamma), bt2 = gl2_add(beta, gl2_mul(g2, g2));
+        const gl2 bt2 = bus.t2_base();
         auto out_byte_loc = [&](int w, int j) -> uint64_t {
             const int m = w & 3;
             if (w < 8) {  // only b (w = 4..7) and d (w = 12..15) operands enter a lookup
@@ -381,14 +376,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_AUX_WAVE
         auto denoms = [&](int grp, gl2* dd) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                if (grp == 0) dd[q] = fp1(in_byte(3, q), N(GC(k, S_A1, q)), N(GC(k, S_D1, (q + 4) & 7)));
-                else if (grp == 1) dd[q] = fp1(in_byte(1, q), N(GC(k, S_C1, q)), N(GC(k, S_B1, (q + 5) & 7)));
-                else if (grp == 2) dd[q] = fp1(N(GC(k, S_D1, q)), N(GC(k, S_A2, q)), N(GC(k, S_D2, (q + 6) & 7)));
-                else {
-                    gl2 d = gl2_add(bt2, gl2_add(gl2_scale(gamma, N(GC(k, S_C2, q))), gl2_add(gl2_scale(g2, N(GC(k, S_L, q))), gl2_scale(g3, N(GC(k, S_T, q))))));
-                    d.a = gl_add(d.a, N(GC(k, S_B1, q)));
-                    dd[q] = d;
-                }
+                if (grp == 0) dd[q] = bus.xor_row(in_byte(3, q), N(GC(k, S_A1, q)), N(GC(k, S_D1, (q + 4) & 7)));
+                else if (grp == 1) dd[q] = bus.xor_row(in_byte(1, q), N(GC(k, S_C1, q)), N(GC(k, S_B1, (q + 5) & 7)));
+                else if (grp == 2) dd[q] = bus.xor_row(N(GC(k, S_D1, q)), N(GC(k, S_A2, q)), N(GC(k, S_D2, (q + 6) & 7)));
+                else dd[q] = bus.t2_row(bt2, N(GC(k, S_B1, q)), N(GC(k, S_C2, q)), N(GC(k, S_L, q)), N(GC(k, S_T, q)));
             }
         };
         // ONE extension-field inversion per lane (Montgomery's trick on two levels): pass 1 multiplies the 8 denominators
@@ -443,26 +434,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_AUX_WAVE
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const uint64_t b0 = N(MB0 + 2 * q), b1 = N(MB0 + 2 * q + 1);
-            const gl2 du = fp1(b0, 0, b0), dv = fp1(b1, 0, b1);
+            const gl2 du = bus.xor_row(b0, bus::None{}, b0), dv = bus.xor_row(b1, bus::None{}, b1);
             p[q] = gl2_mul(du, dv), s[q] = gl2_add(du, dv);
         }
         four(p, s, HM0);
         // bus sends of this row (it is the "next" row of its pair; r = its index in the block): byte b under E[b] as (leaf, position
         // in the root, byte, tree) -- state root (tree 0) on rows 4..8 of a first chunk, data root (tree 1) elsewhere
         {
-            const gl2 g3 = gl2_mul(g2, gamma), g4 = gl2_mul(g2, g2);
             const int r = (int)(i & 15);
             const uint64_t leaf = gl_sub(N(NUM), a.first_number);
             const uint64_t pos0 = gl_sub(gl_add(gl_sub(N(T), N(INC)), (uint64_t)(8 * r)), N(KOF));
-            const gl2 bbase = gl2_add(beta, gl2_add(gl2{leaf, 0}, gl2_add(gl2_scale(g3, N(TR)), gl2_scale(g4, TAG_BYTE))));
+            const gl2 bbase = bus.byte_base(leaf, N(TR));
 #pragma unroll 1
             for (int pair = 0; pair < 4; ++pair) {
                 gl2 h{0, 0};
                 const bool live = a.bus_on && N(ACT);
                 const uint64_t e0 = live ? N(E0 + 2 * pair) : 0, e1 = live ? N(E0 + 2 * pair + 1) : 0;
                 if (e0 | e1) {
-                    const gl2 du = gl2_add(bbase, gl2_add(gl2_scale(gamma, gl_add(pos0, 2 * pair)), gl2_scale(g2, N(MB0 + 2 * pair))));
-                    const gl2 dv = gl2_add(bbase, gl2_add(gl2_scale(gamma, gl_add(pos0, 2 * pair + 1)), gl2_scale(g2, N(MB0 + 2 * pair + 1))));
+                    const gl2 du = bus.byte(bbase, gl_add(pos0, 2 * pair), N(MB0 + 2 * pair));
+                    const gl2 dv = bus.byte(bbase, gl_add(pos0, 2 * pair + 1), N(MB0 + 2 * pair + 1));
                     h = gl2_mul(gl2_add(gl2_scale(dv, e0), gl2_scale(du, e1)), gl2_inv(gl2_mul(du, dv)));
                 }
                 store(HB0 + pair, h);
@@ -473,11 +463,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_AUX_WAVE
         const uint64_t m1 = N(M1), m2 = N(M2);
         gl2 ht{0, 0};
         if (m1 | m2) {
-            const gl2 g3 = gl2_mul(g2, gamma), bt2 = gl2_add(beta, gl2_mul(g2, g2));
             const uint64_t ti = i & 65535, ta = ti & 255, tb = ti >> 8, x = ta ^ tb;
-            const gl2 d1 = fp1(ta, tb, x);
-            gl2 d2 = gl2_add(bt2, gl2_add(gl2_scale(gamma, tb), gl2_add(gl2_scale(g2, x & 127), gl2_scale(g3, x >> 7))));
-            d2.a = gl_add(d2.a, ta);
+            const gl2 d1 = bus.xor_row(ta, tb, x), d2 = bus.t2_row(bus.t2_base(), ta, tb, x & 127, x >> 7);
             ht = gl2_mul(gl2_add(gl2_scale(d2, m1), gl2_scale(d1, m2)), gl2_inv(gl2_mul(d1, d2)));
         }
         store(HT, ht);
@@ -497,26 +484,7 @@ __global__ __launch_bounds__(256) void k_blake_aux_z(const uint64_t* part, uint6
     aux[(size_t)(2 * ZZ + 1) * n + ip] = gl_sub(sb, aux[(size_t)(2 * HT + 1) * n + ip]);
 }
 
-// Z(i) = (exclusive prefix sum of the increments)(i) - i * S / n: with the published S / n subtracted from every increment
-// the running sum closes cyclically
-__global__ __launch_bounds__(256) void k_bus_close(uint64_t* za, uint64_t* zb, size_t n, uint64_t spa, uint64_t spb) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    za[i] = gl_sub(za[i], gl_mul(spa, (uint64_t)i));
-    zb[i] = gl_sub(zb[i], gl_mul(spb, (uint64_t)i));
-}
-int32_t vx_bus_close_dev(vx_ctx* ctx, uint64_t* z_cols, int log_n, uint64_t aux_pub[2]) {
-    const size_t n = (size_t)1 << log_n;
-    uint64_t tot[2];
-    VX_TRY(vx_scan_cols_dev(ctx, z_cols, log_n, 2, tot));
-    const uint64_t ninv = glh::inv(n % glh::P);
-    aux_pub[0] = glh::mul(tot[0], ninv), aux_pub[1] = glh::mul(tot[1], ninv);
-    hipLaunchKernelGGL(k_bus_close, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, z_cols, z_cols + n, n, aux_pub[0], aux_pub[1]);
-    VX_HIP(hipGetLastError());
-    return VX_OK;
-}
-
-int32_t vx_blake_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+int32_t BlakeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     const size_t n = (size_t)1 << log_n;
     uint64_t* part = (uint64_t*)vx_pool_alloc(ctx, 18 * n * 8);
     if (!part) return vx_fail(ctx, VX_ERR_OOM, "blake aux: out of device memory");

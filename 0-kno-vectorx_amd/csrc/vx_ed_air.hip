@@ -324,9 +324,10 @@ __global__ __launch_bounds__(256) void k_ed_mult(const uint32_t* hist, uint64_t*
     mult_col[i] = s;
 }
 
-__global__ __launch_bounds__(256) void k_ed_inv_table(gl2 br, gl2* inv) {
+__global__ __launch_bounds__(256) void k_ed_inv_table(gl2 beta, gl2 gamma, gl2* inv) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    inv[v] = gl2_inv(gl2{gl_add(br.a, v), br.b});
+    const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+    inv[v] = gl2_inv(bus.r16(bus.r16_base(), v));
 }
 struct EdAuxArgs {
     const uint64_t* tr;
@@ -351,32 +352,27 @@ __global__ __launch_bounds__(256) void k_ed_aux(EdAuxArgs a) {
     gl2 hb[N_BUS];
     for (int b = 0; b < N_BUS; ++b) hb[b] = gl2{0, 0};
     if ((r == 0 || r == 1 || r == 255) && a.bus_on && T(SG)) {
-        const gl2 g2 = gl2_mul(a.gamma, a.gamma), g3 = gl2_mul(g2, a.gamma), g4 = gl2_mul(g2, g2);
+        const bus::Bus<gl2> bus(a.beta.a, a.beta.b, a.gamma.a, a.gamma.b);
         const uint64_t slot4 = 4 * (uint64_t)(i >> 8), sign = T(BS), aidx4 = 4 * T(AIDX);
         auto enc = [&](int g, int k) -> uint64_t { return k < 15 ? T(C(g, k)) : T(C(g, 15)) + 32768 * sign; };
-        auto fp = [&](uint64_t t0, uint64_t t1, uint64_t t2, uint64_t t3, int tag) -> gl2 {
-            gl2 d = gl2_add(a.beta, gl2_add(gl2_scale(a.gamma, t1), gl2_add(gl2_scale(g2, t2), gl2_add(gl2_scale(g3, t3), gl2_scale(g4, (uint64_t)tag)))));
-            d.a = gl_add(d.a, t0);
-            return d;
-        };
         auto neg = [](gl2 x) -> gl2 { return gl2{gl_neg(x.a), gl_neg(x.b)}; };
         if (r == 0) {
             for (int b = 0; b < 4; ++b)
-                hb[b] = neg(gl2_inv(fp(aidx4 + b, enc(7, 4 * b) | (enc(7, 4 * b + 1) << 16), enc(7, 4 * b + 2) | (enc(7, 4 * b + 3) << 16), 0, TAG_KEY)));
+                hb[b] = neg(gl2_inv(bus.key(aidx4 + b, enc(7, 4 * b) | (enc(7, 4 * b + 1) << 16), enc(7, 4 * b + 2) | (enc(7, 4 * b + 3) << 16))));
             for (int b = 0; b < 2; ++b)
-                hb[4 + b] = gl2_inv(fp(slot4 + b + 2, enc(7, 8 * b) | (enc(7, 8 * b + 1) << 16) | (enc(7, 8 * b + 2) << 32),
-                                       enc(7, 8 * b + 3) | (enc(7, 8 * b + 4) << 16) | (enc(7, 8 * b + 5) << 32), enc(7, 8 * b + 6) | (enc(7, 8 * b + 7) << 16), TAG_EDMSG));
+                hb[4 + b] = gl2_inv(bus.ed_msg(slot4 + b + 2, enc(7, 8 * b) | (enc(7, 8 * b + 1) << 16) | (enc(7, 8 * b + 2) << 32),
+                                       enc(7, 8 * b + 3) | (enc(7, 8 * b + 4) << 16) | (enc(7, 8 * b + 5) << 32), enc(7, 8 * b + 6) | (enc(7, 8 * b + 7) << 16)));
         } else if (r == 1) {
             auto dh = [&](int q) -> uint64_t {  // half q of the digest: big-endian sum of four byte cells
                 if (q >= 16) return 0;
                 const int b0 = 8 * (q >> 1) + ((q & 1) ? 0 : 4);
                 return (T(BYA(b0)) << 24) | (T(BYA(b0 + 1)) << 16) | (T(BYA(b0 + 2)) << 8) | T(BYA(b0 + 3));
             };
-            for (int b = 0; b < 6; ++b) hb[b] = neg(gl2_inv(fp(2 * slot4 + b, dh(3 * b), dh(3 * b + 1), dh(3 * b + 2), TAG_EDH)));
+            for (int b = 0; b < 6; ++b) hb[b] = neg(gl2_inv(bus.ed_digest(2 * slot4 + b, dh(3 * b), dh(3 * b + 1), dh(3 * b + 2))));
         } else {
             for (int b = 0; b < 2; ++b)
-                hb[4 + b] = gl2_inv(fp(slot4 + b, enc(1, 8 * b) | (enc(1, 8 * b + 1) << 16) | (enc(1, 8 * b + 2) << 32),
-                                       enc(1, 8 * b + 3) | (enc(1, 8 * b + 4) << 16) | (enc(1, 8 * b + 5) << 32), enc(1, 8 * b + 6) | (enc(1, 8 * b + 7) << 16), TAG_EDMSG));
+                hb[4 + b] = gl2_inv(bus.ed_msg(slot4 + b, enc(1, 8 * b) | (enc(1, 8 * b + 1) << 16) | (enc(1, 8 * b + 2) << 32),
+                                       enc(1, 8 * b + 3) | (enc(1, 8 * b + 4) << 16) | (enc(1, 8 * b + 5) << 32), enc(1, 8 * b + 6) | (enc(1, 8 * b + 7) << 16)));
         }
     }
     for (int b = 0; b < N_BUS; ++b) {
@@ -394,16 +390,8 @@ int32_t vx_ed_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const u
     const size_t n = (size_t)1 << log_n;
     gl2* inv = (gl2*)vx_pool_alloc(ctx, 65536 * sizeof(gl2));
     if (!inv) return vx_fail(ctx, VX_ERR_OOM, "ed aux: out of device memory");
-    // beta_r = beta + gamma^4 * TAG_R16 (host arithmetic in the quadratic extension X^2 = 7)
-    auto xmul = [](const uint64_t* x, const uint64_t* y, uint64_t* o) {
-        const uint64_t a = glh::add(glh::mul(x[0], y[0]), glh::mul(7, glh::mul(x[1], y[1]))), b = glh::add(glh::mul(x[0], y[1]), glh::mul(x[1], y[0]));
-        o[0] = a, o[1] = b;
-    };
-    uint64_t g2[2], g4[2];
-    xmul(chal + 2, chal + 2, g2), xmul(g2, g2, g4);
-    const gl2 br{glh::add(chal[0], glh::mul(g4[0], TAG_R16)), glh::add(chal[1], glh::mul(g4[1], TAG_R16))};
-    hipLaunchKernelGGL(k_ed_inv_table, dim3(256), dim3(256), 0, ctx->stream, br, inv);
     EdAuxArgs a{trace, aux, inv, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[1]};
+    hipLaunchKernelGGL(k_ed_inv_table, dim3(256), dim3(256), 0, ctx->stream, a.beta, a.gamma, inv);
     hipLaunchKernelGGL(k_ed_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
     const hipError_t e = hipGetLastError();
     vx_pool_free(ctx, inv);  // recycled only by later work on the same stream

@@ -27,8 +27,8 @@ __global__ __launch_bounds__(64) void k_epoch_aux(const uint64_t* __restrict__ t
     const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << LOG_N;
     if (row >= n) return;
     const bool pre = row == 0, val = tr[(size_t)V * n + row] != 0, dly = tr[(size_t)DL * n + row] != 0;
-    const gl2 g2 = gl2_mul(gamma, gamma), g3 = gl2_mul(g2, gamma), g4 = gl2_mul(g2, g2);
-    const gl2 bbase = gl2_add(beta, gl2_add(g3, gl2_scale(g4, blk::TAG_BYTE)));
+    const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+    const gl2 bbase = bus.byte_base(bus::None{}, bus::K<1>{});  // (0, k, byte, tree 1)
     const uint64_t kbase = pre ? 0 : (uint64_t)plen + 40 * (uint64_t)(row - 1);
     auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
     gl2 hsum{0, 0};
@@ -41,16 +41,14 @@ __global__ __launch_bounds__(64) void k_epoch_aux(const uint64_t* __restrict__ t
         aux[(size_t)(2 * e) * n + row] = h.a, aux[(size_t)(2 * e + 1) * n + row] = h.b;
         hsum = gl2_add(hsum, h);
     };
-    auto d_byte = [&](int j) -> gl2 { return gl2_add(bbase, gl2_add(gl2_scale(gamma, gl_add(kbase, (uint64_t)j)), gl2_scale(g2, cell(j)))); };
+    auto d_byte = [&](int j) -> gl2 { return bus.byte(bbase, gl_add(kbase, (uint64_t)j), cell(j)); };
     auto m_byte = [&](int j) -> bool { return val || (pre && (uint32_t)j < plen) || (dly && j < 4); };
 #pragma unroll 1
     for (int e = 0; e < 20; ++e) pair(e, m_byte(2 * e), m_byte(2 * e + 1), d_byte(2 * e), d_byte(2 * e + 1), true);
     auto d_key = [&](int q) -> gl2 {
         const uint64_t la = cell(8 * q) | (cell(8 * q + 1) << 8) | (cell(8 * q + 2) << 16) | (cell(8 * q + 3) << 24);
         const uint64_t lb = cell(8 * q + 4) | (cell(8 * q + 5) << 8) | (cell(8 * q + 6) << 16) | (cell(8 * q + 7) << 24);
-        gl2 d = gl2_add(beta, gl2_add(gl2_scale(gamma, la), gl2_add(gl2_scale(g2, lb), gl2_scale(g4, edc::TAG_KEY))));
-        d.a = gl_add(d.a, gl_add(gl_mul(gl_sub((uint64_t)row, 1), 4), (uint64_t)q));  // (row - 1) * 4 + q in the field (row 0: multiplicity 0)
-        return d;
+        return bus.key(gl_add(gl_mul(gl_sub((uint64_t)row, 1), 4), (uint64_t)q), la, lb);  // (row - 1) * 4 + q in the field (row 0: multiplicity 0)
     };
 #pragma unroll 1
     for (int e = 0; e < 2; ++e) pair(20 + e, val, val, d_key(2 * e), d_key(2 * e + 1), false);
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(64) void k_epoch_aux(const uint64_t* __restrict__ t
 }
 }  // namespace
 
-int32_t vx_epoch_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+int32_t EpochEndAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     const size_t n = (size_t)1 << log_n;
     uint32_t plen = 6;
     for (int a = 0; a < 4; ++a) plen += (uint32_t)(pub[2 + a] + pub[6 + a]) * (uint32_t)len_of(a);

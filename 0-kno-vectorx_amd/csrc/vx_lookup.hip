@@ -90,25 +90,39 @@ int32_t vx_scan_cols_dev(vx_ctx* ctx, uint64_t* data, int log_n, size_t n_cols, 
     return VX_OK;
 }
 
+// Z(i) = (exclusive prefix sum of the increments)(i) - i * S / n: with the published S / n subtracted from every increment
+// the running sum closes cyclically
+__global__ __launch_bounds__(256) void k_bus_close(uint64_t* za, uint64_t* zb, size_t n, uint64_t spa, uint64_t spb) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    za[i] = gl_sub(za[i], gl_mul(spa, (uint64_t)i));
+    zb[i] = gl_sub(zb[i], gl_mul(spb, (uint64_t)i));
+}
+int32_t vx_bus_close_dev(vx_ctx* ctx, uint64_t* z_cols, int log_n, uint64_t aux_pub[2]) {
+    const size_t n = (size_t)1 << log_n;
+    uint64_t tot[2];
+    VX_TRY(vx_scan_cols_dev(ctx, z_cols, log_n, 2, tot));
+    const uint64_t ninv = glh::inv(n % glh::P);
+    aux_pub[0] = glh::mul(tot[0], ninv), aux_pub[1] = glh::mul(tot[1], ninv);
+    hipLaunchKernelGGL(k_bus_close, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, z_cols, z_cols + n, n, aux_pub[0], aux_pub[1]);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
 // ---- LookupAir (AIR 5) auxiliary columns -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lookup_aux(const uint64_t* tr, size_t n, gl2 beta, gl2 gamma, uint64_t* aux) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const gl2 g2 = gl2_mul(gamma, gamma);
-    auto fp = [&](uint64_t a, uint64_t b, uint64_t c) {
-        gl2 d = gl2_add(beta, gl2_add(gl2_scale(gamma, b), gl2_scale(g2, c)));
-        d.a = gl_add(d.a, a);
-        return d;
-    };
+    const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
     const uint64_t ti = i & 255, ta = ti & 15, tb = ti >> 4;
-    const gl2 d0 = fp(tr[0 * n + i], tr[1 * n + i], tr[2 * n + i]), d1 = fp(tr[3 * n + i], tr[4 * n + i], tr[5 * n + i]);
-    const gl2 dt = fp(ta, tb, ta ^ tb);
+    const gl2 d0 = bus.xor_row(tr[0 * n + i], tr[1 * n + i], tr[2 * n + i]), d1 = bus.xor_row(tr[3 * n + i], tr[4 * n + i], tr[5 * n + i]);
+    const gl2 dt = bus.xor_row(ta, tb, ta ^ tb);
     const gl2 h = gl2_add(gl2_inv(d0), gl2_inv(d1)), ht = gl2_scale(gl2_inv(dt), tr[6 * n + i]);
     aux[0 * n + i] = h.a, aux[1 * n + i] = h.b, aux[2 * n + i] = ht.a, aux[3 * n + i] = ht.b;
     const gl2 dz = gl2_sub(h, ht);  // Z(next) - Z(this): turned into the running sum by the scan
     aux[4 * n + i] = dz.a, aux[5 * n + i] = dz.b;
 }
-int32_t vx_lookup_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+int32_t LookupAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     (void)aux_pub, (void)pub;
     const size_t n = (size_t)1 << log_n;
     hipLaunchKernelGGL(k_lookup_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, n, gl2{chal[0], chal[1]},

@@ -137,7 +137,8 @@ __global__ __launch_bounds__(256) void k_s512_aux(const uint64_t* tr, uint64_t* 
     const bool rcv = slot < m && q < 8 && !(q & 1), snd = slot < m && q >= SEND0;
     gl2 h{0, 0};
     if ((rcv || snd) && bus_on && tr[(size_t)SGF * n + row]) {
-        uint64_t t0, t1, t2, t3;
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        gl2 d;
         if (rcv) {
             auto word = [&](int col0) -> uint64_t {
                 uint64_t v = 0;
@@ -151,15 +152,12 @@ __global__ __launch_bounds__(256) void k_s512_aux(const uint64_t* tr, uint64_t* 
                 const int k = j & 3;
                 l[j] = ((x >> (56 - 16 * k)) & 0xFF) | (((x >> (48 - 16 * k)) & 0xFF) << 8);
             }
-            t0 = 4 * slot + q / 2, t1 = l[0] | (l[1] << 16) | (l[2] << 32), t2 = l[3] | (l[4] << 16) | (l[5] << 32), t3 = l[6] | (l[7] << 16);
+            d = bus.ed_msg(4 * slot + q / 2, l[0] | (l[1] << 16) | (l[2] << 32), l[3] | (l[4] << 16) | (l[5] << 32), l[6] | (l[7] << 16));
         } else {
             const int j = q - SEND0;
             auto ff = [&](int k) -> uint64_t { return k < 16 ? tr[(size_t)(FFV0 + k) * n + row] : 0; };
-            t0 = 8 * slot + j, t1 = ff(3 * j), t2 = ff(3 * j + 1), t3 = ff(3 * j + 2);
+            d = bus.ed_digest(8 * slot + j, ff(3 * j), ff(3 * j + 1), ff(3 * j + 2));
         }
-        const gl2 g2 = gl2_mul(gamma, gamma), g3 = gl2_mul(g2, gamma), g4 = gl2_mul(g2, g2);
-        gl2 d = gl2_add(beta, gl2_add(gl2_scale(gamma, t1), gl2_add(gl2_scale(g2, t2), gl2_add(gl2_scale(g3, t3), gl2_scale(g4, snd ? edc::TAG_EDH : edc::TAG_EDMSG)))));
-        d.a = gl_add(d.a, t0);
         h = gl2_inv(d);
         if (rcv) h = gl2{gl_neg(h.a), gl_neg(h.b)};
     }

@@ -107,16 +107,14 @@ __global__ __launch_bounds__(256) void k_sha_chain_aux(const uint64_t* tr, uint6
             for (int i = 0; i < 32; ++i) w |= (uint32_t)tr[(size_t)(col0 + i) * n + row] << i;
             return (uint64_t)((w >> 24) | ((w >> 8) & 0xFF00)) | ((uint64_t)(((w >> 8) & 0xFF) | ((w & 0xFF) << 8)) << 16);
         };
-        const gl2 g2 = gl2_mul(gamma, gamma), g4 = gl2_mul(g2, g2);
-        gl2 d = gl2_add(beta, gl2_add(gl2_scale(gamma, limbs(W0B)), gl2_add(gl2_scale(g2, limbs(W1B)), gl2_scale(g4, TAG_KEY))));
-        d.a = gl_add(d.a, 4 * (tr[(size_t)KC * n + row] - 1) + ((r & 7) >> 1));
-        h = gl2_inv(d);
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        h = gl2_inv(bus.key(4 * (tr[(size_t)KC * n + row] - 1) + ((r & 7) >> 1), limbs(W0B), limbs(W1B)));
         if (bus_on == 2) h = gl2{gl_neg(h.a), gl_neg(h.b)};
     }
     aux[row] = h.a, aux[n + row] = h.b;
     aux[2 * n + row] = h.a, aux[3 * n + row] = h.b;  // increments; the scan makes them the running sum
 }
-int32_t vx_sha_chain_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+int32_t ShaAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     const size_t n = (size_t)1 << log_n;
     hipLaunchKernelGGL(k_sha_chain_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[9]);
     VX_HIP(hipGetLastError());
@@ -264,22 +262,22 @@ __global__ __launch_bounds__(256) void k_sha_tree_aux(const uint64_t* tr, uint64
     gl2 h[7], hsum{0, 0};
     for (int e = 0; e < 7; ++e) h[e] = gl2{0, 0};
     if (m_word | m_byte | (send ? 1 : 0)) {
-        const gl2 g2 = gl2_mul(gamma, gamma), g3 = gl2_mul(g2, gamma), g4 = gl2_mul(g2, g2);
-        const gl2 tag_w = gl2_scale(g4, blk::TAG_WORD), tag_b = gl2_scale(g4, blk::TAG_BYTE);
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
         const uint64_t c = r >= 8 ? 1 : 0, jj = r & 7, w0 = (msg ? word(W0B, 32) : 0);
         const uint64_t cid = bottom ? 2 * g - N + c : 2 * g + c;  // a leaf's index / an inner child's node id
         gl2 d[13];
         uint64_t m[13];  // 1 = receive (-1), 2 = send (+1), 0 = inactive
-        d[0] = gl2_add(gl2_add(beta, gl2{(uint64_t)tree, 0}), gl2_add(gl2_add(gl2_scale(gamma, cid), gl2_scale(g2, jj)), gl2_add(gl2_scale(g3, w0), tag_w)));
+        const gl2 bword = bus.word_base(), bbyte = bus.byte_base(cid, tree);
+        d[0] = bus.word(bword, tree, cid, jj, w0);
         m[0] = m_word;
         for (int q = 0; q < 4; ++q) {
             const uint64_t byte = (w0 >> (24 - 8 * q)) & 0xFF;
-            d[1 + q] = gl2_add(gl2_add(beta, gl2{cid, 0}), gl2_add(gl2_add(gl2_scale(gamma, 4 * jj + q), gl2_scale(g2, byte)), gl2_add(gl2_scale(g3, tree), tag_b)));
+            d[1 + q] = bus.byte(bbyte, 4 * jj + q, byte);
             m[1 + q] = m_byte;
         }
         for (int j = 0; j < 8; ++j) {
             const uint64_t ff = send ? tr[(size_t)(FFV0 + j) * n + row] : 0;
-            d[5 + j] = gl2_add(gl2_add(beta, gl2{(uint64_t)tree, 0}), gl2_add(gl2_add(gl2_scale(gamma, g), gl2_scale(g2, j)), gl2_add(gl2_scale(g3, ff), tag_w)));
+            d[5 + j] = bus.word(bword, tree, g, j, ff);
             m[5 + j] = send ? 2 : 0;
         }
         auto term = [&](int q) -> gl2 {  // m / D with m in {-1, 0, +1}
@@ -296,19 +294,10 @@ __global__ __launch_bounds__(256) void k_sha_tree_aux(const uint64_t* tr, uint64
     for (int e = 0; e < 7; ++e) aux[(size_t)(2 * e) * n + row] = h[e].a, aux[(size_t)(2 * e + 1) * n + row] = h[e].b;
     aux[(size_t)14 * n + row] = hsum.a, aux[(size_t)15 * n + row] = hsum.b;  // increments; the scan makes them the running sum
 }
-static int32_t sha_tree_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, size_t N, const uint64_t* chal, uint64_t* aux, uint64_t* aux_pub) {
+int32_t vx_sha_tree_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, size_t N, const uint64_t* chal, uint64_t* aux, uint64_t* aux_pub) {
     const size_t n = (size_t)1 << log_n;
     VX_CHECK(n == 256 * N, "sha tree aux: a tree of %zu leaves has %zu rows, not 2^%d", N, 256 * N, log_n);
     hipLaunchKernelGGL(k_sha_tree_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, aux, n, N, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
     VX_HIP(hipGetLastError());
     return vx_bus_close_dev(ctx, aux + 14 * n, log_n, aux_pub);
-}
-int32_t vx_sha_tree_gen_aux_16(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-    return sha_tree_gen_aux(ctx, trace, log_n, 16, chal, aux, aux_pub);
-}
-int32_t vx_sha_tree_gen_aux_256(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-    return sha_tree_gen_aux(ctx, trace, log_n, 256, chal, aux, aux_pub);
-}
-int32_t vx_sha_tree_gen_aux_512(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-    return sha_tree_gen_aux(ctx, trace, log_n, 512, chal, aux, aux_pub);
 }

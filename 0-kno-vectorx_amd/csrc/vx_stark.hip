@@ -18,14 +18,10 @@
 #include <map>
 #include <mutex>
 
-#include "air.cuh"
+#include <array>
+
+#include "air_list.h"
 #include "air_program.h"
-#include "air_blake.cuh"
-#include "air_sha.cuh"
-#include "air_ed.cuh"
-#include "air_epoch.cuh"
-#include "air_sha512.cuh"
-#include "air_sha_tree.cuh"
 #include "glh_poseidon.h"
 #include "vx_internal.h"
 
@@ -346,7 +342,6 @@ __global__ __launch_bounds__(256) void k_fri_combine(CombineArgs a) {
 }
 
 // ------------------------------------------------------------------ AIR registry
-typedef int32_t (*gen_aux_fn)(vx_ctx*, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
 struct AirDesc {
     int id, cols, pub, periodic, period_log, exact_log;
     void (*periodic_values)(std::vector<uint64_t>&);  // one period of every periodic column, back to back
@@ -375,33 +370,13 @@ static void launch_q(QuotArgs& a, hipStream_t s) {
     if (R > 1 && N >= QB * (size_t)R) hipLaunchKernelGGL((k_quotient<Air, R>), dim3((unsigned)(N / (QB * R))), dim3(QB), 0, s, a);
     else hipLaunchKernelGGL((k_quotient<Air, 1>), dim3((unsigned)((N + QB - 1) / QB)), dim3(QB), 0, s, a);
 }
-static void no_periodic(std::vector<uint64_t>& v) { v.clear(); }
-static void mix_periodic(std::vector<uint64_t>& v) { v = {0, 0, 0, 1, 3, 5, 7, 11}; }
-static void blake_periodic(std::vector<uint64_t>& v) {
-    v.assign(16 * 16 + 4 * 65536, 0);
-    for (int k = 0; k < 16; ++k) v[k * 16 + k] = 1;  // sel_k: one-hot on row k of every 16-row block
-    for (uint64_t i = 0; i < 65536; ++i) {           // the XOR tables: row i = (a = i & 255, b = i >> 8)
-        const uint64_t a = i & 255, b = i >> 8;
-        v[256 + i] = a, v[256 + 65536 + i] = b, v[256 + 2 * 65536 + i] = (a ^ b) & 127, v[256 + 3 * 65536 + i] = (a ^ b) >> 7;
-    }
-}
-static void lookup_periodic(std::vector<uint64_t>& v) {
-    v.resize(3 * 256);
-    for (int i = 0; i < 256; ++i) v[i] = i & 15, v[256 + i] = i >> 4, v[512 + i] = (i & 15) ^ (i >> 4);
-}
 template <class Air>
-static AirDesc desc(void (*pv)(std::vector<uint64_t>&), gen_aux_fn ga = nullptr) {
-    return {Air::ID, Air::COLS, Air::PUB, Air::PERIODIC, Air::PERIOD_LOG, Air::EXACT_LOG, pv, launch_q<Air>, count_q<Air>, Air::AUX, Air::CHAL, Air::AUXPUB, Air::plog, ga};
+static AirDesc desc() {
+    return {Air::ID, Air::COLS, Air::PUB, Air::PERIODIC, Air::PERIOD_LOG, Air::EXACT_LOG, Air::periodic_values, launch_q<Air>, count_q<Air>, Air::AUX, Air::CHAL, Air::AUXPUB, Air::plog, Air::gen_aux};
 }
-static const AirDesc AIRS[] = {
-    desc<ShaAir>(ShaAir::periodic_values, vx_sha_chain_gen_aux), desc<BlakeAir>(blake_periodic, vx_blake_air_gen_aux), desc<FibAir>(no_periodic), desc<MixAir>(mix_periodic),
-    desc<LookupAir>(lookup_periodic, vx_lookup_air_gen_aux),
-    desc<ShaTreeAir256>(ShaTreeAir256::periodic_values, vx_sha_tree_gen_aux_256), desc<ShaTreeAir512>(ShaTreeAir512::periodic_values, vx_sha_tree_gen_aux_512),
-    desc<ShaTreeAir16>(ShaTreeAir16::periodic_values, vx_sha_tree_gen_aux_16),
-    desc<EdAir17>(EdAir17::periodic_values, vx_ed_air_gen_aux), desc<EdAir16>(EdAir16::periodic_values, vx_ed_air_gen_aux),
-    desc<Sha512Air16>(Sha512Air16::periodic_values, vx_sha512_air_gen_aux), desc<Sha512Air10>(Sha512Air10::periodic_values, vx_sha512_air_gen_aux), desc<Sha512Air15>(Sha512Air15::periodic_values, vx_sha512_air_gen_aux),
-    desc<EpochEndAir>(EpochEndAir::periodic_values, vx_epoch_air_gen_aux),
-};
+template <class... Airs>
+static std::array<AirDesc, sizeof...(Airs)> descs(AirList<Airs...>) { return {{desc<Airs>()...}}; }
+static const auto AIRS = descs(VxAirs{});
 static std::mutex g_prog_desc_mu;
 static std::map<int, AirDesc> g_prog_desc;  // descriptors of registered programs (node addresses are stable)
 static const AirDesc* find_air(int id) {

@@ -12,14 +12,10 @@
 #include <memory>
 #include <mutex>
 
-#include "air.cuh"
-#include "air_blake.cuh"
-#include "air_sha.cuh"
-#include "air_ed.cuh"
-#include "air_epoch.cuh"
-#include "air_sha512.cuh"
+#include <array>
+
+#include "air_list.h"
 #include "air_program.h"
-#include "air_sha_tree.cuh"
 #include "glh_poseidon.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
@@ -95,9 +91,12 @@ void eval_host(const HostRow& l, const HostRow& n, const Fx* per, const Fx* pub,
     Air::template eval<Fx>(l, n, per, pub, chal, apub, c);
 }
 template <class Air>
-AirV vdesc(void (*pv)(std::vector<uint64_t>&)) {
-    return {Air::ID, Air::COLS, Air::PUB, Air::PERIODIC, Air::PERIOD_LOG, Air::EXACT_LOG, pv, eval_host<Air>, Air::AUX, Air::CHAL, Air::AUXPUB, Air::plog};
+AirV vdesc() {
+    return {Air::ID, Air::COLS, Air::PUB, Air::PERIODIC, Air::PERIOD_LOG, Air::EXACT_LOG, Air::periodic_values, eval_host<Air>, Air::AUX, Air::CHAL, Air::AUXPUB, Air::plog};
 }
+template <class... Airs>
+std::array<AirV, sizeof...(Airs)> vdescs(AirList<Airs...>) { return {{vdesc<Airs>()...}}; }
+const auto AIRS_V = vdescs(VxAirs{});
 // coefficients of P(Y), deg < p, with P(w_p^k) = v[k]: in-place radix-2 inverse NTT on the host (a 2^16-entry lookup
 // table is far too long for the O(p^2) sum the short selectors get away with)
 void host_intt(std::vector<uint64_t>& a) {
@@ -125,25 +124,6 @@ void host_intt(std::vector<uint64_t>& a) {
     const uint64_t pinv = glh::inv(p % glh::P);
     for (uint64_t& x : a) x = glh::mul(x, pinv);
 }
-void v_no_periodic(std::vector<uint64_t>& v) { v.clear(); }
-void v_mix_periodic(std::vector<uint64_t>& v) { v = {0, 0, 0, 1, 3, 5, 7, 11}; }
-void v_blake_periodic(std::vector<uint64_t>& v) {
-    v.assign(16 * 16 + 4 * 65536, 0);
-    for (int k = 0; k < 16; ++k) v[k * 16 + k] = 1;
-    for (uint64_t i = 0; i < 65536; ++i) {
-        const uint64_t a = i & 255, b = i >> 8;
-        v[256 + i] = a, v[256 + 65536 + i] = b, v[256 + 2 * 65536 + i] = (a ^ b) & 127, v[256 + 3 * 65536 + i] = (a ^ b) >> 7;
-    }
-}
-void v_lookup_periodic(std::vector<uint64_t>& v) {
-    v.resize(3 * 256);
-    for (int i = 0; i < 256; ++i) v[i] = i & 15, v[256 + i] = i >> 4, v[512 + i] = (i & 15) ^ (i >> 4);
-}
-const AirV V_AIRS[] = {
-    vdesc<ShaAir>(ShaAir::periodic_values), vdesc<FibAir>(v_no_periodic), vdesc<MixAir>(v_mix_periodic), vdesc<BlakeAir>(v_blake_periodic),
-    vdesc<LookupAir>(v_lookup_periodic), vdesc<ShaTreeAir256>(ShaTreeAir256::periodic_values), vdesc<ShaTreeAir512>(ShaTreeAir512::periodic_values),
-    vdesc<ShaTreeAir16>(ShaTreeAir16::periodic_values), vdesc<EdAir17>(EdAir17::periodic_values), vdesc<EdAir16>(EdAir16::periodic_values), vdesc<Sha512Air16>(Sha512Air16::periodic_values), vdesc<Sha512Air10>(Sha512Air10::periodic_values), vdesc<Sha512Air15>(Sha512Air15::periodic_values), vdesc<EpochEndAir>(EpochEndAir::periodic_values),
-};
 size_t brev(size_t x, int bits) {
     size_t r = 0;
     for (int i = 0; i < bits; ++i) r = (r << 1) | ((x >> i) & 1);
@@ -342,7 +322,7 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
     NEED(r == cfg->rate_bits && cap_h == cfg->cap_height && (int)n_queries == cfg->num_queries && pow_bits == cfg->pow_bits, "config mismatch");
     NEED(L >= 2 && L <= 26 && n_layers <= 16, "bad shape");
     const AirV* air = nullptr;
-    for (const AirV& a : V_AIRS)
+    for (const AirV& a : AIRS_V)
         if (a.id == air_id) air = &a;
     AirV prog_air{};
     if (!air && air_id >= VX_AIR_USER_BASE) {
