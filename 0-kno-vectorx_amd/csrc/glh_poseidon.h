@@ -30,6 +30,22 @@ inline void poseidon(uint64_t* s) {
         memcpy(s, o, sizeof o);
     }
 }
+// hash_n_to_hash_no_pad (hash/hashing.rs): the sponge absorbs 8 words per permutation by overwriting the rate part
+inline void hash_no_pad(const uint64_t* in, size_t len, uint64_t out4[4]) {
+    uint64_t s[12] = {0};
+    for (size_t off = 0; off < len; off += 8) {
+        memcpy(s, in + off, (len - off < 8 ? len - off : 8) * 8);
+        poseidon(s);
+    }
+    memcpy(out4, s, 32);
+}
+// compress / two_to_one: the parent of two digests
+inline void two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out4[4]) {
+    uint64_t s[12] = {0};
+    memcpy(s, l, 32), memcpy(s + 4, r, 32);
+    poseidon(s);
+    memcpy(out4, s, 32);
+}
 struct Challenger {
     uint64_t st[12] = {0}, in[8], out[8];
     int n_in = 0, n_out = 0;

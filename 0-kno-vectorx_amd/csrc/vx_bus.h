@@ -107,6 +107,11 @@ static const uint64_t VX_ROT_MAGIC = 0x3354415458525856ULL;  // "VXRXTAT3"
 // new-set commitment, Ed25519; parent hash (4); SHA-512 proof length, the precommit's round, start_position, epoch-end proof length
 static constexpr size_t VX_ROT_HDR = 28;
 
+// ---- Merkle-openings blob (written by vx_merkle_openings_prove in vx_merkle_open_air.hip, read by vx_merkle_openings_verify in
+// vx_verify.hip): magic, log2(n_leaves), number of openings, length of the MerkleOpenAir proof that follows
+static const uint64_t VX_MOPEN_MAGIC = 0x314e45504f4d5856ULL;  // "VXMOPEN1"
+static constexpr size_t VX_MOPEN_HDR = 4;
+
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {
     for (int j = 0; j < 8; ++j)

@@ -1,0 +1,185 @@
+// Witness and prover of MerkleOpenAir (air_merkle_open.cuh): a batch of openings of one vx_tree proven in one table.
+//   k_merkle_open_trace  one lane per block (path p, level l): the tree in HBM already holds every node of every path, so the
+//                        levels of a path are independent -- the lane gathers the node entering its level and the sibling,
+//                        orders them by the index bit, walks the 30 rounds (poseidon_air.cuh) and writes its 32 rows
+//   k_merkle_open_aux    one lane per block: one extension inversion for the helper of the block's two TAG_OPEN messages, written
+//                        to its 32 rows, and the block's running-sum increment on its first row (vx_bus_close_dev scans it)
+// The levels above the tree's cap (the table proves paths to ONE root: the two-to-one fold of the cap) are folded here with the
+// tree builder's own level kernel.  Parity: tests/test_gpu_merkle_open.py compares trace, auxiliary columns and proof with
+// tests/merkle_open_ref.py and the reference prover.
+#include <string.h>
+
+#include "air_merkle_open.cuh"
+#include "glh_poseidon.h"
+#include "poseidon_air.cuh"
+#include "vx_bus.h"
+#include "vx_internal.h"
+
+namespace {
+using namespace mop;
+
+struct OpenArgs {
+    const uint64_t* levels;  // the tree: level l (n_leaves >> l nodes) at 8 (n_leaves - (n_leaves >> l)), l <= low
+    const uint64_t* upper;   // the fold of the cap: its level j (n_cap >> j nodes) at 8 (n_cap - (n_cap >> j)); level 0 = the cap
+    const uint64_t* idx;     // [n_idx] leaf indices (< n_leaves: checked by the host)
+    size_t n_leaves, n_cap, n_idx, n;
+    int depth, low;          // depth = log2(n_leaves) levels per path; levels below `low` = depth - cap_height are read from the tree
+    uint64_t* tr;            // [COLS][n]
+    uint64_t* claims;        // [n_idx][5]: (index, leaf digest), written by the lane of each path's first level
+};
+
+__global__ __launch_bounds__(64) void k_merkle_open_trace(OpenArgs a) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= a.n / 32) return;
+    uint64_t s[12], shape[COLS - BIT];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = 0;
+#pragma unroll
+    for (int j = 0; j < COLS - BIT; ++j) shape[j] = 0;
+    shape[LVL - BIT] = 1;  // an idle block is the zero state at level 1
+    if (b < a.n_idx * (size_t)a.depth) {
+        const size_t p = b / (size_t)a.depth;
+        const int l = (int)(b - p * (size_t)a.depth);
+        const uint64_t idx = a.idx[p], node = idx >> l, bit = node & 1;
+        const uint64_t* lv = l < a.low ? a.levels + 8 * (a.n_leaves - (a.n_leaves >> l)) : a.upper + 8 * (a.n_cap - (a.n_cap >> (l - a.low)));
+        const uint64_t *cur = lv + 4 * node, *sib = lv + 4 * (node ^ 1), *leaf = a.levels + 4 * idx;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t c = gl_canon(cur[i]), sb = gl_canon(sib[i]), lf = gl_canon(leaf[i]);
+            s[i] = bit ? sb : c, s[4 + i] = bit ? c : sb;
+            shape[SIB - BIT + i] = sb, shape[CUR - BIT + i] = c, shape[LEAF - BIT + i] = lf;
+            if (l == 0) a.claims[5 * p + 1 + i] = lf;
+        }
+        if (l == 0) a.claims[5 * p] = idx;
+        shape[BIT - BIT] = bit, shape[R - BIT] = node, shape[LVL - BIT] = (uint64_t)l + 1, shape[ACT - BIT] = 1;
+        shape[END - BIT] = l == a.depth - 1, shape[FIRSTB - BIT] = l == 0;
+    }
+    poseidon_air_walk(s, a.tr, a.n, 32 * b);
+#pragma unroll
+    for (int j = 0; j < COLS - BIT; ++j) {  // (unrolled: shape[] stays in registers)
+        uint64_t* col = a.tr + (size_t)(BIT + j) * a.n + 32 * b;
+        const uint64_t v = shape[j];
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) col[r] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_merkle_open_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= n / 32) return;
+    const size_t row = 32 * b;
+    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
+    gl2 h{0, 0};
+    const uint64_t firstb = cell(FIRSTB);
+    if (firstb) {  // h = FIRSTB (1 / D_lo + 1 / D_hi) with one inversion
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        const gl2 dlo = bus.open(cell(R), cell(LEAF), cell(LEAF + 1), bus::K<0>{}), dhi = bus.open(cell(R), cell(LEAF + 2), cell(LEAF + 3), bus::K<1>{});
+        h = gl2_scale(gl2_mul(gl2_add(dlo, dhi), gl2_inv(gl2_mul(dlo, dhi))), firstb);
+    }
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+        aux[row + r] = h.a, aux[n + row + r] = h.b;
+        aux[2 * n + row + r] = r == 0 ? h.a : 0, aux[3 * n + row + r] = r == 0 ? h.b : 0;  // increments; the scan makes them the running sum
+    }
+}
+
+int ceil_log2(size_t x) {
+    int l = 0;
+    while (((size_t)1 << l) < x) ++l;
+    return l;
+}
+
+// one table on its own bus: the lookup challenges are the shared-challenge transcript of this table's (public inputs, trace cap)
+int32_t one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cap_words, uint64_t* chal, size_t n_chal) {
+    vx_shared_challenges_n(&pub, &n_pub, &cap, 1, cap_words, chal, n_chal);
+    return VX_OK;
+}
+}  // namespace
+
+int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    (void)pub;
+    const size_t n = (size_t)1 << log_n, blocks = n / 32;
+    hipLaunchKernelGGL(k_merkle_open_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + 2 * n, log_n, aux_pub);
+}
+
+// rows (log2) of the table: the smallest power of two that holds n_idx paths of `depth` blocks
+static int merkle_open_log_n(size_t n_idx, int depth) { return ceil_log2(32 * n_idx * (size_t)depth); }  // >= 5: n_idx, depth >= 1
+
+int32_t vx_merkle_open_trace_dev(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[9]) {
+    const int depth = ceil_log2(tree->n_leaves);
+    VX_CHECK(depth >= 1 && depth <= 40, "merkle openings: a tree of %zu leaves has no path to prove", tree->n_leaves);
+    VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings (1..2^21)", n_idx);
+    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * n_idx * (size_t)depth <= ((size_t)1 << log_n), "merkle openings: %zu paths of %d levels do not fit 2^%d rows", n_idx, depth, log_n);
+    for (size_t i = 0; i < n_idx; ++i) VX_CHECK(leaf_idx[i] < tree->n_leaves, "merkle openings: index %zu (%llu) is not a leaf of the tree", i, (unsigned long long)leaf_idx[i]);
+    const size_t n = (size_t)1 << log_n, n_cap = (size_t)1 << tree->cap_height, up_words = 4 * (2 * n_cap - 1);
+    // scratch: the fold of the cap, the indices, the claims
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (up_words + 6 * n_idx) * 8);
+    VX_CHECK(sc, "merkle openings: out of device memory");
+    uint64_t *upper = sc, *idx_d = sc + up_words, *claims_d = idx_d + n_idx;
+    std::vector<uint64_t> claims(5 * n_idx);
+    uint64_t root[4];
+    int32_t rc = VX_OK;
+    do {
+        hipError_t e = hipMemcpyAsync(upper, tree->levels + tree->total - 4 * n_cap, 4 * n_cap * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle openings: %s", hipGetErrorString(e));
+            break;
+        }
+        vx_merkle_levels_launch(ctx, upper, n_cap, 1);
+        OpenArgs a{tree->levels, upper, idx_d, tree->n_leaves, n_cap, n_idx, n, depth, depth - tree->cap_height, trace_d, claims_d};
+        hipLaunchKernelGGL(k_merkle_open_trace, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, claims.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(root, upper + up_words - 4, 32, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle openings: %s", hipGetErrorString(e));
+    } while (0);
+    vx_pool_free(ctx, sc);
+    VX_TRY(rc);
+    for (int i = 0; i < 4; ++i) pub_out[i] = root[i];
+    pub_out[4] = (uint64_t)depth;
+    glh::hash_no_pad(claims.data(), claims.size(), pub_out + 5);
+    return VX_OK;
+}
+
+extern "C" {
+int32_t vx_merkle_open_air_trace(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, vx_buf* trace_out, uint64_t public_out[9]) {
+    if (!ctx || !tree || !leaf_idx || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "merkle openings: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, COLS, log_n);
+    return vx_merkle_open_trace_dev(ctx, tree, leaf_idx, n_idx, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_merkle_openings_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t n_idx, size_t* n_words) {
+    if (!cfg || !n_words || n_leaves < 2 || (n_leaves & (n_leaves - 1)) || n_idx < 1 || n_idx > ((size_t)1 << 21)) return VX_ERR_ARG;
+    const int log_n = merkle_open_log_n(n_idx, ceil_log2(n_leaves));
+    if (log_n > 26) return VX_ERR_ARG;
+    size_t w = 0;
+    const int32_t rc = vx_stark_proof_bound(VX_AIR_MERKLE_OPEN, cfg, log_n, &w);
+    if (rc != VX_OK) return rc;
+    *n_words = VX_MOPEN_HDR + w;
+    return VX_OK;
+}
+
+int32_t vx_merkle_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, uint64_t* blob_out, size_t blob_cap,
+                                 size_t* blob_len) {
+    if (!ctx || !cfg || !tree || !leaf_idx || !blob_len) return VX_ERR_ARG;
+    const int depth = ceil_log2(tree->n_leaves);
+    VX_CHECK(depth >= 1 && n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings of a tree of %zu leaves", n_idx, tree->n_leaves);
+    const int log_n = merkle_open_log_n(n_idx, depth);
+    VX_CHECK(log_n <= 26, "merkle openings: %zu paths of %d levels need more than 2^26 rows", n_idx, depth);
+    TableJob job;
+    const vx_chal_hook hook{one_table_hook, nullptr};
+    VX_TRY(run_table(ctx, job, VX_AIR_MERKLE_OPEN, log_n, COLS, PUB, cfg, &hook, 0,
+                     [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) { return vx_merkle_open_trace_dev(c, tree, leaf_idx, n_idx, log_n, trace->d, pub); }));
+    const size_t total = VX_MOPEN_HDR + job.len;
+    *blob_len = total;
+    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "merkle openings: the blob needs %zu words, buffer has %zu", total, blob_cap);
+    blob_out[0] = VX_MOPEN_MAGIC, blob_out[1] = (uint64_t)depth, blob_out[2] = n_idx, blob_out[3] = job.len;
+    memcpy(blob_out + VX_MOPEN_HDR, job.proof.data(), job.len * 8);
+    return VX_OK;
+}
+}  // extern "C"

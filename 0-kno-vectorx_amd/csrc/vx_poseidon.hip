@@ -5,6 +5,7 @@
 // column, so each absorb step is one coalesced 512-byte load per wave; the
 // plonky2 leaf index bitrev(t) only decides where the 32-byte digest is written.
 #include "poseidon.cuh"
+#include "poseidon_air.cuh"
 #include "vx_internal.h"
 
 __global__ __launch_bounds__(256) void k_poseidon_batch(uint64_t* states, size_t n) {
@@ -123,43 +124,15 @@ __global__ void k_gather_siblings(const uint64_t* levels, size_t n_leaves, int d
 
 
 // ---- witness of PoseidonAir (the permutation as a STARK table: air_library.py poseidon_builder; 48 columns, 32 rows per permutation).
-// Lane p walks the 30 rounds of permutation p in the PLAIN schedule (constant layer, s-box, MDS: the rows of the table are the
-// states entering each round, not the folded form the hashing kernels use) and writes the state, x^2, x^4 and x^7 of every row;
+// Lane p walks the 30 rounds of permutation p (poseidon_air.cuh) and writes the state, x^2, x^4 and x^7 of every row;
 // rows 30 and 31 of a block hold the output.  trace: column-major [48][32 n_perm].
-static __constant__ uint64_t POSEIDON_RC_PLAIN[360] = VX_POSEIDON_RC_INIT;
 __global__ __launch_bounds__(256) void k_poseidon_air_trace(const uint64_t* in, size_t n_perm, uint64_t* tr) {
     const size_t p = blockIdx.x * (size_t)256 + threadIdx.x;
     if (p >= n_perm) return;
-    constexpr uint32_t C[12] = VX_POSEIDON_MDS_CIRC_INIT;
-    const size_t n = 32 * n_perm;
     uint64_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) s[i] = gl_canon(in[12 * p + i]);
-#pragma unroll 1
-    for (int r = 0; r < 32; ++r) {
-        const size_t row = 32 * p + r;
-        const bool full = r < 4 || (r >= 26 && r < 30);
-        uint64_t y[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const uint64_t x = r < 30 ? gl_add(s[i], POSEIDON_RC_PLAIN[12 * r + i]) : s[i];
-            const uint64_t a = gl_mul(x, x), b = gl_mul(a, a), t = gl_mul(gl_mul(x, a), b);
-            tr[(size_t)i * n + row] = s[i];
-            tr[(size_t)(12 + i) * n + row] = a;
-            tr[(size_t)(24 + i) * n + row] = b;
-            tr[(size_t)(36 + i) * n + row] = t;
-            y[i] = (full || i == 0) ? t : x;
-        }
-        if (r < 30) {
-#pragma unroll
-            for (int q = 0; q < 12; ++q) {
-                unsigned __int128 acc = q == 0 ? (unsigned __int128)y[0] * VX_POSEIDON_MDS_DIAG0 : 0;
-#pragma unroll
-                for (int i = 0; i < 12; ++i) acc += (unsigned __int128)y[(i + q) % 12] * C[i];
-                s[q] = gl_reduce128((uint64_t)(acc >> 64), (uint64_t)acc);
-            }
-        }
-    }
+    poseidon_air_walk(s, tr, 32 * n_perm, 32 * p);
 }
 
 // levels above the leaf digests, down to `cap` nodes (levels = digests of level 0 followed by each parent level)

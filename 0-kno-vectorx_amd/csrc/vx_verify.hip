@@ -729,6 +729,70 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     return verify_bus_group(cfg, tab.data(), n_tab, "the lookup bus between the tables does not balance", err, errlen);
 }
 
+// Merkle openings (the prover is vx_merkle_open_air.hip): the verifier holds the openings it wants proven -- (index, leaf digest)
+// pairs of a tree it knows by its cap -- and is the OTHER PARTY of the table's logUp bus: it rebuilds the table's public inputs
+// from its own arguments (root = the fold of the cap, depth, claims digest), derives the lookup challenges from them and the
+// proof's trace cap, verifies the table under those challenges, and accepts iff what the table sent is what it receives:
+// published total x rows = sum over the claims of 1 / D_lo + 1 / D_hi.  No Merkle path is walked here.
+int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* cap, int cap_height, int log_leaves, const uint64_t* leaf_idx,
+                                  const uint64_t* leaf_digests, size_t n_idx, char* err, size_t errlen) {
+    if (!cfg || !blob || !cap || !leaf_idx || !leaf_digests) return VX_ERR_ARG;
+    NEED(log_leaves >= 1 && log_leaves <= 40 && cap_height >= 0 && cap_height <= 16 && cap_height <= log_leaves, "merkle openings: cap height %d / tree depth %d out of range", cap_height,
+         log_leaves);
+    NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings (1..2^21)", n_idx);
+    NEED(len > VX_MOPEN_HDR && blob[0] == VX_MOPEN_MAGIC, "bad merkle-openings blob");
+    NEED(blob[1] == (uint64_t)log_leaves && blob[2] == (uint64_t)n_idx, "blob is for a different request");
+    NEED(blob[3] == len - VX_MOPEN_HDR, "blob lengths are inconsistent");
+    const uint64_t* proof = blob + VX_MOPEN_HDR;
+    const size_t plen = len - VX_MOPEN_HDR;
+    // the table's public inputs, from the verifier's own arguments
+    uint64_t pub[mop::PUB];
+    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height)), claims(5 * n_idx);
+    for (uint64_t w : fold) NEED(w < glh::P, "merkle openings: non-canonical cap word");
+    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
+        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
+    memcpy(pub, fold.data(), 32);
+    pub[4] = (uint64_t)log_leaves;
+    for (size_t i = 0; i < n_idx; ++i) {
+        NEED(leaf_idx[i] >> log_leaves == 0, "merkle openings: claim %zu names a leaf outside the tree", i);
+        claims[5 * i] = leaf_idx[i];
+        for (int j = 0; j < 4; ++j) {
+            NEED(leaf_digests[4 * i + j] < glh::P, "merkle openings: claim %zu has a non-canonical digest word", i);
+            claims[5 * i + 1 + j] = leaf_digests[4 * i + j];
+        }
+    }
+    glh::hash_no_pad(claims.data(), claims.size(), pub + 5);
+    // the lookup challenges: the shared-challenge transcript of this one table's (public inputs, trace cap)
+    const uint64_t *ppub = nullptr, *pcap = nullptr;
+    size_t n_ppub = 0;
+    NEED(vx_stark_proof_peek(proof, plen, cfg->cap_height, &ppub, &n_ppub, &pcap), "the proof is too short to hold a trace cap");
+    uint64_t chal[4];
+    {
+        const uint64_t* pubs[1] = {pub};
+        const size_t n_pubs[1] = {(size_t)mop::PUB};
+        v_shared_challenges_n(pubs, n_pubs, &pcap, 1, (size_t)4 << cfg->cap_height, chal, 4);
+    }
+    const uint64_t* apub = nullptr;
+    int L = 0;
+    const int32_t rc = vx_stark_verify_ext(cfg, proof, plen, VX_AIR_MERKLE_OPEN, pub, mop::PUB, chal, &apub, &L, err, errlen);
+    if (rc != VX_OK) return rc;
+    // the verifier's side of the bus: it receives every claim once
+    const Fx zero{0, 0};
+    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
+    X2<Fx> sum{zero, zero};
+    for (size_t i = 0; i < n_idx; ++i) {
+        const uint64_t* c = claims.data() + 5 * i;
+        const X2<Fx> dlo = bus.open(Fx{c[0], 0}, Fx{c[1], 0}, Fx{c[2], 0}, bus::K<0>{}), dhi = bus.open(Fx{c[0], 0}, Fx{c[3], 0}, Fx{c[4], 0}, bus::K<1>{});
+        const X2<Fx> prod = dlo * dhi;
+        const Fx ni = fx_inv(prod.a * prod.a - f_mul7(prod.b * prod.b));  // 1 / D_lo + 1 / D_hi = (D_lo + D_hi) / (D_lo D_hi)
+        sum = sum + (dlo + dhi) * X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
+    }
+    const uint64_t rows = ((uint64_t)1 << L) % glh::P;
+    NEED(sum.a.b == 0 && sum.b.b == 0 && glh::mul(apub[0], rows) == sum.a.a && glh::mul(apub[1], rows) == sum.b.a,
+         "the openings the table proves are not the claimed ones (the lookup bus does not balance)");
+    return VX_OK;
+}
+
 // RotateCircuit verify (the provers are vx_rotate.hip and, for the verifier above, vx_header_range.hip; every host verifier lives
 // in this file, which holds no GPU code): the blob must be for this (authority_set_id, authority_set_hash) request and claim out32;
 // then its six STARKs are verified in their two shared-challenge groups against the public inputs those values imply, and both

@@ -29,6 +29,7 @@ SYMBOLS = [
     "vx_verify_epoch_end_header", "vx_rotate_proof_bound", "vx_rotate_prove", "vx_rotate_verify",
     "vx_gather_proofs", "vx_quotient_eval", "vx_decode_header_batch", "vx_decode_precommit_batch", "vx_stark_aux_trace",
     "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_unregister", "vx_poseidon_air_trace",
+    "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -40,6 +41,7 @@ VX_ED_AIR_COLS, VX_ED_AIR_AUX_COLS = 839, 688
 VX_AIR_SHA512 = {16: 11, 15: 14, 10: 13}
 VX_SHA512_AIR_COLS, VX_SHA512_AIR_AUX_COLS = 801, 4
 VX_AIR_EPOCH_END, VX_EPOCH_END_AIR_COLS, VX_EPOCH_END_AIR_AUX_COLS = 15, 52, 46
+VX_AIR_MERKLE_OPEN, VX_MERKLE_OPEN_AIR_COLS, VX_MERKLE_OPEN_AIR_AUX_COLS = 16, 66, 4
 
 
 class JustificationStruct(C.Structure):
@@ -161,6 +163,10 @@ def load_library():
         "vx_stark_aux_trace": [vp, C.c_int, vp, C.c_int, vp, sz, vp, sz, vp, vp],
         "vx_air_register": [C.POINTER(AirProgramStruct), C.POINTER(C.c_int), C.c_char_p, sz], "vx_air_unregister": [C.c_int],
         "vx_poseidon_air_trace": [vp, vp, sz, vp],
+        "vx_merkle_open_air_trace": [vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_merkle_openings_proof_bound": [C.POINTER(StarkConfig), sz, sz, C.POINTER(sz)],
+        "vx_merkle_openings_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_merkle_openings_verify": [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, vp, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -324,6 +330,29 @@ def rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg=None):
     o = np.frombuffer(bytes(out32), dtype=np.uint8).copy()
     err = C.create_string_buffer(256)
     rc = L.vx_rotate_verify(C.byref(cfg), _ptr(b), b.size, authority_set_id, _ptr(ah), _ptr(o), err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+MOPEN_MAGIC, MOPEN_HDR = 0x314E45504F4D5856, 4  # "VXMOPEN1": magic, log2(n_leaves), number of openings, proof length; then the MerkleOpenAir proof
+
+
+def merkle_openings_verify(blob, cap, log_leaves, leaf_idx, leaf_digests, cfg=None):
+    """Host-side check of a vx_merkle_openings_prove blob against the verifier's own claims: the tree's cap [2^cap_height][4],
+    log2(n_leaves), and the openings (leaf_idx[i], leaf_digests[i][4]) in order.  Walks no Merkle path; raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
+    cap_height = cp.shape[0].bit_length() - 1
+    if cp.shape[0] != 1 << cap_height:
+        raise ValueError("a cap has a power-of-two number of digests")
+    idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+    dig = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1)
+    if dig.size != 4 * idx.size:
+        raise ValueError("one 4-word digest per opening")
+    err = C.create_string_buffer(256)
+    rc = L.vx_merkle_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, _ptr(idx), _ptr(dig), idx.size, err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
 
@@ -496,6 +525,32 @@ class Context:
         out = out or self.alloc(48 * 32 * n_perm)
         self._ck(self.L.vx_poseidon_air_trace(self.h, states_buf.h, n_perm, out.h))
         return out
+
+    def merkle_open_air_trace(self, tree, leaf_idx, log_n, out=None):
+        """The witness of MerkleOpenAir for the openings leaf_idx of `tree` -> (Buffer [66][2^log_n], the 9 public inputs)."""
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        out = out or self.alloc(VX_MERKLE_OPEN_AIR_COLS << log_n)
+        pub = np.zeros(9, dtype=np.uint64)
+        self._ck(self.L.vx_merkle_open_air_trace(self.h, tree.h, _ptr(idx), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def merkle_openings_prove(self, tree, leaf_idx, cfg=None, out=None):
+        """Proves the openings leaf_idx of `tree` in one MerkleOpenAir table -> blob words (lib.merkle_openings_verify checks it).
+        out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        cfg = cfg or self.stark_config()
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        need = C.c_size_t(0)
+        if out is None:
+            rc = self.L.vx_merkle_openings_proof_bound(C.byref(cfg), tree.n_leaves, idx.size, C.byref(need))
+            if rc != 0:
+                raise VxError(rc, "merkle openings: %d openings of a tree of %d leaves" % (idx.size, tree.n_leaves))
+            out = np.empty(need.value, dtype=np.uint64)
+        rc = self.L.vx_merkle_openings_prove(self.h, C.byref(cfg), tree.h, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
+        if rc != 0:
+            e = VxError(rc, self.L.vx_last_error(self.h).decode())
+            e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
+            raise e
+        return out[: need.value]
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

@@ -163,7 +163,8 @@ typedef struct vx_stark_config {
  * time as a constraint PROGRAM (vx_air_register below; no auxiliary round).  The tables of the
  * header_range / rotate statements, each declared with its trace generator below: 6 Blake2b header chain
  * (VX_AIR_BLAKE_CHAIN), 4 SHA-256 authority-set commitment (VX_AIR_SHA_CHAIN), 7 / 8 / 9 SHA-256 Merkle trees of 256 /
- * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log. */
+ * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log.
+ * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -218,6 +219,35 @@ int32_t vx_air_unregister(int air_id);
  * round row; rows 30 / 31 of a block hold the permutation's output.  n_perm a power of two.  What a recursive verifier's hashing
  * table is filled with (plonky2 v0.2.0 hash/poseidon.rs; reached from Circuit::prove's recursion, circuits/header_range.rs:167). */
 int32_t vx_poseidon_air_trace(vx_ctx* ctx, const vx_buf* states, size_t n_perm, vx_buf* trace_out);
+/* ---- MerkleOpenAir: a batch of Merkle openings of ONE Poseidon tree proven in one STARK table (AIR id VX_AIR_MERKLE_OPEN; compiled:
+ * csrc/air_merkle_open.cuh) -- verify_merkle_proof_to_cap (plonky2 v0.2.0 hash/merkle_proofs.rs) for any number of leaves of a
+ * vx_tree, the first table of proof aggregation: a verifier accepts this table instead of walking the paths.
+ * One path of D = log2(n_leaves) levels is D blocks of 32 rows (one two-to-one compression each, PoseidonAir's columns and
+ * constraints); the table has no positional shape, so any number of paths of any depth fit the one AIR id at any log_n >= 5.
+ * PROVEN: for every opening (index, leaf digest) that the verifier names, the path from that leaf digest with the index bits as
+ * directions ends in the ROOT, the two-to-one fold of the tree's cap down to one digest (the cap itself at cap height 0).  The
+ * openings leave the table as messages on its logUp bus and the VERIFIER IS THE OTHER PARTY of that bus: the proof is accepted
+ * iff the table's published total equals the sum over the verifier's own claims.  Public inputs (9): root (4), D, and the claims
+ * digest hash_n_to_hash_no_pad((index, d0, d1, d2, d3) of every opening, in order), which makes the lookup challenges depend on
+ * the claims.  STILL OUTSIDE (the next tables): the opened leaf ROWS are not hashed in-proof (claims are leaf digests), there is
+ * one tree per proof, and the transcript and the evaluation at zeta stay on the host.
+ * vx_merkle_open_air_trace: the witness on its own (test surface) -- leaf_idx: n_idx >= 1 leaf indices (host; duplicates
+ *   allowed); trace_out: [VX_MERKLE_OPEN_AIR_COLS][2^log_n] with 2^log_n >= 32 n_idx D; blocks behind the paths are idle.
+ * vx_merkle_openings_prove: trace + proof at the smallest such log_n (>= 5) under lookup challenges that are the shared-challenge
+ *   transcript of this one table's (public inputs, trace cap).  Blob: the magic "VXMOPEN1", log2(n_leaves), n_idx, the proof's
+ *   length; then the table proof (vx_stark_prove layout).  VX_ERR_BUFSZ (with *blob_len set) when the buffer is too small.
+ * vx_merkle_openings_verify (host only, walks no Merkle path): rebuilds the public inputs from cap / leaf_idx / leaf_digests
+ *   (n_idx x 4 words), recomputes the challenges from the proof's cap, verifies the table under them and accepts iff
+ *   published total x 2^log_n = sum over the claims of 1/D_lo + 1/D_hi (the two messages of an opening: (index, d0, d1, 0) and
+ *   (index, d2, d3, 1)). */
+enum { VX_AIR_MERKLE_OPEN = 16, VX_MERKLE_OPEN_AIR_COLS = 66, VX_MERKLE_OPEN_AIR_AUX_COLS = 4 };
+int32_t vx_merkle_open_air_trace(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, vx_buf* trace_out,
+                                 uint64_t public_out[9]);
+int32_t vx_merkle_openings_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t n_idx, size_t* n_words);
+int32_t vx_merkle_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx,
+                                 uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* cap, int cap_height,
+                                  int log_leaves, const uint64_t* leaf_idx, const uint64_t* leaf_digests, size_t n_idx, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */

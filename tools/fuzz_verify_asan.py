@@ -2,7 +2,7 @@
 """Mutation fuzzing of the HOST verifier under AddressSanitizer + UBSan (CPU only; the verifier takes untrusted proofs).
 
 Builds vx_verify.hip host-only with -fsanitize=address,undefined, loads it in a child interpreter started with the sanitizer runtime
-preloaded, and feeds vx_stark_verify / vx_header_range_verify / vx_rotate_verify mutated proofs: seeds are real proofs of the small AIRs made by the CPU
+preloaded, and feeds vx_stark_verify / vx_header_range_verify / vx_rotate_verify / vx_merkle_openings_verify mutated proofs: seeds are real proofs of the small AIRs made by the CPU
 reference prover (oracle/stark_ref.py -- test infrastructure, used here to make inputs only).  Mutations: word flips, random words,
 truncation, extension, the degree-bits / length fields set to every small value, header words of a range blob set to extremes.
 Any sanitizer report aborts the child: the script fails.  Every mutated proof must also be REJECTED (a flipped word that is accepted
@@ -25,6 +25,79 @@ def build():
         return
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-fno-omit-frame-pointer", "-fPIC", "-fvisibility=hidden", "-shared", "-o", SO, SRC], cwd=os.path.dirname(SRC))
+
+
+def fuzz_merkle_openings(L, StarkConfig, rng, iters):
+    """vx_merkle_openings_verify on mutations of a real blob (a reference-prover proof of MerkleOpenAir's restatement,
+    tests/merkle_open_ref.py) and of the verifier's own claims -> (inputs, rejected)"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import merkle_open_ref as M
+    from oracle import oracle as O
+    from oracle import stark_ref as S
+
+    vp, sz = C.c_void_p, C.c_size_t
+    L.vx_merkle_openings_verify.argtypes = [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, vp, vp, sz, C.c_char_p, sz]
+    L.vx_merkle_openings_verify.restype = C.c_int32
+    ocfg = dict(S.DEFAULT_CFG, num_queries=4)
+    cfg = StarkConfig()
+    for k, v in ocfg.items():
+        setattr(cfg, k, v)
+    err = C.create_string_buffer(256)
+    tree = O.MerkleTree(rng.integers(0, O.P, size=(8, 8), dtype=np.uint64), 1)
+    idx = np.array([1, 6, 3], dtype=np.uint64)
+    trace, pub, digs = M.ref_trace(tree, [int(i) for i in idx])
+    seed = M.wrap(M.prove(trace, pub, ocfg), 3, idx.size)
+    cap = np.ascontiguousarray(tree.cap, dtype=np.uint64)
+
+    def verify(b, cap_=cap, cap_h=1, log_leaves=3, idx_=idx, digs_=digs):
+        b, idx_, digs_ = (np.ascontiguousarray(a, dtype=np.uint64) for a in (b, idx_, digs_))
+        return L.vx_merkle_openings_verify(C.byref(cfg), b.ctypes.data_as(vp), b.size, cap_.ctypes.data_as(vp), cap_h, log_leaves, idx_.ctypes.data_as(vp), digs_.ctypes.data_as(vp), idx_.size, err, 256)
+
+    assert verify(seed) == 0, err.value
+    n, total, rejected = seed.size, 0, 0
+    for it in range(max(iters // 4, 50)):
+        p, kw = seed.copy(), {}
+        kind = it % 7
+        if kind == 0:
+            p[rng.integers(n)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+        elif kind == 1:  # the blob header and the proof header set to small and extreme values
+            p[rng.integers(0, M.HDR + 16)] = np.uint64([0, 1, 2, 3, 4, 5, 26, 40, 41, n, n - M.HDR, 2**21, 2**32, 2**63, 2**64 - 1][rng.integers(15)])
+        elif kind == 2:
+            p = p[: rng.integers(0, n)]
+        elif kind == 3:  # ... truncated with a header that agrees with the cut
+            p = p[: rng.integers(M.HDR + 1, n)]
+            p[3] = np.uint64(p.size - M.HDR)
+        elif kind == 4:
+            a, b_ = sorted(int(x) for x in rng.integers(M.HDR, n, size=2))
+            p[a:b_] = rng.integers(0, 2**63, size=b_ - a, dtype=np.uint64)
+        elif kind == 5:  # the verifier's claims: an index or a digest word changed (in or out of range)
+            i2, d2 = idx.copy(), digs.copy()
+            if rng.integers(2):
+                i2[rng.integers(i2.size)] = np.uint64([0, 2, 7, 8, 2**40, 2**64 - 1][rng.integers(6)])
+            else:
+                d2.reshape(-1)[rng.integers(d2.size)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+            if (i2 == idx).all() and (d2 == digs).all():
+                continue
+            kw = dict(idx_=i2, digs_=d2)
+        else:  # the tree the verifier knows: a cap word, the cap height (the cap buffer holds 16 digests for it), the depth
+            c2 = np.zeros((16, 4), dtype=np.uint64)
+            c2[:2] = cap
+            which = int(rng.integers(3))
+            if which == 0:
+                c2[rng.integers(2), rng.integers(4)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+                kw = dict(cap_=c2)
+            elif which == 1:
+                kw = dict(cap_=c2, cap_h=int([-1, 0, 2, 3, 4, 17, 2**30][rng.integers(7)]))
+            else:
+                kw = dict(log_leaves=int([-1, 0, 1, 2, 4, 40, 41, 2**30][rng.integers(8)]))
+        total += 1
+        if not kw and p.size == n and (p == seed).all():
+            continue
+        assert verify(p, **kw) != 0, f"mutation kind {kind} of the merkle-openings blob / claims was ACCEPTED"
+        rejected += 1
+    return total, rejected
 
 
 def child(iters):
@@ -178,6 +251,9 @@ def child(iters):
         assert rot_verify(p) != 0, f"mutation kind {kind} of the rotate blob was ACCEPTED"
         total += 1
         rejected += 1
+    # the Merkle-openings blob and the claims its verifier is called with
+    t2, r2 = fuzz_merkle_openings(L, StarkConfig, rng, iters)
+    total, rejected = total + t2, rejected + r2
     # run-time AIR descriptors (vx_air_register + the host interpreter): random and mutated instruction streams must be refused or
     # registered without a sanitizer report; whatever registers is then run by the verifier on a real proof of another program
     # (it must reject: a different statement) and on that proof's mutations
