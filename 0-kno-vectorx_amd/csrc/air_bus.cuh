@@ -11,7 +11,7 @@
 #include "gl.cuh"
 
 namespace bus {
-enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8 };
+enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9 };
 
 // a slot known at compile time: 0 leaves its term out, 1 adds the bare power of gamma, so a kind that does not use a slot
 // (or whose tag is 0 or 1) costs what the hand-written sum cost
@@ -69,8 +69,11 @@ struct Bus {
     VX_HD X ed_msg(const S& part, const S& u1, const S& u2, const S& u3) const { return denom(beta, part, u1, u2, u3, K<TAG_EDMSG>{}); }
     // a part of the digest (8 slot + part, three 32-bit halves): Sha512Air -> EdAir
     VX_HD X ed_digest(const S& part, const S& h0, const S& h1, const S& h2) const { return denom(beta, part, h0, h1, h2, K<TAG_EDH>{}); }
-    // half of an opened leaf digest (leaf index, d[2 half], d[2 half + 1], half): MerkleOpenAir -> whoever holds the openings (the verifier)
+    // half of an opened leaf digest (leaf index, d[2 half], d[2 half + 1], half): MerkleOpenAir -> whoever holds the openings (the
+    // verifier of vx_merkle_openings_verify; LeafSpongeAir, which hashes the opened rows to these digests)
     template <class H>
     VX_HD X open(const S& index, const S& da, const S& db, const H& half) const { return denom(beta, index, da, db, half, K<TAG_OPEN>{}); }
+    // one word of an opened leaf row (leaf index, position in the row, word): LeafSpongeAir -> whoever holds the rows (the verifier)
+    VX_HD X row(const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, None{}, K<TAG_ROW>{}); }
 };
 }  // namespace bus

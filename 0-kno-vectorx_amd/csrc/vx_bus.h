@@ -111,6 +111,10 @@ static constexpr size_t VX_ROT_HDR = 28;
 // vx_verify.hip): magic, log2(n_leaves), number of openings, length of the MerkleOpenAir proof that follows
 static const uint64_t VX_MOPEN_MAGIC = 0x314e45504f4d5856ULL;  // "VXMOPEN1"
 static constexpr size_t VX_MOPEN_HDR = 4;
+// ---- Merkle-rows blob (written by vx_merkle_rows_prove in vx_leaf_sponge_air.hip, read by vx_merkle_rows_verify in vx_verify.hip):
+// magic, log2(n_leaves), leaf_len, number of openings, lengths of the MerkleOpenAir and the LeafSpongeAir proof that follow
+static const uint64_t VX_MROWS_MAGIC = 0x3153574f524d5856ULL;  // "VXMROWS1"
+static constexpr size_t VX_MROWS_HDR = 6;
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

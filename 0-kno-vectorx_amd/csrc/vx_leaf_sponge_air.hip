@@ -1,0 +1,298 @@
+// Witness and prover of LeafSpongeAir (air_leaf_sponge.cuh): the opened leaf rows of one tree hashed in one table, and the
+// two-table proof vx_merkle_rows_prove (MerkleOpenAir + LeafSpongeAir on one logUp bus).
+//   k_leaf_sponge_states  the blocks of one leaf are a CHAIN (block k needs the output of block k - 1), and the workload has few
+//                         leaves and long chains (84 leaves x 128 permutations at leaf_len 1018): latency-bound.  16 lanes per
+//                         leaf run the cooperative permutation of the tree builder (poseidon.cuh), gather the row from the
+//                         leaf data in any of the three layouts, and store the state ENTERING every block, the row (the
+//                         claims the public inputs digest) and the digest, which is compared with the tree's leaf digest
+//   k_leaf_sponge_trace   one lane per block: the blocks are independent once their entering states exist -- the lane writes
+//                         the shape columns and walks the 30 rounds (poseidon_air.cuh) over its 32 rows
+//   k_leaf_sponge_aux     one lane per block: ONE extension inversion for the block's five helpers (Montgomery batch over the
+//                         products of its denominator pairs), written to its 32 rows, and the block's running-sum increment
+//                         on its first row (vx_bus_close_dev scans it)
+// Parity: tests/test_gpu_leaf_sponge.py compares trace, auxiliary columns and both proofs with tests/leaf_sponge_ref.py and the
+// reference prover.
+#include <string.h>
+
+#include "air_leaf_sponge.cuh"
+#include "air_merkle_open.cuh"
+#include "glh_poseidon.h"
+#include "poseidon.cuh"
+#include "poseidon_air.cuh"
+#include "vx_bus.h"
+#include "vx_internal.h"
+
+namespace {
+using namespace lsp;
+
+struct SpongeArgs {
+    const uint64_t* data;         // the leaves, as vx_merkle_build reads them
+    const uint64_t* idx;          // [n_idx] leaf indices (< n_leaves: checked by the host)
+    const uint64_t* tree_leaves;  // the tree's leaf digests [n_leaves][4], or nullptr (the witness alone: nothing to compare with)
+    size_t n_leaves, leaf_len, n_idx, n_blk;  // n_blk = ceil(leaf_len / 8) blocks per leaf
+    int log_leaves;
+    uint64_t* states;   // [n_idx n_blk][12]: the state entering every block
+    uint64_t* claims;   // [n_idx][1 + leaf_len]: (index, row)
+    uint64_t* digests;  // [n_idx][4]
+    uint64_t* bad;      // 1 + the number of an opening whose digest is not the tree's (0: none)
+};
+
+// (Tried: one lane per leaf with the tree builder's poseidon_permute -- 6.23 ms against 2.30 ms for 84 leaves x 128 blocks,
+// profiles/README.md "LeafSpongeAir": 84 chains cannot fill the chip, so the shorter chain per permutation wins.)
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_leaf_sponge_states(SpongeArgs a) {
+    __shared__ uint64_t lds[16 * 12];
+    const int l = threadIdx.x & 15, grp = threadIdx.x >> 4;
+    const size_t t = blockIdx.x * (size_t)16 + grp;
+    const bool live = t < a.n_idx;
+    const size_t p = live ? t : a.n_idx - 1;  // surplus groups redo the last leaf and do not write
+    const uint64_t j = a.idx[p];
+    const size_t r = LAYOUT == VX_LEAVES_COLS_BITREV ? brev32((uint32_t)j, a.log_leaves) : j;
+    const size_t estride = LAYOUT == VX_LEAVES_ROW_MAJOR ? 1 : a.n_leaves;
+    const uint64_t* src = LAYOUT == VX_LEAVES_ROW_MAJOR ? a.data + r * a.leaf_len : a.data + r;
+    uint64_t* claim = a.claims + p * (a.leaf_len + 1);
+    if (live && l == 0) claim[0] = j;
+    uint64_t s = 0;
+    for (size_t k = 0; k < a.n_blk; ++k) {
+        const size_t e = 8 * k + l;
+        if (l < 8 && e < a.leaf_len) {  // overwrite mode: a word behind the tail keeps the previous output
+            s = gl_canon(src[e * estride]);
+            if (live) claim[1 + e] = s;
+        }
+        if (live && l < 12) a.states[(p * a.n_blk + k) * 12 + l] = s;
+        s = poseidon_permute_coop(s, l, lds + 12 * grp);
+    }
+    if (live && l < 4) {
+        a.digests[4 * p + l] = s;
+        if (a.tree_leaves && gl_canon(a.tree_leaves[4 * j + l]) != s) *a.bad = p + 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __restrict__ states, const uint64_t* __restrict__ idx, size_t n_idx, size_t n_blk, size_t n,
+                                                          uint64_t* __restrict__ tr) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= n / 32) return;
+    uint64_t s[12], shape[COLS - MSG];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = 0;
+#pragma unroll
+    for (int j = 0; j < COLS - MSG; ++j) shape[j] = 0;
+    if (b < n_idx * n_blk) {
+        const size_t p = b / n_blk, k = b - p * n_blk;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s[i] = states[12 * b + i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) shape[i] = s[i];
+        shape[IDX - MSG] = idx[p], shape[POS - MSG] = k, shape[ACT - MSG] = 1;
+        shape[FIRSTB - MSG] = k == 0, shape[LASTB - MSG] = k + 1 == n_blk, shape[NXL - MSG] = k + 2 == n_blk;
+    }
+    poseidon_air_walk(s, tr, n, 32 * b);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) shape[DIG - MSG + i] = s[i];
+#pragma unroll
+    for (int j = 0; j < COLS - MSG; ++j) {  // (unrolled: shape[] stays in registers)
+        uint64_t* col = tr + (size_t)(MSG + j) * n + 32 * b;
+        const uint64_t v = shape[j];
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) col[r] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint32_t wmask) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= n / 32) return;
+    const size_t row = 32 * b;
+    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
+    gl2 h[N_HELP];
+#pragma unroll
+    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
+    if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the five message pairs, with one inversion
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        const uint64_t idx = cell(IDX), pos8 = 8 * cell(POS), last = cell(LASTB);
+        gl2 num[N_HELP], den[N_HELP], pre[N_HELP];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint64_t ma = last ? (wmask >> (2 * e)) & 1 : 1, mb = last ? (wmask >> (2 * e + 1)) & 1 : 1;
+            const gl2 da = bus.row(idx, pos8 + 2 * e, cell(MSG + 2 * e)), db = bus.row(idx, pos8 + 2 * e + 1, cell(MSG + 2 * e + 1));
+            num[e] = gl2_add(gl2_scale(db, ma), gl2_scale(da, mb)), den[e] = gl2_mul(da, db);
+        }
+        {
+            const gl2 dlo = bus.open(idx, cell(DIG), cell(DIG + 1), bus::K<0>{}), dhi = bus.open(idx, cell(DIG + 2), cell(DIG + 3), bus::K<1>{});
+            num[4] = gl2_scale(gl2_add(dlo, dhi), last ? GL_P - 1 : 0), den[4] = gl2_mul(dlo, dhi);  // received: multiplicity -LASTB
+        }
+        pre[0] = den[0];
+#pragma unroll
+        for (int e = 1; e < N_HELP; ++e) pre[e] = gl2_mul(pre[e - 1], den[e]);
+        gl2 inv = gl2_inv(pre[N_HELP - 1]);
+#pragma unroll
+        for (int e = N_HELP - 1; e >= 1; --e) {
+            h[e] = gl2_mul(num[e], gl2_mul(inv, pre[e - 1]));
+            inv = gl2_mul(inv, den[e]);
+        }
+        h[0] = gl2_mul(num[0], inv);
+    }
+    gl2 sum = h[0];
+#pragma unroll
+    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
+#pragma unroll
+    for (int e = 0; e < N_HELP; ++e) {
+        uint64_t *ca = aux + (size_t)(2 * e) * n + row, *cb = aux + (size_t)(2 * e + 1) * n + row;
+        const gl2 v = h[e];
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) ca[r] = v.a, cb[r] = v.b;
+    }
+    uint64_t *za = aux + (size_t)(2 * N_HELP) * n + row, *zb = aux + (size_t)(2 * N_HELP + 1) * n + row;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
+}
+
+int ceil_log2(size_t x) {
+    int l = 0;
+    while (((size_t)1 << l) < x) ++l;
+    return l;
+}
+size_t sponge_blocks(size_t leaf_len) { return (leaf_len + 7) / 8; }
+// rows (log2) of the smallest table that holds n_idx leaves of leaf_len words (>= 5)
+int leaf_sponge_log_n(size_t n_idx, size_t leaf_len) { return ceil_log2(32 * n_idx * sponge_blocks(leaf_len)); }
+constexpr size_t MAX_LEAF_LEN = (size_t)1 << 20;
+
+// L, B, the tail flags; the digest is the caller's
+void sponge_shape_public(size_t leaf_len, uint64_t* pub) {
+    const size_t t = leaf_len % 8;
+    pub[PUB_L] = leaf_len, pub[PUB_B] = sponge_blocks(leaf_len);
+    for (size_t i = 0; i < 8; ++i) pub[PUB_W + i] = i < (t ? t : 8);
+}
+}  // namespace
+
+int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n, blocks = n / 32;
+    uint32_t wmask = 0;
+    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
+    hipLaunchKernelGGL(k_leaf_sponge_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
+
+// The witness of LeafSpongeAir on the device.  data_d: the leaves of the whole tree ([n_leaves x leaf_len] words in `layout`; the
+// caller has checked that the buffer holds them).  tree_leaves (device, may be nullptr): the leaf digests of the tree the openings
+// are proven against -- a row that does not hash to its leaf digest is refused with VX_ERR_STATEMENT before anything is proven.
+static int32_t leaf_sponge_trace_dev(vx_ctx* ctx, const uint64_t* data_d, size_t n_leaves, size_t leaf_len, int layout, const uint64_t* tree_leaves, const uint64_t* leaf_idx,
+                                     size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[PUB]) {
+    const int log_leaves = ceil_log2(n_leaves);
+    VX_CHECK(n_leaves >= 1 && ((size_t)1 << log_leaves) == n_leaves && log_leaves <= 32, "leaf sponge: %zu leaves (a power of two, at most 2^32)", n_leaves);
+    VX_CHECK(layout >= 0 && layout <= 2, "leaf sponge: bad layout %d", layout);
+    VX_CHECK(leaf_len >= 5 && leaf_len <= MAX_LEAF_LEN, "leaf sponge: leaf_len %zu (5..2^20; a row of at most 4 words is its own digest and has no sponge)", leaf_len);
+    VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "leaf sponge: %zu openings (1..2^21)", n_idx);
+    const size_t n_blk = sponge_blocks(leaf_len);
+    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * n_idx * n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", n_idx, n_blk, log_n);
+    for (size_t i = 0; i < n_idx; ++i) VX_CHECK(leaf_idx[i] < n_leaves, "leaf sponge: index %zu (%llu) is not a leaf of the tree", i, (unsigned long long)leaf_idx[i]);
+    const size_t n = (size_t)1 << log_n, w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 1);
+    // scratch: the entering states, the indices, the claims, the digests, the mismatch word
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1) * 8);
+    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
+    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx;
+    std::vector<uint64_t> claims(w_claims);
+    uint64_t bad = 0;
+    int32_t rc = VX_OK;
+    do {
+        hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(bad_d, 0, 8, ctx->stream);
+        if (e != hipSuccess) {
+            rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
+            break;
+        }
+        const SpongeArgs a{data_d, idx_d, tree_leaves, n_leaves, leaf_len, n_idx, n_blk, log_leaves, states, claims_d, digests_d, bad_d};
+        const dim3 grid((unsigned)((n_idx + 15) / 16)), block(256);  // 16 lanes per leaf
+        if (layout == VX_LEAVES_ROW_MAJOR) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_ROW_MAJOR>, grid, block, 0, ctx->stream, a);
+        else if (layout == VX_LEAVES_COLS_BITREV) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS_BITREV>, grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS>, grid, block, 0, ctx->stream, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_leaf_sponge_trace, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, w_claims * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
+    } while (0);
+    vx_pool_free(ctx, sc);
+    VX_TRY(rc);
+    if (bad)
+        return vx_fail(ctx, VX_ERR_STATEMENT, "merkle rows: opening %llu (leaf %llu) does not hash to the tree's leaf digest -- the leaf data is not what the tree was built from",
+                       (unsigned long long)(bad - 1), (unsigned long long)leaf_idx[bad - 1]);
+    sponge_shape_public(leaf_len, pub_out);
+    glh::hash_no_pad(claims.data(), claims.size(), pub_out + PUB_DIGEST);
+    return VX_OK;
+}
+
+extern "C" {
+int32_t vx_leaf_sponge_air_trace(vx_ctx* ctx, const vx_buf* data, size_t off, size_t n_leaves, size_t leaf_len, int layout, const uint64_t* leaf_idx, size_t n_idx, int log_n,
+                                 vx_buf* trace_out, uint64_t public_out[14]) {
+    if (!ctx || !data || !leaf_idx || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_CHECK(leaf_len >= 5 && leaf_len <= MAX_LEAF_LEN && n_leaves <= ((size_t)1 << 32) && off <= data->n && n_leaves * leaf_len <= data->n - off,
+             "leaf sponge: %zu leaves x %zu words (leaf_len 5..2^20) exceed the buffer", n_leaves, leaf_len);
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, COLS, log_n);
+    return leaf_sponge_trace_dev(ctx, data->d + off, n_leaves, leaf_len, layout, nullptr, leaf_idx, n_idx, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_merkle_rows_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t leaf_len, size_t n_idx, size_t* n_words) {
+    if (!cfg || !n_words || n_leaves < 2 || (n_leaves & (n_leaves - 1)) || n_idx < 1 || n_idx > ((size_t)1 << 21) || leaf_len < 5 || leaf_len > MAX_LEAF_LEN) return VX_ERR_ARG;
+    const int log_open = vx_merkle_open_log_n(n_idx, ceil_log2(n_leaves)), log_sponge = leaf_sponge_log_n(n_idx, leaf_len);
+    if (log_open > 26 || log_sponge > 26) return VX_ERR_ARG;
+    size_t wo = 0, ws = 0;
+    int32_t rc = vx_stark_proof_bound(VX_AIR_MERKLE_OPEN, cfg, log_open, &wo);
+    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_LEAF_SPONGE, cfg, log_sponge, &ws);
+    if (rc != VX_OK) return rc;
+    *n_words = VX_MROWS_HDR + wo + ws;
+    return VX_OK;
+}
+
+int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_tree* tree, const vx_buf* data, size_t off, size_t leaf_len, int layout, const uint64_t* leaf_idx,
+                             size_t n_idx, uint64_t* blob_out, size_t blob_cap, size_t* blob_len) {
+    if (!ctx || !cfg || !tree || !data || !leaf_idx || !blob_len) return VX_ERR_ARG;
+    const size_t n_leaves = tree->n_leaves;
+    const int depth = ceil_log2(n_leaves);
+    VX_CHECK(depth >= 1 && depth <= 32 && n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle rows: %zu openings of a tree of %zu leaves", n_idx, n_leaves);
+    VX_CHECK(leaf_len >= 5 && leaf_len <= MAX_LEAF_LEN, "merkle rows: leaf_len %zu (5..2^20; a row of at most 4 words is its own digest: vx_merkle_openings_prove covers it)", leaf_len);
+    VX_CHECK(layout >= 0 && layout <= 2, "merkle rows: bad layout %d", layout);
+    VX_CHECK(off <= data->n && n_leaves * leaf_len <= data->n - off, "merkle rows: %zu leaves x %zu words exceed the buffer", n_leaves, leaf_len);
+    for (size_t i = 0; i < n_idx; ++i) VX_CHECK(leaf_idx[i] < n_leaves, "merkle rows: index %zu (%llu) is not a leaf of the tree", i, (unsigned long long)leaf_idx[i]);
+    const int log_open = vx_merkle_open_log_n(n_idx, depth), log_sponge = leaf_sponge_log_n(n_idx, leaf_len);
+    VX_CHECK(log_open <= 26 && log_sponge <= 26, "merkle rows: %zu openings of %zu words in a tree of depth %d need more than 2^26 rows", n_idx, leaf_len, depth);
+    // two tables on one bus, in transcript order: the openings (a side context, its own host thread), the sponge (this context)
+    BusMeet rv;
+    rv.n_parties = 2;
+    BusParty party[2] = {{&rv, 0}, {&rv, 1}};
+    const vx_chal_hook hooks[2] = {{vx_bus_hook, &party[0]}, {vx_bus_hook, &party[1]}};
+    TableJob open, sponge;
+    vx_ctx* side[1];
+    VX_TRY(side_contexts(ctx, 1, side, "merkle rows: no side context for the openings table"));
+    open.c = side[0], sponge.c = ctx;
+    // the tree and the leaf data are the work of this context's stream; the openings table reads the tree from another one
+    VX_HIP(hipStreamSynchronize(ctx->stream));
+    auto prove_open = [&](vx_ctx* c, TableJob& j) -> int32_t {
+        return run_table(c, j, VX_AIR_MERKLE_OPEN, log_open, mop::COLS, mop::PUB, cfg, &hooks[0], 0,
+                         [&](vx_ctx* c2, vx_buf* trace, uint64_t* pub) { return vx_merkle_open_trace_dev(c2, tree, leaf_idx, n_idx, log_open, trace->d, pub); });
+    };
+    TableJoin threads{{&open}};  // every exit path waits for the thread
+    int32_t rc = VX_OK;
+    if (!start_table(open, rv, 0, prove_open)) rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle rows: no host thread for the openings table");
+    if (rc == VX_OK)
+        rc = run_table(ctx, sponge, VX_AIR_LEAF_SPONGE, log_sponge, COLS, PUB, cfg, &hooks[1], 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+            return leaf_sponge_trace_dev(c, data->d + off, n_leaves, leaf_len, layout, tree->levels, leaf_idx, n_idx, log_sponge, trace->d, pub);
+        });
+    if (rc != VX_OK) rv.fail(1);
+    threads.join();
+    if (rc == VX_OK && open.rc != VX_OK) rc = vx_fail(ctx, open.rc, "merkle rows: %s", vx_last_error(open.c)[0] ? vx_last_error(open.c) : "the openings table failed");
+    if (rc != VX_OK) return rc;
+    const size_t total = VX_MROWS_HDR + open.len + sponge.len;
+    *blob_len = total;
+    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "merkle rows: the blob needs %zu words, buffer has %zu", total, blob_cap);
+    blob_out[0] = VX_MROWS_MAGIC, blob_out[1] = (uint64_t)depth, blob_out[2] = leaf_len, blob_out[3] = n_idx, blob_out[4] = open.len, blob_out[5] = sponge.len;
+    memcpy(blob_out + VX_MROWS_HDR, open.proof.data(), open.len * 8);
+    memcpy(blob_out + VX_MROWS_HDR + open.len, sponge.proof.data(), sponge.len * 8);
+    return VX_OK;
+}
+}  // extern "C"

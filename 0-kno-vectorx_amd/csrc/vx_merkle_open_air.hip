@@ -105,7 +105,7 @@ int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, co
 }
 
 // rows (log2) of the table: the smallest power of two that holds n_idx paths of `depth` blocks
-static int merkle_open_log_n(size_t n_idx, int depth) { return ceil_log2(32 * n_idx * (size_t)depth); }  // >= 5: n_idx, depth >= 1
+int vx_merkle_open_log_n(size_t n_idx, int depth) { return ceil_log2(32 * n_idx * (size_t)depth); }  // >= 5: n_idx, depth >= 1
 
 int32_t vx_merkle_open_trace_dev(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[9]) {
     const int depth = ceil_log2(tree->n_leaves);
@@ -155,7 +155,7 @@ int32_t vx_merkle_open_air_trace(vx_ctx* ctx, const vx_tree* tree, const uint64_
 
 int32_t vx_merkle_openings_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t n_idx, size_t* n_words) {
     if (!cfg || !n_words || n_leaves < 2 || (n_leaves & (n_leaves - 1)) || n_idx < 1 || n_idx > ((size_t)1 << 21)) return VX_ERR_ARG;
-    const int log_n = merkle_open_log_n(n_idx, ceil_log2(n_leaves));
+    const int log_n = vx_merkle_open_log_n(n_idx, ceil_log2(n_leaves));
     if (log_n > 26) return VX_ERR_ARG;
     size_t w = 0;
     const int32_t rc = vx_stark_proof_bound(VX_AIR_MERKLE_OPEN, cfg, log_n, &w);
@@ -169,7 +169,7 @@ int32_t vx_merkle_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const 
     if (!ctx || !cfg || !tree || !leaf_idx || !blob_len) return VX_ERR_ARG;
     const int depth = ceil_log2(tree->n_leaves);
     VX_CHECK(depth >= 1 && n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings of a tree of %zu leaves", n_idx, tree->n_leaves);
-    const int log_n = merkle_open_log_n(n_idx, depth);
+    const int log_n = vx_merkle_open_log_n(n_idx, depth);
     VX_CHECK(log_n <= 26, "merkle openings: %zu paths of %d levels need more than 2^26 rows", n_idx, depth);
     TableJob job;
     const vx_chal_hook hook{one_table_hook, nullptr};

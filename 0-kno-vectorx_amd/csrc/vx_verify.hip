@@ -793,6 +793,109 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
     return VX_OK;
 }
 
+// Merkle rows (the prover is vx_leaf_sponge_air.hip): two tables on one bus.  The verifier holds what a STARK verifier holds --
+// (index, opened ROW) pairs of a tree it knows by its cap -- and is the other party of the ROW bus: LeafSpongeAir sends every word
+// it absorbs, receives the leaf digests MerkleOpenAir sends (TAG_OPEN closes between the two tables), and MerkleOpenAir proves
+// those digests lie under the root.  LeafSpongeAir's public inputs are rebuilt entirely from the arguments; of MerkleOpenAir's,
+// root and depth are.  Its claims digest cannot be: the verifier never sees the leaf digests.  Those four words are taken from
+// the proof's own public inputs (checked canonical); they ONLY feed the shared transcript -- the digests themselves are bound
+// by the sponge table's committed trace, and the challenges depend on the rows through the sponge table's own claims digest.
+// Accepted iff both tables verify under the shared challenges and
+//     total_open x rows_open + total_sponge x rows_sponge = sum over the claims, j < leaf_len of 1 / D_row(index, j, row[j]).
+// No Merkle path is walked and no leaf is hashed; the row-claims digest costs as many permutations as hashing the rows would.
+int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* cap, int cap_height, int log_leaves, size_t leaf_len,
+                              const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, char* err, size_t errlen) {
+    if (!cfg || !blob || !cap || !leaf_idx || !rows) return VX_ERR_ARG;
+    NEED(log_leaves >= 1 && log_leaves <= 32 && cap_height >= 0 && cap_height <= 16 && cap_height <= log_leaves, "merkle rows: cap height %d / tree depth %d out of range", cap_height,
+         log_leaves);
+    NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle rows: %zu openings (1..2^21)", n_idx);
+    NEED(leaf_len >= 5 && leaf_len <= ((size_t)1 << 20), "merkle rows: leaf_len %zu (5..2^20)", leaf_len);
+    NEED(len > VX_MROWS_HDR && blob[0] == VX_MROWS_MAGIC, "bad merkle-rows blob");
+    NEED(blob[1] == (uint64_t)log_leaves && blob[2] == (uint64_t)leaf_len && blob[3] == (uint64_t)n_idx, "blob is for a different request");
+    const size_t body = len - VX_MROWS_HDR;
+    NEED(blob[4] >= 1 && blob[4] < body && blob[5] == body - blob[4], "blob lengths are inconsistent");
+    const uint64_t *p_open = blob + VX_MROWS_HDR, *p_sponge = p_open + blob[4];
+    const size_t l_open = blob[4], l_sponge = blob[5];
+    const uint64_t *ppub[2] = {nullptr, nullptr}, *pcap[2] = {nullptr, nullptr};
+    size_t n_ppub[2] = {0, 0};
+    NEED(vx_stark_proof_peek(p_open, l_open, cfg->cap_height, &ppub[0], &n_ppub[0], &pcap[0]) && vx_stark_proof_peek(p_sponge, l_sponge, cfg->cap_height, &ppub[1], &n_ppub[1], &pcap[1]),
+         "a proof is too short to hold a trace cap");
+    // MerkleOpenAir's public inputs: root and depth from the arguments, the claims digest from the proof itself
+    uint64_t opub[mop::PUB], spub[lsp::PUB];
+    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height));
+    for (uint64_t w : fold) NEED(w < glh::P, "merkle rows: non-canonical cap word");
+    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
+        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
+    memcpy(opub, fold.data(), 32);
+    opub[4] = (uint64_t)log_leaves;
+    NEED(n_ppub[0] == (size_t)mop::PUB, "merkle rows: the openings table has %zu public inputs", n_ppub[0]);
+    for (int j = 5; j < mop::PUB; ++j) {
+        NEED(ppub[0][j] < glh::P, "merkle rows: non-canonical claims digest in the openings table");
+        opub[j] = ppub[0][j];
+    }
+    // LeafSpongeAir's public inputs: leaf_len, blocks per row, tail flags, the digest of (index, row) over all claims
+    std::vector<uint64_t> claims(n_idx * (leaf_len + 1));
+    for (size_t i = 0; i < n_idx; ++i) {
+        NEED(leaf_idx[i] >> log_leaves == 0, "merkle rows: claim %zu names a leaf outside the tree", i);
+        uint64_t* c = claims.data() + i * (leaf_len + 1);
+        c[0] = leaf_idx[i];
+        for (size_t j = 0; j < leaf_len; ++j) {
+            NEED(rows[i * leaf_len + j] < glh::P, "merkle rows: claim %zu has a non-canonical word at %zu", i, j);
+            c[1 + j] = rows[i * leaf_len + j];
+        }
+    }
+    {
+        const size_t t = leaf_len % 8;
+        spub[lsp::PUB_L] = leaf_len, spub[lsp::PUB_B] = (leaf_len + 7) / 8;
+        for (size_t i = 0; i < 8; ++i) spub[lsp::PUB_W + i] = i < (t ? t : 8);
+        glh::hash_no_pad(claims.data(), claims.size(), spub + lsp::PUB_DIGEST);
+    }
+    // the lookup challenges: the shared-challenge transcript of both tables, openings first
+    uint64_t chal[4];
+    {
+        const uint64_t* pubs[2] = {opub, spub};
+        const size_t n_pubs[2] = {(size_t)mop::PUB, (size_t)lsp::PUB};
+        v_shared_challenges_n(pubs, n_pubs, pcap, 2, (size_t)4 << cfg->cap_height, chal, 4);
+    }
+    const uint64_t *apub_o = nullptr, *apub_s = nullptr;
+    int Lo = 0, Ls = 0;
+    int32_t rc = vx_stark_verify_ext(cfg, p_open, l_open, VX_AIR_MERKLE_OPEN, opub, mop::PUB, chal, &apub_o, &Lo, err, errlen);
+    if (rc != VX_OK) return rc;
+    rc = vx_stark_verify_ext(cfg, p_sponge, l_sponge, VX_AIR_LEAF_SPONGE, spub, lsp::PUB, chal, &apub_s, &Ls, err, errlen);
+    if (rc != VX_OK) return rc;
+    // the verifier's side of the row bus: it receives every word of every claim once.  One inversion for all of them
+    // (Montgomery batch: prefix products, one inverse, walked back)
+    const Fx zero{0, 0};
+    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
+    const size_t n_msg = n_idx * leaf_len;
+    std::vector<X2<Fx>> den(n_msg), pre(n_msg);
+    for (size_t i = 0; i < n_idx; ++i) {
+        const uint64_t* c = claims.data() + i * (leaf_len + 1);
+        for (size_t j = 0; j < leaf_len; ++j) {
+            const size_t k = i * leaf_len + j;
+            den[k] = bus.row(Fx{c[0], 0}, Fx{(uint64_t)j, 0}, Fx{c[1 + j], 0});
+            pre[k] = k ? pre[k - 1] * den[k] : den[k];
+        }
+    }
+    X2<Fx> inv;
+    {
+        const X2<Fx>& prod = pre[n_msg - 1];
+        const Fx norm = prod.a * prod.a - f_mul7(prod.b * prod.b);
+        NEED(norm.a != 0 || norm.b != 0, "merkle rows: a claim's message has a zero denominator under the challenges");
+        const Fx ni = fx_inv(norm);
+        inv = X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
+    }
+    X2<Fx> sum{zero, zero};
+    for (size_t k = n_msg; k-- > 0;) {
+        sum = sum + (k ? inv * pre[k - 1] : inv);
+        inv = inv * den[k];
+    }
+    const uint64_t rows_o = ((uint64_t)1 << Lo) % glh::P, rows_s = ((uint64_t)1 << Ls) % glh::P;
+    const uint64_t ta = glh::add(glh::mul(apub_o[0], rows_o), glh::mul(apub_s[0], rows_s)), tb = glh::add(glh::mul(apub_o[1], rows_o), glh::mul(apub_s[1], rows_s));
+    NEED(sum.a.b == 0 && sum.b.b == 0 && ta == sum.a.a && tb == sum.b.a, "the rows the tables prove are not the claimed ones (the lookup bus does not balance)");
+    return VX_OK;
+}
+
 // RotateCircuit verify (the provers are vx_rotate.hip and, for the verifier above, vx_header_range.hip; every host verifier lives
 // in this file, which holds no GPU code): the blob must be for this (authority_set_id, authority_set_hash) request and claim out32;
 // then its six STARKs are verified in their two shared-challenge groups against the public inputs those values imply, and both

@@ -30,6 +30,7 @@ SYMBOLS = [
     "vx_gather_proofs", "vx_quotient_eval", "vx_decode_header_batch", "vx_decode_precommit_batch", "vx_stark_aux_trace",
     "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_unregister", "vx_poseidon_air_trace",
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
+    "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -42,6 +43,7 @@ VX_AIR_SHA512 = {16: 11, 15: 14, 10: 13}
 VX_SHA512_AIR_COLS, VX_SHA512_AIR_AUX_COLS = 801, 4
 VX_AIR_EPOCH_END, VX_EPOCH_END_AIR_COLS, VX_EPOCH_END_AIR_AUX_COLS = 15, 52, 46
 VX_AIR_MERKLE_OPEN, VX_MERKLE_OPEN_AIR_COLS, VX_MERKLE_OPEN_AIR_AUX_COLS = 16, 66, 4
+VX_AIR_LEAF_SPONGE, VX_LEAF_SPONGE_AIR_COLS, VX_LEAF_SPONGE_AIR_AUX_COLS = 17, 66, 12
 
 
 class JustificationStruct(C.Structure):
@@ -167,6 +169,10 @@ def load_library():
         "vx_merkle_openings_proof_bound": [C.POINTER(StarkConfig), sz, sz, C.POINTER(sz)],
         "vx_merkle_openings_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_merkle_openings_verify": [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, vp, vp, sz, C.c_char_p, sz],
+        "vx_leaf_sponge_air_trace": [vp, vp, sz, sz, sz, C.c_int, vp, sz, C.c_int, vp, vp],
+        "vx_merkle_rows_proof_bound": [C.POINTER(StarkConfig), sz, sz, sz, C.POINTER(sz)],
+        "vx_merkle_rows_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, sz, C.c_int, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_merkle_rows_verify": [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, sz, vp, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -353,6 +359,30 @@ def merkle_openings_verify(blob, cap, log_leaves, leaf_idx, leaf_digests, cfg=No
         raise ValueError("one 4-word digest per opening")
     err = C.create_string_buffer(256)
     rc = L.vx_merkle_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, _ptr(idx), _ptr(dig), idx.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+MROWS_MAGIC, MROWS_HDR = 0x3153574F524D5856, 6  # "VXMROWS1": magic, log2(n_leaves), leaf_len, openings, two proof lengths; then the MerkleOpenAir and the LeafSpongeAir proof
+
+
+def merkle_rows_verify(blob, cap, log_leaves, leaf_idx, rows, cfg=None):
+    """Host-side check of a vx_merkle_rows_prove blob against the verifier's own claims: the tree's cap [2^cap_height][4],
+    log2(n_leaves), and the opened rows (leaf_idx[i], rows[i][leaf_len]) in order.  Walks no Merkle path and hashes no leaf; raises
+    VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
+    cap_height = cp.shape[0].bit_length() - 1
+    if cp.shape[0] != 1 << cap_height:
+        raise ValueError("a cap has a power-of-two number of digests")
+    idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64)
+    if rw.ndim != 2 or rw.shape[0] != idx.size:
+        raise ValueError("one row [leaf_len] per opening")
+    err = C.create_string_buffer(256)
+    rc = L.vx_merkle_rows_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, rw.shape[1], _ptr(idx), _ptr(rw), idx.size, err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
 
@@ -546,6 +576,34 @@ class Context:
                 raise VxError(rc, "merkle openings: %d openings of a tree of %d leaves" % (idx.size, tree.n_leaves))
             out = np.empty(need.value, dtype=np.uint64)
         rc = self.L.vx_merkle_openings_prove(self.h, C.byref(cfg), tree.h, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
+        if rc != 0:
+            e = VxError(rc, self.L.vx_last_error(self.h).decode())
+            e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
+            raise e
+        return out[: need.value]
+
+    def leaf_sponge_air_trace(self, data, n_leaves, leaf_len, layout, leaf_idx, log_n, off=0, out=None):
+        """The witness of LeafSpongeAir for the rows leaf_idx of the leaves in `data` (as Context.merkle takes them)
+        -> (Buffer [66][2^log_n], the 14 public inputs)."""
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        out = out or self.alloc(VX_LEAF_SPONGE_AIR_COLS << log_n)
+        pub = np.zeros(14, dtype=np.uint64)
+        self._ck(self.L.vx_leaf_sponge_air_trace(self.h, data.h, off, n_leaves, leaf_len, layout, _ptr(idx), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def merkle_rows_prove(self, tree, data, leaf_len, layout, leaf_idx, cfg=None, out=None, off=0):
+        """Proves the openings leaf_idx of `tree` and hashes the opened rows of `data` (what the tree was built from) in two
+        tables on one bus -> blob words (lib.merkle_rows_verify checks it).  out: a caller's uint64 buffer; when it is too small
+        the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        cfg = cfg or self.stark_config()
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        need = C.c_size_t(0)
+        if out is None:
+            rc = self.L.vx_merkle_rows_proof_bound(C.byref(cfg), tree.n_leaves, leaf_len, idx.size, C.byref(need))
+            if rc != 0:
+                raise VxError(rc, "merkle rows: %d openings of %d words of a tree of %d leaves" % (idx.size, leaf_len, tree.n_leaves))
+            out = np.empty(need.value, dtype=np.uint64)
+        rc = self.L.vx_merkle_rows_prove(self.h, C.byref(cfg), tree.h, data.h, off, leaf_len, layout, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
         if rc != 0:
             e = VxError(rc, self.L.vx_last_error(self.h).decode())
             e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs

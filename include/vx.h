@@ -164,7 +164,8 @@ typedef struct vx_stark_config {
  * header_range / rotate statements, each declared with its trace generator below: 6 Blake2b header chain
  * (VX_AIR_BLAKE_CHAIN), 4 SHA-256 authority-set commitment (VX_AIR_SHA_CHAIN), 7 / 8 / 9 SHA-256 Merkle trees of 256 /
  * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log.
- * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove. */
+ * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove.
+ * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -229,8 +230,9 @@ int32_t vx_poseidon_air_trace(vx_ctx* ctx, const vx_buf* states, size_t n_perm, 
  * openings leave the table as messages on its logUp bus and the VERIFIER IS THE OTHER PARTY of that bus: the proof is accepted
  * iff the table's published total equals the sum over the verifier's own claims.  Public inputs (9): root (4), D, and the claims
  * digest hash_n_to_hash_no_pad((index, d0, d1, d2, d3) of every opening, in order), which makes the lookup challenges depend on
- * the claims.  STILL OUTSIDE (the next tables): the opened leaf ROWS are not hashed in-proof (claims are leaf digests), there is
- * one tree per proof, and the transcript and the evaluation at zeta stay on the host.
+ * the claims.  The opened leaf ROWS are hashed in-proof by LeafSpongeAir (below: vx_merkle_rows_prove, whose claims are rows, not
+ * digests).  STILL OUTSIDE (the next tables): there is one tree per proof, and the FRI fold, the evaluation at zeta and the
+ * transcript stay on the host.
  * vx_merkle_open_air_trace: the witness on its own (test surface) -- leaf_idx: n_idx >= 1 leaf indices (host; duplicates
  *   allowed); trace_out: [VX_MERKLE_OPEN_AIR_COLS][2^log_n] with 2^log_n >= 32 n_idx D; blocks behind the paths are idle.
  * vx_merkle_openings_prove: trace + proof at the smallest such log_n (>= 5) under lookup challenges that are the shared-challenge
@@ -248,6 +250,43 @@ int32_t vx_merkle_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const 
                                  uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* cap, int cap_height,
                                   int log_leaves, const uint64_t* leaf_idx, const uint64_t* leaf_digests, size_t n_idx, char* err, size_t errlen);
+/* ---- LeafSpongeAir: the opened leaf ROWS of one Poseidon tree hashed in one STARK table (AIR id VX_AIR_LEAF_SPONGE; compiled:
+ * csrc/air_leaf_sponge.cuh) -- hash_n_to_hash_no_pad (plonky2 v0.2.0 hash/hashing.rs) of any number of rows of one length, the
+ * second table of proof aggregation: a STARK verifier holds the opened rows, never their digests.  One row of leaf_len words is
+ * B = ceil(leaf_len / 8) blocks of 32 rows (one permutation each, PoseidonAir's columns and constraints; the sponge overwrites
+ * the rate part, a tail block overwrites its first leaf_len mod 8 words only); no positional shape, so any number of rows of any
+ * length >= 5 fit the one AIR id at any log_n >= 5.  leaf_len <= 4 is hash_or_noop's no-op -- the digest is the zero-padded row
+ * itself and vx_merkle_openings_prove / _verify cover it -- so every entry point below REFUSES leaf_len < 5 with VX_ERR_ARG.
+ * Public inputs (14): leaf_len, B, eight tail flags w_i = [word i of a last block is absorbed], and the row-claims digest
+ * hash_n_to_hash_no_pad((index, row[0 .. leaf_len)) of every opening, in order), which makes the lookup challenges depend on
+ * the claims.  Bus: every block sends the words it absorbs as (index, position, word) messages of a second kind, and the last
+ * block of a row receives the two messages (index, digest) that MerkleOpenAir sends -- that kind is closed BETWEEN the tables.
+ * vx_leaf_sponge_air_trace: the witness on its own (test surface) -- data / off / n_leaves / leaf_len / layout as vx_merkle_build
+ *   takes them; leaf_idx: n_idx >= 1 leaf indices (host; duplicates allowed); trace_out: [VX_LEAF_SPONGE_AIR_COLS][2^log_n]
+ *   with 2^log_n >= 32 n_idx B; blocks behind the rows are idle.  Returns the public inputs.
+ * vx_merkle_rows_prove: MerkleOpenAir + LeafSpongeAir for the openings leaf_idx of `tree`, each at its smallest log_n, as two
+ *   parties of ONE logUp bus: the lookup challenges are the shared-challenge transcript of both (public inputs, trace cap) pairs,
+ *   openings first.  data / off / leaf_len / layout must be what `tree` was built from: every computed digest is compared with
+ *   the tree's leaf digest first, and VX_ERR_STATEMENT is returned (nothing proven) when one differs.  Blob: the magic
+ *   "VXMROWS1", log2(n_leaves), leaf_len, n_idx, the two proofs' lengths; then the MerkleOpenAir proof and the LeafSpongeAir
+ *   proof (vx_stark_prove layout).  VX_ERR_BUFSZ (with *blob_len set) when the buffer is too small.
+ * vx_merkle_rows_verify (host only; walks no Merkle path and hashes no leaf): the claims are (leaf_idx[i], rows[i][leaf_len]).
+ *   It rebuilds LeafSpongeAir's public inputs entirely and MerkleOpenAir's root and depth from its own arguments.  It cannot
+ *   know the leaf digests, so MerkleOpenAir's four claims-digest words are taken from that proof's own public inputs (checked
+ *   canonical): they only feed the transcript -- the digests themselves are bound by the sponge table's committed trace, which
+ *   receives every opening the first table sends.  It recomputes the shared challenges, verifies both tables under them and
+ *   accepts iff  total_open x 2^log_n_open + total_sponge x 2^log_n_sponge = sum over the claims and j < leaf_len of
+ *   1 / D_row(index, j, row[j]).  Its row-claims digest costs as many permutations as hashing the rows would; what it no longer
+ *   does is anything per tree level, and the row bus is one whose other party a later table (FRI fold, evaluation at zeta)
+ *   replaces.  STILL OUTSIDE: several trees (roots) per proof, the FRI fold, the evaluation at zeta, the transcript. */
+enum { VX_AIR_LEAF_SPONGE = 17, VX_LEAF_SPONGE_AIR_COLS = 66, VX_LEAF_SPONGE_AIR_AUX_COLS = 12 };
+int32_t vx_leaf_sponge_air_trace(vx_ctx* ctx, const vx_buf* data, size_t off, size_t n_leaves, size_t leaf_len, int layout, const uint64_t* leaf_idx,
+                                 size_t n_idx, int log_n, vx_buf* trace_out, uint64_t public_out[14]);
+int32_t vx_merkle_rows_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t leaf_len, size_t n_idx, size_t* n_words);
+int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_tree* tree, const vx_buf* data, size_t off, size_t leaf_len, int layout,
+                             const uint64_t* leaf_idx, size_t n_idx, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* cap, int cap_height, int log_leaves,
+                              size_t leaf_len, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */

@@ -2,7 +2,7 @@
 """Mutation fuzzing of the HOST verifier under AddressSanitizer + UBSan (CPU only; the verifier takes untrusted proofs).
 
 Builds vx_verify.hip host-only with -fsanitize=address,undefined, loads it in a child interpreter started with the sanitizer runtime
-preloaded, and feeds vx_stark_verify / vx_header_range_verify / vx_rotate_verify / vx_merkle_openings_verify mutated proofs: seeds are real proofs of the small AIRs made by the CPU
+preloaded, and feeds vx_stark_verify / vx_header_range_verify / vx_rotate_verify / vx_merkle_openings_verify / vx_merkle_rows_verify mutated proofs: seeds are real proofs of the small AIRs made by the CPU
 reference prover (oracle/stark_ref.py -- test infrastructure, used here to make inputs only).  Mutations: word flips, random words,
 truncation, extension, the degree-bits / length fields set to every small value, header words of a range blob set to extremes.
 Any sanitizer report aborts the child: the script fails.  Every mutated proof must also be REJECTED (a flipped word that is accepted
@@ -96,6 +96,86 @@ def fuzz_merkle_openings(L, StarkConfig, rng, iters):
         if not kw and p.size == n and (p == seed).all():
             continue
         assert verify(p, **kw) != 0, f"mutation kind {kind} of the merkle-openings blob / claims was ACCEPTED"
+        rejected += 1
+    return total, rejected
+
+
+def fuzz_merkle_rows(L, StarkConfig, rng, iters):
+    """vx_merkle_rows_verify on mutations of a real two-table blob (reference-prover proofs of the restatements of MerkleOpenAir and
+    LeafSpongeAir under shared challenges, tests/leaf_sponge_ref.py) and of the verifier's own claims -> (inputs, rejected)"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import leaf_sponge_ref as R
+    from oracle import oracle as O
+    from oracle import stark_ref as S
+
+    vp, sz = C.c_void_p, C.c_size_t
+    L.vx_merkle_rows_verify.argtypes = [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, sz, vp, vp, sz, C.c_char_p, sz]
+    L.vx_merkle_rows_verify.restype = C.c_int32
+    ocfg = dict(S.DEFAULT_CFG, num_queries=4)
+    cfg = StarkConfig()
+    for k, v in ocfg.items():
+        setattr(cfg, k, v)
+    err = C.create_string_buffer(256)
+    leaf_len = 9
+    leaves = rng.integers(0, O.P, size=(8, leaf_len), dtype=np.uint64)
+    tree = O.MerkleTree(leaves, 1)
+    idx = np.array([1, 6, 3], dtype=np.uint64)
+    rows = np.ascontiguousarray(leaves[[1, 6, 3]])
+    p_open, p_sponge = R.prove_rows(tree, [int(i) for i in idx], rows, ocfg)
+    seed = R.wrap(p_open, p_sponge, 3, leaf_len, idx.size)
+    cap = np.ascontiguousarray(tree.cap, dtype=np.uint64)
+
+    def verify(b, cap_=cap, cap_h=1, log_leaves=3, leaf_len_=leaf_len, idx_=idx, rows_=rows):
+        b, idx_, rows_ = (np.ascontiguousarray(a, dtype=np.uint64) for a in (b, idx_, rows_))
+        assert idx_.size * leaf_len_ <= rows_.size or leaf_len_ > 2**20  # (a leaf_len above 2^20 is refused before the rows are read)
+        return L.vx_merkle_rows_verify(C.byref(cfg), b.ctypes.data_as(vp), b.size, cap_.ctypes.data_as(vp), cap_h, log_leaves, leaf_len_, idx_.ctypes.data_as(vp),
+                                       rows_.ctypes.data_as(vp), idx_.size, err, 256)
+
+    assert verify(seed) == 0, err.value
+    n, total, rejected = seed.size, 0, 0
+    for it in range(max(iters // 4, 50)):
+        p, kw = seed.copy(), {}
+        kind = it % 7
+        if kind == 0:
+            p[rng.integers(n)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+        elif kind == 1:  # the blob header and the first proof's header set to small and extreme values
+            p[rng.integers(0, R.HDR + 16)] = np.uint64([0, 1, 2, 3, 4, 5, 26, 40, 41, n, n - R.HDR, 2**21, 2**32, 2**63, 2**64 - 1][rng.integers(15)])
+        elif kind == 2:
+            p = p[: rng.integers(0, n)]
+        elif kind == 3:  # the split between the two proofs moved, lengths consistent with the blob
+            a = int(rng.integers(0, n - R.HDR + 1))
+            p[4], p[5] = a, n - R.HDR - a
+        elif kind == 4:
+            a, b_ = sorted(int(x) for x in rng.integers(R.HDR, n, size=2))
+            p[a:b_] = rng.integers(0, 2**63, size=b_ - a, dtype=np.uint64)
+        elif kind == 5:  # the verifier's claims: an index or a row word changed (in or out of range)
+            i2, r2 = idx.copy(), rows.copy()
+            if rng.integers(2):
+                i2[rng.integers(i2.size)] = np.uint64([0, 2, 7, 8, 2**40, 2**64 - 1][rng.integers(6)])
+            else:
+                r2.reshape(-1)[rng.integers(r2.size)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+            if (i2 == idx).all() and (r2 == rows).all():
+                continue
+            kw = dict(idx_=i2, rows_=r2)
+        else:  # the tree and the row length the verifier knows
+            c2 = np.zeros((16, 4), dtype=np.uint64)
+            c2[:2] = cap
+            which = int(rng.integers(4))
+            if which == 0:
+                c2[rng.integers(2), rng.integers(4)] ^= np.uint64(1) << np.uint64(rng.integers(64))
+                kw = dict(cap_=c2)
+            elif which == 1:
+                kw = dict(cap_=c2, cap_h=int([-1, 0, 2, 3, 4, 17, 2**30][rng.integers(7)]))
+            elif which == 2:
+                kw = dict(log_leaves=int([-1, 0, 1, 2, 4, 32, 33, 2**30][rng.integers(8)]))
+            else:
+                kw = dict(leaf_len_=int([0, 1, 4, 5, 8, 2**20 + 1, 2**40, 2**64 - 1][rng.integers(8)]))
+        total += 1
+        if not kw and p.size == n and (p == seed).all():
+            continue
+        assert verify(p, **kw) != 0, f"mutation kind {kind} of the merkle-rows blob / claims was ACCEPTED"
         rejected += 1
     return total, rejected
 
@@ -254,6 +334,9 @@ def child(iters):
     # the Merkle-openings blob and the claims its verifier is called with
     t2, r2 = fuzz_merkle_openings(L, StarkConfig, rng, iters)
     total, rejected = total + t2, rejected + r2
+    # the two-table Merkle-rows blob (MerkleOpenAir + LeafSpongeAir on one bus) and the rows its verifier is called with
+    t3, r3 = fuzz_merkle_rows(L, StarkConfig, rng, iters)
+    total, rejected = total + t3, rejected + r3
     # run-time AIR descriptors (vx_air_register + the host interpreter): random and mutated instruction streams must be refused or
     # registered without a sanitizer report; whatever registers is then run by the verifier on a real proof of another program
     # (it must reject: a different statement) and on that proof's mutations
