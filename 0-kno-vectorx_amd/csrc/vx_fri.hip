@@ -101,6 +101,7 @@ __global__ __launch_bounds__(256) void k_fri_leaf_hash(const uint64_t* evals, in
 // gather the leaves (arity ext values, flattened) of n_idx leaf indices
 __global__ void k_fri_gather_leaves(const uint64_t* evals, int log_n, int arity_bits, const uint64_t* idx, size_t n_idx,
                                     uint64_t* out) {
+    VX_TAIL_KERNEL_ENTRY();
     const int arity = 1 << arity_bits;
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= n_idx * arity) return;
@@ -238,6 +239,13 @@ int32_t vx_fri_leaves(vx_ctx* ctx, const vx_buf* evals, int log_n, int arity_bit
 }
 }  // extern "C"
 
+// the leaves (2^arity_bits extension values each) of n_idx leaf indices (on the device) into out_d; enqueue only
+void vx_fri_leaves_enqueue(vx_ctx* ctx, const uint64_t* evals_d, int log_n, int arity_bits, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d) {
+    const size_t tot = n_idx << arity_bits;
+    if (tot == 0) return;
+    hipLaunchKernelGGL(k_fri_gather_leaves, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, evals_d, log_n, arity_bits, idx_d, n_idx, out_d);
+}
+
 int32_t vx_fri_leaves_dev(vx_ctx* ctx, const uint64_t* evals_d, int log_n, int arity_bits, const uint64_t* leaf_idx, size_t n_idx,
                           uint64_t* out) {
     if (!n_idx) return VX_OK;
@@ -245,8 +253,7 @@ int32_t vx_fri_leaves_dev(vx_ctx* ctx, const uint64_t* evals_d, int log_n, int a
     uint64_t* sc;
     VX_TRY(vx_scratch(ctx, n_idx + 2 * tot, &sc));
     VX_HIP(hipMemcpyAsync(sc, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_fri_gather_leaves, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, evals_d, log_n,
-                       arity_bits, (const uint64_t*)sc, n_idx, sc + n_idx);
+    vx_fri_leaves_enqueue(ctx, evals_d, log_n, arity_bits, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(out, sc + n_idx, 2 * tot * 8, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipStreamSynchronize(ctx->stream));

@@ -46,6 +46,18 @@ static inline uint64_t root(int log_n) {
 }
 }  // namespace glh
 
+// Issue priority of the tail kernels (tree tops, small-tree leaves, query-phase gathers): they never fill the chip and do under 2 %
+// of a proof's VALU work, but run beside resident hash / NTT waves, and VALU issue goes by priority before age.  -DVX_TAIL_PRIO=0
+// is the A/B (profiles/README.md).  Nothing that can fill the chip may raise its priority.
+#ifndef VX_TAIL_PRIO
+#define VX_TAIL_PRIO 1
+#endif
+#if VX_TAIL_PRIO
+#define VX_TAIL_KERNEL_ENTRY() __builtin_amdgcn_s_setprio(3)
+#else
+#define VX_TAIL_KERNEL_ENTRY() ((void)0)
+#endif
+
 struct vx_buf {
     uint64_t* d;
     size_t n;
@@ -120,6 +132,11 @@ int32_t vx_lde_dev(vx_ctx* ctx, const uint64_t* src, int log_n, size_t n_cols, i
                    uint64_t* dst, uint64_t* coeffs_out);
 int32_t vx_gather_rows_dev(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n_cols, const uint64_t* leaf_idx, size_t n_idx,
                            uint64_t* out);
+// enqueue-only forms of the three query-phase gathers: indices and destination on the device, nothing uploaded, copied back or waited
+// for (the prover's query phase launches all of a table's gathers into one scratch region and makes one round trip)
+void vx_gather_rows_enqueue(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n_cols, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d);
+void vx_merkle_open_enqueue(vx_ctx* ctx, const vx_tree* tree, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d);
+void vx_fri_leaves_enqueue(vx_ctx* ctx, const uint64_t* evals, int log_n, int arity_bits, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d);
 int32_t vx_fri_fold_dev(vx_ctx* ctx, const uint64_t* evals, int log_n, int arity_bits, const uint64_t beta[2], uint64_t shift,
                         uint64_t* out);
 int32_t vx_fri_layer_tree_dev(vx_ctx* ctx, const uint64_t* evals, int log_n, int arity_bits, int cap_height, vx_tree** out);

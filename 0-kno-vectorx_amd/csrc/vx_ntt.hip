@@ -444,6 +444,7 @@ __global__ void k_scale_pow(uint64_t* d, int log_n, size_t stride, const uint64_
 }
 __global__ void k_gather_rows(const uint64_t* lde, int log_N, size_t n_cols, const uint64_t* idx, size_t n_idx,
                               uint64_t* out) {
+    VX_TAIL_KERNEL_ENTRY();
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= n_idx * n_cols) return;
     size_t k = t / n_cols, c = t - k * n_cols;
@@ -671,6 +672,13 @@ int32_t vx_lde_keep_dev(vx_ctx* ctx, const uint64_t* values, int log_n, size_t n
     return ntt_dit(ctx, coef_brev, n, dst, N, log_n + rate_bits, n_cols, 0, rate_bits, st.d);
 }
 
+// rows idx_d[k] (indices on the device) of an LDE into out_d [n_idx][n_cols]; enqueue only
+void vx_gather_rows_enqueue(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n_cols, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d) {
+    const size_t tot = n_idx * n_cols;
+    if (tot == 0) return;
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, lde, log_N, n_cols, idx_d, n_idx, out_d);
+}
+
 int32_t vx_gather_rows_dev(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n_cols, const uint64_t* leaf_idx, size_t n_idx,
                            uint64_t* out) {
     if (n_idx == 0) return VX_OK;
@@ -678,8 +686,7 @@ int32_t vx_gather_rows_dev(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n
     VX_TRY(vx_scratch(ctx, n_idx + n_idx * n_cols, &sc));
     VX_HIP(hipMemcpyAsync(sc, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
     size_t tot = n_idx * n_cols;
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, lde, log_N, n_cols,
-                       (const uint64_t*)sc, n_idx, sc + n_idx);
+    vx_gather_rows_enqueue(ctx, lde, log_N, n_cols, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(out, sc + n_idx, tot * 8, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipStreamSynchronize(ctx->stream));

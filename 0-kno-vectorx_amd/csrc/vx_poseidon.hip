@@ -61,6 +61,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_HASH_WAV
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void k_hash_leaves_coop(const uint64_t* data, size_t n_leaves, int log_n, size_t leaf_len,
                                                           uint64_t* digests) {
+    VX_TAIL_KERNEL_ENTRY();
     __shared__ uint64_t lds[16 * 12];
     const int l = threadIdx.x & 15, grp = threadIdx.x >> 4;
     uint64_t* g = lds + 12 * grp;
@@ -80,15 +81,57 @@ __global__ __launch_bounds__(256) void k_hash_leaves_coop(const uint64_t* data, 
     }
     if (l < 4 && t < n_leaves) digests[4 * j + l] = s;
 }
-// parent[i] = compress(child[2i], child[2i+1]), 16 lanes per parent
-__global__ __launch_bounds__(256) void k_merkle_level_coop(const uint64_t* child, uint64_t* parent, size_t n_parent) {
-    __shared__ uint64_t lds[16 * 12];
-    const int l = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const size_t t = blockIdx.x * (size_t)16 + grp;
-    const size_t i = t < n_parent ? t : n_parent - 1;
-    uint64_t s = l < 8 ? child[8 * i + l] : 0;
-    s = poseidon_permute_coop(s, l, lds + 12 * grp);
-    if (l < 4 && t < n_parent) parent[4 * i + l] = s;
+// Tree tops.  A block owns 2^s consecutive digests of the level at `off` (`cur` digests wide) and computes the s levels above them
+// itself: the current level lives in LDS (two buffers, read one and write the other), a block barrier separates the levels, and every
+// parent also goes to its usual place in `levels` (k_gather_siblings and the cap read it there).  Narrow levels take 16 lanes per
+// parent (poseidon_permute_coop), one round of TOP_GROUPS parents at a time; levels of at least VX_TOP_LANE_MIN parents take one lane
+// per parent.  The DPP exchange needs all 16 lanes of a group: surplus groups redo the last parent and do not write, and every thread
+// reaches every barrier.  Block size and threshold by measurement (tools/merkle_top_rate.py, profiles/README.md): 2^15 digests to a
+// cap of 16 on an idle GPU take 303 us with 256 threads and one lane from 32 parents up, 394 us with 1024 threads / 128, 534 us with
+// 1024 threads and cooperative rounds only -- a block is a chain of s permutations on ONE compute unit, and four waves per SIMD share
+// its VALU issue.
+#ifndef VX_TOP_THREADS
+#define VX_TOP_THREADS 256
+#endif
+#ifndef VX_TOP_LANE_MIN
+#define VX_TOP_LANE_MIN 32  // > 256 = never
+#endif
+constexpr int TOP_MAX_S = 9, TOP_GROUPS = VX_TOP_THREADS / 16;
+static_assert(VX_TOP_THREADS >= (1 << (TOP_MAX_S - 1)) && VX_TOP_THREADS <= 1024, "one lane per parent of the widest level");
+__global__ __launch_bounds__(VX_TOP_THREADS) void k_merkle_top(uint64_t* levels, size_t off, size_t cur, int s) {
+    VX_TAIL_KERNEL_ENTRY();
+    __shared__ uint64_t buf[2][4 << (TOP_MAX_S - 1)];
+    __shared__ uint64_t xch[12 * TOP_GROUPS];  // exchange area of the non-DPP permutation (unused, and dropped, with DPP)
+    const int tid = threadIdx.x, l = tid & 15, grp = tid >> 4;
+    const uint64_t* child_g = levels + off + 4 * ((size_t)blockIdx.x << s);
+    for (int j = 1; j <= s; ++j) {
+        const int np = 1 << (s - j);
+        off += 4 * cur;
+        cur >>= 1;
+        uint64_t* parent_g = levels + off + 4 * ((size_t)blockIdx.x << (s - j));
+        uint64_t* parent_l = buf[j & 1];
+        const uint64_t* child_l = buf[(j - 1) & 1];
+        if (VX_TOP_LANE_MIN <= 256 && np >= VX_TOP_LANE_MIN) {
+            if (tid < np) {
+                uint64_t st[12];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) st[k] = j == 1 ? child_g[8 * tid + k] : child_l[8 * tid + k];
+                st[8] = st[9] = st[10] = st[11] = 0;
+                poseidon_permute(st);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) parent_l[4 * tid + k] = parent_g[4 * tid + k] = st[k];
+            }
+        } else {
+            for (int base = 0; base < np; base += TOP_GROUPS) {
+                const int t = base + grp, i = t < np ? t : np - 1;
+                uint64_t x = 0;
+                if (l < 8) x = j == 1 ? child_g[8 * i + l] : child_l[8 * i + l];
+                x = poseidon_permute_coop(x, l, xch + 12 * grp);
+                if (l < 4 && t < np) parent_l[4 * i + l] = parent_g[4 * i + l] = x;
+            }
+        }
+        __syncthreads();
+    }
 }
 constexpr size_t COOP_MAX_LEAVES = 16384;  // below this the one-lane kernels cannot fill the chip (1024 SIMDs x 64 lanes)
 
@@ -109,6 +152,7 @@ __global__ __launch_bounds__(256) void k_merkle_level(const uint64_t* child, uin
 
 __global__ void k_gather_siblings(const uint64_t* levels, size_t n_leaves, int depth, const uint64_t* idx, size_t n_idx,
                                   uint64_t* out) {
+    VX_TAIL_KERNEL_ENTRY();
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= n_idx * depth) return;
     size_t k = t / depth;
@@ -135,18 +179,38 @@ __global__ __launch_bounds__(256) void k_poseidon_air_trace(const uint64_t* in, 
     poseidon_air_walk(s, tr, 32 * n_perm, 32 * p);
 }
 
-// levels above the leaf digests, down to `cap` nodes (levels = digests of level 0 followed by each parent level)
+// levels above the leaf digests, down to `cap` nodes (levels = digests of level 0 followed by each parent level): one k_merkle_level
+// launch per level while a level can fill the chip, then the top in at most two launches (2^15 children at most, TOP_MAX_S levels each)
 void vx_merkle_levels_launch(vx_ctx* ctx, uint64_t* levels, size_t n_leaves, size_t cap) {
     size_t off = 0, cur = n_leaves;
-    while (cur > cap) {
+    while (cur > cap && (cur >> 1) > COOP_MAX_LEAVES) {
         const size_t np = cur >> 1;
-        if (np <= COOP_MAX_LEAVES)
-            hipLaunchKernelGGL(k_merkle_level_coop, dim3((unsigned)((np + 15) / 16)), dim3(256), 0, ctx->stream, levels + off, levels + off + 4 * cur, np);
-        else
-            hipLaunchKernelGGL(k_merkle_level, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, levels + off, levels + off + 4 * cur, np);
+        hipLaunchKernelGGL(k_merkle_level, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, levels + off, levels + off + 4 * cur, np);
         off += 4 * cur;
         cur = np;
     }
+    int todo = 0;  // log2(cur / cap)
+    while ((cap << todo) < cur) ++todo;
+    while (todo > 0) {
+        const int s = todo < TOP_MAX_S ? todo : TOP_MAX_S;
+        hipLaunchKernelGGL(k_merkle_top, dim3((unsigned)(cur >> s)), dim3(VX_TOP_THREADS), 0, ctx->stream, levels, off, cur, s);
+        for (int j = 0; j < s; ++j) {
+            off += 4 * cur;
+            cur >>= 1;
+        }
+        todo -= s;
+    }
+}
+
+// the siblings of n_idx leaves (indices on the device, in range) into out_d [n_idx][depth][4]; enqueue only
+void vx_merkle_open_enqueue(vx_ctx* ctx, const vx_tree* tree, const uint64_t* idx_d, size_t n_idx, uint64_t* out_d) {
+    int log_n = 0;
+    while (((size_t)1 << log_n) < tree->n_leaves) ++log_n;
+    const int depth = log_n - tree->cap_height;
+    const size_t tot = n_idx * depth;
+    if (tot == 0) return;
+    hipLaunchKernelGGL(k_gather_siblings, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, tree->levels,
+                       tree->n_leaves, depth, idx_d, n_idx, out_d);
 }
 
 int32_t vx_merkle_build_dev(vx_ctx* ctx, const uint64_t* data, size_t n_leaves, size_t leaf_len, int layout,
@@ -248,8 +312,7 @@ int32_t vx_merkle_open(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_id
     size_t tot = n_idx * depth;
     VX_TRY(vx_scratch(ctx, n_idx + 4 * tot, &sc));
     VX_HIP(hipMemcpyAsync(sc, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_siblings, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, tree->levels,
-                       tree->n_leaves, depth, sc, n_idx, sc + n_idx);
+    vx_merkle_open_enqueue(ctx, tree, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(siblings_out, sc + n_idx, 4 * tot * 8, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipStreamSynchronize(ctx->stream));

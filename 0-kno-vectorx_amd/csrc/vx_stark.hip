@@ -976,42 +976,69 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     std::vector<uint64_t> qidx(nqr);
     for (size_t k = 0; k < nqr; ++k) qidx[k] = ch.challenge() % N;
     const int depth0 = LN - cfg.cap_height;
-    std::vector<uint64_t> rows_t(nqr * cm), rows_a(nqr * ca), rows_q(nqr * nq), sib_t(nqr * depth0 * 4), sib_a(ca ? nqr * depth0 * 4 : 0), sib_q(nqr * depth0 * 4);
-    VX_TRY(vx_gather_rows_dev(ctx, trace_lde, LN, cm, qidx.data(), nqr, rows_t.data()));
-    if (ca) VX_TRY(vx_gather_rows_dev(ctx, trace_lde + N * cm, LN, ca, qidx.data(), nqr, rows_a.data()));
-    VX_TRY(vx_gather_rows_dev(ctx, quot_lde, LN, nq, qidx.data(), nqr, rows_q.data()));
-    if (depth0 > 0) {
-        VX_TRY(vx_merkle_open(ctx, t_trace, qidx.data(), nqr, sib_t.data()));
-        if (ca) VX_TRY(vx_merkle_open(ctx, t_aux, qidx.data(), nqr, sib_a.data()));
-        VX_TRY(vx_merkle_open(ctx, t_quot, qidx.data(), nqr, sib_q.data()));
-    }
-    std::vector<std::vector<uint64_t>> l_leaves(arities.size()), l_sibs(arities.size());
-    std::vector<uint64_t> lidx = qidx;
-    for (size_t l = 0; l < arities.size(); ++l) {
+    // One round trip: the per-layer indices are shifts of qidx, so every index array goes up in one copy, every gather of the table is
+    // launched back to back into one scratch region, and the region comes back in one copy behind one synchronisation.
+    const size_t n_layers = arities.size();
+    std::vector<uint64_t> idx_h((1 + n_layers) * nqr);  // [qidx][leaf index in layer 0's tree][layer 1] ...
+    std::copy(qidx.begin(), qidx.end(), idx_h.begin());
+    for (size_t l = 0; l < n_layers; ++l)
+        for (size_t k = 0; k < nqr; ++k) idx_h[(l + 1) * nqr + k] = idx_h[l * nqr + k] >> arities[l];
+    size_t words = 0;
+    auto take = [&](size_t n) {
+        const size_t at = words;
+        words += n;
+        return at;
+    };
+    const size_t sib0 = depth0 > 0 ? nqr * depth0 * 4 : 0;
+    const size_t o_rows_t = take(nqr * cm), o_rows_a = take(nqr * ca), o_rows_q = take(nqr * nq);
+    const size_t o_sib_t = take(sib0), o_sib_a = take(ca ? sib0 : 0), o_sib_q = take(sib0);
+    std::vector<size_t> o_leaves(n_layers), o_sibs(n_layers);
+    for (size_t l = 0; l < n_layers; ++l) {
         const int a = arities[l], depth = llog[l] - a - cfg.cap_height;
-        for (size_t k = 0; k < nqr; ++k) lidx[k] >>= a;  // leaf index in this layer's tree
-        l_leaves[l].resize(nqr * ((size_t)2 << a));
-        VX_TRY(vx_fri_leaves_dev(ctx, layers[l], llog[l], a, lidx.data(), nqr, l_leaves[l].data()));
-        l_sibs[l].resize(nqr * (depth > 0 ? depth : 0) * 4);
-        if (depth > 0) VX_TRY(vx_merkle_open(ctx, ltrees[l], lidx.data(), nqr, l_sibs[l].data()));
+        o_leaves[l] = take(nqr * ((size_t)2 << a));
+        o_sibs[l] = take(depth > 0 ? nqr * depth * 4 : 0);
     }
+    uint64_t* sc;
+    VX_TRY(vx_scratch(ctx, idx_h.size() + words, &sc));
+    uint64_t* const gat = sc + idx_h.size();
+    VX_HIP(hipMemcpyAsync(sc, idx_h.data(), idx_h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    vx_gather_rows_enqueue(ctx, trace_lde, LN, cm, sc, nqr, gat + o_rows_t);
+    if (ca) vx_gather_rows_enqueue(ctx, trace_lde + N * cm, LN, ca, sc, nqr, gat + o_rows_a);
+    vx_gather_rows_enqueue(ctx, quot_lde, LN, nq, sc, nqr, gat + o_rows_q);
+    if (depth0 > 0) {
+        vx_merkle_open_enqueue(ctx, t_trace, sc, nqr, gat + o_sib_t);
+        if (ca) vx_merkle_open_enqueue(ctx, t_aux, sc, nqr, gat + o_sib_a);
+        vx_merkle_open_enqueue(ctx, t_quot, sc, nqr, gat + o_sib_q);
+    }
+    for (size_t l = 0; l < n_layers; ++l) {
+        const int a = arities[l], depth = llog[l] - a - cfg.cap_height;
+        const uint64_t* lidx_d = sc + (l + 1) * nqr;  // leaf index in this layer's tree
+        vx_fri_leaves_enqueue(ctx, layers[l], llog[l], a, lidx_d, nqr, gat + o_leaves[l]);
+        if (depth > 0) vx_merkle_open_enqueue(ctx, ltrees[l], lidx_d, nqr, gat + o_sibs[l]);
+    }
+    VX_HIP(hipGetLastError());
+    std::vector<uint64_t> q(words);
+    VX_HIP(hipMemcpyAsync(q.data(), gat, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    VX_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t *rows_t = q.data() + o_rows_t, *rows_a = q.data() + o_rows_a, *rows_q = q.data() + o_rows_q;
+    const uint64_t *sib_t = q.data() + o_sib_t, *sib_a = q.data() + o_sib_a, *sib_q = q.data() + o_sib_q;
     for (size_t k = 0; k < nqr; ++k) {
-        proof.insert(proof.end(), rows_t.begin() + k * cm, rows_t.begin() + (k + 1) * cm);
-        proof.insert(proof.end(), sib_t.begin() + k * depth0 * 4, sib_t.begin() + (k + 1) * depth0 * 4);
+        proof.insert(proof.end(), rows_t + k * cm, rows_t + (k + 1) * cm);
+        if (depth0 > 0) proof.insert(proof.end(), sib_t + k * depth0 * 4, sib_t + (k + 1) * depth0 * 4);
         if (ca) {
-            proof.insert(proof.end(), rows_a.begin() + k * ca, rows_a.begin() + (k + 1) * ca);
-            proof.insert(proof.end(), sib_a.begin() + k * depth0 * 4, sib_a.begin() + (k + 1) * depth0 * 4);
+            proof.insert(proof.end(), rows_a + k * ca, rows_a + (k + 1) * ca);
+            if (depth0 > 0) proof.insert(proof.end(), sib_a + k * depth0 * 4, sib_a + (k + 1) * depth0 * 4);
         }
-        proof.insert(proof.end(), rows_q.begin() + k * nq, rows_q.begin() + (k + 1) * nq);
-        proof.insert(proof.end(), sib_q.begin() + k * depth0 * 4, sib_q.begin() + (k + 1) * depth0 * 4);
+        proof.insert(proof.end(), rows_q + k * nq, rows_q + (k + 1) * nq);
+        if (depth0 > 0) proof.insert(proof.end(), sib_q + k * depth0 * 4, sib_q + (k + 1) * depth0 * 4);
         uint64_t x_index = qidx[k];
-        for (size_t l = 0; l < arities.size(); ++l) {
+        for (size_t l = 0; l < n_layers; ++l) {
             const int a = arities[l], depth = llog[l] - a - cfg.cap_height;
             const size_t arity = (size_t)1 << a, within = x_index & (arity - 1);
-            const uint64_t* leaf = l_leaves[l].data() + k * 2 * arity;
+            const uint64_t* leaf = q.data() + o_leaves[l] + k * 2 * arity;
             for (size_t t = 0; t < arity; ++t)  // evals.remove(x_index & (arity - 1))
                 if (t != within) proof.push_back(leaf[2 * t]), proof.push_back(leaf[2 * t + 1]);
-            if (depth > 0) proof.insert(proof.end(), l_sibs[l].begin() + k * depth * 4, l_sibs[l].begin() + (k + 1) * depth * 4);
+            if (depth > 0) proof.insert(proof.end(), q.data() + o_sibs[l] + k * depth * 4, q.data() + o_sibs[l] + (k + 1) * depth * 4);
             x_index >>= a;
         }
     }
