@@ -11,7 +11,7 @@
 #include "gl.cuh"
 
 namespace bus {
-enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9 };
+enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10 };
 
 // a slot known at compile time: 0 leaves its term out, 1 adds the bare power of gamma, so a kind that does not use a slot
 // (or whose tag is 0 or 1) costs what the hand-written sum cost
@@ -75,5 +75,15 @@ struct Bus {
     VX_HD X open(const S& index, const S& da, const S& db, const H& half) const { return denom(beta, index, da, db, half, K<TAG_OPEN>{}); }
     // one word of an opened leaf row (leaf index, position in the row, word): LeafSpongeAir -> whoever holds the rows (the verifier)
     VX_HD X row(const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, None{}, K<TAG_ROW>{}); }
+    // ... of one of several trees (leaf index, position in the row, word, tree): tree 0 is the very message row() builds, so a
+    // one-layer FRI with TREE0 = 0 is already receivable from LeafSpongeAir (that pairing is not built); a multi-tree sponge will
+    // send the others -> FriFoldAir, which receives the leaves of FRI layer l under tree TREE0 + l, and the verifier
+    template <class T>
+    VX_HD X row_of(const T& tree, const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, tree, K<TAG_ROW>{}); }
+    // an end of a query's fold chain (query index, value.a, value.b, end): end 0 = (index, ev_0) entering the chain, whoever
+    // computes the FRI combination (the verifier) -> FriFoldAir; end 1 = (index, ev_NL) leaving it, FriFoldAir -> whoever
+    // evaluates the final polynomial (the verifier)
+    template <class E>
+    VX_HD X fri(const S& index, const S& va, const S& vb, const E& end) const { return denom(beta, index, va, vb, end, K<TAG_FRI>{}); }
 };
 }  // namespace bus

@@ -115,6 +115,14 @@ static constexpr size_t VX_MOPEN_HDR = 4;
 // magic, log2(n_leaves), leaf_len, number of openings, lengths of the MerkleOpenAir and the LeafSpongeAir proof that follow
 static const uint64_t VX_MROWS_MAGIC = 0x3153574f524d5856ULL;  // "VXMROWS1"
 static constexpr size_t VX_MROWS_HDR = 6;
+// ---- FRI-fold blob (written by vx_fri_fold_prove in vx_fri_fold_air.hip, read by vx_fri_fold_verify in vx_verify.hip): magic,
+// log2 of the inner proof's LDE, fold layers, queries, length of the FriFoldAir proof that follows
+static const uint64_t VX_FFOLD_MAGIC = 0x31444c4f46465856ULL;  // "VXFFOLD1"
+static constexpr size_t VX_FFOLD_HDR = 5;
+// FriFoldAir's public inputs from the claims (betas [n_layers][2], ev0 [n_queries][2], leaves [n_queries][n_layers][32]), prover and
+// verifier alike
+void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
+                        uint64_t pub[24]);
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

@@ -1,0 +1,304 @@
+// Witness and prover of FriFoldAir (air_fri_fold.cuh): the FRI fold chain of every query of one inner proof in one table.
+//   k_fri_fold_trace  one lane per ROW.  The rows of a query are a chain only through ev_l, and the prover holds every leaf (slot
+//                     `within` of leaf l IS ev_l), so every row is independent: a lane recomputes its row from (index, layer,
+//                     leaf, beta_l) -- the digits, 1 / x_l by a small power, the one-hots, the four fold levels, the prefix of
+//                     the square-and-multiply accumulator -- and stores its cells itself (adjacent lanes = adjacent rows of a
+//                     column).  A bit row refolds the last leaf: it carries ev_NL.  Fold rows and bit rows run the same code;
+//                     the table is a few hundred rows and latency-bound, so nothing here is tuned
+//   k_fri_fold_aux    one lane per row: ONE extension inversion for the row's 17 helpers (Montgomery batch over the products of
+//                     its denominator pairs) and the row's running-sum increment (vx_bus_close_dev scans it)
+// vx_fri_fold_prove folds every query natively on the host first (the same level algebra in Fx) and refuses a chain that does
+// not hold, or does not end in the final polynomial, with VX_ERR_STATEMENT before anything is proven.
+// Parity: tests/test_gpu_fri_fold.py compares trace, auxiliary columns and proof with tests/fri_fold_ref.py and the reference prover.
+#include <string.h>
+
+#include "air_fri_fold.cuh"
+#include "glh_poseidon.h"
+#include "vx_bus.h"
+#include "vx_internal.h"
+
+namespace {
+using namespace ffa;
+
+struct FoldArgs {
+    const uint64_t* index;   // [n_queries], < 2^LN (checked by the host)
+    const uint64_t* leaves;  // [n_queries][NL][32], canonical (checked by the host)
+    uint64_t beta[2 * MAX_LAYERS];
+    size_t n_queries, n;
+    int LN, NL, rpq;         // rpq = NL + FB rows per query
+    uint64_t winv;           // 1 / w, w the 2^LN-th root of unity
+    uint64_t* tr;            // [COLS][n]
+};
+
+__device__ __forceinline__ uint64_t brev64(uint64_t x, int bits) { return bits ? __brevll(x) >> (64 - bits) : 0; }
+
+__global__ __launch_bounds__(64) void k_fri_fold_trace(FoldArgs a) {
+    constexpr Tab T = make_tab();
+    const size_t i = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (i >= a.n) return;
+    uint64_t* out = a.tr + i;
+    auto put = [&](int col, uint64_t v) { out[(size_t)col * a.n] = v; };
+    const size_t qi = i / (size_t)a.rpq;
+    if (qi >= a.n_queries) {  // an idle row
+#pragma unroll 8
+        for (int j = 0; j < COLS; ++j) put(j, 0);
+        return;
+    }
+    const int k = (int)(i - qi * (size_t)a.rpq);
+    const bool is_fold = k < a.NL;
+    const uint64_t fo = is_fold ? ~(uint64_t)0 : 0;  // the mask of a fold row's cells
+    const uint64_t index = a.index[qi];
+    const int l = is_fold ? k : a.NL - 1;                     // the layer whose leaf this row folds
+    const int pos = is_fold ? 4 * k : 4 * a.NL + (k - a.NL);  // index bits consumed before this row
+    const uint64_t rr = index >> pos, within = is_fold ? rr & 15 : rr & 1;
+    put(ACT, 1), put(FOLD, is_fold), put(FIRST, k == 0), put(LAST, k == a.rpq - 1), put(FBIT, k == a.NL);
+    put(CNT, (uint64_t)k), put(R, rr), put(Q, is_fold ? rr >> 4 : rr >> 1), put(IDX, index);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) put(B + t, (within >> t) & 1);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) put(OH + t, is_fold && (uint64_t)t == within);
+#pragma unroll
+    for (int t = 0; t < MAX_LAYERS; ++t) put(LSEL + t, is_fold && t == k);
+    {  // the accumulator: w^-bitrev(the bits consumed so far), then this row's own steps
+        uint64_t acc = gl_pow(a.winv, brev64(index & (((uint64_t)1 << pos) - 1), pos));
+        put(A, acc);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            acc = gl_sqr(acc);
+            if ((within >> t) & 1) acc = gl_mul(acc, a.winv);
+            put(A + 1 + t, acc);
+        }
+    }
+    const uint64_t y0 = gl_mul(INV7, gl_pow(a.winv, brev64(index, a.LN)));
+    uint64_t yl = y0;  // 1 / x_l = (1 / x_0)^(16^l)
+    for (int t = 0; t < 4 * l; ++t) yl = gl_sqr(yl);
+    put(Y0, y0);
+    const uint64_t wl = (index >> (4 * l)) & 15;
+    const uint64_t* leaf = a.leaves + (qi * (size_t)a.NL + (size_t)l) * 32;
+    gl2 v[16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        v[t] = gl2{leaf[2 * t], leaf[2 * t + 1]};
+        put(LEAF + 2 * t, v[t].a & fo), put(LEAF + 2 * t + 1, v[t].b & fo);
+    }
+    const gl2 ev_in{leaf[2 * wl], leaf[2 * wl + 1]};
+    uint64_t s = gl_mul(yl, T.gp[wl]);
+    gl2 be{a.beta[2 * l], a.beta[2 * l + 1]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        put(SI + j, s & fo), put(BE + 2 * j, be.a & fo), put(BE + 2 * j + 1, be.b & fo);
+#pragma unroll
+        for (int p = 0; p < (8 >> j); ++p) {
+            const gl2 u = v[2 * p], w = v[2 * p + 1];
+            v[p] = gl2_add(gl2_scale(gl2_add(u, w), HALF), gl2_scale(gl2_mul(be, gl2_sub(u, w)), gl_mul(s, T.fc[j][p])));
+            put(vlev(j + 1) + 2 * p, v[p].a & fo), put(vlev(j + 1) + 2 * p + 1, v[p].b & fo);
+        }
+        s = gl_sqr(s), be = gl2_mul(be, be);
+    }
+    // a fold row: the value entering the layer and 1 / x_l; a bit row: ev_NL and 1 / x_NL (s is (1 / x_l)^16 by now: g^16 = 1)
+    const gl2 ev = is_fold ? ev_in : v[0];
+    put(EV, ev.a), put(EV + 1, ev.b), put(Y, is_fold ? yl : s);
+}
+
+__global__ __launch_bounds__(64) void k_fri_fold_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint64_t tree0) {
+    const size_t i = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (i >= n) return;
+    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + i]; };
+    gl2 h[N_HELP];
+#pragma unroll
+    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
+    const uint64_t fold = cell(FOLD), first = cell(FIRST), fbit = cell(FBIT);
+    if (fold | first | fbit) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the 17 message pairs, with one inversion
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        const uint64_t q = cell(Q), tree = gl_add(tree0, cell(CNT));
+        gl2 num[N_HELP], den[N_HELP], pre[N_HELP];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {  // received: multiplicity -FOLD
+            const gl2 da = bus.row_of(tree, q, (uint64_t)(2 * e), cell(LEAF + 2 * e)), db = bus.row_of(tree, q, (uint64_t)(2 * e + 1), cell(LEAF + 2 * e + 1));
+            num[e] = gl2_scale(gl2_add(da, db), fold ? GL_P - 1 : 0), den[e] = gl2_mul(da, db);
+        }
+        {  // the entry (received on the first row), the exit (sent on the first bit row)
+            const uint64_t idx = cell(IDX), va = cell(EV), vb = cell(EV + 1);
+            const gl2 de = bus.fri(idx, va, vb, bus::K<0>{}), dx = bus.fri(idx, va, vb, bus::K<1>{});
+            num[16] = gl2_sub(gl2_scale(de, fbit), gl2_scale(dx, first)), den[16] = gl2_mul(de, dx);
+        }
+        pre[0] = den[0];
+#pragma unroll
+        for (int e = 1; e < N_HELP; ++e) pre[e] = gl2_mul(pre[e - 1], den[e]);
+        gl2 inv = gl2_inv(pre[N_HELP - 1]);
+#pragma unroll
+        for (int e = N_HELP - 1; e >= 1; --e) {
+            h[e] = gl2_mul(num[e], gl2_mul(inv, pre[e - 1]));
+            inv = gl2_mul(inv, den[e]);
+        }
+        h[0] = gl2_mul(num[0], inv);
+    }
+    gl2 sum = h[0];
+#pragma unroll
+    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
+#pragma unroll
+    for (int e = 0; e < N_HELP; ++e) aux[(size_t)(2 * e) * n + i] = h[e].a, aux[(size_t)(2 * e + 1) * n + i] = h[e].b;
+    aux[(size_t)(2 * N_HELP) * n + i] = sum.a, aux[(size_t)(2 * N_HELP + 1) * n + i] = sum.b;  // increments; the scan makes them the running sum
+}
+
+int ceil_log2(size_t x) {
+    int l = 0;
+    while (((size_t)1 << l) < x) ++l;
+    return l;
+}
+// rows (log2) of the smallest table that holds n_queries queries of NL + FB rows (>= 5)
+int fri_fold_log_n(size_t n_queries, int log_lde, size_t n_layers) {
+    const int l = ceil_log2(n_queries * (size_t)(log_lde - 3 * (int)n_layers));
+    return l < 5 ? 5 : l;
+}
+constexpr size_t MAX_QUERIES = (size_t)1 << 20;
+bool shape_ok(int log_lde, size_t n_layers, size_t n_queries) {
+    return log_lde >= 5 && log_lde <= 32 && n_layers >= 1 && n_layers <= (size_t)MAX_LAYERS && 4 * (int)n_layers < log_lde && n_queries >= 1 && n_queries <= MAX_QUERIES;
+}
+#define FF_SHAPE_MSG "fri fold: log_lde %d (5..32), %zu layers (1..8, 4 bits each, at least one index bit left), %zu queries (1..2^20)"
+
+// one table on its own bus: the lookup challenges are the shared-challenge transcript of this table's (public inputs, trace cap)
+int32_t one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cap_words, uint64_t* chal, size_t n_chal) {
+    vx_shared_challenges_n(&pub, &n_pub, &cap, 1, cap_words, chal, n_chal);
+    return VX_OK;
+}
+
+// the claims as the host gets them: ranges and canonical words
+int32_t check_claims(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries) {
+    VX_CHECK(shape_ok(log_lde, n_layers, n_queries), FF_SHAPE_MSG, log_lde, n_layers, n_queries);
+    for (size_t i = 0; i < 2 * n_layers; ++i) VX_CHECK(betas[i] < glh::P, "fri fold: non-canonical beta word %zu", i);
+    for (size_t i = 0; i < n_queries; ++i) {
+        VX_CHECK(index[i] >> log_lde == 0, "fri fold: query %zu has an index outside the LDE", i);
+        VX_CHECK(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri fold: query %zu has a non-canonical ev_0", i);
+    }
+    for (size_t i = 0; i < n_queries * n_layers * 32; ++i) VX_CHECK(leaves[i] < glh::P, "fri fold: non-canonical leaf word (query %zu, layer %zu)", i / (32 * n_layers), i / 32 % n_layers);
+    return VX_OK;
+}
+
+// The witness of FriFoldAir on the device, and the public inputs.  The claims have passed check_claims.
+int32_t fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
+                           size_t n_queries, int log_n, uint64_t* trace_d, uint64_t pub_out[PUB]) {
+    const int rpq = log_lde - 3 * (int)n_layers;
+    VX_CHECK(log_n >= 5 && log_n <= 26 && n_queries * (size_t)rpq <= ((size_t)1 << log_n), "fri fold: %zu queries of %d rows do not fit 2^%d rows", n_queries, rpq, log_n);
+    VX_CHECK(tree0 < ((uint64_t)1 << 32), "fri fold: TREE0 out of range");
+    const size_t w_leaves = n_queries * n_layers * 32;
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (n_queries + w_leaves) * 8);
+    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "fri fold: out of device memory");
+    FoldArgs a{};
+    a.index = sc, a.leaves = sc + n_queries, a.n_queries = n_queries, a.n = (size_t)1 << log_n, a.LN = log_lde, a.NL = (int)n_layers, a.rpq = rpq;
+    a.winv = glh::inv(glh::root(log_lde)), a.tr = trace_d;
+    memcpy(a.beta, betas, 2 * n_layers * 8);
+    hipError_t e = hipMemcpyAsync(sc, index, n_queries * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sc + n_queries, leaves, w_leaves * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_fri_fold_trace, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, ctx->stream, a);
+        e = hipGetLastError();
+    }
+    vx_pool_free(ctx, sc);
+    if (e != hipSuccess) return vx_fail(ctx, VX_ERR_DEVICE, "fri fold: %s", hipGetErrorString(e));
+    vx_fri_fold_public(log_lde, betas, n_layers, tree0, index, ev0, leaves, n_queries, pub_out);
+    return VX_OK;
+}
+
+// ---- the fold on the host (Fx): what the table proves, checked natively before anything is proven
+Fx fold16_host(const uint64_t* leaf, uint64_t within, Fx beta, uint64_t x_inv) {
+    constexpr Tab T = make_tab();
+    Fx v[16];
+    for (int t = 0; t < 16; ++t) v[t] = Fx{leaf[2 * t], leaf[2 * t + 1]};
+    uint64_t s = glh::mul(x_inv, T.gp[within]);
+    for (int j = 0; j < 4; ++j) {
+        for (int p = 0; p < (8 >> j); ++p) {
+            const Fx u = v[2 * p], w = v[2 * p + 1];
+            v[p] = (u + w) * Fx{HALF, 0} + beta * (u - w) * Fx{glh::mul(s, T.fc[j][p]), 0};
+        }
+        s = glh::mul(s, s), beta = beta * beta;
+    }
+    return v[0];
+}
+}  // namespace
+
+// NL, NL + FB, 1 / w, TREE0, the betas (zero behind NL), the claims digest: shared with the verifier (vx_verify.hip)
+void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
+                        uint64_t pub[24]) {
+    pub[PUB_NL] = n_layers, pub[PUB_ROWS] = (uint64_t)log_lde - 3 * n_layers, pub[PUB_WINV] = glh::inv(glh::root(log_lde)), pub[PUB_TREE0] = tree0;
+    for (size_t i = 0; i < 2 * (size_t)MAX_LAYERS; ++i) pub[PUB_BETA + i] = i < 2 * n_layers ? betas[i] : 0;
+    const size_t per = 3 + 32 * n_layers;
+    std::vector<uint64_t> claims(n_queries * per);
+    for (size_t i = 0; i < n_queries; ++i) {
+        uint64_t* c = claims.data() + i * per;
+        c[0] = index[i], c[1] = ev0[2 * i], c[2] = ev0[2 * i + 1];
+        memcpy(c + 3, leaves + i * 32 * n_layers, 32 * n_layers * 8);
+    }
+    glh::hash_no_pad(claims.data(), claims.size(), pub + PUB_DIGEST);
+}
+
+int32_t FriFoldAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_fri_fold_aux, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[PUB_TREE0]);
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
+
+extern "C" {
+int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
+                              size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]) {
+    if (!ctx || !betas || !index || !ev0 || !leaves || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_TRY(check_claims(ctx, log_lde, betas, n_layers, index, ev0, leaves, n_queries));
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "fri fold: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, COLS, log_n);
+    return fri_fold_trace_dev(ctx, log_lde, betas, n_layers, tree0, index, ev0, leaves, n_queries, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_fri_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words) {
+    if (!cfg || !n_words || cfg->arity_bits != 4 || !shape_ok(log_lde, n_layers, n_queries)) return VX_ERR_ARG;
+    const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
+    if (log_n > 26) return VX_ERR_ARG;
+    size_t w = 0;
+    const int32_t rc = vx_stark_proof_bound(VX_AIR_FRI_FOLD, cfg, log_n, &w);
+    if (rc != VX_OK) return rc;
+    *n_words = VX_FFOLD_HDR + w;
+    return VX_OK;
+}
+
+int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
+                          const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len) {
+    if (!ctx || !cfg || !betas || !final_poly || !index || !ev0 || !leaves || !blob_len) return VX_ERR_ARG;
+    VX_CHECK(cfg->arity_bits == 4, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    VX_TRY(check_claims(ctx, log_lde, betas, n_layers, index, ev0, leaves, n_queries));
+    VX_CHECK(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
+    for (size_t i = 0; i < 2 * final_len; ++i) VX_CHECK(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
+    // the statement, natively: leaf_l[within_l] = ev_l, ev_(l+1) = the fold, final_poly(x_NL) = ev_NL
+    const uint64_t w = glh::root(log_lde);
+    for (size_t i = 0; i < n_queries; ++i) {
+        size_t rev = 0;
+        for (int b = 0; b < log_lde; ++b) rev = (rev << 1) | ((index[i] >> b) & 1);
+        uint64_t x = glh::mul(7, glh::pow(w, rev)), xi = glh::inv(x);
+        Fx ev{ev0[2 * i], ev0[2 * i + 1]};
+        for (size_t l = 0; l < n_layers; ++l) {
+            const uint64_t* leaf = leaves + (i * n_layers + l) * 32;
+            const uint64_t within = (index[i] >> (4 * l)) & 15;
+            if (leaf[2 * within] != ev.a || leaf[2 * within + 1] != ev.b)
+                return vx_fail(ctx, VX_ERR_STATEMENT, "fri fold: query %zu, layer %zu: the leaf's slot %llu is not the value the chain enters the layer with", i, l, (unsigned long long)within);
+            ev = fold16_host(leaf, within, Fx{betas[2 * l], betas[2 * l + 1]}, xi);
+            x = glh::pow(x, 16), xi = glh::pow(xi, 16);
+        }
+        Fx fp{0, 0};
+        for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+        if (fp.a != ev.a || fp.b != ev.b)
+            return vx_fail(ctx, VX_ERR_STATEMENT, "fri fold: query %zu, layer %zu: the folded value is not the final polynomial's at x^(16^%zu)", i, n_layers, n_layers);
+    }
+    const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
+    VX_CHECK(log_n <= 26, "fri fold: %zu queries of %d rows need more than 2^26 rows", n_queries, log_lde - 3 * (int)n_layers);
+    TableJob job;
+    const vx_chal_hook hook{one_table_hook, nullptr};
+    VX_TRY(run_table(ctx, job, VX_AIR_FRI_FOLD, log_n, COLS, PUB, cfg, &hook, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+        return fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, log_n, trace->d, pub);
+    }));
+    const size_t total = VX_FFOLD_HDR + job.len;
+    *blob_len = total;
+    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "fri fold: the blob needs %zu words, buffer has %zu", total, blob_cap);
+    blob_out[0] = VX_FFOLD_MAGIC, blob_out[1] = (uint64_t)log_lde, blob_out[2] = n_layers, blob_out[3] = n_queries, blob_out[4] = job.len;
+    memcpy(blob_out + VX_FFOLD_HDR, job.proof.data(), job.len * 8);
+    return VX_OK;
+}
+}  // extern "C"

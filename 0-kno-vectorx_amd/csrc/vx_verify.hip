@@ -297,8 +297,19 @@ void v_shared_challenges_n(const uint64_t* const* pubs, const size_t* n_pubs, co
     for (size_t q = 0; q < n_out; ++q) out[q] = sc.challenge();
 }
 
+// what the query phase of a verified proof hands to vx_stark_fri_claims: the FRI side of every query, as FriFoldAir's claims
+struct FriClaims {
+    int log_lde = 0;
+    std::vector<uint64_t> betas, final_poly, index, ev0, leaves, ev_last;  // leaves: [query][layer][2 arity], the `within` slot filled
+};
+static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen);
 int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public,
                             size_t n_expect_public, const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen) {
+    return stark_verify_impl(cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, nullptr, err, errlen);
+}
+static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen) {
     if (!cfg || !pr) return VX_ERR_ARG;
     // the configuration steers loops below (a circuit.json can carry it): the same ranges the prover accepts (vx_stark.hip)
     if (cfg->rate_bits < 1 || cfg->rate_bits > 3 || cfg->arity_bits < 1 || cfg->arity_bits > 5 || cfg->final_poly_bits < 0 || cfg->final_poly_bits > 27 ||
@@ -487,6 +498,11 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
     const Fx alpha_c = fx_pow(alpha, c);
     const int depth0 = LN - cap_h;
     const uint64_t wN = glh::root(LN);
+    if (fri) {
+        fri->log_lde = LN;
+        for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
+        for (const Fx& f : fpoly) fri->final_poly.push_back(f.a), fri->final_poly.push_back(f.b);
+    }
     for (size_t qi = 0; qi < n_queries; ++qi) {
         size_t x_index = ch.challenge() % N;
         NEED(have(c + nq + (ca ? 12 : 8) * (size_t)depth0), "proof truncated (query %zu)", qi);
@@ -512,6 +528,7 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
             ap = ap * alpha;
         }
         Fx ev = alpha_c * (s0 - y0) * fx_inv(Fx{x, 0} - zeta) + (s1 - y1) * fx_inv(Fx{x, 0} - zeta_next);
+        if (fri) fri->index.push_back(x_index), fri->ev0.push_back(ev.a), fri->ev0.push_back(ev.b);
         int cur_log = LN;
         for (size_t l = 0; l < n_layers; ++l) {
             const int a = arities[l];
@@ -528,6 +545,7 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
                 }
             }
             pos += 2 * (arity - 1);
+            if (fri) fri->leaves.insert(fri->leaves.end(), leaf.begin(), leaf.end());
             NEED(v_merkle(leaf.data(), 2 * arity, x_index >> a, pr + pos, depth, layer_caps[l]), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
             pos += 4 * (size_t)depth;
             // compute_evaluation: interpolate the coset {x g^i} and evaluate at beta
@@ -560,6 +578,7 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
         Fx fp{0, 0};
         for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + fpoly[k];
         NEED(fx_eq(fp, ev), "final polynomial evaluation mismatch (query %zu)", qi);
+        if (fri) fri->ev_last.push_back(ev.a), fri->ev_last.push_back(ev.b);
     }
     NEED(pos == len, "trailing data in proof (%zu of %zu words used)", pos, len);
     if (ca && !ext_chal)  // a stand-alone proof has nobody to cancel a bus total against
@@ -960,6 +979,128 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
     tab[1].air = air[1], tab[1].want = epub, tab[1].n_want = 2;
     tab[2].air = air[2], tab[2].want = hpub, tab[2].n_want = 15;
     return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen);
+}
+
+// FRI fold (the prover is vx_fri_fold_air.hip): the verifier holds what a STARK verifier holds when it enters the query phase's
+// fold loop -- per query the index, ev_0 (its own FRI combination) and the opened leaves of every layer, and the betas and the
+// final polynomial of the transcript -- and is the OTHER PARTY of the table's bus: it rebuilds every public input from its
+// arguments, derives the lookup challenges from them and the proof's trace cap, verifies the table under those challenges, and
+// accepts iff what the table received and sent is what it sends and receives:
+//     published total x rows = sum over the queries of  - sum over the layers l, j < 32 of 1 / D_row(tree l, index >> 4 (l + 1), j, leaf_l[j])
+//                                                        - 1 / D_fri(index, ev_0, 0)  +  1 / D_fri(index, final_poly(x_NL), 1).
+// NOTHING IS FOLDED here: per query one exponentiation for x_NL = x_0^(16^NL) and one Horner evaluation remain.
+static int32_t ff_arg(char* err, size_t errlen, const char* fmt, ...) {
+    if (err && errlen) {
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(err, errlen, fmt, ap);
+        va_end(ap);
+    }
+    return VX_ERR_ARG;
+}
+int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
+                           size_t final_len, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, char* err, size_t errlen) {
+    if (!cfg || !blob || !betas || !final_poly || !index || !ev0 || !leaves) return VX_ERR_ARG;
+    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    NEED(log_lde >= 5 && log_lde <= 32 && n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri fold: log_lde %d / %zu layers out of range", log_lde,
+         n_layers);
+    NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "fri fold: %zu queries (1..2^20)", n_queries);
+    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
+    NEED(len > VX_FFOLD_HDR && blob[0] == VX_FFOLD_MAGIC, "bad fri-fold blob");
+    NEED(blob[1] == (uint64_t)log_lde && blob[2] == (uint64_t)n_layers && blob[3] == (uint64_t)n_queries, "blob is for a different request");
+    NEED(blob[4] == len - VX_FFOLD_HDR, "blob lengths are inconsistent");
+    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri fold: non-canonical beta word %zu", i);
+    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
+    for (size_t i = 0; i < n_queries; ++i) {
+        NEED(index[i] >> log_lde == 0, "fri fold: claim %zu names an index outside the LDE", i);
+        NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri fold: claim %zu has a non-canonical ev_0", i);
+    }
+    for (size_t i = 0; i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "fri fold: claim %zu has a non-canonical leaf word", i / (32 * n_layers));
+    const uint64_t* proof = blob + VX_FFOLD_HDR;
+    const size_t plen = len - VX_FFOLD_HDR;
+    uint64_t pub[ffa::PUB];
+    vx_fri_fold_public(log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, pub);
+    // the lookup challenges: the shared-challenge transcript of this one table's (public inputs, trace cap)
+    const uint64_t *ppub = nullptr, *pcap = nullptr;
+    size_t n_ppub = 0;
+    NEED(vx_stark_proof_peek(proof, plen, cfg->cap_height, &ppub, &n_ppub, &pcap), "the proof is too short to hold a trace cap");
+    uint64_t chal[4];
+    {
+        const uint64_t* pubs[1] = {pub};
+        const size_t n_pubs[1] = {(size_t)ffa::PUB};
+        v_shared_challenges_n(pubs, n_pubs, &pcap, 1, (size_t)4 << cfg->cap_height, chal, 4);
+    }
+    const uint64_t* apub = nullptr;
+    int L = 0;
+    const int32_t rc = vx_stark_verify_ext(cfg, proof, plen, VX_AIR_FRI_FOLD, pub, ffa::PUB, chal, &apub, &L, err, errlen);
+    if (rc != VX_OK) return rc;
+    // the verifier's side of the bus: every leaf word and every entry sent (the table receives them: -), every exit received (+).
+    // One inversion for all of them (Montgomery batch: prefix products, one inverse, walked back)
+    const Fx zero{0, 0};
+    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
+    const size_t per = 32 * n_layers + 2, n_msg = n_queries * per;
+    std::vector<X2<Fx>> den(n_msg), pre(n_msg);
+    const uint64_t w = glh::root(log_lde);
+    for (size_t i = 0; i < n_queries; ++i) {
+        X2<Fx>* d = den.data() + i * per;
+        const Fx idx{index[i], 0};
+        for (size_t l = 0; l < n_layers; ++l)
+            for (size_t j = 0; j < 32; ++j)
+                d[32 * l + j] = bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0});
+        d[per - 2] = bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{});
+        const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
+        Fx fp{0, 0};
+        for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+        d[per - 1] = bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{});
+    }
+    for (size_t k = 0; k < n_msg; ++k) pre[k] = k ? pre[k - 1] * den[k] : den[k];
+    X2<Fx> inv;
+    {
+        const X2<Fx>& prod = pre[n_msg - 1];
+        const Fx norm = prod.a * prod.a - f_mul7(prod.b * prod.b);
+        NEED(norm.a != 0 || norm.b != 0, "fri fold: a claim's message has a zero denominator under the challenges");
+        const Fx ni = fx_inv(norm);
+        inv = X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
+    }
+    X2<Fx> sum{zero, zero};
+    for (size_t k = n_msg; k-- > 0;) {
+        const X2<Fx> t = k ? inv * pre[k - 1] : inv;
+        sum = k % per == per - 1 ? sum + t : sum - t;
+        inv = inv * den[k];
+    }
+    const uint64_t rows = ((uint64_t)1 << L) % glh::P;
+    NEED(sum.a.b == 0 && sum.b.b == 0 && glh::mul(apub[0], rows) == sum.a.a && glh::mul(apub[1], rows) == sum.b.a,
+         "the fold chains the table proves are not the claimed ones (the lookup bus does not balance)");
+    return VX_OK;
+}
+
+// The FRI side of a vx_stark_prove proof as FriFoldAir's claims (prover-side: it VERIFIES the proof on the way -- the transcript
+// is replayed by the verifier's own code -- and hands out what its query phase saw).  The proof omits the `within` slot of every
+// FRI leaf; here it is filled with the value the chain enters the layer with.
+int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int* log_lde, size_t* n_layers, size_t* final_len, size_t* n_queries, uint64_t betas_out[16],
+                            uint64_t* final_poly_out, size_t final_cap, uint64_t* index_out, uint64_t* ev0_out, uint64_t* ev_last_out, size_t query_cap, uint64_t* leaves_out,
+                            size_t leaves_cap, char* err, size_t errlen) {
+    if (!cfg || !proof || !log_lde || !n_layers || !final_len || !n_queries || !betas_out || !final_poly_out || !index_out || !ev0_out || !leaves_out) return VX_ERR_ARG;
+    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri claims: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    FriClaims fc;
+    const int32_t rc = stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, &fc, err, errlen);
+    if (rc != VX_OK) return rc;
+    const size_t nl = fc.betas.size() / 2, nq = fc.index.size();
+    if (nl < 1 || nl > (size_t)ffa::MAX_LAYERS || 4 * (int)nl >= fc.log_lde)
+        return ff_arg(err, errlen, "fri claims: a proof with %zu fold layers over an LDE of 2^%d has no FriFoldAir statement (1..8 layers, one index bit left)", nl, fc.log_lde);
+    *log_lde = fc.log_lde, *n_layers = nl, *final_len = fc.final_poly.size() / 2, *n_queries = nq;
+    if (final_cap < fc.final_poly.size() || query_cap < nq || leaves_cap < fc.leaves.size()) {
+        if (err && errlen) snprintf(err, errlen, "fri claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", final_cap, query_cap, leaves_cap, fc.final_poly.size(), nq, fc.leaves.size());
+        return VX_ERR_BUFSZ;
+    }
+    memset(betas_out, 0, 16 * 8);
+    memcpy(betas_out, fc.betas.data(), fc.betas.size() * 8);
+    memcpy(final_poly_out, fc.final_poly.data(), fc.final_poly.size() * 8);
+    memcpy(index_out, fc.index.data(), nq * 8);
+    memcpy(ev0_out, fc.ev0.data(), 2 * nq * 8);
+    if (ev_last_out) memcpy(ev_last_out, fc.ev_last.data(), 2 * nq * 8);
+    memcpy(leaves_out, fc.leaves.data(), fc.leaves.size() * 8);
+    return VX_OK;
 }
 
 }

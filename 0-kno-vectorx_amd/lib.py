@@ -31,6 +31,7 @@ SYMBOLS = [
     "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_unregister", "vx_poseidon_air_trace",
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
+    "vx_fri_fold_air_trace", "vx_fri_fold_proof_bound", "vx_fri_fold_prove", "vx_fri_fold_verify", "vx_stark_fri_claims",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -44,6 +45,7 @@ VX_SHA512_AIR_COLS, VX_SHA512_AIR_AUX_COLS = 801, 4
 VX_AIR_EPOCH_END, VX_EPOCH_END_AIR_COLS, VX_EPOCH_END_AIR_AUX_COLS = 15, 52, 46
 VX_AIR_MERKLE_OPEN, VX_MERKLE_OPEN_AIR_COLS, VX_MERKLE_OPEN_AIR_AUX_COLS = 16, 66, 4
 VX_AIR_LEAF_SPONGE, VX_LEAF_SPONGE_AIR_COLS, VX_LEAF_SPONGE_AIR_AUX_COLS = 17, 66, 12
+VX_AIR_FRI_FOLD, VX_FRI_FOLD_AIR_COLS, VX_FRI_FOLD_AIR_AUX_COLS = 18, 120, 36
 
 
 class JustificationStruct(C.Structure):
@@ -173,6 +175,11 @@ def load_library():
         "vx_merkle_rows_proof_bound": [C.POINTER(StarkConfig), sz, sz, sz, C.POINTER(sz)],
         "vx_merkle_rows_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, sz, C.c_int, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_merkle_rows_verify": [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, sz, vp, vp, sz, C.c_char_p, sz],
+        "vx_fri_fold_air_trace": [vp, C.c_int, vp, sz, C.c_uint64, vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_fri_fold_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, C.POINTER(sz)],
+        "vx_fri_fold_prove": [vp, C.POINTER(StarkConfig), C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_fri_fold_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, C.c_char_p, sz],
+        "vx_stark_fri_claims": [C.POINTER(StarkConfig), vp, sz, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -385,6 +392,57 @@ def merkle_rows_verify(blob, cap, log_leaves, leaf_idx, rows, cfg=None):
     rc = L.vx_merkle_rows_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, rw.shape[1], _ptr(idx), _ptr(rw), idx.size, err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
+
+
+FFOLD_MAGIC, FFOLD_HDR = 0x31444C4F46465856, 5  # "VXFFOLD1": magic, log2 of the inner LDE, fold layers, queries, proof length; then the FriFoldAir proof
+
+
+def _fri_claims(betas, final_poly, index, ev0, leaves):
+    """the claims of FriFoldAir as contiguous arrays: betas [NL][2], final_poly [len][2], index [n], ev0 [n][2], leaves [n][NL][32]"""
+    be = np.ascontiguousarray(betas, dtype=np.uint64).reshape(-1, 2)
+    fp = np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+    ev = np.ascontiguousarray(ev0, dtype=np.uint64).reshape(-1)
+    lv = np.ascontiguousarray(leaves, dtype=np.uint64).reshape(-1)
+    if ev.size != 2 * idx.size or lv.size != idx.size * be.shape[0] * 32:
+        raise ValueError("one ev_0 [2] and one leaf [32] per layer for every query")
+    return be, fp, idx, ev, lv
+
+
+def fri_fold_verify(blob, log_lde, betas, final_poly, index, ev0, leaves, cfg=None):
+    """Host-side check of a vx_fri_fold_prove blob against the verifier's own claims: the inner proof's LDE size, betas [NL][2] and
+    final polynomial [len][2], and per query (index, ev0 [2], leaves [NL][32]) in order.  Folds nothing; raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
+    err = C.create_string_buffer(256)
+    rc = L.vx_fri_fold_verify(C.byref(cfg), _ptr(b), b.size, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+def stark_fri_claims(proof, cfg=None):
+    """The FRI side of a vx_stark_prove proof (verified on the way) as FriFoldAir's claims -> dict(log_lde, betas [NL][2], final_poly
+    [len][2], index [n], ev0 [n][2], ev_last [n][2] -- the ev_NL the verifier accepted --, leaves [n][NL][32], the slot `within` filled)."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    nq = int(cfg.num_queries)
+    n_lay = int(pr[9]) if pr.size > 9 and int(pr[9]) <= 16 else 0
+    fin = int(pr[10 + n_lay]) if pr.size > 10 + n_lay and int(pr[10 + n_lay]) <= 1 << 27 else 0
+    betas, fpoly = np.zeros(16, dtype=np.uint64), np.zeros(2 * max(fin, 1), dtype=np.uint64)
+    index, ev0, ev_last = np.zeros(max(nq, 1), dtype=np.uint64), np.zeros(2 * max(nq, 1), dtype=np.uint64), np.zeros(2 * max(nq, 1), dtype=np.uint64)
+    leaves = np.zeros(max(nq * n_lay * 32, 1), dtype=np.uint64)
+    log_lde, nl, fl, n = C.c_int(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    rc = L.vx_stark_fri_claims(C.byref(cfg), _ptr(pr), pr.size, C.byref(log_lde), C.byref(nl), C.byref(fl), C.byref(n), _ptr(betas), _ptr(fpoly), fpoly.size, _ptr(index), _ptr(ev0),
+                               _ptr(ev_last), index.size, _ptr(leaves), leaves.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+    NL, Q = nl.value, n.value
+    return dict(log_lde=log_lde.value, betas=betas[: 2 * NL].reshape(NL, 2), final_poly=fpoly[: 2 * fl.value].reshape(-1, 2), index=index[:Q], ev0=ev0[: 2 * Q].reshape(Q, 2),
+                ev_last=ev_last[: 2 * Q].reshape(Q, 2), leaves=leaves[: Q * NL * 32].reshape(Q, NL, 32))
 
 
 ROT_HDR = 28  # words before the first proof in a rotate blob
@@ -604,6 +662,35 @@ class Context:
                 raise VxError(rc, "merkle rows: %d openings of %d words of a tree of %d leaves" % (idx.size, leaf_len, tree.n_leaves))
             out = np.empty(need.value, dtype=np.uint64)
         rc = self.L.vx_merkle_rows_prove(self.h, C.byref(cfg), tree.h, data.h, off, leaf_len, layout, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
+        if rc != 0:
+            e = VxError(rc, self.L.vx_last_error(self.h).decode())
+            e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
+            raise e
+        return out[: need.value]
+
+    def fri_fold_air_trace(self, log_lde, betas, index, ev0, leaves, log_n, tree0=0, out=None):
+        """The witness of FriFoldAir for the claims (index[i], ev0[i][2], leaves[i][NL][32]) under betas [NL][2]
+        -> (Buffer [120][2^log_n], the 24 public inputs)."""
+        be, _, idx, ev, lv = _fri_claims(betas, [0, 0], index, ev0, leaves)
+        out = out or self.alloc(VX_FRI_FOLD_AIR_COLS << log_n)
+        pub = np.zeros(24, dtype=np.uint64)
+        self._ck(self.L.vx_fri_fold_air_trace(self.h, log_lde, _ptr(be), be.shape[0], tree0, _ptr(idx), _ptr(ev), _ptr(lv), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def fri_fold_prove(self, log_lde, betas, final_poly, index, ev0, leaves, cfg=None, out=None):
+        """Proves the fold chains of the claims in one FriFoldAir table -> blob words (lib.fri_fold_verify checks it).  The chains are
+        folded natively first: VxError(VX_ERR_STATEMENT) names the query and layer that do not hold.  out: a caller's uint64 buffer;
+        when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        cfg = cfg or self.stark_config()
+        be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
+        need = C.c_size_t(0)
+        if out is None:
+            rc = self.L.vx_fri_fold_proof_bound(C.byref(cfg), log_lde, be.shape[0], idx.size, C.byref(need))
+            if rc != 0:
+                raise VxError(rc, "fri fold: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries)")
+            out = np.zeros(need.value, dtype=np.uint64)
+        rc = self.L.vx_fri_fold_prove(self.h, C.byref(cfg), log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size, _ptr(out), out.size,
+                                      C.byref(need))
         if rc != 0:
             e = VxError(rc, self.L.vx_last_error(self.h).decode())
             e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs

@@ -165,7 +165,8 @@ typedef struct vx_stark_config {
  * (VX_AIR_BLAKE_CHAIN), 4 SHA-256 authority-set commitment (VX_AIR_SHA_CHAIN), 7 / 8 / 9 SHA-256 Merkle trees of 256 /
  * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log.
  * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove.
- * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove. */
+ * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove.
+ * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -231,8 +232,8 @@ int32_t vx_poseidon_air_trace(vx_ctx* ctx, const vx_buf* states, size_t n_perm, 
  * iff the table's published total equals the sum over the verifier's own claims.  Public inputs (9): root (4), D, and the claims
  * digest hash_n_to_hash_no_pad((index, d0, d1, d2, d3) of every opening, in order), which makes the lookup challenges depend on
  * the claims.  The opened leaf ROWS are hashed in-proof by LeafSpongeAir (below: vx_merkle_rows_prove, whose claims are rows, not
- * digests).  STILL OUTSIDE (the next tables): there is one tree per proof, and the FRI fold, the evaluation at zeta and the
- * transcript stay on the host.
+ * digests).  STILL OUTSIDE (the next tables): there is one tree per proof, and the evaluation at zeta and the transcript stay on
+ * the host (the FRI fold is FriFoldAir, below).
  * vx_merkle_open_air_trace: the witness on its own (test surface) -- leaf_idx: n_idx >= 1 leaf indices (host; duplicates
  *   allowed); trace_out: [VX_MERKLE_OPEN_AIR_COLS][2^log_n] with 2^log_n >= 32 n_idx D; blocks behind the paths are idle.
  * vx_merkle_openings_prove: trace + proof at the smallest such log_n (>= 5) under lookup challenges that are the shared-challenge
@@ -278,7 +279,7 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
  *   accepts iff  total_open x 2^log_n_open + total_sponge x 2^log_n_sponge = sum over the claims and j < leaf_len of
  *   1 / D_row(index, j, row[j]).  Its row-claims digest costs as many permutations as hashing the rows would; what it no longer
  *   does is anything per tree level, and the row bus is one whose other party a later table (FRI fold, evaluation at zeta)
- *   replaces.  STILL OUTSIDE: several trees (roots) per proof, the FRI fold, the evaluation at zeta, the transcript. */
+ *   replaces.  STILL OUTSIDE: several trees (roots) per proof, the evaluation at zeta, the transcript (the FRI fold: FriFoldAir). */
 enum { VX_AIR_LEAF_SPONGE = 17, VX_LEAF_SPONGE_AIR_COLS = 66, VX_LEAF_SPONGE_AIR_AUX_COLS = 12 };
 int32_t vx_leaf_sponge_air_trace(vx_ctx* ctx, const vx_buf* data, size_t off, size_t n_leaves, size_t leaf_len, int layout, const uint64_t* leaf_idx,
                                  size_t n_idx, int log_n, vx_buf* trace_out, uint64_t public_out[14]);
@@ -287,6 +288,49 @@ int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_t
                              const uint64_t* leaf_idx, size_t n_idx, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* cap, int cap_height, int log_leaves,
                               size_t leaf_len, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, char* err, size_t errlen);
+/* ---- FriFoldAir: the FRI fold chain of every query of one inner proof in one STARK table (AIR id VX_AIR_FRI_FOLD; compiled:
+ * csrc/air_fri_fold.cuh) -- the per-query loop of verify_fri_proof (plonky2 v0.2.0 fri/verifier.rs: compute_evaluation at arity 16,
+ * x <- x^16, index >>= 4; vx_stark_verify does the same on the host), the third table of proof aggregation and the first that
+ * carries field arithmetic of a STARK verifier's query phase.  It is compiled for arity_bits = 4 (vx_stark_default_config): every
+ * entry point that takes a configuration REFUSES another arity with VX_ERR_ARG.
+ * The inner proof: an LDE of 2^log_lde points, n_layers >= 1 fold layers with challenges betas[n_layers][2], log_lde - 4 n_layers
+ * >= 1 index bits left, and a final polynomial final_poly[final_len][2].  A CLAIM is one query: index (< 2^log_lde), ev0[2] (the
+ * FRI combination the chain starts from) and leaves[n_layers][32] (the 16 extension values of the query's leaf in every layer,
+ * the slot index's own value included).  PROVEN per claim: leaf_l[(index >> 4l) & 15] = ev_l, ev_(l+1) = the interpolant of
+ * leaf_l's coset at beta_l, with x_0 = 7 w^bitrev(index) and x_(l+1) = x_l^16; ev_NL leaves the table.  One row per (query,
+ * layer) and one per remaining index bit; no positional shape, so any number of queries fits the one AIR id at any log_n >= 5
+ * (default configuration, 2^21 LDE: 9 rows per query, 84 queries in 2^10 rows).  Public inputs (24): n_layers, rows per query,
+ * 1 / w, TREE0, eight betas (zero behind n_layers) and the claims digest hash_n_to_hash_no_pad((index, ev0, leaves) of every
+ * query, in order).  Bus: a fold row receives the 32 words of its leaf as row messages (leaf index, position, word, tree =
+ * TREE0 + layer) -- what a leaf-sponge table over the layer trees sends; until several trees fit one proof the verifier sends them
+ * -- a query's first row receives (index, ev0, 0) and its first bit row sends (index, ev_NL, 1).
+ * vx_fri_fold_air_trace: the witness on its own (test surface; host claims, nothing is checked beyond ranges) -- trace_out:
+ *   [VX_FRI_FOLD_AIR_COLS][2^log_n] with 2^log_n >= n_queries (log_lde - 3 n_layers); rows behind the queries are idle.
+ * vx_fri_fold_prove: folds every query natively on the host first and returns VX_ERR_STATEMENT, naming query and layer, when
+ *   leaf_l[within] != ev_l or final_poly(x_NL) != ev_NL; then trace + proof at the smallest log_n (>= 5) with TREE0 = 0, under
+ *   lookup challenges that are the shared-challenge transcript of this one table.  Blob: the magic "VXFFOLD1", log_lde, n_layers,
+ *   n_queries, the proof's length; then the table proof.  VX_ERR_BUFSZ (with *blob_len set) when the buffer is too small.
+ * vx_fri_fold_verify (host only, FOLDS NOTHING): rebuilds every public input from its arguments, recomputes the challenges,
+ *   verifies the table under them and accepts iff published total x 2^log_n = sum over the claims of - 1/D_row over every leaf
+ *   word, - 1/D(index, ev0, 0), + 1/D(index, final_poly(x_NL), 1): per query one exponentiation and one Horner evaluation.
+ * vx_stark_fri_claims (host only, prover-side): replays a vx_stark_prove proof (it is verified on the way) and hands out its FRI
+ *   side as claims: betas_out[16] (zero behind n_layers), the final polynomial, and per query the index, ev0, optionally the
+ *   ev_NL the verifier accepted (ev_last_out may be NULL), and the FULL leaves of every layer -- the proof omits the slot
+ *   `within`, which is filled with the value the chain enters the layer with.  final_cap / leaves_cap are in words, query_cap in
+ *   queries; VX_ERR_BUFSZ (sizes set) when one is too small.
+ * STILL OUTSIDE: several roots per table (the leaves' Merkle side), the FRI combination / evaluation at zeta, the transcript,
+ * and the final-polynomial evaluation, which stays the verifier's single Horner per query. */
+enum { VX_AIR_FRI_FOLD = 18, VX_FRI_FOLD_AIR_COLS = 120, VX_FRI_FOLD_AIR_AUX_COLS = 36 };
+int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0,
+                              const uint64_t* leaves, size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]);
+int32_t vx_fri_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words);
+int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
+                          const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
+                           size_t final_len, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, char* err, size_t errlen);
+int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int* log_lde, size_t* n_layers, size_t* final_len, size_t* n_queries,
+                            uint64_t betas_out[16], uint64_t* final_poly_out, size_t final_cap, uint64_t* index_out, uint64_t* ev0_out, uint64_t* ev_last_out, size_t query_cap,
+                            uint64_t* leaves_out, size_t leaves_cap, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */
