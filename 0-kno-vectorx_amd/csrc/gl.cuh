@@ -210,5 +210,21 @@ __device__ __forceinline__ gl2 gl2_inv(gl2 x) {
     uint64_t ni = gl_inv(n);
     return {gl_mul(x.a, ni), gl_mul(gl_neg(x.b), ni)};
 }
+// h[e] = num[e] / den[e] for e < N with ONE inversion (Montgomery batch: the products of den[0..e], their inverse, walked back).
+// The helpers of a row or block of a logUp witness (k_leaf_sponge_aux, k_fri_fold_aux); every den[e] is non-zero.
+template <int N>
+__device__ __forceinline__ void gl2_batch_div(const gl2 (&num)[N], const gl2 (&den)[N], gl2 (&h)[N]) {
+    gl2 pre[N];
+    pre[0] = den[0];
+#pragma unroll
+    for (int e = 1; e < N; ++e) pre[e] = gl2_mul(pre[e - 1], den[e]);
+    gl2 inv = gl2_inv(pre[N - 1]);
+#pragma unroll
+    for (int e = N - 1; e >= 1; --e) {
+        h[e] = gl2_mul(num[e], gl2_mul(inv, pre[e - 1]));
+        inv = gl2_mul(inv, den[e]);
+    }
+    h[0] = gl2_mul(num[0], inv);
+}
 
 __device__ __forceinline__ uint32_t brev32(uint32_t x, int bits) { return bits ? (__brev(x) >> (32 - bits)) : 0; }

@@ -1,6 +1,6 @@
 // The round walk of one PoseidonAir block (air_library.py poseidon_builder: 48 columns, 32 rows per permutation), shared by the
 // witness kernels of the tables built from such blocks (k_poseidon_air_trace in vx_poseidon.hip, k_merkle_open_trace in
-// vx_merkle_open_air.hip).  The 30 rounds run in the PLAIN schedule (constant layer, s-box, MDS: the rows of the table are the
+// vx_merkle_open_air.hip, k_leaf_sponge_trace in vx_leaf_sponge_air.hip), and the broadcast of a block's own columns.  The 30 rounds run in the PLAIN schedule (constant layer, s-box, MDS: the rows of the table are the
 // states entering each round, not the folded form the hashing kernels use).
 #pragma once
 #include "gl.cuh"
@@ -36,5 +36,18 @@ __device__ __forceinline__ void poseidon_air_walk(uint64_t (&s)[12], uint64_t* t
                 s[q] = gl_reduce128((uint64_t)(acc >> 64), (uint64_t)acc);
             }
         }
+    }
+}
+
+// The columns a block holds constant: writes v[j] to rows row0 .. row0 + 31 of column col0 + j, j < N (unrolled over j: v[] stays
+// in registers).
+template <int N>
+__device__ __forceinline__ void poseidon_air_block_cols(const uint64_t (&v)[N], uint64_t* tr, size_t n, int col0, size_t row0) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        uint64_t* col = tr + (size_t)(col0 + j) * n + row0;
+        const uint64_t x = v[j];
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) col[r] = x;
     }
 }

@@ -3,10 +3,14 @@
 // sit on ONE logUp bus and must use the same lookup challenges, drawn after every trace is committed.  Each table is proven
 // from its own host thread on its own context; the provers stop after their trace caps (vx_chal_hook) and MEET: every one
 // deposits its public inputs + cap, waits for all the others and derives the challenges from the transcript of all
-// (public inputs, cap) pairs in table order.
+// (public inputs, cap) pairs in table order.  The aggregation provers (vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
+// vx_fri_fold_air.hip) use the same runner; what only they share -- the hook of a table alone on its bus, the blob writer, the
+// blob formats and the public inputs of their AIRs, which the verifier (vx_verify.hip) rebuilds with the same functions -- is
+// declared here as well.
 #pragma once
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -44,6 +48,9 @@ struct BusParty {
     int who;
 };
 int32_t vx_bus_hook(void* party, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal);
+// the hook of a table that is alone on its bus (the other party is the verifier): the lookup challenges are the shared-challenge
+// transcript of this one table's (public inputs, trace cap); `party` is unused
+int32_t vx_one_table_hook(void* party, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal);
 // one table of the statement, proven on its own context (all but the caller's own table from a host thread of their own)
 struct TableJob {
     vx_ctx* c = nullptr;
@@ -76,6 +83,10 @@ struct TableJoin {
 };
 // out[0 .. n): the chain of side contexts behind `ctx` (every table is proven on a context of its own); fails with `msg`
 int32_t side_contexts(vx_ctx* ctx, size_t n, vx_ctx** out, const char* msg);
+// An aggregation blob (the three formats below): magic, the request words, one length per proof, the proofs.  Sets *blob_len and
+// writes the blob, or fails with VX_ERR_BUFSZ ("<what>: the blob needs N words, buffer has M") when blob_out cannot hold it.
+int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
+                  size_t blob_cap, size_t* blob_len);
 
 // The three tables of a justification -- authority-set commitment (ShaChainAir, sends the chosen signers' keys), Ed25519
 // (EdAir) and SHA-512 (Sha512Air) -- as parties first, first + 1, first + 2 of `rv`.  The prover verifies exactly
@@ -119,8 +130,13 @@ static constexpr size_t VX_MROWS_HDR = 6;
 // log2 of the inner proof's LDE, fold layers, queries, length of the FriFoldAir proof that follows
 static const uint64_t VX_FFOLD_MAGIC = 0x31444c4f46465856ULL;  // "VXFFOLD1"
 static constexpr size_t VX_FFOLD_HDR = 5;
-// FriFoldAir's public inputs from the claims (betas [n_layers][2], ev0 [n_queries][2], leaves [n_queries][n_layers][32]), prover and
-// verifier alike
+// The public inputs of the three aggregation AIRs from the claims, prover and verifier alike (each defined beside its AIR's witness).
+// MerkleOpenAir: root, depth, the digest of the claims [n_idx][5] = (index, leaf digest); claims == nullptr leaves the digest to
+// the caller (vx_merkle_rows_verify, which never sees the leaf digests, takes it from the proof)
+void vx_merkle_open_public(const uint64_t root[4], int depth, const uint64_t* claims, size_t n_idx, uint64_t pub[9]);
+// LeafSpongeAir: L, B, the tail flags, the digest of the claims [n_idx][1 + leaf_len] = (index, row)
+void vx_leaf_sponge_public(size_t leaf_len, const uint64_t* claims, size_t n_idx, uint64_t pub[14]);
+// FriFoldAir: from betas [n_layers][2], ev0 [n_queries][2], leaves [n_queries][n_layers][32]
 void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
                         uint64_t pub[24]);
 

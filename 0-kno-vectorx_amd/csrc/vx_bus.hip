@@ -1,6 +1,7 @@
 // Implementation of vx_bus.h: the rendezvous at which the tables of one statement draw their shared lookup challenges
-// (BusMeet), the runner / starter / join of "one table on a bus" that both circuit provers use, and the three tables of a
-// justification.  Host code only: the kernels of every table live with their AIR (vx_*_air.hip).
+// (BusMeet), the runner / starter / join of "one table on a bus" that both circuit provers use, the three tables of a
+// justification, and what the aggregation provers (vx_merkle_openings_prove, vx_merkle_rows_prove, vx_fri_fold_prove) share: the
+// hook of a table alone on its bus and the writer of their blobs.  Host code only: the kernels of every table live with their AIR (vx_*_air.hip).
 #include <string.h>
 
 #include "vx_bus.h"
@@ -65,6 +66,10 @@ int32_t vx_bus_hook(void* u, const uint64_t* pub, size_t n_pub, const uint64_t* 
     BusParty* p = (BusParty*)u;
     return BusMeet::meet(p->rv, p->who, pub, n_pub, cap, cw, chal, n_chal);
 }
+int32_t vx_one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal) {
+    vx_shared_challenges_n(&pub, &n_pub, &cap, 1, cw, chal, n_chal);
+    return VX_OK;
+}
 
 size_t vx_justification_proof_bound(const vx_stark_config* cfg, size_t n_authorities, int32_t* rc_out) {
     size_t w2 = 0, w4 = 0, w5 = 0;
@@ -115,6 +120,19 @@ int32_t side_contexts(vx_ctx* ctx, size_t n, vx_ctx** out, const char* msg) {
     vx_ctx* c = ctx;
     for (size_t t = 0; t < n; ++t) out[t] = c = c ? vx_side_ctx(c) : nullptr;
     VX_CHECK(c, "%s", msg);
+    return VX_OK;
+}
+int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
+                  size_t blob_cap, size_t* blob_len) {
+    size_t total = 1 + request.size() + jobs.size();
+    for (const TableJob* j : jobs) total += j->len;
+    *blob_len = total;
+    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "%s: the blob needs %zu words, buffer has %zu", what, total, blob_cap);
+    uint64_t* w = blob_out;
+    *w++ = magic;
+    for (uint64_t r : request) *w++ = r;
+    for (const TableJob* j : jobs) *w++ = j->len;
+    for (const TableJob* j : jobs) memcpy(w, j->proof.data(), j->len * 8), w += j->len;
     return VX_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "glh_poseidon.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
+#include "vx_table_shapes.h"
 
 namespace {
 using namespace ffa;
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(64) void k_fri_fold_aux(const uint64_t* __restrict_
     if (fold | first | fbit) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the 17 message pairs, with one inversion
         const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
         const uint64_t q = cell(Q), tree = gl_add(tree0, cell(CNT));
-        gl2 num[N_HELP], den[N_HELP], pre[N_HELP];
+        gl2 num[N_HELP], den[N_HELP];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {  // received: multiplicity -FOLD
             const gl2 da = bus.row_of(tree, q, (uint64_t)(2 * e), cell(LEAF + 2 * e)), db = bus.row_of(tree, q, (uint64_t)(2 * e + 1), cell(LEAF + 2 * e + 1));
@@ -122,16 +123,7 @@ __global__ __launch_bounds__(64) void k_fri_fold_aux(const uint64_t* __restrict_
             const gl2 de = bus.fri(idx, va, vb, bus::K<0>{}), dx = bus.fri(idx, va, vb, bus::K<1>{});
             num[16] = gl2_sub(gl2_scale(de, fbit), gl2_scale(dx, first)), den[16] = gl2_mul(de, dx);
         }
-        pre[0] = den[0];
-#pragma unroll
-        for (int e = 1; e < N_HELP; ++e) pre[e] = gl2_mul(pre[e - 1], den[e]);
-        gl2 inv = gl2_inv(pre[N_HELP - 1]);
-#pragma unroll
-        for (int e = N_HELP - 1; e >= 1; --e) {
-            h[e] = gl2_mul(num[e], gl2_mul(inv, pre[e - 1]));
-            inv = gl2_mul(inv, den[e]);
-        }
-        h[0] = gl2_mul(num[0], inv);
+        gl2_batch_div(num, den, h);
     }
     gl2 sum = h[0];
 #pragma unroll
@@ -141,27 +133,11 @@ __global__ __launch_bounds__(64) void k_fri_fold_aux(const uint64_t* __restrict_
     aux[(size_t)(2 * N_HELP) * n + i] = sum.a, aux[(size_t)(2 * N_HELP + 1) * n + i] = sum.b;  // increments; the scan makes them the running sum
 }
 
-int ceil_log2(size_t x) {
-    int l = 0;
-    while (((size_t)1 << l) < x) ++l;
-    return l;
-}
-// rows (log2) of the smallest table that holds n_queries queries of NL + FB rows (>= 5)
-int fri_fold_log_n(size_t n_queries, int log_lde, size_t n_layers) {
-    const int l = ceil_log2(n_queries * (size_t)(log_lde - 3 * (int)n_layers));
-    return l < 5 ? 5 : l;
-}
 constexpr size_t MAX_QUERIES = (size_t)1 << 20;
 bool shape_ok(int log_lde, size_t n_layers, size_t n_queries) {
     return log_lde >= 5 && log_lde <= 32 && n_layers >= 1 && n_layers <= (size_t)MAX_LAYERS && 4 * (int)n_layers < log_lde && n_queries >= 1 && n_queries <= MAX_QUERIES;
 }
 #define FF_SHAPE_MSG "fri fold: log_lde %d (5..32), %zu layers (1..8, 4 bits each, at least one index bit left), %zu queries (1..2^20)"
-
-// one table on its own bus: the lookup challenges are the shared-challenge transcript of this table's (public inputs, trace cap)
-int32_t one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cap_words, uint64_t* chal, size_t n_chal) {
-    vx_shared_challenges_n(&pub, &n_pub, &cap, 1, cap_words, chal, n_chal);
-    return VX_OK;
-}
 
 // the claims as the host gets them: ranges and canonical words
 int32_t check_claims(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries) {
@@ -290,15 +266,10 @@ int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, 
     const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
     VX_CHECK(log_n <= 26, "fri fold: %zu queries of %d rows need more than 2^26 rows", n_queries, log_lde - 3 * (int)n_layers);
     TableJob job;
-    const vx_chal_hook hook{one_table_hook, nullptr};
+    const vx_chal_hook hook{vx_one_table_hook, nullptr};
     VX_TRY(run_table(ctx, job, VX_AIR_FRI_FOLD, log_n, COLS, PUB, cfg, &hook, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
         return fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, log_n, trace->d, pub);
     }));
-    const size_t total = VX_FFOLD_HDR + job.len;
-    *blob_len = total;
-    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "fri fold: the blob needs %zu words, buffer has %zu", total, blob_cap);
-    blob_out[0] = VX_FFOLD_MAGIC, blob_out[1] = (uint64_t)log_lde, blob_out[2] = n_layers, blob_out[3] = n_queries, blob_out[4] = job.len;
-    memcpy(blob_out + VX_FFOLD_HDR, job.proof.data(), job.len * 8);
-    return VX_OK;
+    return pack_blob(ctx, "fri fold", VX_FFOLD_MAGIC, {(uint64_t)log_lde, n_layers, n_queries}, {&job}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

@@ -184,5 +184,4 @@ int32_t vx_epoch_end_trace_dev(vx_ctx* ctx, const uint8_t* header_d, size_t head
 int32_t vx_sha_chain_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, size_t n_keys, const uint8_t* signed_flags, uint64_t bus_on, int log_n, uint64_t* trace_d,
                                uint64_t public_inputs_out[10], uint8_t commitment_out[32]);
 int32_t vx_merkle_open_trace_dev(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[9]);
-int vx_merkle_open_log_n(size_t n_idx, int depth);  // rows (log2) of the smallest MerkleOpenAir table for n_idx paths of `depth` levels
 void vx_merkle_levels_launch(vx_ctx* ctx, uint64_t* levels, size_t n_leaves, size_t cap);

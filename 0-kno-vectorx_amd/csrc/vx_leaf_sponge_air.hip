@@ -21,6 +21,7 @@
 #include "poseidon_air.cuh"
 #include "vx_bus.h"
 #include "vx_internal.h"
+#include "vx_table_shapes.h"
 
 namespace {
 using namespace lsp;
@@ -89,13 +90,7 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __rest
     poseidon_air_walk(s, tr, n, 32 * b);
 #pragma unroll
     for (int i = 0; i < 4; ++i) shape[DIG - MSG + i] = s[i];
-#pragma unroll
-    for (int j = 0; j < COLS - MSG; ++j) {  // (unrolled: shape[] stays in registers)
-        uint64_t* col = tr + (size_t)(MSG + j) * n + 32 * b;
-        const uint64_t v = shape[j];
-#pragma unroll 8
-        for (int r = 0; r < 32; ++r) col[r] = v;
-    }
+    poseidon_air_block_cols(shape, tr, n, MSG, 32 * b);
 }
 
 __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint32_t wmask) {
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restri
     if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the five message pairs, with one inversion
         const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
         const uint64_t idx = cell(IDX), pos8 = 8 * cell(POS), last = cell(LASTB);
-        gl2 num[N_HELP], den[N_HELP], pre[N_HELP];
+        gl2 num[N_HELP], den[N_HELP];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const uint64_t ma = last ? (wmask >> (2 * e)) & 1 : 1, mb = last ? (wmask >> (2 * e + 1)) & 1 : 1;
@@ -120,16 +115,7 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restri
             const gl2 dlo = bus.open(idx, cell(DIG), cell(DIG + 1), bus::K<0>{}), dhi = bus.open(idx, cell(DIG + 2), cell(DIG + 3), bus::K<1>{});
             num[4] = gl2_scale(gl2_add(dlo, dhi), last ? GL_P - 1 : 0), den[4] = gl2_mul(dlo, dhi);  // received: multiplicity -LASTB
         }
-        pre[0] = den[0];
-#pragma unroll
-        for (int e = 1; e < N_HELP; ++e) pre[e] = gl2_mul(pre[e - 1], den[e]);
-        gl2 inv = gl2_inv(pre[N_HELP - 1]);
-#pragma unroll
-        for (int e = N_HELP - 1; e >= 1; --e) {
-            h[e] = gl2_mul(num[e], gl2_mul(inv, pre[e - 1]));
-            inv = gl2_mul(inv, den[e]);
-        }
-        h[0] = gl2_mul(num[0], inv);
+        gl2_batch_div(num, den, h);
     }
     gl2 sum = h[0];
 #pragma unroll
@@ -146,23 +132,16 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restri
     for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
 }
 
-int ceil_log2(size_t x) {
-    int l = 0;
-    while (((size_t)1 << l) < x) ++l;
-    return l;
-}
-size_t sponge_blocks(size_t leaf_len) { return (leaf_len + 7) / 8; }
-// rows (log2) of the smallest table that holds n_idx leaves of leaf_len words (>= 5)
-int leaf_sponge_log_n(size_t n_idx, size_t leaf_len) { return ceil_log2(32 * n_idx * sponge_blocks(leaf_len)); }
 constexpr size_t MAX_LEAF_LEN = (size_t)1 << 20;
+}  // namespace
 
-// L, B, the tail flags; the digest is the caller's
-void sponge_shape_public(size_t leaf_len, uint64_t* pub) {
+// L, B, the tail flags, the digest of the (index, row) claims: shared with the verifier (vx_verify.hip)
+void vx_leaf_sponge_public(size_t leaf_len, const uint64_t* claims, size_t n_idx, uint64_t pub[14]) {
     const size_t t = leaf_len % 8;
     pub[PUB_L] = leaf_len, pub[PUB_B] = sponge_blocks(leaf_len);
     for (size_t i = 0; i < 8; ++i) pub[PUB_W + i] = i < (t ? t : 8);
+    glh::hash_no_pad(claims, n_idx * (leaf_len + 1), pub + PUB_DIGEST);
 }
-}  // namespace
 
 int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     const size_t n = (size_t)1 << log_n, blocks = n / 32;
@@ -221,8 +200,7 @@ static int32_t leaf_sponge_trace_dev(vx_ctx* ctx, const uint64_t* data_d, size_t
     if (bad)
         return vx_fail(ctx, VX_ERR_STATEMENT, "merkle rows: opening %llu (leaf %llu) does not hash to the tree's leaf digest -- the leaf data is not what the tree was built from",
                        (unsigned long long)(bad - 1), (unsigned long long)leaf_idx[bad - 1]);
-    sponge_shape_public(leaf_len, pub_out);
-    glh::hash_no_pad(claims.data(), claims.size(), pub_out + PUB_DIGEST);
+    vx_leaf_sponge_public(leaf_len, claims.data(), n_idx, pub_out);
     return VX_OK;
 }
 
@@ -287,12 +265,6 @@ int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_t
     threads.join();
     if (rc == VX_OK && open.rc != VX_OK) rc = vx_fail(ctx, open.rc, "merkle rows: %s", vx_last_error(open.c)[0] ? vx_last_error(open.c) : "the openings table failed");
     if (rc != VX_OK) return rc;
-    const size_t total = VX_MROWS_HDR + open.len + sponge.len;
-    *blob_len = total;
-    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "merkle rows: the blob needs %zu words, buffer has %zu", total, blob_cap);
-    blob_out[0] = VX_MROWS_MAGIC, blob_out[1] = (uint64_t)depth, blob_out[2] = leaf_len, blob_out[3] = n_idx, blob_out[4] = open.len, blob_out[5] = sponge.len;
-    memcpy(blob_out + VX_MROWS_HDR, open.proof.data(), open.len * 8);
-    memcpy(blob_out + VX_MROWS_HDR + open.len, sponge.proof.data(), sponge.len * 8);
-    return VX_OK;
+    return pack_blob(ctx, "merkle rows", VX_MROWS_MAGIC, {(uint64_t)depth, leaf_len, n_idx}, {&open, &sponge}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

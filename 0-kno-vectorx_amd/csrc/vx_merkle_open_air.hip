@@ -14,6 +14,7 @@
 #include "poseidon_air.cuh"
 #include "vx_bus.h"
 #include "vx_internal.h"
+#include "vx_table_shapes.h"
 
 namespace {
 using namespace mop;
@@ -55,13 +56,7 @@ __global__ __launch_bounds__(64) void k_merkle_open_trace(OpenArgs a) {
         shape[END - BIT] = l == a.depth - 1, shape[FIRSTB - BIT] = l == 0;
     }
     poseidon_air_walk(s, a.tr, a.n, 32 * b);
-#pragma unroll
-    for (int j = 0; j < COLS - BIT; ++j) {  // (unrolled: shape[] stays in registers)
-        uint64_t* col = a.tr + (size_t)(BIT + j) * a.n + 32 * b;
-        const uint64_t v = shape[j];
-#pragma unroll 8
-        for (int r = 0; r < 32; ++r) col[r] = v;
-    }
+    poseidon_air_block_cols(shape, a.tr, a.n, BIT, 32 * b);
 }
 
 __global__ __launch_bounds__(64) void k_merkle_open_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
@@ -83,17 +78,6 @@ __global__ __launch_bounds__(64) void k_merkle_open_aux(const uint64_t* __restri
     }
 }
 
-int ceil_log2(size_t x) {
-    int l = 0;
-    while (((size_t)1 << l) < x) ++l;
-    return l;
-}
-
-// one table on its own bus: the lookup challenges are the shared-challenge transcript of this table's (public inputs, trace cap)
-int32_t one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cap_words, uint64_t* chal, size_t n_chal) {
-    vx_shared_challenges_n(&pub, &n_pub, &cap, 1, cap_words, chal, n_chal);
-    return VX_OK;
-}
 }  // namespace
 
 int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
@@ -104,8 +88,12 @@ int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, co
     return vx_bus_close_dev(ctx, aux + 2 * n, log_n, aux_pub);
 }
 
-// rows (log2) of the table: the smallest power of two that holds n_idx paths of `depth` blocks
-int vx_merkle_open_log_n(size_t n_idx, int depth) { return ceil_log2(32 * n_idx * (size_t)depth); }  // >= 5: n_idx, depth >= 1
+// root, depth, the digest of the (index, leaf digest) claims: shared with the verifier (vx_verify.hip)
+void vx_merkle_open_public(const uint64_t root[4], int depth, const uint64_t* claims, size_t n_idx, uint64_t pub[9]) {
+    memcpy(pub, root, 32);
+    pub[4] = (uint64_t)depth;
+    if (claims) glh::hash_no_pad(claims, 5 * n_idx, pub + 5);
+}
 
 int32_t vx_merkle_open_trace_dev(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[9]) {
     const int depth = ceil_log2(tree->n_leaves);
@@ -139,9 +127,7 @@ int32_t vx_merkle_open_trace_dev(vx_ctx* ctx, const vx_tree* tree, const uint64_
     } while (0);
     vx_pool_free(ctx, sc);
     VX_TRY(rc);
-    for (int i = 0; i < 4; ++i) pub_out[i] = root[i];
-    pub_out[4] = (uint64_t)depth;
-    glh::hash_no_pad(claims.data(), claims.size(), pub_out + 5);
+    vx_merkle_open_public(root, depth, claims.data(), n_idx, pub_out);
     return VX_OK;
 }
 
@@ -172,14 +158,9 @@ int32_t vx_merkle_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const 
     const int log_n = vx_merkle_open_log_n(n_idx, depth);
     VX_CHECK(log_n <= 26, "merkle openings: %zu paths of %d levels need more than 2^26 rows", n_idx, depth);
     TableJob job;
-    const vx_chal_hook hook{one_table_hook, nullptr};
+    const vx_chal_hook hook{vx_one_table_hook, nullptr};
     VX_TRY(run_table(ctx, job, VX_AIR_MERKLE_OPEN, log_n, COLS, PUB, cfg, &hook, 0,
                      [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) { return vx_merkle_open_trace_dev(c, tree, leaf_idx, n_idx, log_n, trace->d, pub); }));
-    const size_t total = VX_MOPEN_HDR + job.len;
-    *blob_len = total;
-    if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "merkle openings: the blob needs %zu words, buffer has %zu", total, blob_cap);
-    blob_out[0] = VX_MOPEN_MAGIC, blob_out[1] = (uint64_t)depth, blob_out[2] = n_idx, blob_out[3] = job.len;
-    memcpy(blob_out + VX_MOPEN_HDR, job.proof.data(), job.len * 8);
-    return VX_OK;
+    return pack_blob(ctx, "merkle openings", VX_MOPEN_MAGIC, {(uint64_t)depth, n_idx}, {&job}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

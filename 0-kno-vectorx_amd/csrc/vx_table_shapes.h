@@ -1,6 +1,7 @@
 // Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers
-// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip) and the host verifier (vx_verify.hip): that both sides size a table
-// the same way is a soundness condition.  Host-only inline functions, no device code.
+// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip, the aggregation provers in vx_merkle_open_air.hip, vx_leaf_sponge_air.hip and
+// vx_fri_fold_air.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
+// condition.  Host-only inline functions, no device code.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -35,3 +36,19 @@ static inline int ed_log_n(size_t n_sig) { return n_sig <= 255 ? 16 : 17; }
 static inline int ed_air_id(size_t n_sig) { return n_sig <= 255 ? VX_AIR_ED25519_16 : VX_AIR_ED25519; }
 static inline int s512_log_n(size_t n_sig) { return n_sig <= 6 ? 10 : n_sig <= 204 ? 15 : 16; }
 static inline int s512_air_id(size_t n_sig) { return n_sig <= 6 ? VX_AIR_SHA512_10 : n_sig <= 204 ? VX_AIR_SHA512_15 : VX_AIR_SHA512; }
+// the aggregation tables: the smallest power of two that holds the request (the provers refuse more than 2^26 rows)
+static inline int ceil_log2(size_t x) {
+    int l = 0;
+    while (((size_t)1 << l) < x) ++l;
+    return l;
+}
+// MerkleOpenAir: one 32-row block per level of each of the n_idx paths (>= 5: n_idx, depth >= 1)
+static inline int vx_merkle_open_log_n(size_t n_idx, int depth) { return ceil_log2(32 * n_idx * (size_t)depth); }
+// LeafSpongeAir: one 32-row block per 8 words of each of the n_idx rows (>= 5)
+static inline size_t sponge_blocks(size_t leaf_len) { return (leaf_len + 7) / 8; }
+static inline int leaf_sponge_log_n(size_t n_idx, size_t leaf_len) { return ceil_log2(32 * n_idx * sponge_blocks(leaf_len)); }
+// FriFoldAir: NL fold rows and log_lde - 4 NL bit rows per query, at least 2^5 rows
+static inline int fri_fold_log_n(size_t n_queries, int log_lde, size_t n_layers) {
+    const int l = ceil_log2(n_queries * (size_t)(log_lde - 3 * (int)n_layers));
+    return l < 5 ? 5 : l;
+}

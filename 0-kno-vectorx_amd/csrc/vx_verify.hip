@@ -4,10 +4,16 @@
 // (fri_combine_initial, compute_evaluation, verify_merkle_proof_to_cap); crates pinned at
 // Cargo.lock:4848-4905, not vendored.  Verification is cheap scalar work (a few thousand
 // Poseidon permutations) and stays on the host, as in the reference.
+// Every host verifier of a statement lives here too, and all of them end in ONE sequence, verify_bus_group: the tables of a logUp
+// bus under their shared challenges, and the balance of the bus against the messages of a party outside the tables -- nobody
+// (vx_header_range_verify, vx_rotate_verify) or the verifier itself (the aggregation verifiers vx_merkle_openings_verify,
+// vx_merkle_rows_verify, vx_fri_fold_verify, which are argument checks, read_blob, their tables and their message list).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -609,10 +615,44 @@ static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
         if (!vx_stark_proof_peek(t[i].proof, t[i].len, cfg->cap_height, &t[i].pub, &t[i].n_pub, &t[i].cap)) return false;
     return true;
 }
+// The messages a party outside the tables puts on their bus -- the verifier itself, in an aggregation proof: the denominator of
+// each, and whether the verifier receives it (+) or sends it (-).
+struct BusMessages {
+    std::vector<X2<Fx>> den;
+    std::vector<uint8_t> sent;
+    void reserve(size_t n) { den.reserve(n), sent.reserve(n); }
+    void receive(const X2<Fx>& d) { den.push_back(d), sent.push_back(0); }
+    void send(const X2<Fx>& d) { den.push_back(d), sent.push_back(1); }
+};
+using BusOutside = std::function<void(const bus::Bus<X2<Fx>>&, BusMessages&)>;
+// sum over the messages of +- 1 / D with ONE inversion (Montgomery batch: prefix products, one inverse, walked back); false when
+// the product of the denominators is zero
+static bool bus_messages_sum(const BusMessages& m, X2<Fx>* sum) {
+    const Fx zero{0, 0};
+    *sum = X2<Fx>{zero, zero};
+    const size_t n = m.den.size();
+    if (!n) return true;
+    std::vector<X2<Fx>> pre(n);
+    for (size_t k = 0; k < n; ++k) pre[k] = k ? pre[k - 1] * m.den[k] : m.den[k];
+    const X2<Fx>& prod = pre[n - 1];
+    const Fx norm = prod.a * prod.a - f_mul7(prod.b * prod.b);
+    if (norm.a == 0 && norm.b == 0) return false;
+    const Fx ni = fx_inv(norm);
+    X2<Fx> inv{prod.a * ni, (zero - prod.b) * ni};
+    for (size_t k = n; k-- > 0;) {
+        const X2<Fx> t = k ? inv * pre[k - 1] : inv;
+        *sum = m.sent[k] ? *sum - t : *sum + t;
+        inv = inv * m.den[k];
+    }
+    return true;
+}
 // The tables of one logUp bus, in bus order (the order of the shared-challenge transcript): the lookup challenges every proof must
 // have used are a transcript of all (public inputs, trace cap) pairs; every table is verified under them against its expected
-// AIR and public inputs; and the bus must close -- a table publishes its total / rows.
-static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, size_t n, const char* unbalanced, char* err, size_t errlen) {
+// AIR and public inputs; and the bus must close -- a table publishes its total / rows, and the sum of total x rows over the
+// tables must be what the messages of the party `outside` them sum to: zero when the tables are a closed statement
+// (vx_header_range_verify, vx_rotate_verify), the verifier's own claims when it is the last party of the bus (the aggregation
+// verifiers vx_merkle_openings_verify, vx_merkle_rows_verify, vx_fri_fold_verify).
+static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, size_t n, const char* unbalanced, char* err, size_t errlen, const BusOutside& outside = nullptr) {
     std::vector<const uint64_t*> pubs(n), caps(n);
     std::vector<size_t> n_pubs(n);
     for (size_t i = 0; i < n; ++i) pubs[i] = t[i].pub, n_pubs[i] = t[i].n_pub, caps[i] = t[i].cap;
@@ -626,7 +666,39 @@ static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, s
         if (rc != VX_OK) return rc;
         for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
     }
-    NEED(bus[0] == 0 && bus[1] == 0, "%s", unbalanced);
+    BusMessages msgs;
+    if (outside) outside(bus::Bus<X2<Fx>>(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0}), msgs);
+    X2<Fx> sum;
+    NEED(bus_messages_sum(msgs, &sum), "a message of the verifier has a zero denominator under the challenges");
+    NEED(sum.a.b == 0 && sum.b.b == 0 && bus[0] == sum.a.a && bus[1] == sum.b.a, "%s", unbalanced);
+    return VX_OK;
+}
+
+// An aggregation blob (vx_bus.h: magic, the request words, one length per proof, the proofs) as the tables of its bus group: the
+// blob must be for this request, every proof present and the lengths must add up to the blob.
+static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const char* what, std::initializer_list<uint64_t> request, BusTable* t, size_t n, char* err,
+                         size_t errlen) {
+    const size_t hdr = 1 + request.size() + n;
+    NEED(len > hdr && blob[0] == magic, "bad %s blob", what);
+    NEED(std::equal(request.begin(), request.end(), blob + 1), "blob is for a different request");
+    size_t body = len - hdr;
+    const uint64_t* p = blob + hdr;
+    for (size_t i = 0; i < n; ++i) {
+        const uint64_t l = blob[hdr - n + i];
+        NEED(l >= 1 && l <= body, "blob lengths are inconsistent");
+        t[i].proof = p, t[i].len = l;
+        p += l, body -= l;
+    }
+    NEED(body == 0, "blob lengths are inconsistent");
+    return VX_OK;
+}
+// the root of a tree known by its cap (a table proves paths to ONE root): the two-to-one fold of the cap
+static int32_t cap_root(const uint64_t* cap, int cap_height, const char* what, uint64_t root[4], char* err, size_t errlen) {
+    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height));
+    for (uint64_t w : fold) NEED(w < glh::P, "%s: non-canonical cap word", what);
+    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
+        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
+    memcpy(root, fold.data(), 32);
     return VX_OK;
 }
 
@@ -748,30 +820,27 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     return verify_bus_group(cfg, tab.data(), n_tab, "the lookup bus between the tables does not balance", err, errlen);
 }
 
-// Merkle openings (the prover is vx_merkle_open_air.hip): the verifier holds the openings it wants proven -- (index, leaf digest)
-// pairs of a tree it knows by its cap -- and is the OTHER PARTY of the table's logUp bus: it rebuilds the table's public inputs
-// from its own arguments (root = the fold of the cap, depth, claims digest), derives the lookup challenges from them and the
-// proof's trace cap, verifies the table under those challenges, and accepts iff what the table sent is what it receives:
-// published total x rows = sum over the claims of 1 / D_lo + 1 / D_hi.  No Merkle path is walked here.
+// The aggregation verifiers: the verifier holds claims and is the LAST PARTY of a logUp bus whose other parties are tables.  Each
+// one below checks its arguments, reads its blob (read_blob), rebuilds the public inputs of its tables from its own arguments
+// (the functions the provers call: vx_bus.h) and lists the messages it puts on the bus itself; verify_bus_group does the rest.
+//
+// Merkle openings (the prover is vx_merkle_open_air.hip): the claims are (index, leaf digest) pairs of a tree known by its cap.
+// MerkleOpenAir sends every opened digest, the verifier receives every claim once:
+//     published total x rows = sum over the claims of 1 / D_lo + 1 / D_hi.
+// No Merkle path is walked here.
 int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* cap, int cap_height, int log_leaves, const uint64_t* leaf_idx,
                                   const uint64_t* leaf_digests, size_t n_idx, char* err, size_t errlen) {
     if (!cfg || !blob || !cap || !leaf_idx || !leaf_digests) return VX_ERR_ARG;
     NEED(log_leaves >= 1 && log_leaves <= 40 && cap_height >= 0 && cap_height <= 16 && cap_height <= log_leaves, "merkle openings: cap height %d / tree depth %d out of range", cap_height,
          log_leaves);
     NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings (1..2^21)", n_idx);
-    NEED(len > VX_MOPEN_HDR && blob[0] == VX_MOPEN_MAGIC, "bad merkle-openings blob");
-    NEED(blob[1] == (uint64_t)log_leaves && blob[2] == (uint64_t)n_idx, "blob is for a different request");
-    NEED(blob[3] == len - VX_MOPEN_HDR, "blob lengths are inconsistent");
-    const uint64_t* proof = blob + VX_MOPEN_HDR;
-    const size_t plen = len - VX_MOPEN_HDR;
-    // the table's public inputs, from the verifier's own arguments
-    uint64_t pub[mop::PUB];
-    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height)), claims(5 * n_idx);
-    for (uint64_t w : fold) NEED(w < glh::P, "merkle openings: non-canonical cap word");
-    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
-        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
-    memcpy(pub, fold.data(), 32);
-    pub[4] = (uint64_t)log_leaves;
+    BusTable tab[1];
+    int32_t rc = read_blob(blob, len, VX_MOPEN_MAGIC, "merkle-openings", {(uint64_t)log_leaves, n_idx}, tab, 1, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
+    uint64_t root[4], pub[mop::PUB];
+    if ((rc = cap_root(cap, cap_height, "merkle openings", root, err, errlen)) != VX_OK) return rc;
+    std::vector<uint64_t> claims(5 * n_idx);
     for (size_t i = 0; i < n_idx; ++i) {
         NEED(leaf_idx[i] >> log_leaves == 0, "merkle openings: claim %zu names a leaf outside the tree", i);
         claims[5 * i] = leaf_idx[i];
@@ -780,47 +849,27 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
             claims[5 * i + 1 + j] = leaf_digests[4 * i + j];
         }
     }
-    glh::hash_no_pad(claims.data(), claims.size(), pub + 5);
-    // the lookup challenges: the shared-challenge transcript of this one table's (public inputs, trace cap)
-    const uint64_t *ppub = nullptr, *pcap = nullptr;
-    size_t n_ppub = 0;
-    NEED(vx_stark_proof_peek(proof, plen, cfg->cap_height, &ppub, &n_ppub, &pcap), "the proof is too short to hold a trace cap");
-    uint64_t chal[4];
-    {
-        const uint64_t* pubs[1] = {pub};
-        const size_t n_pubs[1] = {(size_t)mop::PUB};
-        v_shared_challenges_n(pubs, n_pubs, &pcap, 1, (size_t)4 << cfg->cap_height, chal, 4);
-    }
-    const uint64_t* apub = nullptr;
-    int L = 0;
-    const int32_t rc = vx_stark_verify_ext(cfg, proof, plen, VX_AIR_MERKLE_OPEN, pub, mop::PUB, chal, &apub, &L, err, errlen);
-    if (rc != VX_OK) return rc;
-    // the verifier's side of the bus: it receives every claim once
-    const Fx zero{0, 0};
-    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
-    X2<Fx> sum{zero, zero};
-    for (size_t i = 0; i < n_idx; ++i) {
-        const uint64_t* c = claims.data() + 5 * i;
-        const X2<Fx> dlo = bus.open(Fx{c[0], 0}, Fx{c[1], 0}, Fx{c[2], 0}, bus::K<0>{}), dhi = bus.open(Fx{c[0], 0}, Fx{c[3], 0}, Fx{c[4], 0}, bus::K<1>{});
-        const X2<Fx> prod = dlo * dhi;
-        const Fx ni = fx_inv(prod.a * prod.a - f_mul7(prod.b * prod.b));  // 1 / D_lo + 1 / D_hi = (D_lo + D_hi) / (D_lo D_hi)
-        sum = sum + (dlo + dhi) * X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
-    }
-    const uint64_t rows = ((uint64_t)1 << L) % glh::P;
-    NEED(sum.a.b == 0 && sum.b.b == 0 && glh::mul(apub[0], rows) == sum.a.a && glh::mul(apub[1], rows) == sum.b.a,
-         "the openings the table proves are not the claimed ones (the lookup bus does not balance)");
-    return VX_OK;
+    vx_merkle_open_public(root, log_leaves, claims.data(), n_idx, pub);
+    tab[0].air = VX_AIR_MERKLE_OPEN, tab[0].want = pub, tab[0].n_want = mop::PUB;
+    return verify_bus_group(cfg, tab, 1, "the openings the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(2 * n_idx);
+                                for (const uint64_t* c = claims.data(); c < claims.data() + 5 * n_idx; c += 5) {
+                                    m.receive(bus.open(Fx{c[0], 0}, Fx{c[1], 0}, Fx{c[2], 0}, bus::K<0>{}));
+                                    m.receive(bus.open(Fx{c[0], 0}, Fx{c[3], 0}, Fx{c[4], 0}, bus::K<1>{}));
+                                }
+                            });
 }
 
-// Merkle rows (the prover is vx_leaf_sponge_air.hip): two tables on one bus.  The verifier holds what a STARK verifier holds --
-// (index, opened ROW) pairs of a tree it knows by its cap -- and is the other party of the ROW bus: LeafSpongeAir sends every word
-// it absorbs, receives the leaf digests MerkleOpenAir sends (TAG_OPEN closes between the two tables), and MerkleOpenAir proves
-// those digests lie under the root.  LeafSpongeAir's public inputs are rebuilt entirely from the arguments; of MerkleOpenAir's,
-// root and depth are.  Its claims digest cannot be: the verifier never sees the leaf digests.  Those four words are taken from
-// the proof's own public inputs (checked canonical); they ONLY feed the shared transcript -- the digests themselves are bound
-// by the sponge table's committed trace, and the challenges depend on the rows through the sponge table's own claims digest.
-// Accepted iff both tables verify under the shared challenges and
+// Merkle rows (the prover is vx_leaf_sponge_air.hip): two tables on one bus, openings first.  The claims are what a STARK verifier
+// holds -- (index, opened ROW) pairs of a tree known by its cap.  LeafSpongeAir sends every word it absorbs, receives the leaf
+// digests MerkleOpenAir sends (TAG_OPEN closes between the two tables), and MerkleOpenAir proves those digests lie under the root;
+// the verifier receives every word of every claim once:
 //     total_open x rows_open + total_sponge x rows_sponge = sum over the claims, j < leaf_len of 1 / D_row(index, j, row[j]).
+// LeafSpongeAir's public inputs are rebuilt entirely from the arguments; of MerkleOpenAir's, root and depth are.  Its claims digest
+// cannot be: the verifier never sees the leaf digests.  Those four words are taken from the proof's own public inputs (checked
+// canonical); they ONLY feed the shared transcript -- the digests themselves are bound by the sponge table's committed trace, and
+// the challenges depend on the rows through the sponge table's own claims digest.
 // No Merkle path is walked and no leaf is hashed; the row-claims digest costs as many permutations as hashing the rows would.
 int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* cap, int cap_height, int log_leaves, size_t leaf_len,
                               const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, char* err, size_t errlen) {
@@ -829,30 +878,18 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
          log_leaves);
     NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle rows: %zu openings (1..2^21)", n_idx);
     NEED(leaf_len >= 5 && leaf_len <= ((size_t)1 << 20), "merkle rows: leaf_len %zu (5..2^20)", leaf_len);
-    NEED(len > VX_MROWS_HDR && blob[0] == VX_MROWS_MAGIC, "bad merkle-rows blob");
-    NEED(blob[1] == (uint64_t)log_leaves && blob[2] == (uint64_t)leaf_len && blob[3] == (uint64_t)n_idx, "blob is for a different request");
-    const size_t body = len - VX_MROWS_HDR;
-    NEED(blob[4] >= 1 && blob[4] < body && blob[5] == body - blob[4], "blob lengths are inconsistent");
-    const uint64_t *p_open = blob + VX_MROWS_HDR, *p_sponge = p_open + blob[4];
-    const size_t l_open = blob[4], l_sponge = blob[5];
-    const uint64_t *ppub[2] = {nullptr, nullptr}, *pcap[2] = {nullptr, nullptr};
-    size_t n_ppub[2] = {0, 0};
-    NEED(vx_stark_proof_peek(p_open, l_open, cfg->cap_height, &ppub[0], &n_ppub[0], &pcap[0]) && vx_stark_proof_peek(p_sponge, l_sponge, cfg->cap_height, &ppub[1], &n_ppub[1], &pcap[1]),
-         "a proof is too short to hold a trace cap");
-    // MerkleOpenAir's public inputs: root and depth from the arguments, the claims digest from the proof itself
-    uint64_t opub[mop::PUB], spub[lsp::PUB];
-    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height));
-    for (uint64_t w : fold) NEED(w < glh::P, "merkle rows: non-canonical cap word");
-    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
-        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
-    memcpy(opub, fold.data(), 32);
-    opub[4] = (uint64_t)log_leaves;
-    NEED(n_ppub[0] == (size_t)mop::PUB, "merkle rows: the openings table has %zu public inputs", n_ppub[0]);
+    BusTable tab[2];
+    int32_t rc = read_blob(blob, len, VX_MROWS_MAGIC, "merkle-rows", {(uint64_t)log_leaves, leaf_len, n_idx}, tab, 2, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 2), "a proof is too short to hold a trace cap");
+    uint64_t root[4], opub[mop::PUB], spub[lsp::PUB];
+    if ((rc = cap_root(cap, cap_height, "merkle rows", root, err, errlen)) != VX_OK) return rc;
+    vx_merkle_open_public(root, log_leaves, nullptr, 0, opub);
+    NEED(tab[0].n_pub == (size_t)mop::PUB, "merkle rows: the openings table has %zu public inputs", tab[0].n_pub);
     for (int j = 5; j < mop::PUB; ++j) {
-        NEED(ppub[0][j] < glh::P, "merkle rows: non-canonical claims digest in the openings table");
-        opub[j] = ppub[0][j];
+        NEED(tab[0].pub[j] < glh::P, "merkle rows: non-canonical claims digest in the openings table");
+        opub[j] = tab[0].pub[j];
     }
-    // LeafSpongeAir's public inputs: leaf_len, blocks per row, tail flags, the digest of (index, row) over all claims
     std::vector<uint64_t> claims(n_idx * (leaf_len + 1));
     for (size_t i = 0; i < n_idx; ++i) {
         NEED(leaf_idx[i] >> log_leaves == 0, "merkle rows: claim %zu names a leaf outside the tree", i);
@@ -863,56 +900,15 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
             c[1 + j] = rows[i * leaf_len + j];
         }
     }
-    {
-        const size_t t = leaf_len % 8;
-        spub[lsp::PUB_L] = leaf_len, spub[lsp::PUB_B] = (leaf_len + 7) / 8;
-        for (size_t i = 0; i < 8; ++i) spub[lsp::PUB_W + i] = i < (t ? t : 8);
-        glh::hash_no_pad(claims.data(), claims.size(), spub + lsp::PUB_DIGEST);
-    }
-    // the lookup challenges: the shared-challenge transcript of both tables, openings first
-    uint64_t chal[4];
-    {
-        const uint64_t* pubs[2] = {opub, spub};
-        const size_t n_pubs[2] = {(size_t)mop::PUB, (size_t)lsp::PUB};
-        v_shared_challenges_n(pubs, n_pubs, pcap, 2, (size_t)4 << cfg->cap_height, chal, 4);
-    }
-    const uint64_t *apub_o = nullptr, *apub_s = nullptr;
-    int Lo = 0, Ls = 0;
-    int32_t rc = vx_stark_verify_ext(cfg, p_open, l_open, VX_AIR_MERKLE_OPEN, opub, mop::PUB, chal, &apub_o, &Lo, err, errlen);
-    if (rc != VX_OK) return rc;
-    rc = vx_stark_verify_ext(cfg, p_sponge, l_sponge, VX_AIR_LEAF_SPONGE, spub, lsp::PUB, chal, &apub_s, &Ls, err, errlen);
-    if (rc != VX_OK) return rc;
-    // the verifier's side of the row bus: it receives every word of every claim once.  One inversion for all of them
-    // (Montgomery batch: prefix products, one inverse, walked back)
-    const Fx zero{0, 0};
-    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
-    const size_t n_msg = n_idx * leaf_len;
-    std::vector<X2<Fx>> den(n_msg), pre(n_msg);
-    for (size_t i = 0; i < n_idx; ++i) {
-        const uint64_t* c = claims.data() + i * (leaf_len + 1);
-        for (size_t j = 0; j < leaf_len; ++j) {
-            const size_t k = i * leaf_len + j;
-            den[k] = bus.row(Fx{c[0], 0}, Fx{(uint64_t)j, 0}, Fx{c[1 + j], 0});
-            pre[k] = k ? pre[k - 1] * den[k] : den[k];
-        }
-    }
-    X2<Fx> inv;
-    {
-        const X2<Fx>& prod = pre[n_msg - 1];
-        const Fx norm = prod.a * prod.a - f_mul7(prod.b * prod.b);
-        NEED(norm.a != 0 || norm.b != 0, "merkle rows: a claim's message has a zero denominator under the challenges");
-        const Fx ni = fx_inv(norm);
-        inv = X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
-    }
-    X2<Fx> sum{zero, zero};
-    for (size_t k = n_msg; k-- > 0;) {
-        sum = sum + (k ? inv * pre[k - 1] : inv);
-        inv = inv * den[k];
-    }
-    const uint64_t rows_o = ((uint64_t)1 << Lo) % glh::P, rows_s = ((uint64_t)1 << Ls) % glh::P;
-    const uint64_t ta = glh::add(glh::mul(apub_o[0], rows_o), glh::mul(apub_s[0], rows_s)), tb = glh::add(glh::mul(apub_o[1], rows_o), glh::mul(apub_s[1], rows_s));
-    NEED(sum.a.b == 0 && sum.b.b == 0 && ta == sum.a.a && tb == sum.b.a, "the rows the tables prove are not the claimed ones (the lookup bus does not balance)");
-    return VX_OK;
+    vx_leaf_sponge_public(leaf_len, claims.data(), n_idx, spub);
+    tab[0].air = VX_AIR_MERKLE_OPEN, tab[0].want = opub, tab[0].n_want = mop::PUB;
+    tab[1].air = VX_AIR_LEAF_SPONGE, tab[1].want = spub, tab[1].n_want = lsp::PUB;
+    return verify_bus_group(cfg, tab, 2, "the rows the tables prove are not the claimed ones (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(n_idx * leaf_len);
+                                for (size_t i = 0; i < n_idx; ++i)
+                                    for (size_t j = 0; j < leaf_len; ++j) m.receive(bus.row(Fx{leaf_idx[i], 0}, Fx{(uint64_t)j, 0}, Fx{rows[i * leaf_len + j], 0}));
+                            });
 }
 
 // RotateCircuit verify (the provers are vx_rotate.hip and, for the verifier above, vx_header_range.hip; every host verifier lives
@@ -981,11 +977,10 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
     return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen);
 }
 
-// FRI fold (the prover is vx_fri_fold_air.hip): the verifier holds what a STARK verifier holds when it enters the query phase's
-// fold loop -- per query the index, ev_0 (its own FRI combination) and the opened leaves of every layer, and the betas and the
-// final polynomial of the transcript -- and is the OTHER PARTY of the table's bus: it rebuilds every public input from its
-// arguments, derives the lookup challenges from them and the proof's trace cap, verifies the table under those challenges, and
-// accepts iff what the table received and sent is what it sends and receives:
+// FRI fold (the prover is vx_fri_fold_air.hip), the third aggregation verifier: the claims are what a STARK verifier holds when it
+// enters the query phase's fold loop -- per query the index, ev_0 (its own FRI combination) and the opened leaves of every layer,
+// and the betas and the final polynomial of the transcript.  FriFoldAir receives every leaf word and every entry, which the
+// verifier sends, and sends every exit, which the verifier receives:
 //     published total x rows = sum over the queries of  - sum over the layers l, j < 32 of 1 / D_row(tree l, index >> 4 (l + 1), j, leaf_l[j])
 //                                                        - 1 / D_fri(index, ev_0, 0)  +  1 / D_fri(index, final_poly(x_NL), 1).
 // NOTHING IS FOLDED here: per query one exponentiation for x_NL = x_0^(16^NL) and one Horner evaluation remain.
@@ -1006,9 +1001,10 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
          n_layers);
     NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "fri fold: %zu queries (1..2^20)", n_queries);
     NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
-    NEED(len > VX_FFOLD_HDR && blob[0] == VX_FFOLD_MAGIC, "bad fri-fold blob");
-    NEED(blob[1] == (uint64_t)log_lde && blob[2] == (uint64_t)n_layers && blob[3] == (uint64_t)n_queries, "blob is for a different request");
-    NEED(blob[4] == len - VX_FFOLD_HDR, "blob lengths are inconsistent");
+    BusTable tab[1];
+    const int32_t rc = read_blob(blob, len, VX_FFOLD_MAGIC, "fri-fold", {(uint64_t)log_lde, n_layers, n_queries}, tab, 1, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
     for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri fold: non-canonical beta word %zu", i);
     for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
     for (size_t i = 0; i < n_queries; ++i) {
@@ -1016,62 +1012,25 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
         NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri fold: claim %zu has a non-canonical ev_0", i);
     }
     for (size_t i = 0; i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "fri fold: claim %zu has a non-canonical leaf word", i / (32 * n_layers));
-    const uint64_t* proof = blob + VX_FFOLD_HDR;
-    const size_t plen = len - VX_FFOLD_HDR;
     uint64_t pub[ffa::PUB];
     vx_fri_fold_public(log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, pub);
-    // the lookup challenges: the shared-challenge transcript of this one table's (public inputs, trace cap)
-    const uint64_t *ppub = nullptr, *pcap = nullptr;
-    size_t n_ppub = 0;
-    NEED(vx_stark_proof_peek(proof, plen, cfg->cap_height, &ppub, &n_ppub, &pcap), "the proof is too short to hold a trace cap");
-    uint64_t chal[4];
-    {
-        const uint64_t* pubs[1] = {pub};
-        const size_t n_pubs[1] = {(size_t)ffa::PUB};
-        v_shared_challenges_n(pubs, n_pubs, &pcap, 1, (size_t)4 << cfg->cap_height, chal, 4);
-    }
-    const uint64_t* apub = nullptr;
-    int L = 0;
-    const int32_t rc = vx_stark_verify_ext(cfg, proof, plen, VX_AIR_FRI_FOLD, pub, ffa::PUB, chal, &apub, &L, err, errlen);
-    if (rc != VX_OK) return rc;
-    // the verifier's side of the bus: every leaf word and every entry sent (the table receives them: -), every exit received (+).
-    // One inversion for all of them (Montgomery batch: prefix products, one inverse, walked back)
-    const Fx zero{0, 0};
-    const bus::Bus<X2<Fx>> bus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0});
-    const size_t per = 32 * n_layers + 2, n_msg = n_queries * per;
-    std::vector<X2<Fx>> den(n_msg), pre(n_msg);
-    const uint64_t w = glh::root(log_lde);
-    for (size_t i = 0; i < n_queries; ++i) {
-        X2<Fx>* d = den.data() + i * per;
-        const Fx idx{index[i], 0};
-        for (size_t l = 0; l < n_layers; ++l)
-            for (size_t j = 0; j < 32; ++j)
-                d[32 * l + j] = bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0});
-        d[per - 2] = bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{});
-        const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
-        Fx fp{0, 0};
-        for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
-        d[per - 1] = bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{});
-    }
-    for (size_t k = 0; k < n_msg; ++k) pre[k] = k ? pre[k - 1] * den[k] : den[k];
-    X2<Fx> inv;
-    {
-        const X2<Fx>& prod = pre[n_msg - 1];
-        const Fx norm = prod.a * prod.a - f_mul7(prod.b * prod.b);
-        NEED(norm.a != 0 || norm.b != 0, "fri fold: a claim's message has a zero denominator under the challenges");
-        const Fx ni = fx_inv(norm);
-        inv = X2<Fx>{prod.a * ni, (zero - prod.b) * ni};
-    }
-    X2<Fx> sum{zero, zero};
-    for (size_t k = n_msg; k-- > 0;) {
-        const X2<Fx> t = k ? inv * pre[k - 1] : inv;
-        sum = k % per == per - 1 ? sum + t : sum - t;
-        inv = inv * den[k];
-    }
-    const uint64_t rows = ((uint64_t)1 << L) % glh::P;
-    NEED(sum.a.b == 0 && sum.b.b == 0 && glh::mul(apub[0], rows) == sum.a.a && glh::mul(apub[1], rows) == sum.b.a,
-         "the fold chains the table proves are not the claimed ones (the lookup bus does not balance)");
-    return VX_OK;
+    tab[0].air = VX_AIR_FRI_FOLD, tab[0].want = pub, tab[0].n_want = ffa::PUB;
+    return verify_bus_group(cfg, tab, 1, "the fold chains the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(n_queries * (32 * n_layers + 2));
+                                const uint64_t w = glh::root(log_lde);
+                                for (size_t i = 0; i < n_queries; ++i) {
+                                    const Fx idx{index[i], 0};
+                                    for (size_t l = 0; l < n_layers; ++l)
+                                        for (size_t j = 0; j < 32; ++j)
+                                            m.send(bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0}));
+                                    m.send(bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
+                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
+                                    Fx fp{0, 0};
+                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+                                    m.receive(bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                }
+                            });
 }
 
 // The FRI side of a vx_stark_prove proof as FriFoldAir's claims (prover-side: it VERIFIES the proof on the way -- the transcript

@@ -350,16 +350,22 @@ def rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg=None):
 MOPEN_MAGIC, MOPEN_HDR = 0x314E45504F4D5856, 4  # "VXMOPEN1": magic, log2(n_leaves), number of openings, proof length; then the MerkleOpenAir proof
 
 
+def _cap(cap):
+    """a tree's cap as a contiguous [2^cap_height][4] array -> (cap, cap_height)"""
+    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
+    cap_height = cp.shape[0].bit_length() - 1
+    if cp.shape[0] != 1 << cap_height:
+        raise ValueError("a cap has a power-of-two number of digests")
+    return cp, cap_height
+
+
 def merkle_openings_verify(blob, cap, log_leaves, leaf_idx, leaf_digests, cfg=None):
     """Host-side check of a vx_merkle_openings_prove blob against the verifier's own claims: the tree's cap [2^cap_height][4],
     log2(n_leaves), and the openings (leaf_idx[i], leaf_digests[i][4]) in order.  Walks no Merkle path; raises VxError with the reason."""
     L = load_library()
     cfg = cfg or default_stark_config()
     b = np.ascontiguousarray(blob, dtype=np.uint64)
-    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
-    cap_height = cp.shape[0].bit_length() - 1
-    if cp.shape[0] != 1 << cap_height:
-        raise ValueError("a cap has a power-of-two number of digests")
+    cp, cap_height = _cap(cap)
     idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
     dig = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1)
     if dig.size != 4 * idx.size:
@@ -380,10 +386,7 @@ def merkle_rows_verify(blob, cap, log_leaves, leaf_idx, rows, cfg=None):
     L = load_library()
     cfg = cfg or default_stark_config()
     b = np.ascontiguousarray(blob, dtype=np.uint64)
-    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
-    cap_height = cp.shape[0].bit_length() - 1
-    if cp.shape[0] != 1 << cap_height:
-        raise ValueError("a cap has a power-of-two number of digests")
+    cp, cap_height = _cap(cap)
     idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
     rw = np.ascontiguousarray(rows, dtype=np.uint64)
     if rw.ndim != 2 or rw.shape[0] != idx.size:
@@ -622,23 +625,31 @@ class Context:
         self._ck(self.L.vx_merkle_open_air_trace(self.h, tree.h, _ptr(idx), idx.size, log_n, out.h, _ptr(pub)))
         return out, pub
 
-    def merkle_openings_prove(self, tree, leaf_idx, cfg=None, out=None):
-        """Proves the openings leaf_idx of `tree` in one MerkleOpenAir table -> blob words (lib.merkle_openings_verify checks it).
-        out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+    def _prove_blob(self, cfg, out, bound, bound_msg, prove):
+        """The body of the aggregation provers: bound(cfg, need) sizes the blob when the caller gave no `out` (refused with
+        bound_msg), prove(cfg, out, need) writes it -> the blob words.  A failed proof raises the context's error with the
+        needed length as `.needed`."""
         cfg = cfg or self.stark_config()
-        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
         need = C.c_size_t(0)
         if out is None:
-            rc = self.L.vx_merkle_openings_proof_bound(C.byref(cfg), tree.n_leaves, idx.size, C.byref(need))
+            rc = bound(C.byref(cfg), C.byref(need))
             if rc != 0:
-                raise VxError(rc, "merkle openings: %d openings of a tree of %d leaves" % (idx.size, tree.n_leaves))
+                raise VxError(rc, bound_msg)
             out = np.empty(need.value, dtype=np.uint64)
-        rc = self.L.vx_merkle_openings_prove(self.h, C.byref(cfg), tree.h, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
+        rc = prove(C.byref(cfg), out, C.byref(need))
         if rc != 0:
             e = VxError(rc, self.L.vx_last_error(self.h).decode())
             e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
             raise e
         return out[: need.value]
+
+    def merkle_openings_prove(self, tree, leaf_idx, cfg=None, out=None):
+        """Proves the openings leaf_idx of `tree` in one MerkleOpenAir table -> blob words (lib.merkle_openings_verify checks it).
+        out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_merkle_openings_proof_bound(c, tree.n_leaves, idx.size, need),
+                                "merkle openings: %d openings of a tree of %d leaves" % (idx.size, tree.n_leaves),
+                                lambda c, o, need: self.L.vx_merkle_openings_prove(self.h, c, tree.h, _ptr(idx), idx.size, _ptr(o), o.size, need))
 
     def leaf_sponge_air_trace(self, data, n_leaves, leaf_len, layout, leaf_idx, log_n, off=0, out=None):
         """The witness of LeafSpongeAir for the rows leaf_idx of the leaves in `data` (as Context.merkle takes them)
@@ -653,20 +664,10 @@ class Context:
         """Proves the openings leaf_idx of `tree` and hashes the opened rows of `data` (what the tree was built from) in two
         tables on one bus -> blob words (lib.merkle_rows_verify checks it).  out: a caller's uint64 buffer; when it is too small
         the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
-        cfg = cfg or self.stark_config()
         idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
-        need = C.c_size_t(0)
-        if out is None:
-            rc = self.L.vx_merkle_rows_proof_bound(C.byref(cfg), tree.n_leaves, leaf_len, idx.size, C.byref(need))
-            if rc != 0:
-                raise VxError(rc, "merkle rows: %d openings of %d words of a tree of %d leaves" % (idx.size, leaf_len, tree.n_leaves))
-            out = np.empty(need.value, dtype=np.uint64)
-        rc = self.L.vx_merkle_rows_prove(self.h, C.byref(cfg), tree.h, data.h, off, leaf_len, layout, _ptr(idx), idx.size, _ptr(out), out.size, C.byref(need))
-        if rc != 0:
-            e = VxError(rc, self.L.vx_last_error(self.h).decode())
-            e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
-            raise e
-        return out[: need.value]
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_merkle_rows_proof_bound(c, tree.n_leaves, leaf_len, idx.size, need),
+                                "merkle rows: %d openings of %d words of a tree of %d leaves" % (idx.size, leaf_len, tree.n_leaves),
+                                lambda c, o, need: self.L.vx_merkle_rows_prove(self.h, c, tree.h, data.h, off, leaf_len, layout, _ptr(idx), idx.size, _ptr(o), o.size, need))
 
     def fri_fold_air_trace(self, log_lde, betas, index, ev0, leaves, log_n, tree0=0, out=None):
         """The witness of FriFoldAir for the claims (index[i], ev0[i][2], leaves[i][NL][32]) under betas [NL][2]
@@ -681,21 +682,11 @@ class Context:
         """Proves the fold chains of the claims in one FriFoldAir table -> blob words (lib.fri_fold_verify checks it).  The chains are
         folded natively first: VxError(VX_ERR_STATEMENT) names the query and layer that do not hold.  out: a caller's uint64 buffer;
         when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
-        cfg = cfg or self.stark_config()
         be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
-        need = C.c_size_t(0)
-        if out is None:
-            rc = self.L.vx_fri_fold_proof_bound(C.byref(cfg), log_lde, be.shape[0], idx.size, C.byref(need))
-            if rc != 0:
-                raise VxError(rc, "fri fold: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries)")
-            out = np.zeros(need.value, dtype=np.uint64)
-        rc = self.L.vx_fri_fold_prove(self.h, C.byref(cfg), log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size, _ptr(out), out.size,
-                                      C.byref(need))
-        if rc != 0:
-            e = VxError(rc, self.L.vx_last_error(self.h).decode())
-            e.needed = need.value  # VX_ERR_BUFSZ: the words the blob needs
-            raise e
-        return out[: need.value]
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_fri_fold_proof_bound(c, log_lde, be.shape[0], idx.size, need),
+                                "fri fold: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries)",
+                                lambda c, o, need: self.L.vx_fri_fold_prove(self.h, c, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size,
+                                                                            _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()
