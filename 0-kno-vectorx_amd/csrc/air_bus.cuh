@@ -11,7 +11,7 @@
 #include "gl.cuh"
 
 namespace bus {
-enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10 };
+enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10, TAG_ROOT = 11 };
 
 // a slot known at compile time: 0 leaves its term out, 1 adds the bare power of gamma, so a kind that does not use a slot
 // (or whose tag is 0 or 1) costs what the hand-written sum cost
@@ -28,6 +28,13 @@ struct Bus {
     VX_HD static S lit(uint64_t n) {
         if constexpr (std::is_same<S, uint64_t>::value) return n;
         else return S::from(n);
+    }
+    // 2 t + N for a slot that packs a small compile-time part under a field value (a tree id is below 2^32: no reduction needed)
+    template <uint64_t N>
+    VX_HD static S twice_plus(const S& t, K<N>) {
+        if constexpr (std::is_same<S, uint64_t>::value) return 2 * t + N;
+        else if constexpr (N == 0) return t + t;
+        else return t + t + lit(N);
     }
     VX_HD static X plus(const X& acc, const S& t) { return acc + t; }
     VX_HD static X plus(const X& acc, None) { return acc; }
@@ -73,11 +80,20 @@ struct Bus {
     // verifier of vx_merkle_openings_verify; LeafSpongeAir, which hashes the opened rows to these digests)
     template <class H>
     VX_HD X open(const S& index, const S& da, const S& db, const H& half) const { return denom(beta, index, da, db, half, K<TAG_OPEN>{}); }
+    // ... of one of several trees (leaf index, d[2 half], d[2 half + 1], half + 2 tree): tree 0 is the very message open() builds.
+    // MerkleOpenSetAir -> LeafSpongeSetAir
+    template <uint64_t H>
+    VX_HD X open_of(const S& tree, const S& index, const S& da, const S& db, K<H> half) const { return denom(beta, index, da, db, twice_plus(tree, half), K<TAG_OPEN>{}); }
+    // half of the root a path of one of several trees ended in, with that tree's depth (2 tree + half, r[2 half], r[2 half + 1],
+    // depth): MerkleOpenSetAir -> whoever knows the trees (the verifier of vx_fri_queries_verify)
+    template <uint64_t H>
+    VX_HD X root(const S& tree, const S& ra, const S& rb, K<H> half, const S& depth) const { return denom(beta, twice_plus(tree, half), ra, rb, depth, K<TAG_ROOT>{}); }
     // one word of an opened leaf row (leaf index, position in the row, word): LeafSpongeAir -> whoever holds the rows (the verifier)
     VX_HD X row(const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, None{}, K<TAG_ROW>{}); }
     // ... of one of several trees (leaf index, position in the row, word, tree): tree 0 is the very message row() builds, so a
-    // one-layer FRI with TREE0 = 0 is already receivable from LeafSpongeAir (that pairing is not built); a multi-tree sponge will
-    // send the others -> FriFoldAir, which receives the leaves of FRI layer l under tree TREE0 + l, and the verifier
+    // one-layer FRI with TREE0 = 0 is already receivable from LeafSpongeAir (that pairing is not built).  LeafSpongeSetAir sends
+    // them for every tree -> FriFoldAir, which receives the leaves of FRI layer l under tree TREE0 + l (vx_fri_queries_prove), or
+    // the verifier (vx_fri_fold_verify)
     template <class T>
     VX_HD X row_of(const T& tree, const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, tree, K<TAG_ROW>{}); }
     // an end of a query's fold chain (query index, value.a, value.b, end): end 0 = (index, ev_0) entering the chain, whoever

@@ -17,7 +17,7 @@
 template <class... Airs>
 struct AirList {};
 using VxAirs = AirList<ShaAir, BlakeAir, FibAir, MixAir, LookupAir, ShaTreeAir256, ShaTreeAir512, ShaTreeAir16, EdAir17, EdAir16, Sha512Air16, Sha512Air10, Sha512Air15,
-                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir>;
+                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir, MerkleOpenSetAir, LeafSpongeSetAir>;
 
 template <class... Airs>
 constexpr bool air_list_ok(AirList<Airs...>) {

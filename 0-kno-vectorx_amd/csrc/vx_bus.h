@@ -4,7 +4,7 @@
 // from its own host thread on its own context; the provers stop after their trace caps (vx_chal_hook) and MEET: every one
 // deposits its public inputs + cap, waits for all the others and derives the challenges from the transcript of all
 // (public inputs, cap) pairs in table order.  The aggregation provers (vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
-// vx_fri_fold_air.hip) use the same runner; what only they share -- the hook of a table alone on its bus, the blob writer, the
+// vx_fri_fold_air.hip, vx_fri_queries.hip) use the same runner; what only they share -- the hook of a table alone on its bus, the blob writer, the
 // blob formats and the public inputs of their AIRs, which the verifier (vx_verify.hip) rebuilds with the same functions -- is
 // declared here as well.
 #pragma once
@@ -139,6 +139,39 @@ void vx_leaf_sponge_public(size_t leaf_len, const uint64_t* claims, size_t n_idx
 // FriFoldAir: from betas [n_layers][2], ev0 [n_queries][2], leaves [n_queries][n_layers][32]
 void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
                         uint64_t pub[24]);
+// ... with a digest the caller states (the statement digest of vx_fri_queries_prove: its verifier holds no leaves)
+void vx_fri_fold_public_digest(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t digest[4], uint64_t pub[24]);
+
+
+// ---- FRI-queries blob (written by vx_fri_queries_prove in vx_fri_queries.hip, read by vx_fri_queries_verify in vx_verify.hip):
+// magic, log2 of the inner proof's LDE, fold layers, queries, lengths of the MerkleOpenSetAir, the LeafSpongeSetAir and the
+// FriFoldAir proof that follow
+static const uint64_t VX_FQRY_MAGIC = 0x3130595251465856ULL;  // "VXFQRY01"
+static constexpr size_t VX_FQRY_HDR = 7;
+// The set tables (several trees in one table).  Their public inputs, stated once for prover and verifier: MerkleOpenSetAir has the
+// four words of a digest it does not constrain; LeafSpongeSetAir L, B, the tail flags and such a digest.  The digest is the claims
+// digest of the set where a table is made alone (vx_*_set_air_trace), the STATEMENT digest in vx_fri_queries_prove.
+static constexpr int VX_OPEN_SET_MAX_TREES = 64;
+void vx_merkle_open_set_public(const uint64_t digest[4], uint64_t pub[4]);
+void vx_leaf_sponge_set_public(size_t leaf_len, const uint64_t digest[4], uint64_t pub[14]);
+// the statement of a FRI query phase: hash_n_to_hash_no_pad(log_lde, NL, n_q, betas, final_poly, the NL roots, (index, ev_0) of
+// every query) -- everything the verifier puts on the bus is a function of it
+void vx_fri_queries_statement(int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* roots, const uint64_t* index,
+                              const uint64_t* ev0, size_t n_queries, uint64_t digest[4]);
+// the witnesses of the set tables on the device (vx_merkle_open_air.hip, vx_leaf_sponge_air.hip) and FriFoldAir's, with its native
+// statement check (vx_fri_fold_air.hip), for the circuit prover
+int32_t vx_merkle_open_set_trace_dev(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
+                                     uint64_t* trace_d, uint64_t pub_out[4]);
+// leaves of FRI layers: tree t is the layer evals_d[t] of 2^(log_leaves[t] + 4) extension values in natural order; tree_leaves[t]
+// (may be nullptr as a whole): the leaf digests of the tree the leaves must hash to -- VX_ERR_STATEMENT otherwise
+int32_t vx_leaf_sponge_set_trace_dev(vx_ctx* ctx, const uint64_t* const* evals_d, const int* log_leaves, const uint64_t* const* tree_leaves, size_t n_trees, const uint64_t* tree_of,
+                                     const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[14]);
+int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
+                              size_t n_queries, int log_n, uint64_t* trace_d, uint64_t pub_out[24]);
+// folds every query natively on the host: VX_ERR_STATEMENT on `ctx`, naming query and layer, when a chain does not hold or does
+// not end in the final polynomial; VX_ERR_ARG for claims out of range
+int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* ev0,
+                              const uint64_t* leaves, size_t n_queries);
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

@@ -151,8 +151,10 @@ int32_t check_claims(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_l
     return VX_OK;
 }
 
-// The witness of FriFoldAir on the device, and the public inputs.  The claims have passed check_claims.
-int32_t fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
+}  // namespace
+
+// The witness of FriFoldAir on the device, and the public inputs (vx_bus.h).  The claims have passed check_claims.
+int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
                            size_t n_queries, int log_n, uint64_t* trace_d, uint64_t pub_out[PUB]) {
     const int rpq = log_lde - 3 * (int)n_layers;
     VX_CHECK(log_n >= 5 && log_n <= 26 && n_queries * (size_t)rpq <= ((size_t)1 << log_n), "fri fold: %zu queries of %d rows do not fit 2^%d rows", n_queries, rpq, log_n);
@@ -176,6 +178,7 @@ int32_t fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size
     return VX_OK;
 }
 
+namespace {
 // ---- the fold on the host (Fx): what the table proves, checked natively before anything is proven
 Fx fold16_host(const uint64_t* leaf, uint64_t within, Fx beta, uint64_t x_inv) {
     constexpr Tab T = make_tab();
@@ -194,10 +197,13 @@ Fx fold16_host(const uint64_t* leaf, uint64_t within, Fx beta, uint64_t x_inv) {
 }  // namespace
 
 // NL, NL + FB, 1 / w, TREE0, the betas (zero behind NL), the claims digest: shared with the verifier (vx_verify.hip)
-void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
-                        uint64_t pub[24]) {
+void vx_fri_fold_public_digest(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t digest[4], uint64_t pub[24]) {
     pub[PUB_NL] = n_layers, pub[PUB_ROWS] = (uint64_t)log_lde - 3 * n_layers, pub[PUB_WINV] = glh::inv(glh::root(log_lde)), pub[PUB_TREE0] = tree0;
     for (size_t i = 0; i < 2 * (size_t)MAX_LAYERS; ++i) pub[PUB_BETA + i] = i < 2 * n_layers ? betas[i] : 0;
+    memcpy(pub + PUB_DIGEST, digest, 32);
+}
+void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries,
+                        uint64_t pub[24]) {
     const size_t per = 3 + 32 * n_layers;
     std::vector<uint64_t> claims(n_queries * per);
     for (size_t i = 0; i < n_queries; ++i) {
@@ -205,41 +211,14 @@ void vx_fri_fold_public(int log_lde, const uint64_t* betas, size_t n_layers, uin
         c[0] = index[i], c[1] = ev0[2 * i], c[2] = ev0[2 * i + 1];
         memcpy(c + 3, leaves + i * 32 * n_layers, 32 * n_layers * 8);
     }
-    glh::hash_no_pad(claims.data(), claims.size(), pub + PUB_DIGEST);
+    uint64_t digest[4];
+    glh::hash_no_pad(claims.data(), claims.size(), digest);
+    vx_fri_fold_public_digest(log_lde, betas, n_layers, tree0, digest, pub);
 }
 
-int32_t FriFoldAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_fri_fold_aux, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[PUB_TREE0]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
-}
-
-extern "C" {
-int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
-                              size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]) {
-    if (!ctx || !betas || !index || !ev0 || !leaves || !trace_out || !public_out) return VX_ERR_ARG;
-    VX_TRY(check_claims(ctx, log_lde, betas, n_layers, index, ev0, leaves, n_queries));
-    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "fri fold: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
-             trace_out->n, COLS, log_n);
-    return fri_fold_trace_dev(ctx, log_lde, betas, n_layers, tree0, index, ev0, leaves, n_queries, log_n, trace_out->d, public_out);
-}
-
-int32_t vx_fri_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words) {
-    if (!cfg || !n_words || cfg->arity_bits != 4 || !shape_ok(log_lde, n_layers, n_queries)) return VX_ERR_ARG;
-    const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
-    if (log_n > 26) return VX_ERR_ARG;
-    size_t w = 0;
-    const int32_t rc = vx_stark_proof_bound(VX_AIR_FRI_FOLD, cfg, log_n, &w);
-    if (rc != VX_OK) return rc;
-    *n_words = VX_FFOLD_HDR + w;
-    return VX_OK;
-}
-
-int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
-                          const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len) {
-    if (!ctx || !cfg || !betas || !final_poly || !index || !ev0 || !leaves || !blob_len) return VX_ERR_ARG;
-    VX_CHECK(cfg->arity_bits == 4, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+// ranges, then the statement natively (vx_bus.h): every chain holds and ends in the final polynomial
+int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* ev0,
+                              const uint64_t* leaves, size_t n_queries) {
     VX_TRY(check_claims(ctx, log_lde, betas, n_layers, index, ev0, leaves, n_queries));
     VX_CHECK(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
     for (size_t i = 0; i < 2 * final_len; ++i) VX_CHECK(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
@@ -263,12 +242,48 @@ int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, 
         if (fp.a != ev.a || fp.b != ev.b)
             return vx_fail(ctx, VX_ERR_STATEMENT, "fri fold: query %zu, layer %zu: the folded value is not the final polynomial's at x^(16^%zu)", i, n_layers, n_layers);
     }
+    return VX_OK;
+}
+
+int32_t FriFoldAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_fri_fold_aux, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[PUB_TREE0]);
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
+
+extern "C" {
+int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves,
+                              size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]) {
+    if (!ctx || !betas || !index || !ev0 || !leaves || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_TRY(check_claims(ctx, log_lde, betas, n_layers, index, ev0, leaves, n_queries));
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "fri fold: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, COLS, log_n);
+    return vx_fri_fold_trace_dev(ctx, log_lde, betas, n_layers, tree0, index, ev0, leaves, n_queries, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_fri_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words) {
+    if (!cfg || !n_words || cfg->arity_bits != 4 || !shape_ok(log_lde, n_layers, n_queries)) return VX_ERR_ARG;
+    const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
+    if (log_n > 26) return VX_ERR_ARG;
+    size_t w = 0;
+    const int32_t rc = vx_stark_proof_bound(VX_AIR_FRI_FOLD, cfg, log_n, &w);
+    if (rc != VX_OK) return rc;
+    *n_words = VX_FFOLD_HDR + w;
+    return VX_OK;
+}
+
+int32_t vx_fri_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
+                          const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len) {
+    if (!ctx || !cfg || !betas || !final_poly || !index || !ev0 || !leaves || !blob_len) return VX_ERR_ARG;
+    VX_CHECK(cfg->arity_bits == 4, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    VX_TRY(vx_fri_fold_check_dev(ctx, log_lde, betas, n_layers, final_poly, final_len, index, ev0, leaves, n_queries));
     const int log_n = fri_fold_log_n(n_queries, log_lde, n_layers);
     VX_CHECK(log_n <= 26, "fri fold: %zu queries of %d rows need more than 2^26 rows", n_queries, log_lde - 3 * (int)n_layers);
     TableJob job;
     const vx_chal_hook hook{vx_one_table_hook, nullptr};
     VX_TRY(run_table(ctx, job, VX_AIR_FRI_FOLD, log_n, COLS, PUB, cfg, &hook, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-        return fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, log_n, trace->d, pub);
+        return vx_fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, log_n, trace->d, pub);
     }));
     return pack_blob(ctx, "fri fold", VX_FFOLD_MAGIC, {(uint64_t)log_lde, n_layers, n_queries}, {&job}, blob_out, blob_cap, blob_len);
 }

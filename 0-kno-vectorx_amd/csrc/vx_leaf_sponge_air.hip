@@ -10,6 +10,10 @@
 //   k_leaf_sponge_aux     one lane per block: ONE extension inversion for the block's five helpers (Montgomery batch over the
 //                         products of its denominator pairs), written to its 32 rows, and the block's running-sum increment
 //                         on its first row (vx_bus_close_dev scans it)
+// LeafSpongeSetAir (rows of several trees, the sponge table of vx_fri_queries_prove) runs the same three kernels: the states kernel
+// in a fourth layout -- the leaf of a FRI layer, 16 extension values at natural positions bitrev(16 j + t), what vx_fri_layer_tree
+// hashes -- with a per-leaf entry (tree, layer values, the tree's leaf digests, log2 of its leaves); trace and aux with the TREE
+// column written and used in the denominators.
 // Parity: tests/test_gpu_leaf_sponge.py compares trace, auxiliary columns and both proofs with tests/leaf_sponge_ref.py and the
 // reference prover.
 #include <string.h>
@@ -26,6 +30,14 @@
 namespace {
 using namespace lsp;
 
+constexpr int LAYOUT_FRI_LAYER = 3;  // behind the three vx_merkle_build layouts: the leaves of FRI layers, one entry per leaf
+struct SetLeaf {
+    const uint64_t* data;         // the layer: 2^(log_leaves + 4) extension values (a, b) in natural order
+    const uint64_t* tree_leaves;  // its tree's leaf digests, or nullptr
+    uint64_t tree;
+    int log_leaves;
+};
+
 struct SpongeArgs {
     const uint64_t* data;         // the leaves, as vx_merkle_build reads them
     const uint64_t* idx;          // [n_idx] leaf indices (< n_leaves: checked by the host)
@@ -36,6 +48,7 @@ struct SpongeArgs {
     uint64_t* claims;   // [n_idx][1 + leaf_len]: (index, row)
     uint64_t* digests;  // [n_idx][4]
     uint64_t* bad;      // 1 + the number of an opening whose digest is not the tree's (0: none)
+    const SetLeaf* set;  // LAYOUT_FRI_LAYER: [n_idx]; data, tree_leaves, n_leaves, log_leaves above are unused, leaf_len is 32
 };
 
 // (Tried: one lane per leaf with the tree builder's poseidon_permute -- 6.23 ms against 2.30 ms for 84 leaves x 128 blocks,
@@ -48,36 +61,48 @@ __global__ __launch_bounds__(256) void k_leaf_sponge_states(SpongeArgs a) {
     const bool live = t < a.n_idx;
     const size_t p = live ? t : a.n_idx - 1;  // surplus groups redo the last leaf and do not write
     const uint64_t j = a.idx[p];
-    const size_t r = LAYOUT == VX_LEAVES_COLS_BITREV ? brev32((uint32_t)j, a.log_leaves) : j;
+    constexpr bool FRI = LAYOUT == LAYOUT_FRI_LAYER;
+    constexpr size_t CLAIM_HDR = FRI ? 2 : 1;  // the set's claims name the tree: (tree, index, row)
+    int log_leaves = a.log_leaves;
+    const uint64_t *data = a.data, *tree_leaves = a.tree_leaves;
+    uint64_t* claim = a.claims + p * (a.leaf_len + CLAIM_HDR);
+    if constexpr (FRI) {
+        const SetLeaf sl = a.set[p];
+        log_leaves = sl.log_leaves, data = sl.data, tree_leaves = sl.tree_leaves;
+        if (live && l == 0) claim[0] = sl.tree;
+    }
+    const size_t r = (LAYOUT == VX_LEAVES_COLS_BITREV || FRI) ? brev32((uint32_t)j, log_leaves) : j;
     const size_t estride = LAYOUT == VX_LEAVES_ROW_MAJOR ? 1 : a.n_leaves;
-    const uint64_t* src = LAYOUT == VX_LEAVES_ROW_MAJOR ? a.data + r * a.leaf_len : a.data + r;
-    uint64_t* claim = a.claims + p * (a.leaf_len + 1);
-    if (live && l == 0) claim[0] = j;
+    const uint64_t* src = LAYOUT == VX_LEAVES_ROW_MAJOR ? data + r * a.leaf_len : FRI ? data + 2 * r : data + r;
+    if (live && l == 0) claim[CLAIM_HDR - 1] = j;
     uint64_t s = 0;
     for (size_t k = 0; k < a.n_blk; ++k) {
         const size_t e = 8 * k + l;
         if (l < 8 && e < a.leaf_len) {  // overwrite mode: a word behind the tail keeps the previous output
-            s = gl_canon(src[e * estride]);
-            if (live) claim[1 + e] = s;
+            if constexpr (FRI) s = gl_canon(src[((size_t)brev32((uint32_t)(e >> 1), 4) << (log_leaves + 1)) + (e & 1)]);  // word e: half e & 1 of value e / 2
+            else s = gl_canon(src[e * estride]);
+            if (live) claim[CLAIM_HDR + e] = s;
         }
         if (live && l < 12) a.states[(p * a.n_blk + k) * 12 + l] = s;
         s = poseidon_permute_coop(s, l, lds + 12 * grp);
     }
     if (live && l < 4) {
         a.digests[4 * p + l] = s;
-        if (a.tree_leaves && gl_canon(a.tree_leaves[4 * j + l]) != s) *a.bad = p + 1;
+        if (tree_leaves && gl_canon(tree_leaves[4 * j + l]) != s) *a.bad = p + 1;
     }
 }
 
+template <bool SET>  // SET: LeafSpongeSetAir, the leaf's tree from `set`
 __global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __restrict__ states, const uint64_t* __restrict__ idx, size_t n_idx, size_t n_blk, size_t n,
-                                                          uint64_t* __restrict__ tr) {
+                                                          uint64_t* __restrict__ tr, const SetLeaf* __restrict__ set) {
+    constexpr int NC = SET ? SET_COLS : COLS;
     const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
     if (b >= n / 32) return;
-    uint64_t s[12], shape[COLS - MSG];
+    uint64_t s[12], shape[NC - MSG];
 #pragma unroll
     for (int i = 0; i < 12; ++i) s[i] = 0;
 #pragma unroll
-    for (int j = 0; j < COLS - MSG; ++j) shape[j] = 0;
+    for (int j = 0; j < NC - MSG; ++j) shape[j] = 0;
     if (b < n_idx * n_blk) {
         const size_t p = b / n_blk, k = b - p * n_blk;
 #pragma unroll
@@ -86,6 +111,7 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __rest
         for (int i = 0; i < 8; ++i) shape[i] = s[i];
         shape[IDX - MSG] = idx[p], shape[POS - MSG] = k, shape[ACT - MSG] = 1;
         shape[FIRSTB - MSG] = k == 0, shape[LASTB - MSG] = k + 1 == n_blk, shape[NXL - MSG] = k + 2 == n_blk;
+        if constexpr (SET) shape[TREE - MSG] = set[p].tree;
     }
     poseidon_air_walk(s, tr, n, 32 * b);
 #pragma unroll
@@ -93,6 +119,7 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __rest
     poseidon_air_block_cols(shape, tr, n, MSG, 32 * b);
 }
 
+template <bool SET>
 __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint32_t wmask) {
     const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
     if (b >= n / 32) return;
@@ -104,15 +131,25 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restri
     if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the five message pairs, with one inversion
         const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
         const uint64_t idx = cell(IDX), pos8 = 8 * cell(POS), last = cell(LASTB);
+        uint64_t tree = 0;
+        if constexpr (SET) tree = cell(TREE);
+        auto d_row = [&](uint64_t position, uint64_t word) {
+            if constexpr (SET) return bus.row_of(tree, idx, position, word);
+            else return bus.row(idx, position, word);
+        };
+        auto d_open = [&](uint64_t da, uint64_t db, auto half) {
+            if constexpr (SET) return bus.open_of(tree, idx, da, db, half);
+            else return bus.open(idx, da, db, half);
+        };
         gl2 num[N_HELP], den[N_HELP];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const uint64_t ma = last ? (wmask >> (2 * e)) & 1 : 1, mb = last ? (wmask >> (2 * e + 1)) & 1 : 1;
-            const gl2 da = bus.row(idx, pos8 + 2 * e, cell(MSG + 2 * e)), db = bus.row(idx, pos8 + 2 * e + 1, cell(MSG + 2 * e + 1));
+            const gl2 da = d_row(pos8 + 2 * e, cell(MSG + 2 * e)), db = d_row(pos8 + 2 * e + 1, cell(MSG + 2 * e + 1));
             num[e] = gl2_add(gl2_scale(db, ma), gl2_scale(da, mb)), den[e] = gl2_mul(da, db);
         }
         {
-            const gl2 dlo = bus.open(idx, cell(DIG), cell(DIG + 1), bus::K<0>{}), dhi = bus.open(idx, cell(DIG + 2), cell(DIG + 3), bus::K<1>{});
+            const gl2 dlo = d_open(cell(DIG), cell(DIG + 1), bus::K<0>{}), dhi = d_open(cell(DIG + 2), cell(DIG + 3), bus::K<1>{});
             num[4] = gl2_scale(gl2_add(dlo, dhi), last ? GL_P - 1 : 0), den[4] = gl2_mul(dlo, dhi);  // received: multiplicity -LASTB
         }
         gl2_batch_div(num, den, h);
@@ -147,9 +184,82 @@ int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, co
     const size_t n = (size_t)1 << log_n, blocks = n / 32;
     uint32_t wmask = 0;
     for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
-    hipLaunchKernelGGL(k_leaf_sponge_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
+    hipLaunchKernelGGL(k_leaf_sponge_aux<false>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
     VX_HIP(hipGetLastError());
     return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
+
+int32_t LeafSpongeSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n, blocks = n / 32;
+    uint32_t wmask = 0;
+    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
+    hipLaunchKernelGGL(k_leaf_sponge_aux<true>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
+
+// LeafSpongeSetAir's public inputs: L, B, the tail flags, a digest the table does not constrain (prover and verifier alike: vx_bus.h)
+void vx_leaf_sponge_set_public(size_t leaf_len, const uint64_t digest[4], uint64_t pub[14]) {
+    const size_t t = leaf_len % 8;
+    pub[PUB_L] = leaf_len, pub[PUB_B] = sponge_blocks(leaf_len);
+    for (size_t i = 0; i < 8; ++i) pub[PUB_W + i] = i < (t ? t : 8);
+    memcpy(pub + PUB_DIGEST, digest, 32);
+}
+
+// The witness of LeafSpongeSetAir on the device for leaves of FRI layers (vx_bus.h): leaf i is leaf leaf_idx[i] of layer
+// tree_of[i].  pub_out: L = 32, B = 4, the tail flags, the digest of the claims (tree, index, row).
+int32_t vx_leaf_sponge_set_trace_dev(vx_ctx* ctx, const uint64_t* const* evals_d, const int* log_leaves, const uint64_t* const* tree_leaves, size_t n_trees, const uint64_t* tree_of,
+                                     const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, uint64_t pub_out[PUB]) {
+    constexpr size_t leaf_len = 32, n_blk = 4;
+    VX_CHECK(n_trees >= 1 && n_trees <= VX_OPEN_SET_MAX_TREES, "leaf sponge: %zu trees (1..%d)", n_trees, VX_OPEN_SET_MAX_TREES);
+    for (size_t t = 0; t < n_trees; ++t) VX_CHECK(evals_d[t] && log_leaves[t] >= 0 && log_leaves[t] <= 26, "leaf sponge: layer %zu of 2^%d leaves (0..26)", t, log_leaves[t]);
+    VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 19), "leaf sponge: %zu openings (1..2^19)", n_idx);
+    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * n_idx * n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", n_idx, n_blk, log_n);
+    std::vector<SetLeaf> set(n_idx);
+    for (size_t i = 0; i < n_idx; ++i) {
+        VX_CHECK(tree_of[i] < n_trees, "leaf sponge: opening %zu names tree %llu of %zu", i, (unsigned long long)tree_of[i], n_trees);
+        const size_t t = tree_of[i];
+        VX_CHECK(leaf_idx[i] >> log_leaves[t] == 0, "leaf sponge: index %zu (%llu) is not a leaf of tree %zu", i, (unsigned long long)leaf_idx[i], t);
+        set[i] = SetLeaf{evals_d[t], tree_leaves ? tree_leaves[t] : nullptr, tree_of[i], log_leaves[t]};
+    }
+    const size_t n = (size_t)1 << log_n, w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 2), w_set = n_idx * sizeof(SetLeaf) / 8;
+    static_assert(sizeof(SetLeaf) % 8 == 0, "SetLeaf is a whole number of words");
+    // scratch: the entering states, the indices, the claims, the digests, the mismatch word, the per-leaf table
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1 + w_set) * 8);
+    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
+    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx, *set_d = bad_d + 1;
+    std::vector<uint64_t> claims(w_claims);
+    uint64_t bad = 0;
+    int32_t rc = VX_OK;
+    do {
+        hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(set_d, set.data(), w_set * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(bad_d, 0, 8, ctx->stream);
+        if (e != hipSuccess) {
+            rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
+            break;
+        }
+        const SpongeArgs a{nullptr, idx_d, nullptr, 0, leaf_len, n_idx, n_blk, 0, states, claims_d, digests_d, bad_d, (const SetLeaf*)set_d};
+        hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_FRI_LAYER>, dim3((unsigned)((n_idx + 15) / 16)), dim3(256), 0, ctx->stream, a);  // 16 lanes per leaf
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_leaf_sponge_trace<true>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d, (const SetLeaf*)set_d);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, w_claims * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
+    } while (0);
+    vx_pool_free(ctx, sc);
+    VX_TRY(rc);
+    if (bad)
+        return vx_fail(ctx, VX_ERR_STATEMENT, "leaf sponge: opening %llu (leaf %llu of tree %llu) does not hash to the tree's leaf digest -- the layer is not what the tree was built from",
+                       (unsigned long long)(bad - 1), (unsigned long long)leaf_idx[bad - 1], (unsigned long long)tree_of[bad - 1]);
+    uint64_t digest[4];
+    glh::hash_no_pad(claims.data(), claims.size(), digest);
+    vx_leaf_sponge_set_public(leaf_len, digest, pub_out);
+    return VX_OK;
 }
 
 // The witness of LeafSpongeAir on the device.  data_d: the leaves of the whole tree ([n_leaves x leaf_len] words in `layout`; the
@@ -180,14 +290,14 @@ static int32_t leaf_sponge_trace_dev(vx_ctx* ctx, const uint64_t* data_d, size_t
             rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
             break;
         }
-        const SpongeArgs a{data_d, idx_d, tree_leaves, n_leaves, leaf_len, n_idx, n_blk, log_leaves, states, claims_d, digests_d, bad_d};
+        const SpongeArgs a{data_d, idx_d, tree_leaves, n_leaves, leaf_len, n_idx, n_blk, log_leaves, states, claims_d, digests_d, bad_d, nullptr};
         const dim3 grid((unsigned)((n_idx + 15) / 16)), block(256);  // 16 lanes per leaf
         if (layout == VX_LEAVES_ROW_MAJOR) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_ROW_MAJOR>, grid, block, 0, ctx->stream, a);
         else if (layout == VX_LEAVES_COLS_BITREV) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS_BITREV>, grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS>, grid, block, 0, ctx->stream, a);
         e = hipGetLastError();
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_leaf_sponge_trace, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d);
+            hipLaunchKernelGGL(k_leaf_sponge_trace<false>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d, (const SetLeaf*)nullptr);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, w_claims * 8, hipMemcpyDeviceToHost, ctx->stream);
@@ -213,6 +323,21 @@ int32_t vx_leaf_sponge_air_trace(vx_ctx* ctx, const vx_buf* data, size_t off, si
     VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
              trace_out->n, COLS, log_n);
     return leaf_sponge_trace_dev(ctx, data->d + off, n_leaves, leaf_len, layout, nullptr, leaf_idx, n_idx, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_leaf_sponge_set_air_trace(vx_ctx* ctx, const vx_buf* const* evals, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx,
+                                     int log_n, vx_buf* trace_out, uint64_t public_out[14]) {
+    if (!ctx || !evals || !log_leaves || !tree_of || !leaf_idx || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_CHECK(n_trees >= 1 && n_trees <= VX_OPEN_SET_MAX_TREES, "leaf sponge: %zu trees (1..%d)", n_trees, VX_OPEN_SET_MAX_TREES);
+    const uint64_t* ev[VX_OPEN_SET_MAX_TREES];
+    for (size_t t = 0; t < n_trees; ++t) {
+        VX_CHECK(evals[t] && log_leaves[t] >= 0 && log_leaves[t] <= 26 && evals[t]->n >= ((size_t)32 << log_leaves[t]), "leaf sponge: layer %zu does not hold 2^%d leaves of 32 words", t,
+                 log_leaves[t]);
+        ev[t] = evals[t]->d;
+    }
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)SET_COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, SET_COLS, log_n);
+    return vx_leaf_sponge_set_trace_dev(ctx, ev, log_leaves, nullptr, n_trees, tree_of, leaf_idx, n_idx, log_n, trace_out->d, public_out);
 }
 
 int32_t vx_merkle_rows_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t leaf_len, size_t n_idx, size_t* n_words) {

@@ -7,6 +7,12 @@
 // The levels above the tree's cap (the table proves paths to ONE root: the two-to-one fold of the cap) are folded here with the
 // tree builder's own level kernel.  Parity: tests/test_gpu_merkle_open.py compares trace, auxiliary columns and proof with
 // tests/merkle_open_ref.py and the reference prover.
+// MerkleOpenSetAir (paths into several trees, the openings table of vx_fri_queries_prove):
+//   k_merkle_open_set_trace  as k_merkle_open_trace, one lane per block; the path of a block and the first block of a path are
+//                            tables the host precomputes (the paths have different depths), the tree of a path one entry of a small
+//                            device table (node storage, the fold of its cap, depth, root): three dependent loads, no search
+//   k_merkle_open_set_aux    one lane per block: one extension inversion for both helpers (the opening, the root)
+// Parity: tests/test_gpu_fri_queries.py against tests/fri_queries_ref.py.
 #include <string.h>
 
 #include "air_merkle_open.cuh"
@@ -78,7 +84,165 @@ __global__ __launch_bounds__(64) void k_merkle_open_aux(const uint64_t* __restri
     }
 }
 
+// ---- MerkleOpenSetAir
+struct SetTree {             // one tree of the set
+    const uint64_t* levels;  // as OpenArgs
+    const uint64_t* upper;
+    const uint64_t* root;    // the last node of `upper`
+    size_t n_leaves, n_cap;
+    int depth, low;
+};
+struct OpenSetArgs {
+    const SetTree* trees;
+    const uint64_t* path;      // [n_idx][3]: tree, leaf index, first block (all checked by the host)
+    const uint32_t* blk_path;  // [n_active]: the path of every active block
+    size_t n_active, n;
+    uint64_t* tr;              // [SET_COLS][n]
+    uint64_t* claims;          // [n_idx][6]: (tree, index, leaf digest), written by the lane of each path's first level
+};
+
+__global__ __launch_bounds__(64) void k_merkle_open_set_trace(OpenSetArgs a) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= a.n / 32) return;
+    uint64_t s[12], shape[SET_COLS - BIT];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = 0;
+#pragma unroll
+    for (int j = 0; j < SET_COLS - BIT; ++j) shape[j] = 0;
+    shape[LVL - BIT] = 1;  // an idle block is the zero state at level 1 (tree 0, root 0, depth 0: nothing reads them)
+    if (b < a.n_active) {
+        const size_t p = a.blk_path[b];
+        const uint64_t* pe = a.path + 3 * p;
+        const SetTree t = a.trees[pe[0]];
+        const int l = (int)(b - pe[2]);
+        const uint64_t idx = pe[1], node = idx >> l, bit = node & 1;
+        const uint64_t* lv = l < t.low ? t.levels + 8 * (t.n_leaves - (t.n_leaves >> l)) : t.upper + 8 * (t.n_cap - (t.n_cap >> (l - t.low)));
+        const uint64_t *cur = lv + 4 * node, *sib = lv + 4 * (node ^ 1), *leaf = t.levels + 4 * idx;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint64_t c = gl_canon(cur[i]), sb = gl_canon(sib[i]), lf = gl_canon(leaf[i]);
+            s[i] = bit ? sb : c, s[4 + i] = bit ? c : sb;
+            shape[SIB - BIT + i] = sb, shape[CUR - BIT + i] = c, shape[LEAF - BIT + i] = lf, shape[ROOT - BIT + i] = gl_canon(t.root[i]);
+            if (l == 0) a.claims[6 * p + 2 + i] = lf;
+        }
+        if (l == 0) a.claims[6 * p] = pe[0], a.claims[6 * p + 1] = idx;
+        shape[BIT - BIT] = bit, shape[R - BIT] = node, shape[LVL - BIT] = (uint64_t)l + 1, shape[ACT - BIT] = 1;
+        shape[END - BIT] = l == t.depth - 1, shape[FIRSTB - BIT] = l == 0;
+        shape[TREE - BIT] = pe[0], shape[DEPTH - BIT] = (uint64_t)t.depth;
+    }
+    poseidon_air_walk(s, a.tr, a.n, 32 * b);
+    poseidon_air_block_cols(shape, a.tr, a.n, BIT, 32 * b);
+}
+
+__global__ __launch_bounds__(64) void k_merkle_open_set_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
+    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (b >= n / 32) return;
+    const size_t row = 32 * b;
+    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
+    gl2 h[2] = {gl2{0, 0}, gl2{0, 0}};
+    const uint64_t firstb = cell(FIRSTB), end = cell(END);
+    if (firstb | end) {  // h = FIRSTB (1 / D_lo + 1 / D_hi) of the opening, h2 = END (...) of the root, with one inversion
+        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
+        const uint64_t tree = cell(TREE), r = cell(R), depth = cell(DEPTH);
+        const gl2 dlo = bus.open_of(tree, r, cell(LEAF), cell(LEAF + 1), bus::K<0>{}), dhi = bus.open_of(tree, r, cell(LEAF + 2), cell(LEAF + 3), bus::K<1>{});
+        const gl2 rlo = bus.root(tree, cell(ROOT), cell(ROOT + 1), bus::K<0>{}, depth), rhi = bus.root(tree, cell(ROOT + 2), cell(ROOT + 3), bus::K<1>{}, depth);
+        const gl2 num[2] = {gl2_scale(gl2_add(dlo, dhi), firstb), gl2_scale(gl2_add(rlo, rhi), end)}, den[2] = {gl2_mul(dlo, dhi), gl2_mul(rlo, rhi)};
+        gl2_batch_div(num, den, h);
+    }
+    const gl2 sum = gl2_add(h[0], h[1]);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        uint64_t *ca = aux + (size_t)(2 * e) * n + row, *cb = aux + (size_t)(2 * e + 1) * n + row;
+        const gl2 v = h[e];
+#pragma unroll 8
+        for (int r = 0; r < 32; ++r) ca[r] = v.a, cb[r] = v.b;
+    }
+    uint64_t *za = aux + 4 * n + row, *zb = aux + 5 * n + row;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
+}
+
 }  // namespace
+
+int32_t MerkleOpenSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    (void)pub;
+    const size_t n = (size_t)1 << log_n, blocks = n / 32;
+    hipLaunchKernelGGL(k_merkle_open_set_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + 4 * n, log_n, aux_pub);
+}
+
+// The witness of MerkleOpenSetAir on the device: path i opens leaf leaf_idx[i] of trees[tree_of[i]].  pub_out: the digest of the
+// claims (tree, index, leaf digest).
+int32_t vx_merkle_open_set_trace_dev(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
+                                     uint64_t* trace_d, uint64_t pub_out[4]) {
+    VX_CHECK(n_trees >= 1 && n_trees <= VX_OPEN_SET_MAX_TREES, "merkle openings: %zu trees (1..%d)", n_trees, VX_OPEN_SET_MAX_TREES);
+    VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings (1..2^21)", n_idx);
+    VX_CHECK(log_n >= 5 && log_n <= 26, "merkle openings: 2^%d rows (5 <= log_n <= 26)", log_n);
+    const size_t n = (size_t)1 << log_n;
+    std::vector<SetTree> tab(n_trees);
+    size_t up_words = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        VX_CHECK(trees[t], "merkle openings: tree %zu is missing", t);
+        const int depth = ceil_log2(trees[t]->n_leaves);
+        VX_CHECK(depth >= 1 && depth <= 40 && trees[t]->cap_height >= 0 && trees[t]->cap_height <= depth, "merkle openings: tree %zu of %zu leaves has no path to prove", t,
+                 trees[t]->n_leaves);
+        up_words += 4 * (((size_t)2 << trees[t]->cap_height) - 1);
+    }
+    // the first block of every path, the path of every block
+    std::vector<uint64_t> path(3 * n_idx);
+    std::vector<uint32_t> blk_path;
+    for (size_t i = 0; i < n_idx; ++i) {
+        VX_CHECK(tree_of[i] < n_trees, "merkle openings: opening %zu names tree %llu of %zu", i, (unsigned long long)tree_of[i], n_trees);
+        const vx_tree* t = trees[tree_of[i]];
+        VX_CHECK(leaf_idx[i] < t->n_leaves, "merkle openings: index %zu (%llu) is not a leaf of tree %llu", i, (unsigned long long)leaf_idx[i], (unsigned long long)tree_of[i]);
+        path[3 * i] = tree_of[i], path[3 * i + 1] = leaf_idx[i], path[3 * i + 2] = blk_path.size();
+        VX_CHECK(blk_path.size() + (size_t)ceil_log2(t->n_leaves) <= n / 32, "merkle openings: the paths do not fit 2^%d rows", log_n);
+        blk_path.insert(blk_path.end(), (size_t)ceil_log2(t->n_leaves), (uint32_t)i);
+    }
+    const size_t n_active = blk_path.size(), w_tab = (n_trees * sizeof(SetTree) + 7) / 8, w_blk = (n_active + 1) / 2;
+    // scratch: the folds of the caps, the tree table, the paths, the block map, the claims
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (up_words + w_tab + 3 * n_idx + w_blk + 6 * n_idx) * 8);
+    VX_CHECK(sc, "merkle openings: out of device memory");
+    uint64_t *upper = sc, *tab_d = upper + up_words, *path_d = tab_d + w_tab, *blk_d = path_d + 3 * n_idx, *claims_d = blk_d + w_blk;
+    std::vector<uint64_t> claims(6 * n_idx);
+    int32_t rc = VX_OK;
+    do {
+        hipError_t e = hipSuccess;
+        uint64_t* up = upper;
+        for (size_t t = 0; t < n_trees && e == hipSuccess; ++t) {
+            const vx_tree* tr = trees[t];
+            const size_t n_cap = (size_t)1 << tr->cap_height;
+            const int depth = ceil_log2(tr->n_leaves);
+            e = hipMemcpyAsync(up, tr->levels + tr->total - 4 * n_cap, 4 * n_cap * 8, hipMemcpyDeviceToDevice, ctx->stream);
+            vx_merkle_levels_launch(ctx, up, n_cap, 1);
+            tab[t] = SetTree{tr->levels, up, up + 8 * n_cap - 8, tr->n_leaves, n_cap, depth, depth - tr->cap_height};
+            up += 4 * (2 * n_cap - 1);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(tab_d, tab.data(), n_trees * sizeof(SetTree), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(path_d, path.data(), path.size() * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk_d, blk_path.data(), n_active * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle openings: %s", hipGetErrorString(e));
+            break;
+        }
+        const OpenSetArgs a{(const SetTree*)tab_d, path_d, (const uint32_t*)blk_d, n_active, n, trace_d, claims_d};
+        hipLaunchKernelGGL(k_merkle_open_set_trace, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, a);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, claims.size() * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle openings: %s", hipGetErrorString(e));
+    } while (0);
+    vx_pool_free(ctx, sc);
+    VX_TRY(rc);
+    uint64_t digest[4];
+    glh::hash_no_pad(claims.data(), claims.size(), digest);
+    vx_merkle_open_set_public(digest, pub_out);
+    return VX_OK;
+}
+
+// MerkleOpenSetAir's public inputs: the digest the table does not constrain (prover and verifier alike: vx_bus.h)
+void vx_merkle_open_set_public(const uint64_t digest[4], uint64_t pub[4]) { memcpy(pub, digest, 32); }
 
 int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
     (void)pub;
@@ -137,6 +301,14 @@ int32_t vx_merkle_open_air_trace(vx_ctx* ctx, const vx_tree* tree, const uint64_
     VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)COLS << log_n), "merkle openings: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
              trace_out->n, COLS, log_n);
     return vx_merkle_open_trace_dev(ctx, tree, leaf_idx, n_idx, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_merkle_open_set_air_trace(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
+                                     vx_buf* trace_out, uint64_t public_out[4]) {
+    if (!ctx || !trees || !tree_of || !leaf_idx || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)SET_COLS << log_n), "merkle openings: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, SET_COLS, log_n);
+    return vx_merkle_open_set_trace_dev(ctx, trees, n_trees, tree_of, leaf_idx, n_idx, log_n, trace_out->d, public_out);
 }
 
 int32_t vx_merkle_openings_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t n_idx, size_t* n_words) {

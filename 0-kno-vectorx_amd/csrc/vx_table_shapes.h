@@ -1,6 +1,6 @@
 // Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers
-// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip, the aggregation provers in vx_merkle_open_air.hip, vx_leaf_sponge_air.hip and
-// vx_fri_fold_air.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
+// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip, the aggregation provers in vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
+// vx_fri_fold_air.hip and vx_fri_queries.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
 // condition.  Host-only inline functions, no device code.
 #pragma once
 #include <stddef.h>
@@ -52,3 +52,12 @@ static inline int fri_fold_log_n(size_t n_queries, int log_lde, size_t n_layers)
     const int l = ceil_log2(n_queries * (size_t)(log_lde - 3 * (int)n_layers));
     return l < 5 ? 5 : l;
 }
+// The three tables of a FRI query phase (vx_fri_queries_prove / vx_fri_queries_verify): n_layers layer trees of depth
+// log_lde - 4 (l + 1), every leaf 32 words.  MerkleOpenSetAir: one path per (query, layer); LeafSpongeSetAir: one leaf of four
+// blocks per (query, layer); FriFoldAir as above
+static inline int fri_queries_open_log_n(size_t n_queries, int log_lde, size_t n_layers) {
+    size_t levels = 0;
+    for (size_t l = 0; l < n_layers; ++l) levels += (size_t)(log_lde - 4 * ((int)l + 1));
+    return ceil_log2(32 * n_queries * levels);
+}
+static inline int fri_queries_sponge_log_n(size_t n_queries, size_t n_layers) { return ceil_log2(32 * n_queries * n_layers * 4); }

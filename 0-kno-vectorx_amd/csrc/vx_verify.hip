@@ -1033,6 +1033,68 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
                             });
 }
 
+// FRI queries (the prover is vx_fri_queries.hip), the first aggregation verifier that holds NO leaves: three tables on one bus --
+// MerkleOpenSetAir, LeafSpongeSetAir, FriFoldAir -- close TAG_OPEN and TAG_ROW among themselves in every layer tree.  The verifier
+// holds what a succinct verifier holds: the layer caps, the betas, the final polynomial and (index, ev_0) per query.  It sends
+// every entry, receives every exit, and receives the root and depth every path ended in -- the tables do not know which root
+// belongs to which tree, the verifier does (cap_root of caps[l], depth log_lde - 4 (l + 1)):
+//     sum over the tables of total x rows = sum over the queries of  - 1 / D_fri(index, ev_0, 0)  +  1 / D_fri(index, final_poly(x_NL), 1)
+//                                                                     + sum over the layers l of 1 / D_root(l, lo) + 1 / D_root(l, hi).
+// EVERY public input of all three tables is rebuilt from the arguments (their digest words are the statement digest, vx_bus.h).
+// No path is walked, no leaf hashed, nothing folded.
+int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
+                              size_t final_len, const uint64_t* caps, int cap_height, const uint64_t* index, const uint64_t* ev0, size_t n_queries, char* err, size_t errlen) {
+    if (!cfg || !blob || !betas || !final_poly || !caps || !index || !ev0) return VX_ERR_ARG;
+    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    NEED(log_lde >= 5 && log_lde <= 30 && n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri queries: log_lde %d / %zu layers out of range", log_lde,
+         n_layers);
+    NEED(cap_height >= 0 && cap_height <= 16 && cap_height <= log_lde - 4 * (int)n_layers, "fri queries: cap height %d out of range (at most log_lde - 4 layers)", cap_height);
+    NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "fri queries: %zu queries (1..2^20)", n_queries);
+    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri queries: a final polynomial of %zu coefficients", final_len);
+    const int log_open = fri_queries_open_log_n(n_queries, log_lde, n_layers), log_sponge = fri_queries_sponge_log_n(n_queries, n_layers);
+    NEED(log_open <= 26 && log_sponge <= 26, "fri queries: the request needs a table of more than 2^26 rows");
+    BusTable tab[3];
+    int32_t rc = read_blob(blob, len, VX_FQRY_MAGIC, "fri-queries", {(uint64_t)log_lde, n_layers, n_queries}, tab, 3, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 3), "a proof is too short to hold a trace cap");
+    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri queries: non-canonical beta word %zu", i);
+    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri queries: non-canonical final-polynomial word %zu", i);
+    for (size_t i = 0; i < n_queries; ++i) {
+        NEED(index[i] >> log_lde == 0, "fri queries: claim %zu names an index outside the LDE", i);
+        NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri queries: claim %zu has a non-canonical ev_0", i);
+    }
+    std::vector<uint64_t> roots(4 * n_layers);
+    for (size_t l = 0; l < n_layers; ++l)
+        if ((rc = cap_root(caps + l * ((size_t)4 << cap_height), cap_height, "fri queries", roots.data() + 4 * l, err, errlen)) != VX_OK) return rc;
+    uint64_t stmt[4], opub[mop::SET_PUB], spub[lsp::PUB], fpub[ffa::PUB];
+    vx_fri_queries_statement(log_lde, betas, n_layers, final_poly, final_len, roots.data(), index, ev0, n_queries, stmt);
+    vx_merkle_open_set_public(stmt, opub);
+    vx_leaf_sponge_set_public(32, stmt, spub);
+    vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, fpub);
+    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
+    tab[1].air = VX_AIR_LEAF_SPONGE_SET, tab[1].want = spub, tab[1].n_want = lsp::PUB;
+    tab[2].air = VX_AIR_FRI_FOLD, tab[2].want = fpub, tab[2].n_want = ffa::PUB;
+    return verify_bus_group(cfg, tab, 3, "the query phase the tables prove is not the claimed one (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(n_queries * (2 + 2 * n_layers));
+                                const uint64_t w = glh::root(log_lde);
+                                for (size_t i = 0; i < n_queries; ++i) {
+                                    const Fx idx{index[i], 0};
+                                    m.send(bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
+                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
+                                    Fx fp{0, 0};
+                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+                                    m.receive(bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                    for (size_t l = 0; l < n_layers; ++l) {
+                                        const uint64_t* r = roots.data() + 4 * l;
+                                        const Fx tree{(uint64_t)l, 0}, depth{(uint64_t)(log_lde - 4 * ((int)l + 1)), 0};
+                                        m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
+                                        m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
+                                    }
+                                }
+                            });
+}
+
 // The FRI side of a vx_stark_prove proof as FriFoldAir's claims (prover-side: it VERIFIES the proof on the way -- the transcript
 // is replayed by the verifier's own code -- and hands out what its query phase saw).  The proof omits the `within` slot of every
 // FRI leaf; here it is filled with the value the chain enters the layer with.

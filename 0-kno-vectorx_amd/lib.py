@@ -32,6 +32,7 @@ SYMBOLS = [
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
     "vx_fri_fold_air_trace", "vx_fri_fold_proof_bound", "vx_fri_fold_prove", "vx_fri_fold_verify", "vx_stark_fri_claims",
+    "vx_merkle_open_set_air_trace", "vx_leaf_sponge_set_air_trace", "vx_fri_queries_proof_bound", "vx_fri_queries_prove", "vx_fri_queries_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -46,6 +47,8 @@ VX_AIR_EPOCH_END, VX_EPOCH_END_AIR_COLS, VX_EPOCH_END_AIR_AUX_COLS = 15, 52, 46
 VX_AIR_MERKLE_OPEN, VX_MERKLE_OPEN_AIR_COLS, VX_MERKLE_OPEN_AIR_AUX_COLS = 16, 66, 4
 VX_AIR_LEAF_SPONGE, VX_LEAF_SPONGE_AIR_COLS, VX_LEAF_SPONGE_AIR_AUX_COLS = 17, 66, 12
 VX_AIR_FRI_FOLD, VX_FRI_FOLD_AIR_COLS, VX_FRI_FOLD_AIR_AUX_COLS = 18, 120, 36
+VX_AIR_MERKLE_OPEN_SET, VX_MERKLE_OPEN_SET_AIR_COLS, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 19, 72, 6
+VX_AIR_LEAF_SPONGE_SET, VX_LEAF_SPONGE_SET_AIR_COLS, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 20, 67, 12
 
 
 class JustificationStruct(C.Structure):
@@ -179,6 +182,11 @@ def load_library():
         "vx_fri_fold_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, C.POINTER(sz)],
         "vx_fri_fold_prove": [vp, C.POINTER(StarkConfig), C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_fri_fold_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, C.c_char_p, sz],
+        "vx_merkle_open_set_air_trace": [vp, vp, sz, vp, vp, sz, C.c_int, vp, vp],
+        "vx_leaf_sponge_set_air_trace": [vp, vp, vp, sz, vp, vp, sz, C.c_int, vp, vp],
+        "vx_fri_queries_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, C.POINTER(sz)],
+        "vx_fri_queries_prove": [vp, C.POINTER(StarkConfig), C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_fri_queries_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, vp, sz, vp, C.c_int, vp, vp, sz, C.c_char_p, sz],
         "vx_stark_fri_claims": [C.POINTER(StarkConfig), vp, sz, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
@@ -421,6 +429,30 @@ def fri_fold_verify(blob, log_lde, betas, final_poly, index, ev0, leaves, cfg=No
     be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
     err = C.create_string_buffer(256)
     rc = L.vx_fri_fold_verify(C.byref(cfg), _ptr(b), b.size, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+FQRY_MAGIC, FQRY_HDR = 0x3130595251465856, 7  # "VXFQRY01": magic, log2 of the inner LDE, fold layers, queries, three proof lengths; then the proofs
+
+
+def fri_queries_verify(blob, log_lde, betas, final_poly, caps, index, ev0, cfg=None):
+    """Host-side check of a vx_fri_queries_prove blob against what a succinct verifier holds: the inner proof's LDE size, betas
+    [NL][2], the final polynomial [len][2], the layer caps [NL][2^cap_height][4] and per query (index, ev0 [2]) in order.  Holds no
+    leaves, walks no path, folds nothing; raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    be = np.ascontiguousarray(betas, dtype=np.uint64).reshape(-1, 2)
+    fp = np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
+    cp = np.ascontiguousarray(caps, dtype=np.uint64).reshape(be.shape[0], -1, 4)
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+    ev = np.ascontiguousarray(ev0, dtype=np.uint64).reshape(-1)
+    cap_height = cp.shape[1].bit_length() - 1
+    if ev.size != 2 * idx.size or cp.shape[1] != 1 << cap_height:
+        raise ValueError("one ev_0 [2] for every query and one cap of 2^cap_height digests for every layer")
+    err = C.create_string_buffer(256)
+    rc = L.vx_fri_queries_verify(C.byref(cfg), _ptr(b), b.size, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(cp), cap_height, _ptr(idx), _ptr(ev), idx.size, err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
 
@@ -687,6 +719,52 @@ class Context:
                                 "fri fold: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries)",
                                 lambda c, o, need: self.L.vx_fri_fold_prove(self.h, c, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size,
                                                                             _ptr(o), o.size, need))
+
+    def merkle_open_set_air_trace(self, trees, tree_of, leaf_idx, log_n, out=None):
+        """The witness of MerkleOpenSetAir: opening i is leaf leaf_idx[i] of trees[tree_of[i]] -> (Buffer [72][2^log_n], the 4
+        public inputs: the digest of the claims (tree, index, leaf digest))."""
+        to = np.ascontiguousarray(tree_of, dtype=np.uint64).reshape(-1)
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        if to.size != idx.size:
+            raise ValueError("one tree for every opening")
+        th = (C.c_void_p * len(trees))(*[t.h for t in trees])
+        out = out or self.alloc(VX_MERKLE_OPEN_SET_AIR_COLS << log_n)
+        pub = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.vx_merkle_open_set_air_trace(self.h, th, len(trees), _ptr(to), _ptr(idx), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def leaf_sponge_set_air_trace(self, evals, log_leaves, tree_of, leaf_idx, log_n, out=None):
+        """The witness of LeafSpongeSetAir for leaves of FRI layers: tree t is the layer evals[t] of 2^(log_leaves[t] + 4) extension
+        values in natural order, opening i is its leaf leaf_idx[i] for t = tree_of[i] -> (Buffer [67][2^log_n], the 14 public
+        inputs: L = 32, B = 4, the tail flags, the digest of the claims (tree, index, row))."""
+        to = np.ascontiguousarray(tree_of, dtype=np.uint64).reshape(-1)
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        if to.size != idx.size or len(evals) != len(log_leaves):
+            raise ValueError("one tree for every opening, one log_leaves for every layer")
+        eh = (C.c_void_p * len(evals))(*[e.h for e in evals])
+        ll = (C.c_int * len(evals))(*[int(v) for v in log_leaves])
+        out = out or self.alloc(VX_LEAF_SPONGE_SET_AIR_COLS << log_n)
+        pub = np.zeros(14, dtype=np.uint64)
+        self._ck(self.L.vx_leaf_sponge_set_air_trace(self.h, eh, ll, len(evals), _ptr(to), _ptr(idx), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def fri_queries_prove(self, log_lde, betas, final_poly, trees, evals, index, cfg=None, out=None):
+        """Proves the FRI query phase of the queries `index`: trees[l] (fri_layer_tree, arity_bits 4) and evals[l] (the layer it was
+        built from, natural order) for every fold layer -> blob words (lib.fri_queries_verify checks it).  Three tables on one bus:
+        the openings, the leaf hashes, the fold chains.  The chains are folded natively first: VxError(VX_ERR_STATEMENT) names the
+        query and layer that do not hold.  out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries
+        the needed length as `.needed`."""
+        be = np.ascontiguousarray(betas, dtype=np.uint64).reshape(-1, 2)
+        fp = np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+        if len(trees) != be.shape[0] or len(evals) != be.shape[0]:
+            raise ValueError("one tree and one layer for every beta")
+        th = (C.c_void_p * len(trees))(*[t.h for t in trees])
+        eh = (C.c_void_p * len(evals))(*[e.h for e in evals])
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_fri_queries_proof_bound(c, log_lde, be.shape[0], idx.size, need),
+                                "fri queries: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries, tables of at most 2^26 rows)",
+                                lambda c, o, need: self.L.vx_fri_queries_prove(self.h, c, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], th, eh, _ptr(idx), idx.size,
+                                                                               _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

@@ -166,7 +166,8 @@ typedef struct vx_stark_config {
  * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log.
  * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove.
  * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove.
- * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove. */
+ * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove.
+ * 19 (VX_AIR_MERKLE_OPEN_SET) / 20 (VX_AIR_LEAF_SPONGE_SET) are 16 / 17 for several trees in one table: see vx_fri_queries_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -232,8 +233,8 @@ int32_t vx_poseidon_air_trace(vx_ctx* ctx, const vx_buf* states, size_t n_perm, 
  * iff the table's published total equals the sum over the verifier's own claims.  Public inputs (9): root (4), D, and the claims
  * digest hash_n_to_hash_no_pad((index, d0, d1, d2, d3) of every opening, in order), which makes the lookup challenges depend on
  * the claims.  The opened leaf ROWS are hashed in-proof by LeafSpongeAir (below: vx_merkle_rows_prove, whose claims are rows, not
- * digests).  STILL OUTSIDE (the next tables): there is one tree per proof, and the evaluation at zeta and the transcript stay on
- * the host (the FRI fold is FriFoldAir, below).
+ * digests).  This table has one tree; MerkleOpenSetAir (below: vx_fri_queries_prove) takes several.  STILL OUTSIDE (the next
+ * tables): the evaluation at zeta and the transcript stay on the host (the FRI fold is FriFoldAir, below).
  * vx_merkle_open_air_trace: the witness on its own (test surface) -- leaf_idx: n_idx >= 1 leaf indices (host; duplicates
  *   allowed); trace_out: [VX_MERKLE_OPEN_AIR_COLS][2^log_n] with 2^log_n >= 32 n_idx D; blocks behind the paths are idle.
  * vx_merkle_openings_prove: trace + proof at the smallest such log_n (>= 5) under lookup challenges that are the shared-challenge
@@ -279,7 +280,8 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
  *   accepts iff  total_open x 2^log_n_open + total_sponge x 2^log_n_sponge = sum over the claims and j < leaf_len of
  *   1 / D_row(index, j, row[j]).  Its row-claims digest costs as many permutations as hashing the rows would; what it no longer
  *   does is anything per tree level, and the row bus is one whose other party a later table (FRI fold, evaluation at zeta)
- *   replaces.  STILL OUTSIDE: several trees (roots) per proof, the evaluation at zeta, the transcript (the FRI fold: FriFoldAir). */
+ *   replaces.  Several trees of one leaf length in one table: LeafSpongeSetAir (below).  STILL OUTSIDE: a per-tree leaf length,
+ *   the evaluation at zeta, the transcript (the FRI fold: FriFoldAir). */
 enum { VX_AIR_LEAF_SPONGE = 17, VX_LEAF_SPONGE_AIR_COLS = 66, VX_LEAF_SPONGE_AIR_AUX_COLS = 12 };
 int32_t vx_leaf_sponge_air_trace(vx_ctx* ctx, const vx_buf* data, size_t off, size_t n_leaves, size_t leaf_len, int layout, const uint64_t* leaf_idx,
                                  size_t n_idx, int log_n, vx_buf* trace_out, uint64_t public_out[14]);
@@ -302,7 +304,7 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
  * (default configuration, 2^21 LDE: 9 rows per query, 84 queries in 2^10 rows).  Public inputs (24): n_layers, rows per query,
  * 1 / w, TREE0, eight betas (zero behind n_layers) and the claims digest hash_n_to_hash_no_pad((index, ev0, leaves) of every
  * query, in order).  Bus: a fold row receives the 32 words of its leaf as row messages (leaf index, position, word, tree =
- * TREE0 + layer) -- what a leaf-sponge table over the layer trees sends; until several trees fit one proof the verifier sends them
+ * TREE0 + layer) -- what LeafSpongeSetAir sends in vx_fri_queries_prove; the verifier of vx_fri_fold_verify sends them itself
  * -- a query's first row receives (index, ev0, 0) and its first bit row sends (index, ev_NL, 1).
  * vx_fri_fold_air_trace: the witness on its own (test surface; host claims, nothing is checked beyond ranges) -- trace_out:
  *   [VX_FRI_FOLD_AIR_COLS][2^log_n] with 2^log_n >= n_queries (log_lde - 3 n_layers); rows behind the queries are idle.
@@ -318,8 +320,8 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
  *   ev_NL the verifier accepted (ev_last_out may be NULL), and the FULL leaves of every layer -- the proof omits the slot
  *   `within`, which is filled with the value the chain enters the layer with.  final_cap / leaves_cap are in words, query_cap in
  *   queries; VX_ERR_BUFSZ (sizes set) when one is too small.
- * STILL OUTSIDE: several roots per table (the leaves' Merkle side), the FRI combination / evaluation at zeta, the transcript,
- * and the final-polynomial evaluation, which stays the verifier's single Horner per query. */
+ * STILL OUTSIDE here: the leaves' Merkle side (vx_fri_queries_prove, below, puts it on the same bus), the FRI combination /
+ * evaluation at zeta, the transcript, and the final-polynomial evaluation, which stays the verifier's single Horner per query. */
 enum { VX_AIR_FRI_FOLD = 18, VX_FRI_FOLD_AIR_COLS = 120, VX_FRI_FOLD_AIR_AUX_COLS = 36 };
 int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0,
                               const uint64_t* leaves, size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]);
@@ -331,6 +333,47 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
 int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int* log_lde, size_t* n_layers, size_t* final_len, size_t* n_queries,
                             uint64_t betas_out[16], uint64_t* final_poly_out, size_t final_cap, uint64_t* index_out, uint64_t* ev0_out, uint64_t* ev_last_out, size_t query_cap,
                             uint64_t* leaves_out, size_t leaves_cap, char* err, size_t errlen);
+/* ---- The FRI query phase on one bus: the layer leaves opened, hashed and folded (vx_fri_queries_prove).  An inner proof's FRI
+ * has n_layers layer trees with different roots and depths (log_lde - 4 (l + 1)), every leaf 32 words.  Two SET tables carry
+ * several trees in one table:
+ *   MerkleOpenSetAir (AIR id VX_AIR_MERKLE_OPEN_SET; csrc/air_merkle_open.cuh): MerkleOpenAir with six more block-constant columns
+ *     TREE, ROOT[4], DEPTH.  Root and depth are no public inputs: the END block of a path SENDS them (TAG_ROOT: 2 tree + half, two
+ *     root words, depth) and whoever knows the trees receives them.  Openings go out as (index, two digest words, half + 2 tree).
+ *     Public inputs (4): a digest the table does not constrain.
+ *   LeafSpongeSetAir (AIR id VX_AIR_LEAF_SPONGE_SET; csrc/air_leaf_sponge.cuh): LeafSpongeAir with one more block-constant column
+ *     TREE; row words go out with their tree in the fourth slot, the digest is received with it.  L, B and the tail flags stay public
+ *     inputs (14 as in LeafSpongeAir): all trees of one table share a leaf length.
+ * vx_merkle_open_set_air_trace / vx_leaf_sponge_set_air_trace: the witnesses on their own (test surfaces).  Opening i is leaf
+ *   leaf_idx[i] of tree tree_of[i] (< n_trees <= 64; duplicates allowed); trace_out: [VX_*_SET_AIR_COLS][2^log_n].  The sponge
+ *   surface takes FRI layers: evals[t] holds 2^(log_leaves[t] + 4) extension values in natural order, as vx_fri_layer_tree reads
+ *   them (leaf j = the 16 values at bitrev(16 j + t)); L = 32.  public_out: the public inputs, whose digest is the claims digest of
+ *   the set -- hash_n_to_hash_no_pad of (tree, index, leaf digest) resp. (tree, index, row) of every opening in order.
+ * vx_fri_queries_prove: trees[l] / evals[l]: the tree vx_fri_layer_tree built (arity_bits 4, one cap height <= log_lde - 4
+ *   n_layers for all layers) and the layer it was built from, l < n_layers <= 8; index[n_queries] < 2^log_lde.  Gathers ev_0 and
+ *   every query's leaf in every layer on the device, folds every query natively first (VX_ERR_STATEMENT names query and layer; a
+ *   layer that does not hash to its tree's leaves is VX_ERR_STATEMENT too; nothing is proven then), and proves MerkleOpenSetAir
+ *   (one path per (query, layer)), LeafSpongeSetAir (one leaf per (query, layer)) and FriFoldAir (TREE0 = 0: tree id = layer) under
+ *   shared challenges, in that bus order.  The four digest words of all three tables are the STATEMENT digest:
+ *   hash_n_to_hash_no_pad(log_lde, n_layers, n_queries, betas, final_poly, the n_layers roots, (index, ev_0) of every query), a
+ *   root being the two-to-one fold of a cap.  VX_ERR_ARG: arity_bits != 4, n_layers > 8, cap height > log_lde - 4 n_layers, a
+ *   table of more than 2^26 rows.  Blob: "VXFQRY01", log_lde, n_layers, n_queries, three lengths, three proofs.
+ * vx_fri_queries_verify (host only): holds the layer caps caps[n_layers][4 << cap_height], the betas, the final polynomial and
+ *   (index, ev0) per query -- NO leaves; walks no path, hashes no leaf, folds nothing.  Rebuilds every public input of all three
+ *   tables from its arguments, sends (index, ev_0) of every query, receives (index, final_poly(x_NL)) and, per layer, the two
+ *   halves of (root of caps[l], depth log_lde - 4 (l + 1)); accepts iff all three tables verify and the bus balances.
+ * STILL OUTSIDE: the commitment trees (a per-tree leaf length), ev_0 from a FRI-combination table, binding to the layer trees
+ * vx_stark_prove builds itself. */
+enum { VX_AIR_MERKLE_OPEN_SET = 19, VX_MERKLE_OPEN_SET_AIR_COLS = 72, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 6 };
+enum { VX_AIR_LEAF_SPONGE_SET = 20, VX_LEAF_SPONGE_SET_AIR_COLS = 67, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 12 };
+int32_t vx_merkle_open_set_air_trace(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
+                                     vx_buf* trace_out, uint64_t public_out[4]);
+int32_t vx_leaf_sponge_set_air_trace(vx_ctx* ctx, const vx_buf* const* evals, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx,
+                                     int log_n, vx_buf* trace_out, uint64_t public_out[14]);
+int32_t vx_fri_queries_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words);
+int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
+                             const vx_tree* const* trees, const vx_buf* const* evals, const uint64_t* index, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
+                              size_t final_len, const uint64_t* caps, int cap_height, const uint64_t* index, const uint64_t* ev0, size_t n_queries, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */

@@ -28,13 +28,14 @@ def declarations():
 
 def rust_type(c):
     c = c.strip()
-    m = re.match(r"^(const\s+)?([a-z_0-9]+)\s*(\**)\s*(?:const\s*)?$", c)
+    m = re.match(r"^(const\s+)?([a-z_0-9]+)\s*((?:\*\s*(?:const\s*)?)*)$", c)
     if not m:
         raise ValueError(f"cannot map C type {c!r}")
-    const, base, stars = bool(m.group(1)), BASE[m.group(2)], len(m.group(3))
-    t = base
-    for k in range(stars):
-        t = ("*const " if (const and k == 0) else "*mut ") + t
+    # level k points to a const object when the type to its left is const: the base for k = 0, `* const` of level k - 1 otherwise
+    consts = [bool(m.group(1))] + [bool(q) for q in re.findall(r"\*\s*(const)?", m.group(3))]
+    t = BASE[m.group(2)]
+    for k in range(len(consts) - 1):
+        t = ("*const " if consts[k] else "*mut ") + t
     return t
 
 
