@@ -47,16 +47,30 @@ __device__ __forceinline__ uint64_t gl_dbl(uint64_t a) { return gl_add(a, a); }
 // (hi, lo) 128-bit -> [0, 2^64), NOT necessarily canonical (may be in [p, 2^64)).
 // value = lo + hl*2^64 + hh*2^96 = lo - hh + hl*(2^32-1)  (mod p).
 #ifndef GL_REDUCE_C
-// Hand-scheduled: 8 vector instructions instead of the 12 the compiler needs for the two conditional +-eps
+// Hand-scheduled: 7 vector instructions instead of the 12 the compiler needs for the two conditional +-eps
 // corrections (tools/isa_rate.hip: v_mad_u64_u32 issues at nearly the rate of any VOP3 add, so instruction COUNT
 // is what the integer kernels pay for).  A = lo - hh wraps with borrow b; T = A + hl*eps wraps with carry c
 // (the mad's own carry-out); V = T + (c-b)*2^64, and 2^64 = eps, so R = T + d*eps with d = c-b in {-1,0,1},
 // applied as T - d (v_mad_i64_i32 by -1) and d added to the high word.  |d| = 1 cannot wrap again: c=1,b=0
-// means T <= 2^64 - 2^33; c=0,b=1 means T >= 2^64 - 2^32 + 1.  gfx90a+ needs 2 wait states between a VALU
-// write of VCC / an SGPR and a VALU read of it; inside an asm block that is ours to honour (s_nop 1).
+// means T <= 2^64 - 2^33; c=0,b=1 means T >= 2^64 - 2^32 + 1.  c never leaves VCC: v_addc_co_u32 d, vcc, 0, mb, vcc
+// adds it to the borrow mask mb = -b, and that sum IS d (no v_cndmask to make c a mask, no subtraction of two masks).
+// gfx90a+ needs 2 wait states between a VALU write of VCC / an SGPR and a VALU read of it; inside an asm block
+// that is ours to honour (s_nop 1).
+__device__ __forceinline__ uint64_t gl_reduce_tail(uint32_t hl, uint64_t a, uint32_t mb) {
+    uint64_t t, r;
+    uint32_t d;
+    asm("v_mad_u64_u32 %0, vcc, %2, -1, %3\n\t"
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %1, vcc, 0, %4, vcc"
+        : "=&v"(t), "=v"(d)
+        : "v"(hl), "v"(a), "v"(mb)
+        : "vcc");
+    asm("v_mad_i64_i32 %0, vcc, %1, -1, %2" : "=v"(r) : "v"(d), "v"(t) : "vcc");
+    return r + ((uint64_t)d << 32);
+}
 __device__ __forceinline__ uint64_t gl_reduce128_nc(uint64_t hi, uint64_t lo) {
     const uint32_t hh = (uint32_t)(hi >> 32), hl = (uint32_t)hi;
-    uint32_t al, ah, mb, mc;
+    uint32_t al, ah, mb;
     asm("v_sub_co_u32 %0, vcc, %3, %5\n\t"
         "s_nop 1\n\t"
         "v_subbrev_co_u32 %1, vcc, 0, %4, vcc\n\t"
@@ -65,17 +79,7 @@ __device__ __forceinline__ uint64_t gl_reduce128_nc(uint64_t hi, uint64_t lo) {
         : "=&v"(al), "=&v"(ah), "=&v"(mb)
         : "v"((uint32_t)lo), "v"((uint32_t)(lo >> 32)), "v"(hh)
         : "vcc");
-    const uint64_t a = ((uint64_t)ah << 32) | al;
-    uint64_t t, sc;
-    asm("v_mad_u64_u32 %0, %1, %3, -1, %4\n\t"
-        "s_nop 1\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, %1"
-        : "=&v"(t), "=&s"(sc), "=&v"(mc)
-        : "v"(hl), "v"(a));
-    const uint32_t d = mb - mc;  // c - b
-    uint64_t r;
-    asm("v_mad_i64_i32 %0, vcc, %1, -1, %2" : "=v"(r) : "v"(d), "v"(t) : "vcc");
-    return r + ((uint64_t)d << 32);
+    return gl_reduce_tail(hl, ((uint64_t)ah << 32) | al, mb);
 }
 #else
 __device__ __forceinline__ uint64_t gl_reduce128_nc(uint64_t hi, uint64_t lo) {
@@ -144,11 +148,43 @@ __device__ __forceinline__ uint64_t gl_acc_reduce(const gl_acc& a) {
 }
 
 // inputs: any 64-bit representatives; output in [0, 2^64) (non-canonical)
+#if !defined(GL_MUL_C) && !defined(GL_REDUCE_C) && !defined(GL_MUL_UNFUSED)
+// One fused multiply-reduce, 13 vector instructions instead of the 15 of gl_mul128 + gl_reduce128_nc (-DGL_MUL_UNFUSED brings
+// those back): the carry-out k of the cross term t2 = a1 b0 + t1 is never made a VGPR value.  k has weight 2^96 = -1 (mod p),
+// so with hi' = a1 b1 + hi(t2) (no k: hi' <= (2^32-1)^2 + 2^32 - 1 cannot overflow) the product is lo + hl' eps - hh' - k, and k
+// is the BORROW-IN of the reduction's first subtraction, read from the SGPR pair the multiply-add left it in (the VOP3 form of
+// v_subb_co takes any SGPR pair as carry-in).  Bounds: hi' + k 2^32 is the true high half of a product below 2^128, so
+// hh' + k <= 2^32 - 1: A = lo - (hh' + k) borrows at most once (b in {0,1}) exactly as with gl_reduce128_nc's hh, and that
+// function's argument for |d| = 1 (c=1,b=0: T <= 2^64 - 2^33; c=0,b=1: T >= A >= 2^64 - 2^32 + 1) uses nothing but hh <= 2^32 - 1
+// and hl eps <= 2^64 - 2^33 + 1.  k travels between the asm statements as a 64-bit "s" operand, never in VCC (the compiler's
+// own multiply-add for hi' sits between them and may write VCC); the statement that reads it opens with its own s_nop, since
+// the compiler pads no hazard whose consumer is inside an asm string.
+__device__ __forceinline__ uint64_t gl_mul_nc(uint64_t a, uint64_t b) {
+    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
+    const uint64_t t0 = (uint64_t)a0 * b0;
+    const uint64_t t1 = (uint64_t)a0 * b1 + (t0 >> 32);
+    uint64_t t2, k;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(t2), "=s"(k) : "v"(a1), "v"(b0), "v"(t1));
+    const uint64_t hi = (uint64_t)a1 * b1 + (t2 >> 32);  // hi'
+    uint32_t al, ah, mb;
+    asm("s_nop 1\n\t"
+        "v_subb_co_u32_e64 %0, vcc, %3, %5, %6\n\t"
+        "s_nop 1\n\t"
+        "v_subbrev_co_u32 %1, vcc, 0, %4, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %2, vcc, %3, %3, vcc"
+        : "=&v"(al), "=&v"(ah), "=&v"(mb)
+        : "v"((uint32_t)t0), "v"((uint32_t)t2), "v"((uint32_t)(hi >> 32)), "s"(k)
+        : "vcc");
+    return gl_reduce_tail((uint32_t)hi, ((uint64_t)ah << 32) | al, mb);
+}
+#else
 __device__ __forceinline__ uint64_t gl_mul_nc(uint64_t a, uint64_t b) {
     uint64_t hi, lo;
     gl_mul128(a, b, hi, lo);
     return gl_reduce128_nc(hi, lo);
 }
+#endif
 __device__ __forceinline__ uint64_t gl_mul(uint64_t a, uint64_t b) { return gl_canon(gl_mul_nc(a, b)); }
 __device__ __forceinline__ uint64_t gl_sqr(uint64_t a) { return gl_mul(a, a); }
 // multiply by a small constant c < 2^32

@@ -250,6 +250,9 @@ __device__ __forceinline__ void poseidon_mds_split_out(uint64_t s0, uint64_t* xl
     }
 }
 
+// CANON = false leaves the output as any 64-bit representative: for a sponge's inner permutations, whose output only meets
+// gl_add_nc (the next permutation's first constant add) or is overwritten by the next absorb
+template <bool CANON = true>
 __device__ __forceinline__ void poseidon_permute(uint64_t* s) {
     int rc = 12;  // constants of round k+1 are added by the MDS layer of round k
 #pragma unroll
@@ -305,8 +308,10 @@ __device__ __forceinline__ void poseidon_permute(uint64_t* s) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) s[i] = poseidon_sbox(s[i]);
     poseidon_mds<0>(s, 0);
+    if (CANON) {
 #pragma unroll
-    for (int i = 0; i < 12; ++i) s[i] = gl_canon(s[i]);
+        for (int i = 0; i < 12; ++i) s[i] = gl_canon(s[i]);
+    }
 }
 
 // ---- cooperative permutation: one state element per lane, 16-lane groups (lanes 12..15 idle) -------------------
@@ -398,7 +403,8 @@ __device__ __forceinline__ uint64_t poseidon_mds_coop_dpp(uint64_t s, int l, con
     const uint64_t y = ((uint64_t)yhi << 32) | (uint32_t)w;
     return y + (carry ? (uint64_t)GL_EPS : 0);
 }
-// s = this lane's state element (l < 12); returns the permuted element, canonical
+// s = this lane's state element (l < 12); returns the permuted element, canonical unless CANON = false (as poseidon_permute)
+template <bool CANON = true>
 __device__ __forceinline__ uint64_t poseidon_permute_coop(uint64_t s, int l, uint64_t* g) {
     const int lc = l < 12 ? l : 0;
 #if VX_POSEIDON_COOP_DPP
@@ -413,7 +419,7 @@ __device__ __forceinline__ uint64_t poseidon_permute_coop(uint64_t s, int l, uin
         if (full || l == 0) s = poseidon_sbox(s);
         s = poseidon_mds_coop_dpp(s, l, k);
     }
-    return gl_canon(s);
+    return CANON ? gl_canon(s) : s;
 #endif
 #pragma unroll 1
     for (int r = 0; r < 30; ++r) {
@@ -422,5 +428,5 @@ __device__ __forceinline__ uint64_t poseidon_permute_coop(uint64_t s, int l, uin
         if (full || l == 0) s = poseidon_sbox(s);
         s = poseidon_mds_coop(s, l, g);
     }
-    return gl_canon(s);
+    return CANON ? gl_canon(s) : s;
 }

@@ -37,18 +37,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_HASH_WAV
     if (leaf_len <= 4) {
         for (size_t e = 0; e < leaf_len; ++e) s[e] = src[e * estride];
     } else {
+        // only the last permutation of the leaf canonicalises: an inner one hands elements 8..11 to the next permutation's
+        // gl_add_nc and has elements 0..7 (all of them, or the first few at the tail) overwritten by the next absorb
         size_t e = 0;
-        for (; e + 8 <= leaf_len; e += 8) {
+        for (; e + 8 < leaf_len; e += 8) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) s[k] = src[(e + k) * estride];
-            poseidon_permute(s);
+            poseidon_permute<false>(s);
         }
-        if (e < leaf_len) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (e + k < leaf_len) s[k] = src[(e + k) * estride];
-            poseidon_permute(s);
-        }
+        for (int k = 0; k < 8; ++k)  // the last 1..8 elements
+            if (e + k < leaf_len) s[k] = src[(e + k) * estride];
+        poseidon_permute(s);
     }
     uint64_t* d = digests + 4 * j;
     d[0] = s[0];
@@ -76,8 +76,9 @@ __global__ __launch_bounds__(256) void k_hash_leaves_coop(const uint64_t* data, 
     } else {
         for (size_t e = 0; e < leaf_len; e += 8) {
             if (l < 8 && e + l < leaf_len) s = src[(e + l) * estride];
-            s = poseidon_permute_coop(s, l, g);
+            s = poseidon_permute_coop<false>(s, l, g);  // inner permutations stay non-canonical (as in k_hash_leaves)
         }
+        s = gl_canon(s);
     }
     if (l < 4 && t < n_leaves) digests[4 * j + l] = s;
 }
