@@ -93,11 +93,14 @@ struct Bus {
     // ... of one of several trees (leaf index, position in the row, word, tree): tree 0 is the very message row() builds, so a
     // one-layer FRI with TREE0 = 0 is already receivable from LeafSpongeAir (that pairing is not built).  LeafSpongeSetAir sends
     // them for every tree -> FriFoldAir, which receives the leaves of FRI layer l under tree TREE0 + l (vx_fri_queries_prove), or
-    // the verifier (vx_fri_fold_verify)
+    // the verifier (vx_fri_fold_verify).  FriCombineAir RECEIVES the opened commitment-tree rows one word per message under tree
+    // TREE0 + 0 main / 1 auxiliary / 2 quotient (TREE0 = 8 in its entry points); today the verifier sends them
+    // (vx_fri_combine_verify, vx_fri_combine_fold_verify)
     template <class T>
     VX_HD X row_of(const T& tree, const S& index, const S& position, const S& word) const { return denom(beta, index, position, word, tree, K<TAG_ROW>{}); }
     // an end of a query's fold chain (query index, value.a, value.b, end): end 0 = (index, ev_0) entering the chain, whoever
-    // computes the FRI combination (the verifier) -> FriFoldAir; end 1 = (index, ev_NL) leaving it, FriFoldAir -> whoever
+    // computes the FRI combination (FriCombineAir in vx_fri_combine_fold_prove, else the verifier) -> FriFoldAir, or FriCombineAir
+    // -> the verifier (vx_fri_combine_verify); end 1 = (index, ev_NL) leaving it, FriFoldAir -> whoever
     // evaluates the final polynomial (the verifier)
     template <class E>
     VX_HD X fri(const S& index, const S& va, const S& vb, const E& end) const { return denom(beta, index, va, vb, end, K<TAG_FRI>{}); }

@@ -173,6 +173,41 @@ int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
 int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* ev0,
                               const uint64_t* leaves, size_t n_queries);
 
+// ---- FRI-combine blob (written by vx_fri_combine_prove in vx_fri_combine_air.hip, read by vx_fri_combine_verify in vx_verify.hip):
+// magic, log2 of the inner proof's LDE, main / auxiliary / quotient columns, queries, length of the FriCombineAir proof that follows
+static const uint64_t VX_FCOMB_MAGIC = 0x31424d4f43465856ULL;  // "VXFCOMB1"
+static constexpr size_t VX_FCOMB_HDR = 7;
+// ---- FRI-combine-fold blob (vx_fri_combine_fold_prove / _verify): magic, log_lde, cm, ca, nq, fold layers, queries, lengths of
+// the FriCombineAir and the FriFoldAir proof that follow
+static const uint64_t VX_FCFLD_MAGIC = 0x31444c4643465856ULL;  // "VXFCFLD1"
+static constexpr size_t VX_FCFLD_HDR = 9;
+// What FriCombineAir's statement is made of besides the queries: the inner proof's shape, alpha, zeta and the openings at zeta
+// (open_local / open_next [cm + ca][2], open_quot [nq][2]).  The trace domain has 2^(log_lde - rate_bits) rows: zeta' = zeta w_n.
+struct FriCombineStmt {
+    int log_lde, rate_bits;
+    size_t cm, ca, nq;
+    const uint64_t *alpha, *zeta, *open_local, *open_next, *open_quot;
+};
+// ranges and canonical words of the claims (index [n], rows [n][cm + ca + nq], ev0 [n][2]); VX_ERR_ARG on `ctx`
+int32_t vx_fri_combine_check_claims(vx_ctx* ctx, const FriCombineStmt& st, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries);
+// alpha^c, zeta', y0, y1: computed once per proof by prover and verifier alike
+void vx_fri_combine_reduced(const FriCombineStmt& st, uint64_t alphac[2], uint64_t zetan[2], uint64_t y0[2], uint64_t y1[2]);
+// FriCombineAir's public inputs: with the claims digest hash_n_to_hash_no_pad(shape, alpha, zeta, openings, (index, rows, ev_0) of
+// every query), or with a digest the caller states (the group's statement digest)
+void vx_fri_combine_public(const FriCombineStmt& st, uint64_t tree0, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries, uint64_t pub[22]);
+void vx_fri_combine_public_digest(const FriCombineStmt& st, uint64_t tree0, const uint64_t digest[4], uint64_t pub[22]);
+// log_lde, rate_bits, cm, ca, nq, n_queries, alpha, zeta, the openings: the head of both digests
+void vx_fri_combine_statement_words(const FriCombineStmt& st, size_t n_queries, std::vector<uint64_t>& w);
+int32_t vx_fri_combine_trace_dev(vx_ctx* ctx, const FriCombineStmt& st, uint64_t tree0, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries, int log_n,
+                                 uint64_t* trace_d, uint64_t pub_out[22]);
+// combines every query natively on the host: VX_ERR_STATEMENT on `ctx`, naming the query, when a claimed ev_0 differs or x = zeta
+int32_t vx_fri_combine_check_dev(vx_ctx* ctx, const FriCombineStmt& st, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries);
+// the combination natively on the host -> ev0_out [n_queries][2]; VX_ERR_STATEMENT on `ctx` when x = zeta or zeta w_n
+int32_t vx_fri_combine_host(vx_ctx* ctx, const FriCombineStmt& st, const uint64_t* index, const uint64_t* rows, size_t n_queries, uint64_t* ev0_out);
+// the statement digest of vx_fri_combine_fold_prove: both tables' four digest words
+void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index,
+                                   const uint64_t* rows, const uint64_t* leaves, size_t n_queries, uint64_t digest[4]);
+
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {
     for (int j = 0; j < 8; ++j)

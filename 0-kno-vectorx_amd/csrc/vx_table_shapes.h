@@ -61,3 +61,8 @@ static inline int fri_queries_open_log_n(size_t n_queries, int log_lde, size_t n
     return ceil_log2(32 * n_queries * levels);
 }
 static inline int fri_queries_sponge_log_n(size_t n_queries, size_t n_layers) { return ceil_log2(32 * n_queries * n_layers * 4); }
+// FriCombineAir: cm + ca + nq absorb rows and log_lde bit rows per query, at least 2^5 rows
+static inline int fri_combine_log_n(size_t n_queries, int log_lde, size_t cm, size_t ca, size_t nq) {
+    const int l = ceil_log2(n_queries * (cm + ca + nq + (size_t)log_lde));
+    return l < 5 ? 5 : l;
+}

@@ -307,6 +307,11 @@ void v_shared_challenges_n(const uint64_t* const* pubs, const size_t* n_pubs, co
 struct FriClaims {
     int log_lde = 0;
     std::vector<uint64_t> betas, final_poly, index, ev0, leaves, ev_last;  // leaves: [query][layer][2 arity], the `within` slot filled
+    // ... and, for vx_stark_combine_claims, what the FRI combination reads: FriCombineAir's claims
+    bool want_combine = false;
+    size_t cm = 0, ca = 0, nq = 0;
+    uint64_t alpha[2] = {0, 0}, zeta[2] = {0, 0};
+    std::vector<uint64_t> openings, rows;  // openings: local [c][2], next [c][2], quotient [nq][2]; rows: [query][c + nq]
 };
 static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
                                  const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen);
@@ -508,6 +513,11 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
         fri->log_lde = LN;
         for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
         for (const Fx& f : fpoly) fri->final_poly.push_back(f.a), fri->final_poly.push_back(f.b);
+        if (fri->want_combine) {
+            fri->cm = cm, fri->ca = ca, fri->nq = nq, fri->alpha[0] = alpha.a, fri->alpha[1] = alpha.b, fri->zeta[0] = zeta.a, fri->zeta[1] = zeta.b;
+            for (const std::vector<Fx>* o : {&o_local, &o_next, &o_quot})
+                for (const Fx& v : *o) fri->openings.push_back(v.a), fri->openings.push_back(v.b);
+        }
     }
     for (size_t qi = 0; qi < n_queries; ++qi) {
         size_t x_index = ch.challenge() % N;
@@ -535,6 +545,11 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
         }
         Fx ev = alpha_c * (s0 - y0) * fx_inv(Fx{x, 0} - zeta) + (s1 - y1) * fx_inv(Fx{x, 0} - zeta_next);
         if (fri) fri->index.push_back(x_index), fri->ev0.push_back(ev.a), fri->ev0.push_back(ev.b);
+        if (fri && fri->want_combine) {
+            fri->rows.insert(fri->rows.end(), row_t, row_t + cm);
+            fri->rows.insert(fri->rows.end(), row_a, row_a + ca);
+            fri->rows.insert(fri->rows.end(), row_q, row_q + nq);
+        }
         int cur_log = LN;
         for (size_t l = 0; l < n_layers; ++l) {
             const int a = arities[l];
@@ -1121,6 +1136,134 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
     memcpy(ev0_out, fc.ev0.data(), 2 * nq * 8);
     if (ev_last_out) memcpy(ev_last_out, fc.ev_last.data(), 2 * nq * 8);
     memcpy(leaves_out, fc.leaves.data(), fc.leaves.size() * 8);
+    return VX_OK;
+}
+
+// FRI combine (the prover is vx_fri_combine_air.hip), the fourth aggregation verifier: the claims are what a STARK verifier holds
+// when it enters the query phase -- alpha, zeta, the openings at zeta and, per query, the index, the opened trace / auxiliary /
+// quotient row and ev_0.  FriCombineAir receives every row word, which the verifier sends, and sends every (index, ev_0, 0),
+// which the verifier receives:
+//     published total x rows = sum over the queries of  - sum over j < cm + ca + nq of 1 / D_row(tree 8 + t_j, index, position_j, w_j)
+//                                                        + 1 / D_fri(index, ev_0, 0).
+// NOTHING IS COMBINED per query: y0, y1, alpha^c and zeta' are computed once.
+static int32_t fc_stmt_check(const FriCombineStmt& st, const uint64_t* index, const uint64_t* rows, size_t n_queries, const char* what, char* err, size_t errlen) {
+    NEED(st.log_lde >= 5 && st.log_lde <= 32 && st.rate_bits >= 1 && st.rate_bits < st.log_lde, "%s: log_lde %d / rate_bits %d out of range", what, st.log_lde, st.rate_bits);
+    const size_t M = (size_t)1 << 20;
+    NEED(st.cm >= 1 && st.cm <= M && st.ca <= M && st.nq >= 1 && st.nq <= M, "%s: %zu / %zu / %zu columns out of range", what, st.cm, st.ca, st.nq);
+    NEED(n_queries >= 1 && n_queries <= M, "%s: %zu queries (1..2^20)", what, n_queries);
+    const size_t c = st.cm + st.ca, absn = c + st.nq;
+    for (int i = 0; i < 2; ++i) NEED(st.alpha[i] < glh::P && st.zeta[i] < glh::P, "%s: non-canonical alpha or zeta", what);
+    for (size_t i = 0; i < 2 * c; ++i) NEED(st.open_local[i] < glh::P && st.open_next[i] < glh::P, "%s: non-canonical opening word %zu", what, i);
+    for (size_t i = 0; i < 2 * st.nq; ++i) NEED(st.open_quot[i] < glh::P, "%s: non-canonical quotient opening word %zu", what, i);
+    for (size_t i = 0; i < n_queries; ++i) NEED(index[i] >> st.log_lde == 0, "%s: claim %zu names an index outside the LDE", what, i);
+    for (size_t i = 0; i < n_queries * absn; ++i) NEED(rows[i] < glh::P, "%s: claim %zu has a non-canonical row word", what, i / absn);
+    return VX_OK;
+}
+// the row words of one query as the verifier sends them: tree TREE0 + t, position within the tree's row
+static void fc_send_rows(const bus::Bus<X2<Fx>>& bus, BusMessages& m, const FriCombineStmt& st, uint64_t index, const uint64_t* row) {
+    const size_t c = st.cm + st.ca, absn = c + st.nq;
+    for (size_t j = 0; j < absn; ++j) {
+        const uint64_t t = j < st.cm ? 0 : j < c ? 1 : 2, pos = j < st.cm ? j : j < c ? j - st.cm : j - c;
+        m.send(bus.row_of(Fx{fca::TREE0 + t, 0}, Fx{index, 0}, Fx{pos, 0}, Fx{row[j], 0}));
+    }
+}
+int32_t vx_fri_combine_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2], const uint64_t zeta[2],
+                              const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0,
+                              size_t n_queries, char* err, size_t errlen) {
+    if (!cfg || !blob || !alpha || !zeta || !open_local || !open_next || !open_quot || !index || !rows || !ev0) return VX_ERR_ARG;
+    const FriCombineStmt st{log_lde, cfg->rate_bits, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot};
+    int32_t rc = fc_stmt_check(st, index, rows, n_queries, "fri combine", err, errlen);
+    if (rc != VX_OK) return rc;
+    for (size_t i = 0; i < n_queries; ++i) NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri combine: claim %zu has a non-canonical ev_0", i);
+    NEED(fri_combine_log_n(n_queries, log_lde, cm, ca, nq) <= 26, "fri combine: the request needs a table of more than 2^26 rows");
+    BusTable tab[1];
+    rc = read_blob(blob, len, VX_FCOMB_MAGIC, "fri-combine", {(uint64_t)log_lde, cm, ca, nq, n_queries}, tab, 1, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
+    uint64_t pub[fca::PUB];
+    vx_fri_combine_public(st, fca::TREE0, index, rows, ev0, n_queries, pub);
+    tab[0].air = VX_AIR_FRI_COMBINE, tab[0].want = pub, tab[0].n_want = fca::PUB;
+    const size_t absn = cm + ca + nq;
+    return verify_bus_group(cfg, tab, 1, "the combinations the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(n_queries * (absn + 1));
+                                for (size_t i = 0; i < n_queries; ++i) {
+                                    fc_send_rows(bus, m, st, index[i], rows + i * absn);
+                                    m.receive(bus.fri(Fx{index[i], 0}, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
+                                }
+                            });
+}
+
+// FRI combine + fold (the prover is vx_fri_combine_fold_prove): two tables on one bus, combine first.  TAG_FRI end 0 closes BETWEEN
+// the tables, so the verifier holds NO ev_0: it sends every row word and every leaf word and receives the exit of every chain:
+//     sum over the tables of total x rows = sum over the queries of  - the row words  - the leaf words  + 1 / D_fri(index, final_poly(x_NL), 1).
+// Every public input of both tables is rebuilt from the arguments; their digest words are one statement digest over all of them.
+int32_t vx_fri_combine_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2],
+                                   const uint64_t zeta[2], const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* betas, size_t n_layers,
+                                   const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* rows, const uint64_t* leaves, size_t n_queries, char* err,
+                                   size_t errlen) {
+    if (!cfg || !blob || !alpha || !zeta || !open_local || !open_next || !open_quot || !betas || !final_poly || !index || !rows || !leaves) return VX_ERR_ARG;
+    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri combine-fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    const FriCombineStmt st{log_lde, cfg->rate_bits, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot};
+    int32_t rc = fc_stmt_check(st, index, rows, n_queries, "fri combine-fold", err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri combine-fold: log_lde %d / %zu layers out of range", log_lde, n_layers);
+    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri combine-fold: a final polynomial of %zu coefficients", final_len);
+    NEED(fri_combine_log_n(n_queries, log_lde, cm, ca, nq) <= 26 && fri_fold_log_n(n_queries, log_lde, n_layers) <= 26, "fri combine-fold: the request needs a table of more than 2^26 rows");
+    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri combine-fold: non-canonical beta word %zu", i);
+    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri combine-fold: non-canonical final-polynomial word %zu", i);
+    for (size_t i = 0; i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "fri combine-fold: claim %zu has a non-canonical leaf word", i / (32 * n_layers));
+    BusTable tab[2];
+    rc = read_blob(blob, len, VX_FCFLD_MAGIC, "fri-combine-fold", {(uint64_t)log_lde, cm, ca, nq, n_layers, n_queries}, tab, 2, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, 2), "a proof is too short to hold a trace cap");
+    uint64_t stmt[4], cpub[fca::PUB], fpub[ffa::PUB];
+    vx_fri_combine_fold_statement(st, betas, n_layers, final_poly, final_len, index, rows, leaves, n_queries, stmt);
+    vx_fri_combine_public_digest(st, fca::TREE0, stmt, cpub);
+    vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, fpub);
+    tab[0].air = VX_AIR_FRI_COMBINE, tab[0].want = cpub, tab[0].n_want = fca::PUB;
+    tab[1].air = VX_AIR_FRI_FOLD, tab[1].want = fpub, tab[1].n_want = ffa::PUB;
+    const size_t absn = cm + ca + nq;
+    return verify_bus_group(cfg, tab, 2, "the query-phase arithmetic the tables prove is not the claimed one (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(n_queries * (absn + 32 * n_layers + 1));
+                                const uint64_t w = glh::root(log_lde);
+                                for (size_t i = 0; i < n_queries; ++i) {
+                                    fc_send_rows(bus, m, st, index[i], rows + i * absn);
+                                    for (size_t l = 0; l < n_layers; ++l)
+                                        for (size_t j = 0; j < 32; ++j)
+                                            m.send(bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0}));
+                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
+                                    Fx fp{0, 0};
+                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+                                    m.receive(bus.fri(Fx{index[i], 0}, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                }
+                            });
+}
+
+// The combination side of a vx_stark_prove proof as FriCombineAir's claims (prover-side: the proof is VERIFIED on the way, by the
+// verifier's own code with a sink in its query loop): the shape, alpha, zeta, the openings at zeta (local [c][2], next [c][2],
+// quotient [nq][2], back to back) and per query the index, the c + nq opened row words and ev_0.
+int32_t vx_stark_combine_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int* log_lde, size_t* cm, size_t* ca, size_t* nq, size_t* n_queries, uint64_t alpha_out[2],
+                                uint64_t zeta_out[2], uint64_t* openings_out, size_t openings_cap, uint64_t* index_out, uint64_t* ev0_out, size_t query_cap, uint64_t* rows_out,
+                                size_t rows_cap, char* err, size_t errlen) {
+    if (!cfg || !proof || !log_lde || !cm || !ca || !nq || !n_queries || !alpha_out || !zeta_out || !openings_out || !index_out || !ev0_out || !rows_out) return VX_ERR_ARG;
+    FriClaims fc;
+    fc.want_combine = true;
+    const int32_t rc = stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, &fc, err, errlen);
+    if (rc != VX_OK) return rc;
+    const size_t n = fc.index.size();
+    *log_lde = fc.log_lde, *cm = fc.cm, *ca = fc.ca, *nq = fc.nq, *n_queries = n;
+    if (openings_cap < fc.openings.size() || query_cap < n || rows_cap < fc.rows.size()) {
+        if (err && errlen)
+            snprintf(err, errlen, "combine claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", openings_cap, query_cap, rows_cap, fc.openings.size(), n, fc.rows.size());
+        return VX_ERR_BUFSZ;
+    }
+    memcpy(alpha_out, fc.alpha, 16), memcpy(zeta_out, fc.zeta, 16);
+    memcpy(openings_out, fc.openings.data(), fc.openings.size() * 8);
+    memcpy(index_out, fc.index.data(), n * 8);
+    memcpy(ev0_out, fc.ev0.data(), 2 * n * 8);
+    memcpy(rows_out, fc.rows.data(), fc.rows.size() * 8);
     return VX_OK;
 }
 

@@ -33,6 +33,8 @@ SYMBOLS = [
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
     "vx_fri_fold_air_trace", "vx_fri_fold_proof_bound", "vx_fri_fold_prove", "vx_fri_fold_verify", "vx_stark_fri_claims",
     "vx_merkle_open_set_air_trace", "vx_leaf_sponge_set_air_trace", "vx_fri_queries_proof_bound", "vx_fri_queries_prove", "vx_fri_queries_verify",
+    "vx_fri_combine_air_trace", "vx_fri_combine_proof_bound", "vx_fri_combine_prove", "vx_fri_combine_verify", "vx_stark_combine_claims",
+    "vx_fri_combine_fold_proof_bound", "vx_fri_combine_fold_prove", "vx_fri_combine_fold_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -49,6 +51,7 @@ VX_AIR_LEAF_SPONGE, VX_LEAF_SPONGE_AIR_COLS, VX_LEAF_SPONGE_AIR_AUX_COLS = 17, 6
 VX_AIR_FRI_FOLD, VX_FRI_FOLD_AIR_COLS, VX_FRI_FOLD_AIR_AUX_COLS = 18, 120, 36
 VX_AIR_MERKLE_OPEN_SET, VX_MERKLE_OPEN_SET_AIR_COLS, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 19, 72, 6
 VX_AIR_LEAF_SPONGE_SET, VX_LEAF_SPONGE_SET_AIR_COLS, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 20, 67, 12
+VX_AIR_FRI_COMBINE, VX_FRI_COMBINE_AIR_COLS, VX_FRI_COMBINE_AIR_AUX_COLS = 21, 28, 4
 
 
 class JustificationStruct(C.Structure):
@@ -187,6 +190,15 @@ def load_library():
         "vx_fri_queries_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, C.POINTER(sz)],
         "vx_fri_queries_prove": [vp, C.POINTER(StarkConfig), C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_fri_queries_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, vp, sz, vp, C.c_int, vp, vp, sz, C.c_char_p, sz],
+        "vx_fri_combine_air_trace": [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_fri_combine_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, sz, sz, C.POINTER(sz)],
+        "vx_fri_combine_prove": [vp, C.POINTER(StarkConfig), C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_fri_combine_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_char_p, sz],
+        "vx_stark_combine_claims": [C.POINTER(StarkConfig), vp, sz, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp, vp, vp, sz, vp, vp, sz, vp, sz,
+                                    C.c_char_p, sz],
+        "vx_fri_combine_fold_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, sz, sz, sz, C.POINTER(sz)],
+        "vx_fri_combine_fold_prove": [vp, C.POINTER(StarkConfig), C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_fri_combine_fold_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, C.c_char_p, sz],
         "vx_stark_fri_claims": [C.POINTER(StarkConfig), vp, sz, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
@@ -480,6 +492,80 @@ def stark_fri_claims(proof, cfg=None):
                 ev_last=ev_last[: 2 * Q].reshape(Q, 2), leaves=leaves[: Q * NL * 32].reshape(Q, NL, 32))
 
 
+FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
+FCFLD_MAGIC, FCFLD_HDR = 0x31444C4643465856, 9  # "VXFCFLD1": magic, log2 of the inner LDE, cm, ca, nq, fold layers, queries, two proof lengths; then the proofs
+
+
+def _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0=None):
+    """the claims of FriCombineAir as contiguous arrays: alpha / zeta [2], open_local / open_next [cm + ca][2], open_quot [nq][2],
+    index [n], rows [n][cm + ca + nq], ev0 [n][2] (None: not part of the statement)"""
+    al = np.ascontiguousarray(alpha, dtype=np.uint64).reshape(-1)
+    ze = np.ascontiguousarray(zeta, dtype=np.uint64).reshape(-1)
+    ol = np.ascontiguousarray(open_local, dtype=np.uint64).reshape(-1)
+    on = np.ascontiguousarray(open_next, dtype=np.uint64).reshape(-1)
+    oq = np.ascontiguousarray(open_quot, dtype=np.uint64).reshape(-1)
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+    rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+    ev = None if ev0 is None else np.ascontiguousarray(ev0, dtype=np.uint64).reshape(-1)
+    c = cm + ca
+    if al.size != 2 or ze.size != 2 or ol.size != 2 * c or on.size != 2 * c or oq.size != 2 * nq or rw.size != idx.size * (c + nq) or (ev is not None and ev.size != 2 * idx.size):
+        raise ValueError("alpha / zeta [2], openings [cm + ca][2] / [nq][2], one row [cm + ca + nq] and one ev_0 [2] for every query")
+    return al, ze, ol, on, oq, idx, rw, ev
+
+
+def fri_combine_verify(blob, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0, cfg=None):
+    """Host-side check of a vx_fri_combine_prove blob against the verifier's own claims: the inner proof's shape, alpha, zeta, the
+    openings at zeta and per query (index, rows [cm + ca + nq], ev0 [2]) in order.  Combines nothing per query; raises VxError."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    al, ze, ol, on, oq, idx, rw, ev = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0)
+    err = C.create_string_buffer(256)
+    rc = L.vx_fri_combine_verify(C.byref(cfg), _ptr(b), b.size, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(idx), _ptr(rw), _ptr(ev), idx.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+def fri_combine_fold_verify(blob, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, betas, final_poly, index, rows, leaves, cfg=None):
+    """Host-side check of a vx_fri_combine_fold_prove blob: the combine claims WITHOUT ev_0 and the fold claims (betas [NL][2], the
+    final polynomial [len][2], leaves [n][NL][32]).  Combines and folds nothing; raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    al, ze, ol, on, oq, idx, rw, _ = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows)
+    be, fp, _, _, lv = _fri_claims(betas, final_poly, index, np.zeros(2 * idx.size, dtype=np.uint64), leaves)
+    err = C.create_string_buffer(256)
+    rc = L.vx_fri_combine_fold_verify(C.byref(cfg), _ptr(b), b.size, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(be), be.shape[0], _ptr(fp), fp.shape[0],
+                                      _ptr(idx), _ptr(rw), _ptr(lv), idx.size, err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+def stark_combine_claims(proof, cfg=None):
+    """The combination side of a vx_stark_prove proof (verified on the way) as FriCombineAir's claims -> dict(log_lde, cm, ca, nq,
+    alpha [2], zeta [2], open_local [c][2], open_next [c][2], open_quot [nq][2], index [n], ev0 [n][2], rows [n][c + nq])."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    log_lde, cm, ca, nq, n = C.c_int(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    alpha, zeta = np.zeros(2, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    bufs = [np.zeros(1, dtype=np.uint64) for _ in range(4)]  # openings, index, ev0, rows: sized by a first call
+    err = C.create_string_buffer(256)
+    for _ in range(2):
+        op, index, ev0, rows = bufs
+        rc = L.vx_stark_combine_claims(C.byref(cfg), _ptr(pr), pr.size, C.byref(log_lde), C.byref(cm), C.byref(ca), C.byref(nq), C.byref(n), _ptr(alpha), _ptr(zeta), _ptr(op), op.size,
+                                       _ptr(index), _ptr(ev0), index.size, _ptr(rows), rows.size, err, 256)
+        if rc != -4:
+            break
+        c, absn = cm.value + ca.value, cm.value + ca.value + nq.value
+        bufs = [np.zeros(4 * c + 2 * nq.value, dtype=np.uint64), np.zeros(n.value, dtype=np.uint64), np.zeros(2 * n.value, dtype=np.uint64), np.zeros(n.value * absn, dtype=np.uint64)]
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+    c, Q = cm.value + ca.value, n.value
+    return dict(log_lde=log_lde.value, cm=cm.value, ca=ca.value, nq=nq.value, alpha=alpha, zeta=zeta, open_local=op[: 2 * c].reshape(c, 2), open_next=op[2 * c: 4 * c].reshape(c, 2),
+                open_quot=op[4 * c: 4 * c + 2 * nq.value].reshape(-1, 2), index=index[:Q], ev0=ev0[: 2 * Q].reshape(Q, 2), rows=rows[: Q * (c + nq.value)].reshape(Q, c + nq.value))
+
+
 ROT_HDR = 28  # words before the first proof in a rotate blob
 
 
@@ -719,6 +805,37 @@ class Context:
                                 "fri fold: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries)",
                                 lambda c, o, need: self.L.vx_fri_fold_prove(self.h, c, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size,
                                                                             _ptr(o), o.size, need))
+
+    def fri_combine_air_trace(self, log_lde, rate_bits, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0, log_n, tree0=0, out=None):
+        """The witness of FriCombineAir for the claims (index[i], rows[i][cm + ca + nq], ev0[i][2]) -> (Buffer [28][2^log_n], the 22
+        public inputs)."""
+        al, ze, ol, on, oq, idx, rw, ev = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0)
+        out = out or self.alloc(VX_FRI_COMBINE_AIR_COLS << log_n)
+        pub = np.zeros(22, dtype=np.uint64)
+        self._ck(self.L.vx_fri_combine_air_trace(self.h, log_lde, rate_bits, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), tree0, _ptr(idx), _ptr(rw), _ptr(ev), idx.size,
+                                                 log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def fri_combine_prove(self, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0, cfg=None, out=None):
+        """Proves the FRI combination of the claims in one FriCombineAir table -> blob words (lib.fri_combine_verify checks it).  Every
+        query is combined natively first: VxError(VX_ERR_STATEMENT) names the query whose ev_0 differs.  out: a caller's uint64
+        buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        al, ze, ol, on, oq, idx, rw, ev = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_fri_combine_proof_bound(c, log_lde, cm, ca, nq, idx.size, need),
+                                "fri combine: bad shape or configuration (log_lde 5..32, cm, nq >= 1, 1..2^20 queries, a table of at most 2^26 rows)",
+                                lambda c, o, need: self.L.vx_fri_combine_prove(self.h, c, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(idx), _ptr(rw), _ptr(ev),
+                                                                               idx.size, _ptr(o), o.size, need))
+
+    def fri_combine_fold_prove(self, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, betas, final_poly, index, rows, leaves, cfg=None, out=None):
+        """Proves the FRI combination and the fold chains of the queries in two tables on one bus -> blob words
+        (lib.fri_combine_fold_verify checks it).  ev_0 is computed here and closes between the tables.  The statement is checked
+        natively first: VxError(VX_ERR_STATEMENT) names query and stage."""
+        al, ze, ol, on, oq, idx, rw, _ = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows)
+        be, fp, _, _, lv = _fri_claims(betas, final_poly, index, np.zeros(2 * idx.size, dtype=np.uint64), leaves)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_fri_combine_fold_proof_bound(c, log_lde, cm, ca, nq, be.shape[0], idx.size, need),
+                                "fri combine-fold: bad shape or configuration (arity_bits 4, 1..8 layers, cm, nq >= 1, 1..2^20 queries, tables of at most 2^26 rows)",
+                                lambda c, o, need: self.L.vx_fri_combine_fold_prove(self.h, c, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(be), be.shape[0],
+                                                                                    _ptr(fp), fp.shape[0], _ptr(idx), _ptr(rw), _ptr(lv), idx.size, _ptr(o), o.size, need))
 
     def merkle_open_set_air_trace(self, trees, tree_of, leaf_idx, log_n, out=None):
         """The witness of MerkleOpenSetAir: opening i is leaf leaf_idx[i] of trees[tree_of[i]] -> (Buffer [72][2^log_n], the 4

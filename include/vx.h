@@ -167,7 +167,8 @@ typedef struct vx_stark_config {
  * 16 (VX_AIR_MERKLE_OPEN) proves a batch of Poseidon Merkle openings: the first aggregation table, see vx_merkle_openings_prove.
  * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove.
  * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove.
- * 19 (VX_AIR_MERKLE_OPEN_SET) / 20 (VX_AIR_LEAF_SPONGE_SET) are 16 / 17 for several trees in one table: see vx_fri_queries_prove. */
+ * 19 (VX_AIR_MERKLE_OPEN_SET) / 20 (VX_AIR_LEAF_SPONGE_SET) are 16 / 17 for several trees in one table: see vx_fri_queries_prove.
+ * 21 (VX_AIR_FRI_COMBINE) proves the FRI combination of every query, the value the fold chain starts from: see vx_fri_combine_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -234,7 +235,7 @@ int32_t vx_poseidon_air_trace(vx_ctx* ctx, const vx_buf* states, size_t n_perm, 
  * digest hash_n_to_hash_no_pad((index, d0, d1, d2, d3) of every opening, in order), which makes the lookup challenges depend on
  * the claims.  The opened leaf ROWS are hashed in-proof by LeafSpongeAir (below: vx_merkle_rows_prove, whose claims are rows, not
  * digests).  This table has one tree; MerkleOpenSetAir (below: vx_fri_queries_prove) takes several.  STILL OUTSIDE (the next
- * tables): the evaluation at zeta and the transcript stay on the host (the FRI fold is FriFoldAir, below).
+ * tables): the evaluation at zeta and the transcript stay on the host (the FRI fold is FriFoldAir, the FRI combination FriCombineAir, below).
  * vx_merkle_open_air_trace: the witness on its own (test surface) -- leaf_idx: n_idx >= 1 leaf indices (host; duplicates
  *   allowed); trace_out: [VX_MERKLE_OPEN_AIR_COLS][2^log_n] with 2^log_n >= 32 n_idx D; blocks behind the paths are idle.
  * vx_merkle_openings_prove: trace + proof at the smallest such log_n (>= 5) under lookup challenges that are the shared-challenge
@@ -320,8 +321,9 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
  *   ev_NL the verifier accepted (ev_last_out may be NULL), and the FULL leaves of every layer -- the proof omits the slot
  *   `within`, which is filled with the value the chain enters the layer with.  final_cap / leaves_cap are in words, query_cap in
  *   queries; VX_ERR_BUFSZ (sizes set) when one is too small.
- * STILL OUTSIDE here: the leaves' Merkle side (vx_fri_queries_prove, below, puts it on the same bus), the FRI combination /
- * evaluation at zeta, the transcript, and the final-polynomial evaluation, which stays the verifier's single Horner per query. */
+ * STILL OUTSIDE here: the leaves' Merkle side (vx_fri_queries_prove, below, puts it on the same bus), the FRI combination
+ * (FriCombineAir, below: vx_fri_combine_fold_prove closes ev_0 between the two tables), the evaluation at zeta, the transcript, and
+ * the final-polynomial evaluation, which stays the verifier's single Horner per query. */
 enum { VX_AIR_FRI_FOLD = 18, VX_FRI_FOLD_AIR_COLS = 120, VX_FRI_FOLD_AIR_AUX_COLS = 36 };
 int32_t vx_fri_fold_air_trace(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, uint64_t tree0, const uint64_t* index, const uint64_t* ev0,
                               const uint64_t* leaves, size_t n_queries, int log_n, vx_buf* trace_out, uint64_t public_out[24]);
@@ -361,8 +363,8 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
  *   (index, ev0) per query -- NO leaves; walks no path, hashes no leaf, folds nothing.  Rebuilds every public input of all three
  *   tables from its arguments, sends (index, ev_0) of every query, receives (index, final_poly(x_NL)) and, per layer, the two
  *   halves of (root of caps[l], depth log_lde - 4 (l + 1)); accepts iff all three tables verify and the bus balances.
- * STILL OUTSIDE: the commitment trees (a per-tree leaf length), ev_0 from a FRI-combination table, binding to the layer trees
- * vx_stark_prove builds itself. */
+ * STILL OUTSIDE: the commitment trees' Merkle side (a per-tree leaf length), binding to the layer trees vx_stark_prove builds
+ * itself; ev_0 comes from FriCombineAir (below), not yet on this three-table bus. */
 enum { VX_AIR_MERKLE_OPEN_SET = 19, VX_MERKLE_OPEN_SET_AIR_COLS = 72, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 6 };
 enum { VX_AIR_LEAF_SPONGE_SET = 20, VX_LEAF_SPONGE_SET_AIR_COLS = 67, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 12 };
 int32_t vx_merkle_open_set_air_trace(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
@@ -374,6 +376,68 @@ int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
                              const vx_tree* const* trees, const vx_buf* const* evals, const uint64_t* index, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
                               size_t final_len, const uint64_t* caps, int cap_height, const uint64_t* index, const uint64_t* ev0, size_t n_queries, char* err, size_t errlen);
+/* ---- FriCombineAir: the FRI combination of every query of one inner proof in one STARK table (AIR id VX_AIR_FRI_COMBINE; compiled:
+ * csrc/air_fri_combine.cuh) -- what a STARK verifier computes per query before the fold loop (plonky2 v0.2.0 fri/verifier.rs
+ * fri_combine_initial; vx_stark_verify does the same on the host), the fourth table of proof aggregation.
+ * The inner proof: an LDE of 2^log_lde points over a trace of 2^(log_lde - rate_bits) rows, cm main, ca auxiliary (may be 0) and
+ * nq quotient columns (c = cm + ca), the challenge alpha[2], the point zeta[2], and the openings open_local[c][2], open_next[c][2],
+ * open_quot[nq][2].  A CLAIM is one query: index (< 2^log_lde), rows[c + nq] (the opened main, auxiliary and quotient row, back to
+ * back) and ev0[2].  PROVEN per claim, with y0 = sum alpha^j local_j + sum alpha^(c+j) quot_j, y1 = sum alpha^j next_j:
+ *   s1 = sum_(j<c) alpha^j w_j,  s0 = s1 + sum_(j<nq) alpha^(c+j) q_j,  x = 7 w^bitrev(index, log_lde),
+ *   ev0 = alpha^c (s0 - y0) / (x - zeta) + (s1 - y1) / (x - zeta w_n).
+ * One word per absorb row, c + nq absorb rows and log_lde bit rows per query; no positional shape, so any number of queries of any
+ * shape fits the one AIR id at any log_n >= 5 (the hash-chain table, 2^21 LDE: 1046 rows per query, 84 queries in 2^17 rows).
+ * Public inputs (22): rows per query, cm, ca, nq, TREE0, w, alpha, alpha^c, zeta, zeta w_n, y0, y1 and the claims digest
+ * hash_n_to_hash_no_pad(log_lde, rate_bits, cm, ca, nq, n_queries, alpha, zeta, the openings, (index, rows, ev0) of every query).
+ * Bus: every absorb row receives its word as a row message (index, position in its tree's row, word, tree = TREE0 + 0 main / 1
+ * auxiliary / 2 quotient) -- what a leaf sponge over the commitment trees sends; the verifier of vx_fri_combine_verify sends them
+ * itself -- and the query's last row sends (index, ev0, 0), the entry FriFoldAir receives.
+ * vx_fri_combine_air_trace: the witness on its own (test surface; host claims, nothing is checked beyond ranges) -- trace_out:
+ *   [VX_FRI_COMBINE_AIR_COLS][2^log_n] with 2^log_n >= n_queries (c + nq + log_lde); rows behind the queries are idle.
+ * vx_fri_combine_prove: combines every query natively on the host first and returns VX_ERR_STATEMENT, naming the query, when the
+ *   claimed ev0 differs or x = zeta; then trace + proof at the smallest log_n (>= 5) with TREE0 = 8 (behind FriFoldAir's layer
+ *   ids), rate_bits from the configuration, under lookup challenges that are the shared-challenge transcript of this one table.
+ *   Blob: the magic "VXFCOMB1", log_lde, cm, ca, nq, n_queries, the proof's length; then the table proof.  VX_ERR_BUFSZ (with
+ *   *blob_len set) when the buffer is too small; VX_ERR_ARG for an index outside the LDE or a table of more than 2^26 rows.
+ * vx_fri_combine_verify (host only, COMBINES NOTHING per query): computes y0, y1, alpha^c and zeta w_n once, rebuilds every public
+ *   input, recomputes the challenges, verifies the table and accepts iff published total x 2^log_n = sum over the claims of
+ *   - 1/D_row over every row word + 1/D(index, ev0, 0).
+ * vx_stark_combine_claims (host only, prover-side): replays a vx_stark_prove proof (it is verified on the way) and hands out the
+ *   combination's claims: the shape, alpha, zeta, openings_out (local, next, quotient back to back: 4 c + 2 nq words) and per query
+ *   the index, ev0 and the c + nq row words.  openings_cap / rows_cap are in words, query_cap in queries; VX_ERR_BUFSZ (sizes
+ *   set) when one is too small.
+ * vx_fri_combine_fold_prove / _verify: FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0, unchanged) as two parties of ONE bus,
+ *   combine first: (index, ev0, 0) closes BETWEEN the tables, so the verifier is handed NO ev0.  Its arguments: the shape, alpha,
+ *   zeta, the openings, betas, the final polynomial and per query the index, rows and leaves[n_layers][32].  Both tables' digest
+ *   words are one statement digest over all of them.  Accepts iff both tables verify and sum of total x 2^log_n = sum over the
+ *   queries of - the row words - the leaf words + 1/D(index, final_poly(x_NL), 1).  The prover runs the native combination and
+ *   fold checks first (VX_ERR_STATEMENT names query and stage).  Blob: "VXFCFLD1", log_lde, cm, ca, nq, n_layers, n_queries, two
+ *   lengths, two proofs.
+ * STILL OUTSIDE: the Merkle side of the commitment trees (a per-tree leaf length), binding to the layer trees vx_stark_prove
+ * builds itself, the constraint identity at zeta and the transcript. */
+enum { VX_AIR_FRI_COMBINE = 21, VX_FRI_COMBINE_AIR_COLS = 28, VX_FRI_COMBINE_AIR_AUX_COLS = 4 };
+int32_t vx_fri_combine_air_trace(vx_ctx* ctx, int log_lde, int rate_bits, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2], const uint64_t zeta[2], const uint64_t* open_local,
+                                 const uint64_t* open_next, const uint64_t* open_quot, uint64_t tree0, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries,
+                                 int log_n, vx_buf* trace_out, uint64_t public_out[22]);
+int32_t vx_fri_combine_proof_bound(const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, size_t n_queries, size_t* n_words);
+int32_t vx_fri_combine_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2], const uint64_t zeta[2],
+                             const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0,
+                             size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_fri_combine_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2],
+                              const uint64_t zeta[2], const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* index, const uint64_t* rows,
+                              const uint64_t* ev0, size_t n_queries, char* err, size_t errlen);
+int32_t vx_stark_combine_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int* log_lde, size_t* cm, size_t* ca, size_t* nq, size_t* n_queries,
+                                uint64_t alpha_out[2], uint64_t zeta_out[2], uint64_t* openings_out, size_t openings_cap, uint64_t* index_out, uint64_t* ev0_out, size_t query_cap,
+                                uint64_t* rows_out, size_t rows_cap, char* err, size_t errlen);
+int32_t vx_fri_combine_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, size_t n_layers, size_t n_queries, size_t* n_words);
+int32_t vx_fri_combine_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2], const uint64_t zeta[2],
+                                  const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
+                                  size_t final_len, const uint64_t* index, const uint64_t* rows, const uint64_t* leaves, size_t n_queries, uint64_t* blob_out, size_t blob_cap,
+                                  size_t* blob_len);
+int32_t vx_fri_combine_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2],
+                                   const uint64_t zeta[2], const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* betas, size_t n_layers,
+                                   const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* rows, const uint64_t* leaves, size_t n_queries, char* err,
+                                   size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */
