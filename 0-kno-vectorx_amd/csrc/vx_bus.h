@@ -1,61 +1,26 @@
-// Host-side plumbing shared by the circuit provers (vx_header_range_prove in vx_header_range.hip, vx_rotate_prove in
-// vx_rotate.hip), implemented in vx_bus.hip: the tables of one statement
-// sit on ONE logUp bus and must use the same lookup challenges, drawn after every trace is committed.  Each table is proven
-// from its own host thread on its own context; the provers stop after their trace caps (vx_chal_hook) and MEET: every one
-// deposits its public inputs + cap, waits for all the others and derives the challenges from the transcript of all
-// (public inputs, cap) pairs in table order.  The aggregation provers (vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
-// vx_fri_fold_air.hip, vx_fri_queries.hip) use the same runner; what only they share -- the hook of a table alone on its bus, the blob writer, the
-// blob formats and the public inputs of their AIRs, which the verifier (vx_verify.hip) rebuilds with the same functions -- is
-// declared here as well.
+// Host-side plumbing shared by every prover of "several tables on one logUp bus", implemented in vx_bus.hip: the circuit provers
+// (vx_header_range_prove in vx_header_range.hip, vx_rotate_prove in vx_rotate.hip) and the aggregation provers (vx_merkle_open_air.hip,
+// vx_leaf_sponge_air.hip, vx_fri_fold_air.hip, vx_fri_combine_air.hip, vx_fri_queries.hip).  The tables of one statement must use
+// the same lookup challenges, drawn after every trace is committed: the rendezvous and the bookkeeping of such a group are
+// bus_meet.h (host-pure); TableGroup below is the group on the device -- a prover says which tables there are (TableSpec), which one
+// runs on the caller's context and thread, and in which order failures are reported.  What only the aggregation provers share --
+// the hook of a table alone on its bus, the blob writer, the blob formats and the public inputs of their AIRs, which the verifier
+// (vx_verify.hip) rebuilds with the same functions -- is declared here as well.
 #pragma once
-#include <condition_variable>
+#include <array>
 #include <functional>
 #include <initializer_list>
-#include <mutex>
-#include <thread>
 #include <vector>
 
+#include "bus_meet.h"
 #include "vx_internal.h"
 
-// A statement proven by several processes (one per GPU, vx_header_range_prove_ex with n_shards > 1): `local[t]` says which
-// of the n_parties tables are proven here; once every LOCAL table has arrived -- or failed: a failed table arrives as a
-// failure marker, so that the other shards are not left waiting -- one thread calls `xch` with an array of n_parties slots
-// (only the local ones filled) and gets the union back.
-struct BusMeet {
-    static constexpr int MAX = 72, MAX_PUB = 32;
-    std::mutex m;
-    std::condition_variable cv;
-    int n_parties = 0, arrived = 0;
-    bool failed = false, done = false;
-    std::vector<uint64_t> pub[MAX], cap[MAX];
-    bool local[MAX], deposited[MAX], local_failed[MAX];
-    size_t capw = 64;  // words of a trace cap (4 << cap_height); set by the caller for a sharded proof, by the first arrival otherwise
-    const vx_hr_exchange* xch = nullptr;
-    BusMeet() {
-        for (int t = 0; t < MAX; ++t) local[t] = true, deposited[t] = local_failed[t] = false;
-    }
-    int n_local() const {
-        int k = 0;
-        for (int t = 0; t < n_parties; ++t) k += local[t] ? 1 : 0;
-        return k;
-    }
-    static int32_t meet(BusMeet* r, int who, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cap_words, uint64_t* chal, size_t n_chal);
-    void fail(int who = -1);  // who >= 0: the table whose prover gave up (counts as arrived when it had not deposited yet)
-    void finish_locked(size_t cap_words);  // all local tables are in: exchange with the other shards (if any), release everybody
-};
-struct BusParty {
-    BusMeet* rv;
-    int who;
-};
-int32_t vx_bus_hook(void* party, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal);
 // the hook of a table that is alone on its bus (the other party is the verifier): the lookup challenges are the shared-challenge
 // transcript of this one table's (public inputs, trace cap); `party` is unused
 int32_t vx_one_table_hook(void* party, const uint64_t* pub, size_t n_pub, const uint64_t* cap, size_t cw, uint64_t* chal, size_t n_chal);
-// one table of the statement, proven on its own context (all but the caller's own table from a host thread of their own)
+// one table's context and proof
 struct TableJob {
     vx_ctx* c = nullptr;
-    std::thread th;
-    int32_t rc = VX_OK;
     std::vector<uint64_t> proof;
     size_t len = 0;
 };
@@ -65,46 +30,61 @@ struct TableJob {
 using TableGen = std::function<int32_t(vx_ctx* c, vx_buf* trace, uint64_t* pub)>;
 int32_t run_table(vx_ctx* c, TableJob& j, int air_id, int log_n, size_t n_cols, size_t n_pub, const vx_stark_config* cfg, const vx_chal_hook* hook, int consume_trace,
                   const TableGen& gen);
-// the bound -> size -> prove part alone, for a table whose trace exists before its prover starts (rotate's epoch-end table)
-int32_t prove_table(vx_ctx* c, TableJob& j, int air_id, int log_n, const vx_stark_config* cfg, const vx_chal_hook* hook, int consume_trace, vx_buf* trace, const uint64_t* pub,
-                    size_t n_pub);
-// Runs j.rc = fn(j.c, j) on a host thread of its own; a table that fails tells the rendezvous (rv.fail(who)) so that the other
-// provers are not left waiting at their hooks -- also when the thread cannot be created, which returns false.  `j`, `rv` and
-// whatever `fn` refers to must outlive the join: declare a TableJoin after them.
-bool start_table(TableJob& j, BusMeet& rv, int who, std::function<int32_t(vx_ctx*, TableJob&)> fn);
-// joins the threads of its jobs, at the latest when it goes out of scope (every exit path waits for the threads)
-struct TableJoin {
-    std::vector<TableJob*> jobs;
-    void join() {
-        for (TableJob* j : jobs)
-            if (j->th.joinable()) j->th.join();
-    }
-    ~TableJoin() { join(); }
+// A table of a group, described once.  Without a `gen` the trace and the public inputs exist before the group proves (rotate's
+// epoch-end table): `trace` and `pub` are set by the time TableGroup::prove is called.
+struct TableSpec {
+    const char* name;  // for messages
+    int air_id, log_n;
+    size_t n_cols, n_pub;
+    int consume_trace;
+    TableGen gen;
+    vx_buf* trace = nullptr;
+    const uint64_t* pub = nullptr;
 };
-// out[0 .. n): the chain of side contexts behind `ctx` (every table is proven on a context of its own); fails with `msg`
-int32_t side_contexts(vx_ctx* ctx, size_t n, vx_ctx** out, const char* msg);
-// An aggregation blob (the three formats below): magic, the request words, one length per proof, the proofs.  Sets *blob_len and
+// AIR id and rows of a table: what its proof bound depends on
+struct TableShape {
+    int air_id, log_n;
+};
+// *n_words = hdr_words + the vx_stark_proof_bound of every table
+int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, std::initializer_list<TableShape> tables, size_t* n_words);
+// The tables of one statement on the device, in table order.  prove(): the table `here` (-1: none) is proven on the caller's
+// context and thread, every other local table on a host thread of its own and on the next of the chain of side contexts behind
+// `ctx`, in table order (every table has a context of its own: own stream, scratch, pool); they meet at their challenge hooks.
+// Returns VX_OK when every local proof exists in job[]; otherwise the failure of the first table in `order` (default: `here`,
+// then the rest in table order) that failed on its own -- not one released by another's failure -- as "<what>: <its message>" on
+// `ctx`.  Leaving the group earlier, by any path, fails its local tables at the rendezvous (the other shards of a sharded proof
+// are not left waiting).  Whatever the gens refer to must be declared before the group.
+struct TableGroup {
+    vx_ctx* ctx;
+    const vx_stark_config* cfg;
+    const char* what;
+    TableSpec spec[BusGroup::MAX];
+    TableJob job[BusGroup::MAX];
+    vx_chal_hook hook[BusGroup::MAX];
+    BusGroup g;
+    TableGroup(vx_ctx* ctx, const vx_stark_config* cfg, const char* what) : ctx(ctx), cfg(cfg), what(what) {}
+    ~TableGroup() { g.finish(); }
+    int add(TableSpec s, int bus = 0, bool local = true);
+    int32_t contexts(int here);  // assigns job[k].c (prove does it, unless the caller needed a table's context earlier)
+    int32_t prove(int here, std::vector<int> order = {});
+
+   private:
+    int32_t run(int k);
+    bool have_contexts = false;
+};
+// An aggregation blob (the formats below): magic, the request words, one length per proof, the proofs.  Sets *blob_len and
 // writes the blob, or fails with VX_ERR_BUFSZ ("<what>: the blob needs N words, buffer has M") when blob_out cannot hold it.
 int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
                   size_t blob_cap, size_t* blob_len);
 
 // The three tables of a justification -- authority-set commitment (ShaChainAir, sends the chosen signers' keys), Ed25519
-// (EdAir) and SHA-512 (Sha512Air) -- as parties first, first + 1, first + 2 of `rv`.  The prover verifies exactly
-// floor(2n/3) + 1 signatures (the first signed ones).  `pre` (may be empty) runs on the commitment's thread before anything
-// is proven: the native statement checks whose failure must name the error.
-struct JustificationTables {
-    BusParty party[3];
-    vx_chal_hook hooks[3];
-    TableJob job[3];  // commitment, Ed25519, SHA-512
-    std::vector<uint8_t> chosen;
-    size_t n_sig = 0;
-};
+// (EdAir) and SHA-512 (Sha512Air) -- added to `g` as the next three parties of `bus`; returns the index of the first.  The prover
+// verifies exactly floor(2n/3) + 1 signatures (the first signed ones).  `pre` (may be empty) runs on the commitment's thread before
+// anything is proven: the native statement checks whose failure must name the error.  Bit t of `mask`: table t is proven here.
+int vx_justification_add(TableGroup& g, const vx_justification* just, std::function<int32_t(vx_ctx*)> pre, int bus = 0, unsigned mask = 7);
+// the shapes of the three for n_sig verified signatures (the proof bound assumes the quorum)
+std::array<TableShape, 3> vx_justification_shapes(size_t n_authorities, size_t n_sig);
 size_t vx_justification_proof_bound(const vx_stark_config* cfg, size_t n_authorities, int32_t* rc);
-int32_t vx_justification_tables_start(vx_ctx* const ctxs[3], const vx_justification* just, const vx_stark_config* cfg, BusMeet* rv, int first,
-                                      int32_t (*pre)(vx_ctx*, void*), void* pre_user, JustificationTables* jt, unsigned mask = 7 /* bit t: start table t here */);
-// joins the three threads; the first failure with a message of its own is reported on `ctx` (the justification's own rules
-// come first); returns VX_OK when all three proofs exist
-int32_t vx_justification_tables_join(vx_ctx* ctx, JustificationTables* jt);
 // verifier side: expected public inputs and AIR ids of the three tables for the request; the counts are read from the
 // proofs' own public inputs (ppub_chain[8] authorities, ppub_ed[0] signatures) and must satisfy signed * 3 > authorities * 2
 int32_t vx_justification_expect(const uint64_t* ppub_chain, size_t n_chain, const uint64_t* ppub_ed, size_t n_ed, size_t n_s512, const uint8_t authority_set_hash[32],
@@ -130,7 +110,7 @@ static constexpr size_t VX_MROWS_HDR = 6;
 // log2 of the inner proof's LDE, fold layers, queries, length of the FriFoldAir proof that follows
 static const uint64_t VX_FFOLD_MAGIC = 0x31444c4f46465856ULL;  // "VXFFOLD1"
 static constexpr size_t VX_FFOLD_HDR = 5;
-// The public inputs of the three aggregation AIRs from the claims, prover and verifier alike (each defined beside its AIR's witness).
+// The public inputs of the aggregation AIRs from the claims, prover and verifier alike (each defined beside its AIR's witness).
 // MerkleOpenAir: root, depth, the digest of the claims [n_idx][5] = (index, leaf digest); claims == nullptr leaves the digest to
 // the caller (vx_merkle_rows_verify, which never sees the leaf digests, takes it from the proof)
 void vx_merkle_open_public(const uint64_t root[4], int depth, const uint64_t* claims, size_t n_idx, uint64_t pub[9]);

@@ -343,12 +343,10 @@ int32_t vx_fri_combine_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
 }
 
 int32_t vx_fri_combine_fold_proof_bound(const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, size_t n_layers, size_t n_queries, size_t* n_words) {
-    size_t wc = 0, wf = 0;
-    int32_t rc = vx_fri_combine_proof_bound(cfg, log_lde, cm, ca, nq, n_queries, &wc);
-    if (rc == VX_OK) rc = vx_fri_fold_proof_bound(cfg, log_lde, n_layers, n_queries, &wf);
-    if (rc != VX_OK) return rc;
-    *n_words = VX_FCFLD_HDR + (wc - VX_FCOMB_HDR) + (wf - VX_FFOLD_HDR);
-    return VX_OK;
+    size_t one = 0;  // (the bounds of the tables alone check the request)
+    VX_TRY(vx_fri_combine_proof_bound(cfg, log_lde, cm, ca, nq, n_queries, &one));
+    VX_TRY(vx_fri_fold_proof_bound(cfg, log_lde, n_layers, n_queries, &one));
+    return vx_tables_proof_bound(cfg, VX_FCFLD_HDR, {{VX_AIR_FRI_COMBINE, fri_combine_log_n(n_queries, log_lde, cm, ca, nq)}, {VX_AIR_FRI_FOLD, fri_fold_log_n(n_queries, log_lde, n_layers)}}, n_words);
 }
 
 int32_t vx_fri_combine_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, size_t cm, size_t ca, size_t nq, const uint64_t alpha[2], const uint64_t zeta[2],
@@ -369,34 +367,18 @@ int32_t vx_fri_combine_fold_prove(vx_ctx* ctx, const vx_stark_config* cfg, int l
     uint64_t stmt[4];
     vx_fri_combine_fold_statement(st, betas, n_layers, final_poly, final_len, index, rows, leaves, n_queries, stmt);
     // two tables on one bus, in transcript order: the combination on a side context and a host thread of its own, the fold here
-    BusMeet rv;
-    rv.n_parties = 2;
-    BusParty party[2] = {{&rv, 0}, {&rv, 1}};
-    const vx_chal_hook hooks[2] = {{vx_bus_hook, &party[0]}, {vx_bus_hook, &party[1]}};
-    TableJob comb, fold;
-    vx_ctx* side[1];
-    VX_TRY(side_contexts(ctx, 1, side, "fri combine-fold: no side context for the combination table"));
-    comb.c = side[0], fold.c = ctx;
-    auto prove_comb = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return run_table(c, j, VX_AIR_FRI_COMBINE, log_c, COLS, PUB, cfg, &hooks[0], 0, [&](vx_ctx* c2, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_fri_combine_trace_dev(c2, st, TREE0, index, rows, ev0.data(), n_queries, log_c, trace->d, pub));
-            vx_fri_combine_public_digest(st, TREE0, stmt, pub);
-            return (int32_t)VX_OK;
-        });
-    };
-    TableJoin threads{{&comb}};  // every exit path waits for the thread
-    int32_t rc = VX_OK;
-    if (!start_table(comb, rv, 0, prove_comb)) rc = vx_fail(ctx, VX_ERR_DEVICE, "fri combine-fold: no host thread for the combination table");
-    if (rc == VX_OK)
-        rc = run_table(ctx, fold, VX_AIR_FRI_FOLD, log_f, ffa::COLS, ffa::PUB, cfg, &hooks[1], 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0.data(), leaves, n_queries, log_f, trace->d, pub));
-            vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, pub);
-            return (int32_t)VX_OK;
-        });
-    if (rc != VX_OK) rv.fail(1);
-    threads.join();
-    if (rc == VX_OK && comb.rc != VX_OK) rc = vx_fail(ctx, comb.rc, "fri combine-fold: %s", vx_last_error(comb.c)[0] ? vx_last_error(comb.c) : "the combination table failed");
-    if (rc != VX_OK) return rc;
-    return pack_blob(ctx, "fri combine-fold", VX_FCFLD_MAGIC, {(uint64_t)log_lde, cm, ca, nq, n_layers, n_queries}, {&comb, &fold}, blob_out, blob_cap, blob_len);
+    TableGroup g(ctx, cfg, "fri combine-fold");
+    g.add({"combination", VX_AIR_FRI_COMBINE, log_c, COLS, PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+               VX_TRY(vx_fri_combine_trace_dev(c, st, TREE0, index, rows, ev0.data(), n_queries, log_c, trace->d, pub));
+               vx_fri_combine_public_digest(st, TREE0, stmt, pub);
+               return (int32_t)VX_OK;
+           }});
+    const int fold = g.add({"fold", VX_AIR_FRI_FOLD, log_f, ffa::COLS, ffa::PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+                                VX_TRY(vx_fri_fold_trace_dev(c, log_lde, betas, n_layers, 0, index, ev0.data(), leaves, n_queries, log_f, trace->d, pub));
+                                vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, pub);
+                                return (int32_t)VX_OK;
+                            }});
+    VX_TRY(g.prove(fold));
+    return pack_blob(ctx, "fri combine-fold", VX_FCFLD_MAGIC, {(uint64_t)log_lde, cm, ca, nq, n_layers, n_queries}, {&g.job[0], &g.job[1]}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

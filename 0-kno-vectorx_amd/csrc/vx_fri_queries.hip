@@ -1,5 +1,5 @@
 // vx_fri_queries_prove: the query phase of one inner proof's FRI on ONE logUp bus -- the layer leaves opened (MerkleOpenSetAir),
-// hashed (LeafSpongeSetAir) and folded (FriFoldAir), three tables of one BusMeet in that bus order.  TAG_OPEN closes between the
+// hashed (LeafSpongeSetAir) and folded (FriFoldAir), three tables of one group (vx_bus.h) in that bus order.  TAG_OPEN closes between the
 // first two, TAG_ROW between the last two, in every one of the NL layer trees (tree id = layer); what is left for the party
 // outside -- the verifier, vx_fri_queries_verify in vx_verify.hip -- is the entry and the exit of every chain (TAG_FRI) and the
 // root and depth every path ended in (TAG_ROOT).  The four digest words among the public inputs of all three tables are the
@@ -40,13 +40,11 @@ void vx_fri_queries_statement(int log_lde, const uint64_t* betas, size_t n_layer
 extern "C" {
 int32_t vx_fri_queries_proof_bound(const vx_stark_config* cfg, int log_lde, size_t n_layers, size_t n_queries, size_t* n_words) {
     if (!cfg || !n_words || !shape_ok(cfg, log_lde, n_layers, n_queries)) return VX_ERR_ARG;
-    size_t wo = 0, ws = 0, wf = 0;
-    int32_t rc = vx_stark_proof_bound(VX_AIR_MERKLE_OPEN_SET, cfg, fri_queries_open_log_n(n_queries, log_lde, n_layers), &wo);
-    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_LEAF_SPONGE_SET, cfg, fri_queries_sponge_log_n(n_queries, n_layers), &ws);
-    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_FRI_FOLD, cfg, fri_fold_log_n(n_queries, log_lde, n_layers), &wf);
-    if (rc != VX_OK) return rc;
-    *n_words = VX_FQRY_HDR + wo + ws + wf;
-    return VX_OK;
+    return vx_tables_proof_bound(cfg, VX_FQRY_HDR,
+                                 {{VX_AIR_MERKLE_OPEN_SET, fri_queries_open_log_n(n_queries, log_lde, n_layers)},
+                                  {VX_AIR_LEAF_SPONGE_SET, fri_queries_sponge_log_n(n_queries, n_layers)},
+                                  {VX_AIR_FRI_FOLD, fri_fold_log_n(n_queries, log_lde, n_layers)}},
+                                 n_words);
 }
 
 int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
@@ -100,46 +98,24 @@ int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
     const int log_open = fri_queries_open_log_n(n_queries, log_lde, NL), log_sponge = fri_queries_sponge_log_n(n_queries, NL), log_fold = fri_fold_log_n(n_queries, log_lde, NL);
     // three tables on one bus, in transcript order: the openings and the sponge on side contexts and host threads of their own,
     // the fold on this context
-    BusMeet rv;
-    rv.n_parties = 3;
-    BusParty party[3] = {{&rv, 0}, {&rv, 1}, {&rv, 2}};
-    const vx_chal_hook hooks[3] = {{vx_bus_hook, &party[0]}, {vx_bus_hook, &party[1]}, {vx_bus_hook, &party[2]}};
-    TableJob open, sponge, fold;
-    vx_ctx* side[2];
-    VX_TRY(side_contexts(ctx, 2, side, "fri queries: no side contexts for the openings and the sponge table"));
-    open.c = side[0], sponge.c = side[1], fold.c = ctx;
-    auto prove_open = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return run_table(c, j, VX_AIR_MERKLE_OPEN_SET, log_open, mop::SET_COLS, mop::SET_PUB, cfg, &hooks[0], 0, [&](vx_ctx* c2, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_merkle_open_set_trace_dev(c2, trees, NL, tree_of.data(), leaf_of.data(), tree_of.size(), log_open, trace->d, pub));
-            vx_merkle_open_set_public(stmt, pub);
-            return (int32_t)VX_OK;
-        });
-    };
-    auto prove_sponge = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return run_table(c, j, VX_AIR_LEAF_SPONGE_SET, log_sponge, lsp::SET_COLS, lsp::PUB, cfg, &hooks[1], 0, [&](vx_ctx* c2, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_leaf_sponge_set_trace_dev(c2, evals_d, log_leaves, tree_leaves, NL, tree_of.data(), leaf_of.data(), tree_of.size(), log_sponge, trace->d, pub));
-            vx_leaf_sponge_set_public(32, stmt, pub);
-            return (int32_t)VX_OK;
-        });
-    };
-    TableJoin threads{{&open, &sponge}};  // every exit path waits for the threads
-    int32_t rc = VX_OK;
-    if (!start_table(open, rv, 0, prove_open)) rc = vx_fail(ctx, VX_ERR_DEVICE, "fri queries: no host thread for the openings table");
-    if (rc == VX_OK && !start_table(sponge, rv, 1, prove_sponge)) rc = vx_fail(ctx, VX_ERR_DEVICE, "fri queries: no host thread for the sponge table");
-    if (rc == VX_OK)
-        rc = run_table(ctx, fold, VX_AIR_FRI_FOLD, log_fold, ffa::COLS, ffa::PUB, cfg, &hooks[2], 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_fri_fold_trace_dev(c, log_lde, betas, NL, 0, index, ev0.data(), leaves.data(), n_queries, log_fold, trace->d, pub));
-            vx_fri_fold_public_digest(log_lde, betas, NL, 0, stmt, pub);
-            return (int32_t)VX_OK;
-        });
-    if (rc != VX_OK) rv.fail(2);
-    threads.join();
-    // a table that refused the statement (a layer that is not what its tree was built from) names the error
-    for (TableJob* j : {&sponge, &open})
-        if (j->rc == VX_ERR_STATEMENT) return vx_fail(ctx, VX_ERR_STATEMENT, "fri queries: %s", vx_last_error(j->c));
-    for (TableJob* j : {&open, &sponge})
-        if (rc == VX_OK && j->rc != VX_OK) rc = vx_fail(ctx, j->rc, "fri queries: %s", vx_last_error(j->c)[0] ? vx_last_error(j->c) : "a table failed");
-    if (rc != VX_OK) return rc;
-    return pack_blob(ctx, "fri queries", VX_FQRY_MAGIC, {(uint64_t)log_lde, NL, n_queries}, {&open, &sponge, &fold}, blob_out, blob_cap, blob_len);
+    TableGroup g(ctx, cfg, "fri queries");
+    g.add({"openings", VX_AIR_MERKLE_OPEN_SET, log_open, mop::SET_COLS, mop::SET_PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+               VX_TRY(vx_merkle_open_set_trace_dev(c, trees, NL, tree_of.data(), leaf_of.data(), tree_of.size(), log_open, trace->d, pub));
+               vx_merkle_open_set_public(stmt, pub);
+               return (int32_t)VX_OK;
+           }});
+    // (a layer that is not what its tree was built from is refused here: VX_ERR_STATEMENT, "does not hash")
+    g.add({"sponge", VX_AIR_LEAF_SPONGE_SET, log_sponge, lsp::SET_COLS, lsp::PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+               VX_TRY(vx_leaf_sponge_set_trace_dev(c, evals_d, log_leaves, tree_leaves, NL, tree_of.data(), leaf_of.data(), tree_of.size(), log_sponge, trace->d, pub));
+               vx_leaf_sponge_set_public(32, stmt, pub);
+               return (int32_t)VX_OK;
+           }});
+    const int fold = g.add({"fold", VX_AIR_FRI_FOLD, log_fold, ffa::COLS, ffa::PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+                                VX_TRY(vx_fri_fold_trace_dev(c, log_lde, betas, NL, 0, index, ev0.data(), leaves.data(), n_queries, log_fold, trace->d, pub));
+                                vx_fri_fold_public_digest(log_lde, betas, NL, 0, stmt, pub);
+                                return (int32_t)VX_OK;
+                            }});
+    VX_TRY(g.prove(fold));
+    return pack_blob(ctx, "fri queries", VX_FQRY_MAGIC, {(uint64_t)log_lde, NL, n_queries}, {&g.job[0], &g.job[1], &g.job[2]}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

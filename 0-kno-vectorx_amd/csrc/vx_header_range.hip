@@ -39,7 +39,7 @@ static int32_t hr_prove(vx_ctx* ctx, const vx_buf* headers, size_t stride, const
     VX_TRY(vx_verify_subchain(ctx, headers, stride, sizes, n_fetched, max_headers, trusted_block, trusted_hash, target_block, out96));
     const size_t HDR = VX_HR_BLOB_FIXED_WORDS + S;
     const int tl = tree_log_n(max_headers);
-    // 2. the tables, all on ONE logUp bus under shared lookup challenges (BusMeet), in bus order:
+    // 2. the tables, all on ONE logUp bus under shared lookup challenges (one TableGroup, vx_bus.h), in bus order:
     //    0 .. S-1  BlakeChainAir   map segment s: every compression of its headers; sends state-root and data-root bytes
     //    S         ShaTreeAir      the two SHA-256 Merkle trees over exactly those roots (subchain_verification.rs:213-220, 268-274)
     //   with a justification (header_range.rs:49-54 -> justification.rs:195-257):
@@ -47,133 +47,78 @@ static int32_t hr_prove(vx_ctx* ctx, const vx_buf* headers, size_t stride, const
     //    S+2       EdAir           [S]B = R + [h]A for every signed authority (:229-243); receives the keys, exchanges R || A / H with
     //    S+3       Sha512Air       H = SHA-512(R || A || precommit)
     //   table t is proven here when t mod n_shards == shard
-    const int n_tables = (int)S + 1 + (just ? 3 : 0);
     auto mine = [&](int t) { return (uint32_t)t % n_shards == shard; };
-    BusMeet rv;
-    rv.n_parties = n_tables;
-    rv.capw = (size_t)4 << cfg->cap_height;
-    for (int t = 0; t < n_tables; ++t) rv.local[t] = mine(t);
-    rv.xch = n_shards > 1 ? xch : nullptr;
-    // From here on the other shards of a sharded proof count on this one at the exchange: every exit goes through the tail below.
-    int32_t rc = VX_OK;
     std::vector<size_t> bounds, seg_chunks;
     hr_segments(sizes, n_fetched, S, bounds, seg_chunks);
-    // the hash every segment starts from: the Blake2b-256 digest of the header before it
-    std::vector<uint8_t> digests;
-    if (S > 1) {
-        digests.resize(32 * n_fetched);
-        rc = vx_blake2b_256_batch(ctx, headers, stride, sizes, n_fetched, digests.data());
-    }
-    // the leaves of the two Merkle trees: decode_header on the GPU (all four compact modes)
+    std::vector<uint8_t> digests;  // the hash every segment starts from: the Blake2b-256 digest of the header before it
     std::vector<uint32_t> numbers(n_fetched);
     std::vector<uint8_t> modes(n_fetched), oks(n_fetched), parents(32 * n_fetched), sroots(32 * n_fetched), droots(32 * n_fetched);
-    if (rc == VX_OK && mine((int)S))
-        rc = vx_decode_header_batch(ctx, headers, stride, sizes, n_fetched, numbers.data(), modes.data(), oks.data(), parents.data(), sroots.data(), droots.data());
-    // one context per local table: the first local segment runs on `ctx` from this thread, everything else on a chain of side contexts
-    std::vector<BusParty> party(n_tables);
-    std::vector<vx_chal_hook> hooks(n_tables);
-    for (int t = 0; t < n_tables; ++t) party[t] = {&rv, t}, hooks[t] = {vx_bus_hook, &party[t]};
+    // the target header is justified by > 2/3 of the committed authority set: every rule natively first (error behaviour of
+    // the reference's hint, justification.rs:29-83) -- on the commitment table's thread, or here when that table is another shard's
+    auto pre = [=](vx_ctx* c) {
+        return vx_verify_simple_justification(c, target_block, out96, just->authority_set_id, just->authority_set_hash, just->precommit, just->pubkeys, just->signatures,
+                                              just->validator_signed, just->num_authorities, just->max_authorities);
+    };
+    // From here on the other shards of a sharded proof count on this one at the exchange: whichever way this function is left, the
+    // group fails the local tables that were never started (they arrive as failure markers) before it goes.
+    TableGroup g(ctx, cfg, "header_range");
+    g.g.shard(n_shards > 1 ? xch : nullptr, (size_t)4 << cfg->cap_height);
+    for (int s = 0; s < (int)S; ++s) {
+        const size_t a = bounds[s], b = bounds[s + 1];
+        const int log_n = blake_log_n(seg_chunks[s]);
+        g.add({"hash-chain segment", VX_AIR_BLAKE_CHAIN, log_n, VX_BLAKE_AIR_COLS, 20, /*consume_trace=*/1,
+               [&, a, b, log_n](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+                   vx_buf view{headers->d + a * stride / 8, headers->n - a * stride / 8};
+                   VX_TRY(vx_blake_chain_trace(c, &view, stride, sizes + a, b - a, a ? digests.data() + 32 * (a - 1) : trusted_hash, trusted_block + 1 + (uint32_t)a, max_headers, (uint32_t)a,
+                                               0, log_n, trace, pub, nullptr));
+                   if (b == n_fetched) {
+                       uint8_t tgt[32];
+                       for (int q = 0; q < 8; ++q) {
+                           uint32_t l = (uint32_t)pub[8 + q];
+                           memcpy(tgt + 4 * q, &l, 4);
+                       }
+                       if (memcmp(tgt, out96, 32) != 0) return vx_fail(c, VX_ERR_STATEMENT, "header_range: chain digest differs from the subchain target hash");
+                   }
+                   return (int32_t)VX_OK;
+               }},
+              0, mine(s));
+    }
+    g.add({"Merkle", tree_id, tl, VX_SHA_TREE_AIR_COLS, 17, /*consume_trace=*/0,
+           [&](vx_ctx* c, vx_buf* tt, uint64_t* tpub) {
+               VX_TRY(vx_sha_tree_trace_dev(c, sroots.data(), droots.data(), n_fetched, tl - 8, tt->d, tpub));
+               uint8_t roots[64];
+               for (int q = 0; q < 16; ++q)
+                   for (int b = 0; b < 4; ++b) roots[4 * q + b] = (uint8_t)(tpub[q] >> (24 - 8 * b));
+               if (memcmp(roots, out96 + 32, 64) != 0) return vx_fail(c, VX_ERR_STATEMENT, "header_range: Merkle AIR roots differ from the subchain roots");
+               return (int32_t)VX_OK;
+           }},
+          0, mine((int)S));
+    if (just) vx_justification_add(g, just, pre, 0, (mine((int)S + 1) ? 1u : 0) | (mine((int)S + 2) ? 2u : 0) | (mine((int)S + 3) ? 4u : 0));
+    if (S > 1) {
+        digests.resize(32 * n_fetched);
+        VX_TRY(vx_blake2b_256_batch(ctx, headers, stride, sizes, n_fetched, digests.data()));
+    }
+    // the leaves of the two Merkle trees: decode_header on the GPU (all four compact modes)
+    if (mine((int)S)) VX_TRY(vx_decode_header_batch(ctx, headers, stride, sizes, n_fetched, numbers.data(), modes.data(), oks.data(), parents.data(), sroots.data(), droots.data()));
+    if (just && !mine((int)S + 1)) VX_TRY(pre(ctx));
+    // the first local segment runs on `ctx` from this thread, every other local table on the chain of side contexts; failures are
+    // reported in the order: the justification's tables (its own rules name the error first), the Merkle table, the segments
     int main_seg = -1;
     for (int t = 0; t < (int)S && main_seg < 0; ++t)
         if (mine(t)) main_seg = t;
-    std::vector<vx_ctx*> tctx(n_tables, nullptr), side;
-    for (int t = 0; t < n_tables; ++t)
-        if (mine(t) && t != main_seg) side.push_back(nullptr);
-    if (rc == VX_OK) rc = side_contexts(ctx, side.size(), side.data(), "header_range: no side context for every table (the provers meet at their challenge hooks, each on its own context)");
-    for (int t = 0, k = 0; t < n_tables && rc == VX_OK; ++t)
-        if (mine(t)) tctx[t] = t == main_seg ? ctx : side[k++];
-    std::vector<TableJob> seg(S);
-    auto prove_segment = [&](int s, vx_ctx* c, TableJob& j) -> int32_t {
-        const size_t a = bounds[s], b = bounds[s + 1];
-        const int log_n = blake_log_n(seg_chunks[s]);
-        return run_table(c, j, VX_AIR_BLAKE_CHAIN, log_n, VX_BLAKE_AIR_COLS, 20, cfg, &hooks[s], /*consume_trace=*/1, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-            vx_buf view{headers->d + a * stride / 8, headers->n - a * stride / 8};
-            VX_TRY(vx_blake_chain_trace(c, &view, stride, sizes + a, b - a, a ? digests.data() + 32 * (a - 1) : trusted_hash, trusted_block + 1 + (uint32_t)a, max_headers, (uint32_t)a, 0,
-                                        log_n, trace, pub, nullptr));
-            if (b == n_fetched) {
-                uint8_t tgt[32];
-                for (int q = 0; q < 8; ++q) {
-                    uint32_t l = (uint32_t)pub[8 + q];
-                    memcpy(tgt + 4 * q, &l, 4);
-                }
-                if (memcmp(tgt, out96, 32) != 0) return vx_fail(c, VX_ERR_STATEMENT, "header_range: chain digest differs from the subchain target hash");
-            }
-            return (int32_t)VX_OK;
-        });
-    };
-    TableJob tree;
-    auto prove_tree = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return run_table(c, j, tree_id, tl, VX_SHA_TREE_AIR_COLS, 17, cfg, &hooks[S], /*consume_trace=*/0, [&](vx_ctx* c, vx_buf* tt, uint64_t* tpub) {
-            VX_TRY(vx_sha_tree_trace_dev(c, sroots.data(), droots.data(), n_fetched, tl - 8, tt->d, tpub));
-            uint8_t roots[64];
-            for (int q = 0; q < 16; ++q)
-                for (int b = 0; b < 4; ++b) roots[4 * q + b] = (uint8_t)(tpub[q] >> (24 - 8 * b));
-            if (memcmp(roots, out96 + 32, 64) != 0) return vx_fail(c, VX_ERR_STATEMENT, "header_range: Merkle AIR roots differ from the subchain roots");
-            return (int32_t)VX_OK;
-        });
-    };
-    // the target header is justified by > 2/3 of the committed authority set: every rule natively first (error behaviour of
-    // the reference's hint, justification.rs:29-83) -- on the commitment table's thread, or here when that table is another shard's
-    struct PreArgs {
-        const vx_justification* just;
-        uint32_t target_block;
-        const uint8_t* target_hash;
-    } pre_args{just, target_block, out96};
-    auto pre = [](vx_ctx* c, void* u) -> int32_t {
-        const PreArgs* a = (const PreArgs*)u;
-        return vx_verify_simple_justification(c, a->target_block, a->target_hash, a->just->authority_set_id, a->just->authority_set_hash, a->just->precommit,
-                                              a->just->pubkeys, a->just->signatures, a->just->validator_signed, a->just->num_authorities, a->just->max_authorities);
-    };
-    if (rc == VX_OK && just && !mine((int)S + 1)) {
-        rc = pre(ctx, &pre_args);
-        if (rc != VX_OK)  // nothing has been started yet; the other shards see this shard's tables fail
-            for (int t = 0; t < n_tables; ++t)
-                if (mine(t)) rv.fail(t);
-    }
-    JustificationTables jt;
-    if (rc == VX_OK) {
-        TableJoin threads;  // (after everything the table threads refer to)
-        for (int s = 0; s < (int)S; ++s) threads.jobs.push_back(&seg[s]);
-        threads.jobs.insert(threads.jobs.end(), {&tree, &jt.job[0], &jt.job[1], &jt.job[2]});
-        auto start = [&](TableJob& j, int t, std::function<int32_t(vx_ctx*, TableJob&)> fn) {
-            j.c = tctx[t];
-            if (!start_table(j, rv, t, std::move(fn))) j.rc = VX_ERR_DEVICE;
-        };
-        for (int s = 0; s < (int)S; ++s)
-            if (mine(s) && s != main_seg) start(seg[s], s, [&, s](vx_ctx* c, TableJob& j) { return prove_segment(s, c, j); });
-        if (mine((int)S)) start(tree, (int)S, prove_tree);
-        if (just) {
-            vx_ctx* jc[3] = {tctx[S + 1], tctx[S + 2], tctx[S + 3]};
-            const unsigned mask = (mine((int)S + 1) ? 1u : 0) | (mine((int)S + 2) ? 2u : 0) | (mine((int)S + 3) ? 4u : 0);
-            rc = vx_justification_tables_start(jc, just, cfg, &rv, (int)S + 1, pre, &pre_args, &jt, mask);
-            if (rc != VX_OK) (void)vx_fail(ctx, rc, "header_range: no host thread for the justification tables");
-        }
-        if (main_seg >= 0) {
-            seg[main_seg].c = ctx;
-            if (rc == VX_OK) seg[main_seg].rc = prove_segment(main_seg, ctx, seg[main_seg]);
-            else seg[main_seg].rc = rc;
-            if (seg[main_seg].rc != VX_OK) rv.fail(main_seg);
-        }
-        threads.join();
-        const int32_t rc_just = just ? vx_justification_tables_join(ctx, &jt) : VX_OK;  // (the justification's own rules name the error first)
-        if (rc == VX_OK) {
-            if (rc_just != VX_OK) rc = rc_just;
-            else if (tree.rc != VX_OK) rc = vx_fail(ctx, tree.rc, "%s", vx_last_error(tree.c));
-            else
-                for (int s = 0; s < (int)S && rc == VX_OK; ++s)
-                    if (seg[s].rc != VX_OK) rc = s == main_seg ? seg[s].rc : vx_fail(ctx, seg[s].rc, "%s", vx_last_error(seg[s].c));
-        }
-    }
-    // The tail: no table thread is running any more, and every local table has met the others, failed at the rendezvous or was never started.
-    // TODO(ADVICE r3): an exit before the tables start (digests, header decode, side contexts) must rv.fail(t) its local tables here, or the other shards wait at the exchange
-    if (rc != VX_OK) return rc;
-    size_t total = HDR + tree.len + (just ? jt.job[0].len + jt.job[1].len + jt.job[2].len : 0);
+    std::vector<int> report;
+    for (int t = (int)S + 1; t < g.g.n; ++t) report.push_back(t);
+    report.push_back((int)S);
+    for (int s = 0; s < (int)S; ++s) report.push_back(s);
+    VX_TRY(g.prove(main_seg, report));
+    const TableJob *seg = g.job, &tree = g.job[S], *jt = &g.job[S + 1];  // (jt only with a justification)
+    size_t total = HDR + tree.len + (just ? jt[0].len + jt[1].len + jt[2].len : 0);
     for (int s = 0; s < (int)S; ++s) total += seg[s].len;
     *proof_len = total;
     if (!proof_out || proof_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "header_range: proof needs %zu words, buffer has %zu", total, proof_cap);
     size_t off = HDR;
     for (int s = 0; s < (int)S; ++s) memcpy(proof_out + off, seg[s].proof.data(), seg[s].len * 8), off += seg[s].len;
-    const TableJob* order[4] = {just ? &jt.job[0] : nullptr, &tree, just ? &jt.job[1] : nullptr, just ? &jt.job[2] : nullptr};  // commitment, Merkle, Ed25519, SHA-512
+    const TableJob* order[4] = {just ? &jt[0] : nullptr, &tree, just ? &jt[1] : nullptr, just ? &jt[2] : nullptr};  // commitment, Merkle, Ed25519, SHA-512
     for (int q = 0; q < 4; ++q)
         if (order[q]) memcpy(proof_out + off, order[q]->proof.data(), order[q]->len * 8), off += order[q]->len;
     proof_out[0] = VX_HR_MAGIC;
@@ -182,10 +127,10 @@ static int32_t hr_prove(vx_ctx* ctx, const vx_buf* headers, size_t stride, const
     proof_out[3] = target_block;
     memcpy(proof_out + 4, out96, 96);
     proof_out[16] = S;
-    proof_out[17] = just ? jt.job[0].len : 0;
+    proof_out[17] = just ? jt[0].len : 0;
     proof_out[18] = tree.len;
-    proof_out[19] = just ? jt.job[1].len : 0;
-    proof_out[20] = just ? jt.job[2].len : 0;
+    proof_out[19] = just ? jt[1].len : 0;
+    proof_out[20] = just ? jt[2].len : 0;
     uint64_t round = 0;
     if (just) memcpy(&round, just->precommit + 37, 8);  // 0x01 || hash 32 || block 4 || round 8 || set id 8 (decoder.rs:159-200)
     proof_out[21] = round;

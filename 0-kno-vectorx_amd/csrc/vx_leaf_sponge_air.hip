@@ -344,12 +344,7 @@ int32_t vx_merkle_rows_proof_bound(const vx_stark_config* cfg, size_t n_leaves, 
     if (!cfg || !n_words || n_leaves < 2 || (n_leaves & (n_leaves - 1)) || n_idx < 1 || n_idx > ((size_t)1 << 21) || leaf_len < 5 || leaf_len > MAX_LEAF_LEN) return VX_ERR_ARG;
     const int log_open = vx_merkle_open_log_n(n_idx, ceil_log2(n_leaves)), log_sponge = leaf_sponge_log_n(n_idx, leaf_len);
     if (log_open > 26 || log_sponge > 26) return VX_ERR_ARG;
-    size_t wo = 0, ws = 0;
-    int32_t rc = vx_stark_proof_bound(VX_AIR_MERKLE_OPEN, cfg, log_open, &wo);
-    if (rc == VX_OK) rc = vx_stark_proof_bound(VX_AIR_LEAF_SPONGE, cfg, log_sponge, &ws);
-    if (rc != VX_OK) return rc;
-    *n_words = VX_MROWS_HDR + wo + ws;
-    return VX_OK;
+    return vx_tables_proof_bound(cfg, VX_MROWS_HDR, {{VX_AIR_MERKLE_OPEN, log_open}, {VX_AIR_LEAF_SPONGE, log_sponge}}, n_words);
 }
 
 int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_tree* tree, const vx_buf* data, size_t off, size_t leaf_len, int layout, const uint64_t* leaf_idx,
@@ -365,31 +360,15 @@ int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_t
     const int log_open = vx_merkle_open_log_n(n_idx, depth), log_sponge = leaf_sponge_log_n(n_idx, leaf_len);
     VX_CHECK(log_open <= 26 && log_sponge <= 26, "merkle rows: %zu openings of %zu words in a tree of depth %d need more than 2^26 rows", n_idx, leaf_len, depth);
     // two tables on one bus, in transcript order: the openings (a side context, its own host thread), the sponge (this context)
-    BusMeet rv;
-    rv.n_parties = 2;
-    BusParty party[2] = {{&rv, 0}, {&rv, 1}};
-    const vx_chal_hook hooks[2] = {{vx_bus_hook, &party[0]}, {vx_bus_hook, &party[1]}};
-    TableJob open, sponge;
-    vx_ctx* side[1];
-    VX_TRY(side_contexts(ctx, 1, side, "merkle rows: no side context for the openings table"));
-    open.c = side[0], sponge.c = ctx;
+    TableGroup g(ctx, cfg, "merkle rows");
+    g.add({"openings", VX_AIR_MERKLE_OPEN, log_open, mop::COLS, mop::PUB, 0,
+           [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) { return vx_merkle_open_trace_dev(c, tree, leaf_idx, n_idx, log_open, trace->d, pub); }});
+    const int sponge = g.add({"sponge", VX_AIR_LEAF_SPONGE, log_sponge, COLS, PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+                                  return leaf_sponge_trace_dev(c, data->d + off, n_leaves, leaf_len, layout, tree->levels, leaf_idx, n_idx, log_sponge, trace->d, pub);
+                              }});
     // the tree and the leaf data are the work of this context's stream; the openings table reads the tree from another one
     VX_HIP(hipStreamSynchronize(ctx->stream));
-    auto prove_open = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return run_table(c, j, VX_AIR_MERKLE_OPEN, log_open, mop::COLS, mop::PUB, cfg, &hooks[0], 0,
-                         [&](vx_ctx* c2, vx_buf* trace, uint64_t* pub) { return vx_merkle_open_trace_dev(c2, tree, leaf_idx, n_idx, log_open, trace->d, pub); });
-    };
-    TableJoin threads{{&open}};  // every exit path waits for the thread
-    int32_t rc = VX_OK;
-    if (!start_table(open, rv, 0, prove_open)) rc = vx_fail(ctx, VX_ERR_DEVICE, "merkle rows: no host thread for the openings table");
-    if (rc == VX_OK)
-        rc = run_table(ctx, sponge, VX_AIR_LEAF_SPONGE, log_sponge, COLS, PUB, cfg, &hooks[1], 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-            return leaf_sponge_trace_dev(c, data->d + off, n_leaves, leaf_len, layout, tree->levels, leaf_idx, n_idx, log_sponge, trace->d, pub);
-        });
-    if (rc != VX_OK) rv.fail(1);
-    threads.join();
-    if (rc == VX_OK && open.rc != VX_OK) rc = vx_fail(ctx, open.rc, "merkle rows: %s", vx_last_error(open.c)[0] ? vx_last_error(open.c) : "the openings table failed");
-    if (rc != VX_OK) return rc;
-    return pack_blob(ctx, "merkle rows", VX_MROWS_MAGIC, {(uint64_t)depth, leaf_len, n_idx}, {&open, &sponge}, blob_out, blob_cap, blob_len);
+    VX_TRY(g.prove(sponge));
+    return pack_blob(ctx, "merkle rows", VX_MROWS_MAGIC, {(uint64_t)depth, leaf_len, n_idx}, {&g.job[0], &g.job[1]}, blob_out, blob_cap, blob_len);
 }
 }  // extern "C"

@@ -5,11 +5,10 @@
 // new set's commitment is proved (second SHA-256 chain STARK) and returned as the 32 output bytes.  Two logUp buses:
 //   A  current-set commitment -> Ed25519 <-> SHA-512                 (the justification, vx_bus.h)
 //   B  Blake2b header hash -> EpochEndAir -> new-set commitment     (the header bytes of the log ARE the committed keys)
-// Every table goes through the runner / starter / join of vx_bus.h (vx_bus.hip) and is sized by vx_table_shapes.h; the verifier
+// Every table is a TableSpec of one TableGroup (vx_bus.h) and is sized by vx_table_shapes.h; the verifier
 // is vx_rotate_verify in vx_verify.hip.
 #include <cstdio>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "vx_bus.h"
@@ -142,76 +141,51 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     // 1. the tables.  Bus A: the justification by the CURRENT set (rotate.rs:297-302) -- its commitment (binds the EVM input hash;
     //    sends the chosen signers' keys), the Ed25519 table and the SHA-512 table (vx_bus.h).  Bus B: the Blake2b table of the header
     //    hash (this context) sends the bytes of the ScheduledChange log to the epoch-end table, which sends the keys it reads there to
-    //    the NEW set's commitment table.  Every table but the first is proven on a side context from a host thread.
-    BusMeet rv, rvb;
-    rv.n_parties = rvb.n_parties = 3;
-    BusParty pb[3] = {{&rvb, 0}, {&rvb, 1}, {&rvb, 2}};
-    const vx_chal_hook hb[3] = {{vx_bus_hook, &pb[0]}, {vx_bus_hook, &pb[1]}, {vx_bus_hook, &pb[2]}};
-    JustificationTables jt;
-    TableJob epoch, newset;
-    vx_ctx* side[5];
-    VX_TRY(side_contexts(ctx, 5, side, "rotate: no side context for every table"));
-    epoch.c = side[3], newset.c = side[4];
-    // the epoch-end trace (512 rows) is written from this thread: its prefix gives the byte window the Blake2b table sends
-    vx_buf* et = nullptr;
+    //    the NEW set's commitment table.
+    //    One group of six, in table order: the hash, the justification's three, the epoch-end table, the new set's commitment.
     uint64_t epub[10];
     uint32_t wlen = 0;
-    VX_TRY(vx_alloc(epoch.c, (size_t)VX_EPOCH_END_AIR_COLS << VX_EPOCH_END_LOG_ROWS, &et));
+    const int bl = blake_log_n((header_size + 127) / 128), sl = sha_log_n(num_authorities);
+    TableGroup g(ctx, cfg, "rotate");
+    // 2. header hash = Blake2b-256 of the first header_size bytes (rotate.rs:293); the trace of its compressions
+    //    is the witness of the hash STARK (one-header chain anchored at the header's own parent hash)
+    const int hash = g.add({"header hash", VX_AIR_BLAKE_CHAIN, bl, VX_BLAKE_AIR_COLS, 20, /*consume_trace=*/1,
+                            [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
+                                VX_TRY(vx_blake_chain_trace(c, header, MAX_HEADER_SIZE, &header_size, 1, parent, epoch_end_block_number, 0, start_position + 1, wlen, bl, trace, pub, header_hash));
+                                // 3. justification by the current set over (epoch_end_block_number, header hash) (rotate.rs:297-302), natively
+                                return vx_verify_simple_justification(c, epoch_end_block_number, header_hash, just->authority_set_id, just->authority_set_hash, just->precommit,
+                                                                      just->pubkeys, just->signatures, just->validator_signed, just->num_authorities, just->max_authorities);
+                            }},
+                           1);
+    const int j0 = vx_justification_add(g, just, nullptr, 0);
+    const int epoch = g.add({"epoch end", VX_AIR_EPOCH_END, VX_EPOCH_END_LOG_ROWS, VX_EPOCH_END_AIR_COLS, 10, /*consume_trace=*/0, nullptr, nullptr, epub}, 1);
+    // the output (rotate.rs:317-320): receives every key from the epoch-end table
+    const int newset = g.add({"new-set commitment", VX_AIR_SHA_CHAIN, sl, VX_SHA_AIR_COLS, 10, /*consume_trace=*/0,
+                              [&](vx_ctx* c, vx_buf* st, uint64_t* spub) { return vx_sha_chain_trace_dev(c, new_pubkeys, num_authorities, nullptr, 2, sl, st->d, spub, new_commit); }},
+                             1);
+    VX_TRY(g.contexts(hash));
+    // the epoch-end trace (512 rows) is written from this thread: its prefix gives the byte window the Blake2b table sends
+    vx_ctx* ec = g.job[epoch].c;
+    vx_buf* et = nullptr;
+    VX_TRY(vx_alloc(ec, (size_t)VX_EPOCH_END_AIR_COLS << VX_EPOCH_END_LOG_ROWS, &et));
     struct FreeEt {
         vx_ctx* c;
-        vx_buf*& b;
-        ~FreeEt() {
-            if (b) (void)vx_free(c, b);
-        }
-    } free_et{epoch.c, et};
+        vx_buf* b;
+        ~FreeEt() { (void)vx_free(c, b); }
+    } free_et{ec, et};
     {
-        const int32_t r = vx_epoch_end_trace_dev(epoch.c, (const uint8_t*)header->d, header->n * 8, start_position, num_authorities, 1, et->d, epub, &wlen);
-        if (r != VX_OK) return vx_fail(ctx, r, "rotate: %s", vx_last_error(epoch.c));
+        const int32_t r = vx_epoch_end_trace_dev(ec, (const uint8_t*)header->d, header->n * 8, start_position, num_authorities, 1, et->d, epub, &wlen);
+        if (r != VX_OK) return vx_fail(ctx, r, "rotate: %s", vx_last_error(ec));
     }
     if (start_position + 1 < 72 || (uint64_t)start_position + 1 + wlen > header_size)  // (the hash covers header_size bytes; 72 = parent hash + number + state root)
         return vx_fail(ctx, VX_ERR_STATEMENT, "rotate: the log at %u..%llu lies outside the hashed digest bytes of the %u-byte header", start_position + 1,
                        (unsigned long long)start_position + 1 + wlen, header_size);
-    TableJob hash;
-    hash.c = ctx;
-    auto prove_epoch = [&](vx_ctx* c, TableJob& j) -> int32_t {
-        return prove_table(c, j, VX_AIR_EPOCH_END, VX_EPOCH_END_LOG_ROWS, cfg, &hb[1], /*consume_trace=*/0, et, epub, 10);
-    };
-    auto prove_newset = [&](vx_ctx* c, TableJob& j) -> int32_t {  // the output (rotate.rs:317-320): receives every key from the epoch-end table
-        const int sl = sha_log_n(num_authorities);
-        return run_table(c, j, VX_AIR_SHA_CHAIN, sl, VX_SHA_AIR_COLS, 10, cfg, &hb[2], /*consume_trace=*/0, [&](vx_ctx* c, vx_buf* st, uint64_t* spub) {
-            return vx_sha_chain_trace_dev(c, new_pubkeys, num_authorities, nullptr, 2, sl, st->d, spub, new_commit);
-        });
-    };
-    TableJoin threads{{&jt.job[0], &jt.job[1], &jt.job[2], &epoch, &newset}};  // every exit path waits for the threads
-    {
-        const int32_t rs = vx_justification_tables_start(side, just, cfg, &rv, 0, nullptr, nullptr, &jt);
-        if (rs != VX_OK) return vx_fail(ctx, rs, "rotate: no host thread for the justification tables");
-    }
-    // (the tables of bus B name themselves when they fail; BusMeet::fail looks at the party only when an exchange is set, which
-    // this circuit never does, so that is the plain rvb.fail())
-    int32_t rc = VX_OK;
-    if (!start_table(epoch, rvb, 1, prove_epoch) || !start_table(newset, rvb, 2, prove_newset))
-        rc = vx_fail(ctx, VX_ERR_DEVICE, "rotate: no host thread for the epoch-end tables");
-    // 2. header hash = Blake2b-256 of the first header_size bytes (rotate.rs:293); the trace of its compressions
-    //    is the witness of the hash STARK (one-header chain anchored at the header's own parent hash)
-    const int bl = blake_log_n((header_size + 127) / 128);
-    if (rc == VX_OK)
-        rc = run_table(ctx, hash, VX_AIR_BLAKE_CHAIN, bl, VX_BLAKE_AIR_COLS, 20, cfg, &hb[0], /*consume_trace=*/1, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-            VX_TRY(vx_blake_chain_trace(c, header, MAX_HEADER_SIZE, &header_size, 1, parent, epoch_end_block_number, 0, start_position + 1, wlen, bl, trace, pub, header_hash));
-            // 3. justification by the current set over (epoch_end_block_number, header hash) (rotate.rs:297-302), natively
-            return vx_verify_simple_justification(c, epoch_end_block_number, header_hash, just->authority_set_id, just->authority_set_hash, just->precommit, just->pubkeys,
-                                                  just->signatures, just->validator_signed, just->num_authorities, just->max_authorities);
-        });
-    if (rc != VX_OK) rvb.fail(0);
-    // 4. collect the side tables
-    threads.join();
-    const int32_t rc_just = vx_justification_tables_join(ctx, &jt);
-    if (rc == VX_OK && rc_just != VX_OK) rc = rc_just;
-    for (TableJob* j : {&epoch, &newset})
-        if (rc == VX_OK && j->rc != VX_OK) rc = vx_fail(ctx, j->rc, "rotate: %s", vx_last_error(j->c)[0] ? vx_last_error(j->c) : "an epoch-end table failed");
-    if (rc != VX_OK) return rc;
+    g.spec[epoch].trace = et;
+    // 4. prove: the hash here, every other table on a side context from a host thread
+    VX_TRY(g.prove(hash));
+    const TableJob &jhash = g.job[hash], &jepoch = g.job[epoch], &jnewset = g.job[newset], *jt = &g.job[j0];
     // blob order: header hash, current-set commitment, new-set commitment, Ed25519, SHA-512, epoch end
-    const TableJob* order[6] = {&hash, &jt.job[0], &newset, &jt.job[1], &jt.job[2], &epoch};
+    const TableJob* order[6] = {&jhash, &jt[0], &jnewset, &jt[1], &jt[2], &jepoch};
     size_t total = VX_ROT_HDR;
     for (const TableJob* j : order) total += j->len;
     *proof_len = total;
@@ -226,17 +200,17 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     memcpy(proof_out + 4, header_hash, 32);
     memcpy(proof_out + 8, just->authority_set_hash, 32);
     memcpy(proof_out + 12, new_commit, 32);
-    proof_out[16] = hash.len;
-    proof_out[17] = jt.job[0].len;
-    proof_out[18] = newset.len;
-    proof_out[19] = jt.job[1].len;
+    proof_out[16] = jhash.len;
+    proof_out[17] = jt[0].len;
+    proof_out[18] = jnewset.len;
+    proof_out[19] = jt[1].len;
     memcpy(proof_out + 20, parent, 32);
-    proof_out[24] = jt.job[2].len;
+    proof_out[24] = jt[2].len;
     uint64_t round = 0;
     memcpy(&round, just->precommit + 37, 8);  // 0x01 || hash 32 || block 4 || round 8 || set id 8 (decoder.rs:159-200)
     proof_out[25] = round;
     proof_out[26] = start_position;
-    proof_out[27] = epoch.len;
+    proof_out[27] = jepoch.len;
     return VX_OK;
 }
 
