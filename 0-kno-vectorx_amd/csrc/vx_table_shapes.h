@@ -29,7 +29,8 @@ static inline int tree_log_n(uint32_t max_headers) {
     while ((1u << (l - 8)) < max_headers) ++l;
     return l;
 }
-// the EdDSA tables by the number of signatures they verify: 256 rows per signature (one slot stays idle) / 164 rows per hash.
+// the EdDSA tables by the number of signatures they verify: 256 rows per signature (one slot stays idle: 255 of 2^16 / 256) / 160 rows per hash
+// (SLOT_ROWS in air_sha512.cuh, no idle slot needed: 6 = floor(2^10 / 160), 204 = floor(2^15 / 160)).
 // The prover needs floor(2n/3) + 1 of the n authorities (justification.rs:164-186), so it verifies exactly that many.
 static inline size_t sig_quorum(size_t n_auth) { return 2 * n_auth / 3 + 1; }
 static inline int ed_log_n(size_t n_sig) { return n_sig <= 255 ? 16 : 17; }
