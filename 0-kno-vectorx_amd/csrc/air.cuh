@@ -31,6 +31,7 @@
 
 #include "air_bus.cuh"
 #include "gl.cuh"
+#include "glh.h"
 
 // the witness generator of an AIR's auxiliary round: trace + challenges -> auxiliary columns [AUX][n] (+ 2*AUXPUB published words, host).
 // Every AIR names its own as `gen_aux` (nullptr exactly when AUX = 0); the registry (air_list.h) reads it from the type.
@@ -75,23 +76,6 @@ struct is_device_field : std::false_type {};
 template <int R>
 struct is_device_field<FpN<R>> : std::true_type {};
 
-// host-side extension-field element (verifier: constraints evaluated at zeta)
-struct Fx {
-    uint64_t a, b;
-    static constexpr uint64_t P_ = 0xFFFFFFFF00000001ULL;
-    static inline uint64_t addm(uint64_t x, uint64_t y) {
-        uint64_t s = x + y;
-        return (s < x || s >= P_) ? s - P_ : s;
-    }
-    static inline uint64_t subm(uint64_t x, uint64_t y) { return x >= y ? x - y : x + (P_ - y); }
-    static inline uint64_t mulm(uint64_t x, uint64_t y) { return (uint64_t)(((unsigned __int128)x * y) % P_); }
-    Fx operator+(Fx o) const { return {addm(a, o.a), addm(b, o.b)}; }
-    Fx operator-(Fx o) const { return {subm(a, o.a), subm(b, o.b)}; }
-    Fx operator*(Fx o) const {
-        return {addm(mulm(a, o.a), mulm(7, mulm(b, o.b))), addm(mulm(a, o.b), mulm(b, o.a))};
-    }
-    static Fx from(uint64_t x) { return {x % P_, 0}; }
-};
 struct HostRow {
     const Fx* v;
     Fx operator[](int col) const { return v[col]; }

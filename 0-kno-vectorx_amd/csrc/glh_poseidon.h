@@ -6,8 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "glh.h"
 #include "poseidon_constants.h"
-#include "vx_internal.h"
 
 namespace glh {
 inline void poseidon(uint64_t* s) {
@@ -45,6 +45,22 @@ inline void two_to_one(const uint64_t l[4], const uint64_t r[4], uint64_t out4[4
     memcpy(s, l, 32), memcpy(s + 4, r, 32);
     poseidon(s);
     memcpy(out4, s, 32);
+}
+// the digest of a Merkle leaf (hash_or_noop): a row of at most 4 words is its own digest, zero-padded
+inline void hash_or_noop(const uint64_t* in, size_t len, uint64_t out4[4]) {
+    if (len > 4) return hash_no_pad(in, len, out4);
+    memset(out4, 0, 32);
+    memcpy(out4, in, len * 8);
+}
+// verify_merkle_proof_to_cap: leaf `idx` under `n_sib` siblings (4 words each) must arrive at its entry of the cap
+inline bool merkle_path_ok(const uint64_t* leaf, size_t leaf_len, size_t idx, const uint64_t* sib, size_t n_sib, const uint64_t* cap) {
+    uint64_t cur[4];
+    hash_or_noop(leaf, leaf_len, cur);
+    for (size_t k = 0; k < n_sib; ++k, idx >>= 1) {
+        if (idx & 1) two_to_one(sib + 4 * k, cur, cur);
+        else two_to_one(cur, sib + 4 * k, cur);
+    }
+    return memcmp(cur, cap + 4 * idx, 32) == 0;
 }
 struct Challenger {
     uint64_t st[12] = {0}, in[8], out[8];

@@ -90,7 +90,6 @@ size_t vx_justification_proof_bound(const vx_stark_config* cfg, size_t n_authori
 int32_t vx_justification_expect(const uint64_t* ppub_chain, size_t n_chain, const uint64_t* ppub_ed, size_t n_ed, size_t n_s512, const uint8_t authority_set_hash[32],
                                 uint64_t authority_set_id, const uint8_t block_hash[32], uint32_t block_number, uint64_t round, uint64_t spub[10], uint64_t epub[2],
                                 uint64_t hpub[15], int air[3], char* err, size_t errlen);
-void vx_shared_challenges_host(const uint64_t* const* pubs, const size_t* n_pubs, const uint64_t* const* caps, size_t k, size_t cap_words, uint64_t* out, size_t n_out);
 
 // ---- rotate blob (written by vx_rotate_prove in vx_rotate.hip, read by vx_rotate_verify in vx_verify.hip)
 static const uint64_t VX_ROT_MAGIC = 0x3354415458525856ULL;  // "VXRXTAT3"

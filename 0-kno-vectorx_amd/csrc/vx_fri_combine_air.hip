@@ -19,7 +19,7 @@
 
 #include "air_fri_combine.cuh"
 #include "air_fri_fold.cuh"
-#include "glh_poseidon.h"
+#include "stark_proof.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
 #include "vx_table_shapes.h"
@@ -138,11 +138,6 @@ bool shape_ok(int log_lde, int rate_bits, size_t cm, size_t ca, size_t nq, size_
            n_queries <= MAX_QUERIES;
 }
 #define FC_SHAPE_MSG "fri combine: log_lde %d (5..32), rate_bits %d (1..log_lde - 1), %zu main (1..2^20), %zu auxiliary (0..2^20), %zu quotient columns (1..2^20), %zu queries (1..2^20)"
-
-Fx fxinv(Fx x) {
-    const uint64_t ni = glh::inv(glh::sub(glh::mul(x.a, x.a), glh::mul(7, glh::mul(x.b, x.b))));
-    return {glh::mul(x.a, ni), glh::mul(glh::sub(0, x.b), ni)};
-}
 }  // namespace
 
 int32_t vx_fri_combine_check_claims(vx_ctx* ctx, const FriCombineStmt& st, const uint64_t* index, const uint64_t* rows, const uint64_t* ev0, size_t n_queries) {
@@ -161,19 +156,9 @@ int32_t vx_fri_combine_check_claims(vx_ctx* ctx, const FriCombineStmt& st, const
 
 // what prover and verifier compute ONCE per proof: alpha^c, zeta' = zeta w_n and the reduced openings
 void vx_fri_combine_reduced(const FriCombineStmt& st, uint64_t alphac[2], uint64_t zetan[2], uint64_t y0[2], uint64_t y1[2]) {
-    const size_t c = st.cm + st.ca;
-    const Fx alpha{st.alpha[0], st.alpha[1]};
-    Fx ap{1, 0}, a0{0, 0}, a1{0, 0};
-    for (size_t j = 0; j < c; ++j) {
-        a0 = a0 + ap * Fx{st.open_local[2 * j], st.open_local[2 * j + 1]};
-        a1 = a1 + ap * Fx{st.open_next[2 * j], st.open_next[2 * j + 1]};
-        ap = ap * alpha;
-    }
+    const stark_proof::Reduced red = stark_proof::reduce_openings(Fx{st.alpha[0], st.alpha[1]}, st.open_local, st.open_next, st.open_quot, st.cm + st.ca, st.nq);
+    const Fx ap = red.alpha_c, a0 = red.y0, a1 = red.y1;
     alphac[0] = ap.a, alphac[1] = ap.b;
-    for (size_t j = 0; j < st.nq; ++j) {
-        a0 = a0 + ap * Fx{st.open_quot[2 * j], st.open_quot[2 * j + 1]};
-        ap = ap * alpha;
-    }
     const Fx zn = Fx{st.zeta[0], st.zeta[1]} * Fx{glh::root(st.log_lde - st.rate_bits), 0};
     zetan[0] = zn.a, zetan[1] = zn.b, y0[0] = a0.a, y0[1] = a0.b, y1[0] = a1.a, y1[1] = a1.b;
 }
@@ -260,7 +245,7 @@ int32_t vx_fri_combine_host(vx_ctx* ctx, const FriCombineStmt& st, const uint64_
             if (j + 1 == c) s1 = s0;
             ap = ap * alpha;
         }
-        const Fx ev = Fx{ac[0], ac[1]} * (s0 - Fx{y0[0], y0[1]}) * fxinv(e0) + (s1 - Fx{y1[0], y1[1]}) * fxinv(e1);
+        const Fx ev = Fx{ac[0], ac[1]} * (s0 - Fx{y0[0], y0[1]}) * fx_inv(e0) + (s1 - Fx{y1[0], y1[1]}) * fx_inv(e1);
         ev0_out[2 * i] = ev.a, ev0_out[2 * i + 1] = ev.b;
     }
     return VX_OK;

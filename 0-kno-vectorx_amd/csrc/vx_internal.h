@@ -9,42 +9,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/vx.h"
 #pragma GCC visibility pop
-
-// ---- host-side Goldilocks (table generation, transcript) ----------------------------
-namespace glh {
-static const uint64_t P = 0xFFFFFFFF00000001ULL;
-static inline uint64_t add(uint64_t a, uint64_t b) {
-    uint64_t s = a + b;
-    return (s < a || s >= P) ? s - P : s;
-}
-static inline uint64_t sub(uint64_t a, uint64_t b) { return a >= b ? a - b : a + (P - b); }
-// x mod p for any 128-bit x, without the 128-bit division `% P` compiles to (__umodti3, ~30 ns -- the host transcript absorbs
-// thousands of elements per proof): x = lo + hl 2^64 + hh 2^96 = lo - hh + hl (2^32 - 1) (mod p), 2^64 = 2^32 - 1, 2^96 = -1.
-static inline uint64_t reduce128(unsigned __int128 x) {
-    const uint64_t lo = (uint64_t)x, hi = (uint64_t)(x >> 64), hh = hi >> 32, hl = hi & 0xFFFFFFFFULL;
-    uint64_t t0, t2;
-    if (__builtin_sub_overflow(lo, hh, &t0)) t0 -= 0xFFFFFFFFULL;  // + p (mod 2^64); t0 >= 2^64 - 2^32 here, cannot wrap again
-    if (__builtin_add_overflow(t0, hl * 0xFFFFFFFFULL, &t2)) t2 += 0xFFFFFFFFULL;  // - p (mod 2^64); the wrapped sum is < 2^64 - 2^32
-    return t2 >= P ? t2 - P : t2;
-}
-static inline uint64_t mul(uint64_t a, uint64_t b) { return reduce128((unsigned __int128)a * b); }
-static inline uint64_t pow(uint64_t a, uint64_t e) {
-    uint64_t r = 1;
-    while (e) {
-        if (e & 1) r = mul(r, a);
-        a = mul(a, a);
-        e >>= 1;
-    }
-    return r;
-}
-static inline uint64_t inv(uint64_t a) { return pow(a, P - 2); }
-static const uint64_t ROOT_2_32 = 1753635133440165772ULL;  // 7^((p-1)/2^32)
-static inline uint64_t root(int log_n) {
-    uint64_t r = ROOT_2_32;
-    for (int i = 32; i > log_n; --i) r = mul(r, r);
-    return r;
-}
-}  // namespace glh
+#include "glh.h"
 
 // Issue priority of the tail kernels (tree tops, small-tree leaves, query-phase gathers): they never fill the chip and do under 2 %
 // of a proof's VALU work, but run beside resident hash / NTT waves, and VALU issue goes by priority before age.  -DVX_TAIL_PRIO=0
@@ -167,8 +132,6 @@ void vx_shared_challenges(const uint64_t* pub_a, size_t n_a, const uint64_t* cap
 // receives a pointer to the values published with the auxiliary cap, and log_n_out the degree bits
 int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
                             size_t n_expect_public, const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen);
-// (public inputs, trace cap) of a serialised proof, for deriving shared challenges; false if the proof is too short
-bool vx_stark_proof_peek(const uint64_t* proof, size_t len, int cap_height, const uint64_t** pub, size_t* n_pub, const uint64_t** cap);
 int32_t vx_lde_keep_dev(vx_ctx* ctx, const uint64_t* values, int log_n, size_t n_cols, int rate_bits, uint64_t shift, uint64_t* coef_brev,
                         uint64_t* dst);
 int32_t vx_scan_cols_dev(vx_ctx* ctx, uint64_t* data, int log_n, size_t n_cols, uint64_t* totals_host);

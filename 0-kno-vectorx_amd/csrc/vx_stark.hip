@@ -22,42 +22,10 @@
 
 #include "air_list.h"
 #include "air_program.h"
-#include "glh_poseidon.h"
+#include "stark_proof.h"
 #include "vx_internal.h"
 
-// ------------------------------------------------------------------ challenger over the host Poseidon (glh_poseidon.h)
-namespace {
-inline void h_poseidon(uint64_t* s) { glh::poseidon(s); }
-struct Ext {
-    uint64_t a, b;
-};
-inline Ext e_add(Ext x, Ext y) { return {glh::add(x.a, y.a), glh::add(x.b, y.b)}; }
-inline Ext e_sub(Ext x, Ext y) { return {glh::sub(x.a, y.a), glh::sub(x.b, y.b)}; }
-inline Ext e_mul(Ext x, Ext y) {
-    return {glh::add(glh::mul(x.a, y.a), glh::mul(7, glh::mul(x.b, y.b))), glh::add(glh::mul(x.a, y.b), glh::mul(x.b, y.a))};
-}
-inline Ext e_scale(Ext x, uint64_t s) { return {glh::mul(x.a, s), glh::mul(x.b, s)}; }
-inline Ext e_inv(Ext x) {
-    uint64_t n = glh::sub(glh::mul(x.a, x.a), glh::mul(7, glh::mul(x.b, x.b)));
-    uint64_t ni = glh::inv(n);
-    return {glh::mul(x.a, ni), glh::mul(glh::sub(0, x.b), ni)};
-}
-inline Ext e_pow(Ext x, uint64_t e) {
-    Ext r{1, 0};
-    while (e) {
-        if (e & 1) r = e_mul(r, x);
-        x = e_mul(x, x);
-        e >>= 1;
-    }
-    return r;
-}
-struct Challenger : glh::Challenger {  // plonky2 iop/challenger.rs (glh_poseidon.h)
-    Ext ext_challenge() {
-        uint64_t a = challenge(), b = challenge();
-        return {a, b};
-    }
-};
-}  // namespace
+namespace sp = stark_proof;
 
 // ------------------------------------------------------------------ kernels
 __device__ __forceinline__ uint64_t root_pow_f(const uint64_t* tw, uint64_t e, int log_s) {
@@ -451,25 +419,11 @@ struct DevMem {  // RAII for the prover's temporaries (recycled through the ctx 
     }
 };
 
-static const uint64_t VX_PROOF_MAGIC = 0x314b524154535856ULL;  // "VXSTARK1"
-
-static void push_cap(vx_ctx* ctx, const vx_tree* t, std::vector<uint64_t>& out) {
+// the cap of a tree into its place in the proof
+static void read_cap(vx_ctx* ctx, const vx_tree* t, uint64_t* out) {
     size_t cap = (size_t)4 << t->cap_height;
-    size_t o = out.size();
-    out.resize(o + cap);
-    (void)hipMemcpyAsync(out.data() + o, t->levels + t->total - cap, cap * 8, hipMemcpyDeviceToHost, ctx->stream);
+    (void)hipMemcpyAsync(out, t->levels + t->total - cap, cap * 8, hipMemcpyDeviceToHost, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
-}
-
-static std::vector<int> fri_arity_plan(int degree_bits, const vx_stark_config& cfg) {
-    // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits)
-    std::vector<int> r;
-    int d = degree_bits;
-    while (d > cfg.final_poly_bits && d + cfg.rate_bits - cfg.arity_bits >= cfg.cap_height) {
-        r.push_back(cfg.arity_bits);
-        d -= cfg.arity_bits;
-    }
-    return r;
 }
 
 struct DevMem;
@@ -493,17 +447,7 @@ int32_t vx_stark_default_config(vx_stark_config* cfg) {
 int32_t vx_stark_proof_bound(int air_id, const vx_stark_config* cfg, int log_n, size_t* n_words) {
     const AirDesc* air = find_air(air_id);
     if (!air || !cfg || !n_words || log_n < 2 || cfg->rate_bits < 1) return VX_ERR_ARG;
-    const size_t c = (size_t)air->cols + air->aux, nq = 4, LN = log_n + cfg->rate_bits, cap = (size_t)4 << cfg->cap_height;
-    const std::vector<int> ar = fri_arity_plan(log_n, *cfg);
-    size_t per_query = c + nq + 2 * 4 * LN, words = 16 + ar.size() + air->pub + 2 * cap + 2 * (2 * c + nq) + ar.size() * cap + 1;
-    if (air->aux) per_query += 4 * LN, words += cap + 2 * (size_t)air->auxpub;  // the auxiliary tree: cap, published values, one more path
-    size_t cur = LN;
-    for (int a : ar) {
-        per_query += 2 * (((size_t)1 << a) - 1) + 4 * cur;
-        cur -= a;
-    }
-    words += 2 * (((size_t)1 << cur) >> cfg->rate_bits) + cfg->num_queries * per_query;
-    *n_words = words;
+    *n_words = sp::Shape(air_id, air->cols, air->aux, air->pub, air->auxpub, log_n, *cfg).bound_words();
     return VX_OK;
 }
 
@@ -680,12 +624,7 @@ static int32_t quotient_eval_dev(vx_ctx* ctx, const AirDesc* air, int L, int r, 
 
 // Lookup challenges shared by two tables: a transcript of both tables' public inputs and trace caps.
 void vx_shared_challenges_n(const uint64_t* const* pubs, const size_t* n_pubs, const uint64_t* const* caps, size_t k, size_t cap_words, uint64_t* out, size_t n_out) {
-    Challenger sc;
-    for (size_t t = 0; t < k; ++t) {
-        sc.observe(pubs[t], n_pubs[t]);
-        sc.observe(caps[t], cap_words);
-    }
-    for (size_t q = 0; q < n_out; ++q) out[q] = sc.challenge();
+    sp::shared_challenges_n(pubs, n_pubs, caps, k, cap_words, out, n_out);
 }
 void vx_shared_challenges(const uint64_t* pub_a, size_t n_a, const uint64_t* cap_a, const uint64_t* pub_b, size_t n_b, const uint64_t* cap_b,
                           size_t cap_words, uint64_t* out, size_t n_out) {
@@ -704,12 +643,15 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     VX_CHECK(air, "stark prove: unknown AIR id %d", air_id);
     const vx_stark_config cfg = *cfg_in;
     VX_CHECK(cfg.rate_bits >= 1 && cfg.rate_bits <= 3, "stark prove: rate_bits %d not in [1,3]", cfg.rate_bits);
-    VX_CHECK(cfg.arity_bits >= 1 && cfg.arity_bits <= 5 && cfg.final_poly_bits >= 0 && cfg.num_queries >= 1 && cfg.num_queries <= 1024 &&
-                 cfg.pow_bits >= 0 && cfg.pow_bits <= 32, "stark prove: bad FRI config");
     const int L = log_n, r = cfg.rate_bits, LN = L + r;
     VX_CHECK(L >= air->period_log && L >= 2 && LN <= 27, "stark prove: log_n %d out of range", L);
     VX_CHECK(!air->exact_log || L == air->period_log, "stark prove: AIR %d has positional columns of period 2^%d, the trace must have exactly that many rows", air_id, air->period_log);
     VX_CHECK(cfg.cap_height >= 0 && cfg.cap_height <= LN, "stark prove: cap_height %d > log2(lde size) %d", cfg.cap_height, LN);
+    {  // the verifier's ranges; a final_poly_bits above 27 plans the same layers as 27 (log_n <= 26) and is not in the proof, so it stays accepted
+        vx_stark_config k = cfg;
+        if (k.final_poly_bits > 27) k.final_poly_bits = 27;
+        VX_CHECK(sp::config_ok(k), "stark prove: bad FRI config");
+    }
     VX_CHECK((int)n_public == air->pub && (n_public == 0 || public_inputs), "stark prove: AIR %d takes %d public inputs", air_id, air->pub);
     // c = every committed trace column (main ++ auxiliary); the first cm come from the caller, the other ca are derived
     // after the lookup challenges are known
@@ -717,10 +659,13 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     VX_CHECK(trace_len >= n * cm, "stark prove: trace holds %zu < %zu elements", trace_len, n * cm);
     VX_CHECK(air->chal <= 8 && 2 * air->auxpub <= 8 && (ca == 0 || air_has_gen_aux(air)), "stark prove: AIR %d auxiliary round is misconfigured (a program needs its gen_aux callback to be proven)", air_id);
     for (size_t i = 0; i < n_public; ++i) VX_CHECK(public_inputs[i] < glh::P, "stark prove: public input %zu not canonical", i);
-    const int Q = 2, nq = 2 * Q;  // quotient_degree_factor 2 (constraint degree 3), 2 challenges
+    const int nq = sp::NQ, Q = nq / 2;  // quotient_degree_factor 2 (constraint degree 3), 2 challenges
     const uint64_t g = 7;         // F::coset_shift()
     DevMem mem(ctx);
-    std::vector<uint64_t> proof;
+    const sp::Shape shape(air_id, cm, ca, n_public, air->auxpub, L, cfg);
+    sp::Writer proof(shape, public_inputs);
+    const std::vector<int>& arities = shape.arities;
+    const size_t final_len = shape.final_len;
 
     // ---- 1. trace commitment: PolynomialBatch::from_values
     uint64_t* trace_lde = mem.alloc(N * c);
@@ -738,26 +683,10 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     vx_tree* t_trace = nullptr;
     VX_TRY(vx_merkle_build_dev(ctx, trace_lde, N, cm, VX_LEAVES_COLS_BITREV, cfg.cap_height, &t_trace));
     mem.trees.push_back(t_trace);
+    read_cap(ctx, t_trace, proof.cap_trace());
 
-    const std::vector<int> arities = fri_arity_plan(L, cfg);
-    int final_log = LN;
-    for (int a : arities) final_log -= a;
-    const size_t final_len = ((size_t)1 << final_log) >> r;
-
-    proof.push_back(VX_PROOF_MAGIC);
-    for (uint64_t w : {(uint64_t)air_id, (uint64_t)L, (uint64_t)cm, (uint64_t)nq, (uint64_t)r, (uint64_t)cfg.cap_height,
-                       (uint64_t)cfg.num_queries, (uint64_t)cfg.pow_bits, (uint64_t)arities.size()})
-        proof.push_back(w);
-    for (int a : arities) proof.push_back((uint64_t)a);
-    proof.push_back((uint64_t)final_len);
-    proof.push_back((uint64_t)n_public);
-    for (size_t i = 0; i < n_public; ++i) proof.push_back(public_inputs[i]);
-    const size_t cap_words = (size_t)4 << cfg.cap_height;
-    push_cap(ctx, t_trace, proof);
-
-    Challenger ch;
-    ch.observe(public_inputs, n_public);
-    ch.observe(proof.data() + proof.size() - cap_words, cap_words);
+    sp::Transcript ch;
+    ch.trace(proof);
     // ---- 1b. auxiliary round (lookup arguments): challenges after the trace cap, derived columns in a second tree
     uint64_t chal[8] = {0}, apub[8] = {0};
     uint64_t* aux_d = nullptr;  // [ca][n]: values, then (after the in-place inverse NTT) coefficients in bit-reversed positions
@@ -766,25 +695,23 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
         if (hook) {
             // lookup challenges SHARED with other tables (a bus between AIRs): the caller derives them once every
             // table's trace cap exists; this transcript absorbs them so that everything after depends on them
-            const int32_t hr = hook->fn(hook->user, public_inputs, n_public, proof.data() + proof.size() - cap_words, cap_words, chal, (size_t)air->chal);
+            const int32_t hr = hook->fn(hook->user, public_inputs, n_public, proof.cap_trace(), shape.cap_words, chal, (size_t)air->chal);
             if (hr != VX_OK) return vx_fail(ctx, hr, "stark prove: no shared challenges (the prover of the other table on the bus gave up)");
             for (int q = 0; q < air->chal; ++q) VX_CHECK(chal[q] < glh::P, "stark prove: shared challenge %d is not canonical", q);
-            ch.observe(chal, (size_t)air->chal);
-        } else
-            for (int q = 0; q < air->chal; ++q) chal[q] = ch.challenge();
+        }
+        ch.lookup_challenges(chal, (size_t)air->chal, hook ? chal : nullptr);
         aux_d = mem.alloc(n * ca);
         VX_CHECK(aux_d, "stark prove: out of device memory (auxiliary trace)");
         VX_TRY(air_gen_aux(ctx, air, trace_d, L, chal, public_inputs, aux_d, apub));
         VX_TRY(vx_lde_consume_dev(ctx, aux_d, L, ca, r, g, trace_lde + N * cm));
         VX_TRY(vx_merkle_build_dev(ctx, trace_lde + N * cm, N, ca, VX_LEAVES_COLS_BITREV, cfg.cap_height, &t_aux));
         mem.trees.push_back(t_aux);
-        for (int q = 0; q < 2 * air->auxpub; ++q) proof.push_back(apub[q]);
-        push_cap(ctx, t_aux, proof);
-        ch.observe(apub, 2 * (size_t)air->auxpub);
-        ch.observe(proof.data() + proof.size() - cap_words, cap_words);
+        std::copy(apub, apub + 2 * air->auxpub, proof.apub());
+        read_cap(ctx, t_aux, proof.cap_aux());
+        ch.aux(proof);
     }
-    uint64_t alphas[2] = {ch.challenge(), 0};
-    alphas[1] = ch.challenge();
+    uint64_t alphas[2];
+    ch.alphas(alphas);
 
     // ---- 2. quotient polynomials (compute_quotient_polys) on the size-N coset
     uint64_t* qv = mem.alloc(2 * N);
@@ -802,15 +729,10 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     vx_tree* t_quot = nullptr;
     VX_TRY(vx_merkle_build_dev(ctx, quot_lde, N, nq, VX_LEAVES_COLS_BITREV, cfg.cap_height, &t_quot));
     mem.trees.push_back(t_quot);
-    push_cap(ctx, t_quot, proof);
-    ch.observe(proof.data() + proof.size() - cap_words, cap_words);
-    const Ext zeta = ch.ext_challenge();
-    const uint64_t wn = glh::root(L);
-    const Ext zeta_next = e_scale(zeta, wn);
-    {
-        Ext zn = e_pow(zeta, n);
-        VX_CHECK(!(zn.a == 1 && zn.b == 0), "stark prove: zeta landed in the trace subgroup");
-    }
+    read_cap(ctx, t_quot, proof.cap_quot());
+    const Fx zeta = ch.zeta(proof);
+    const Fx zeta_next = fx_scale(zeta, glh::root(L));
+    VX_CHECK(!fx_eq(fx_pow(zeta, n), Fx{1, 0}), "stark prove: zeta landed in the trace subgroup");
 
     // ---- 3. openings (StarkOpeningSet::new): barycentric dot products over the committed LDE values at the
     // coset points g * w_n^i (every 2^r-th LDE point) -- neither the trace values nor coefficients are needed
@@ -827,12 +749,12 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
         // the coefficients are at hand (bit-reversed positions): plain evaluation, no barycentric factor
         PowBrevArgs pa{};
         pa.log_n = L;
-        Ext z0 = zeta, z1 = zeta_next;
+        Fx z0 = zeta, z1 = zeta_next;
         for (int b = 0; b < L; ++b) {
             pa.z0[b] = {z0.a, z0.b};
             pa.z1[b] = {z1.a, z1.b};
-            z0 = e_mul(z0, z0);
-            z1 = e_mul(z1, z1);
+            z0 = z0 * z0;
+            z1 = z1 * z1;
         }
         hipLaunchKernelGGL(k_pow_brev_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, pa, w0, w1);
         hipLaunchKernelGGL(k_bary_dot, dim3((unsigned)((cm + BARY_CPB - 1) / BARY_CPB), BARY_SPLIT), dim3(256), 0, ctx->stream, (const uint64_t*)coef_main, n, 0, n, cm, (const uint64_t*)w0,
@@ -851,38 +773,22 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     for (int sp = 1; sp < BARY_SPLIT; ++sp)  // the partial sums of the split blocks
         for (size_t j = 0; j < open_words; ++j) h_open[j] = glh::add(h_open[j], h_open[sp * open_words + j]);
     const uint64_t gn_ = glh::pow(g, n), fsc = glh::inv(glh::mul(n % glh::P, gn_));
-    const Ext f0 = e_scale(e_sub(e_pow(zeta, n), Ext{gn_, 0}), fsc);       // (zeta^n - g^n) / (n g^n)
-    const Ext f1 = e_scale(e_sub(e_pow(zeta_next, n), Ext{gn_, 0}), fsc);  // ((w zeta)^n - g^n) / (n g^n)
-    std::vector<Ext> o_local(c), o_next(c), o_quot(nq);
-    const Ext one_{1, 0};
-    const Ext t0 = coef_main ? one_ : f0, t1 = coef_main ? one_ : f1;  // coefficient sums need no factor
-    for (size_t j = 0; j < c; ++j) {
-        o_local[j] = e_mul(t0, Ext{h_open[4 * j], h_open[4 * j + 1]});
-        o_next[j] = e_mul(t1, Ext{h_open[4 * j + 2], h_open[4 * j + 3]});
-    }
-    for (int j = 0; j < nq; ++j) o_quot[j] = e_mul(f0, Ext{h_open[4 * (c + j)], h_open[4 * (c + j) + 1]});
-    for (const Ext& e : o_local) proof.push_back(e.a), proof.push_back(e.b);
-    for (const Ext& e : o_next) proof.push_back(e.a), proof.push_back(e.b);
-    for (const Ext& e : o_quot) proof.push_back(e.a), proof.push_back(e.b);
-    // challenger.observe_openings: batch 0 = local ++ quotient, batch 1 = next
-    for (const Ext& e : o_local) ch.observe(e.a), ch.observe(e.b);
-    for (const Ext& e : o_quot) ch.observe(e.a), ch.observe(e.b);
-    for (const Ext& e : o_next) ch.observe(e.a), ch.observe(e.b);
+    const Fx f0 = fx_scale(fx_pow(zeta, n) - Fx{gn_, 0}, fsc);       // (zeta^n - g^n) / (n g^n)
+    const Fx f1 = fx_scale(fx_pow(zeta_next, n) - Fx{gn_, 0}, fsc);  // ((w zeta)^n - g^n) / (n g^n)
+    const Fx one_{1, 0};
+    const Fx t0 = coef_main ? one_ : f0, t1 = coef_main ? one_ : f1;  // coefficient sums need no factor
+    auto open = [&](uint64_t* out, Fx factor, size_t at) {
+        const Fx o = factor * Fx{h_open[at], h_open[at + 1]};
+        out[0] = o.a, out[1] = o.b;
+    };
+    for (size_t j = 0; j < c; ++j) open(proof.open_local() + 2 * j, t0, 4 * j), open(proof.open_next() + 2 * j, t1, 4 * j + 2);
+    for (size_t j = 0; j < (size_t)nq; ++j) open(proof.open_quot() + 2 * j, f0, 4 * (c + j));
 
     // ---- 4. FRI batch polynomial (prove_openings), in evaluation space
-    const Ext alpha = ch.ext_challenge();
+    const Fx alpha = ch.alpha(proof);
     std::vector<uint64_t> apow(2 * (c + nq));
-    Ext cur{1, 0}, y0{0, 0}, y1{0, 0}, alpha_c{1, 0};
-    for (size_t j = 0; j < c + nq; ++j) {
-        apow[2 * j] = cur.a;
-        apow[2 * j + 1] = cur.b;
-        if (j < c) {
-            y0 = e_add(y0, e_mul(cur, o_local[j]));
-            y1 = e_add(y1, e_mul(cur, o_next[j]));
-        } else y0 = e_add(y0, e_mul(cur, o_quot[j - c]));
-        cur = e_mul(cur, alpha);
-        if (j + 1 == c) alpha_c = cur;
-    }
+    const sp::Reduced red = sp::reduce_openings(alpha, proof.open_local(), proof.open_next(), proof.open_quot(), c, nq, apow.data());
+    const Fx y0 = red.y0, y1 = red.y1, alpha_c = red.alpha_c;
     uint64_t* d_apow = mem.alloc(apow.size());
     std::vector<uint64_t*> layers;
     layers.push_back(mem.alloc(2 * N));
@@ -920,9 +826,8 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
         mem.trees.push_back(t);
         ltrees.push_back(t);
         llog.push_back(cur_log);
-        push_cap(ctx, t, proof);
-        ch.observe(proof.data() + proof.size() - cap_words, cap_words);
-        const Ext beta = ch.ext_challenge();
+        read_cap(ctx, t, proof.layer_cap(ltrees.size() - 1));
+        const Fx beta = ch.beta(proof, ltrees.size() - 1);
         const uint64_t b2[2] = {beta.a, beta.b};
         uint64_t* nxt = mem.alloc((size_t)2 << (cur_log - a));
         VX_CHECK(nxt, "stark prove: out of device memory (FRI layer)");
@@ -940,14 +845,14 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
         const uint64_t wi = glh::inv(glh::root(cur_log)), minv = glh::inv(fm % glh::P), sinv = glh::inv(shift);
         uint64_t sk = 1;
         for (size_t k = 0; k < fm; ++k) {
-            Ext acc{0, 0};
+            Fx acc{0, 0};
             const uint64_t wk = glh::pow(wi, k);
             uint64_t wcur = 1;
             for (size_t i = 0; i < fm; ++i) {
-                acc = e_add(acc, e_scale(Ext{fv[2 * i], fv[2 * i + 1]}, wcur));
+                acc = acc + fx_scale(Fx{fv[2 * i], fv[2 * i + 1]}, wcur);
                 wcur = glh::mul(wcur, wk);
             }
-            acc = e_scale(acc, glh::mul(minv, sk));
+            acc = fx_scale(acc, glh::mul(minv, sk));
             fc[2 * k] = acc.a;
             fc[2 * k + 1] = acc.b;
             sk = glh::mul(sk, sinv);
@@ -955,26 +860,22 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     }
     for (size_t k = final_len; k < fm; ++k)
         VX_CHECK(fc[2 * k] == 0 && fc[2 * k + 1] == 0, "stark prove: final polynomial has degree >= %zu: the trace violates the AIR constraints", final_len);
-    for (size_t k = 0; k < 2 * final_len; ++k) proof.push_back(fc[k]);
-    ch.observe(fc.data(), 2 * final_len);
+    std::copy(fc.begin(), fc.begin() + 2 * final_len, proof.final_poly());
+    ch.final_poly(proof);
 
     // ---- 6. proof of work (fri_proof_of_work), smallest nonce
     {
-        uint64_t st[12];
-        memcpy(st, ch.st, sizeof st);
-        for (int i = 0; i < ch.n_in; ++i) st[i] = ch.in[i];
-        uint64_t nonce = 0;
-        VX_TRY(vx_fri_pow(ctx, st, ch.n_in, cfg.pow_bits, &nonce));
-        proof.push_back(nonce);
-        ch.observe(nonce);
-        const uint64_t resp = ch.challenge();
-        VX_CHECK(cfg.pow_bits == 0 || (resp >> (64 - cfg.pow_bits)) == 0, "stark prove: PoW response check failed");
+        uint64_t st[12], nonce = 0;
+        const int n_in = ch.grind_state(st);
+        VX_TRY(vx_fri_pow(ctx, st, n_in, cfg.pow_bits, &nonce));
+        *proof.nonce() = nonce;
+        VX_CHECK(ch.pow_ok(nonce, cfg.pow_bits), "stark prove: PoW response check failed");
     }
 
     // ---- 7. query phase (fri_prover_query_rounds)
     const size_t nqr = cfg.num_queries;
     std::vector<uint64_t> qidx(nqr);
-    for (size_t k = 0; k < nqr; ++k) qidx[k] = ch.challenge() % N;
+    for (size_t k = 0; k < nqr; ++k) qidx[k] = ch.query_index(N);
     const int depth0 = LN - cfg.cap_height;
     // One round trip: the per-layer indices are shifts of qidx, so every index array goes up in one copy, every gather of the table is
     // launched back to back into one scratch region, and the region comes back in one copy behind one synchronisation.
@@ -1023,27 +924,29 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     const uint64_t *rows_t = q.data() + o_rows_t, *rows_a = q.data() + o_rows_a, *rows_q = q.data() + o_rows_q;
     const uint64_t *sib_t = q.data() + o_sib_t, *sib_a = q.data() + o_sib_a, *sib_q = q.data() + o_sib_q;
     for (size_t k = 0; k < nqr; ++k) {
-        proof.insert(proof.end(), rows_t + k * cm, rows_t + (k + 1) * cm);
-        if (depth0 > 0) proof.insert(proof.end(), sib_t + k * depth0 * 4, sib_t + (k + 1) * depth0 * 4);
-        if (ca) {
-            proof.insert(proof.end(), rows_a + k * ca, rows_a + (k + 1) * ca);
-            if (depth0 > 0) proof.insert(proof.end(), sib_a + k * depth0 * 4, sib_a + (k + 1) * depth0 * 4);
+        const sp::Query<uint64_t> rec = proof.query(k);
+        std::copy(rows_t + k * cm, rows_t + (k + 1) * cm, rec.row_t());
+        std::copy(rows_a + k * ca, rows_a + (k + 1) * ca, rec.row_a());
+        std::copy(rows_q + k * nq, rows_q + (k + 1) * nq, rec.row_q());
+        if (depth0 > 0) {
+            std::copy(sib_t + k * depth0 * 4, sib_t + (k + 1) * depth0 * 4, rec.sib_t());
+            if (ca) std::copy(sib_a + k * depth0 * 4, sib_a + (k + 1) * depth0 * 4, rec.sib_a());
+            std::copy(sib_q + k * depth0 * 4, sib_q + (k + 1) * depth0 * 4, rec.sib_q());
         }
-        proof.insert(proof.end(), rows_q + k * nq, rows_q + (k + 1) * nq);
-        if (depth0 > 0) proof.insert(proof.end(), sib_q + k * depth0 * 4, sib_q + (k + 1) * depth0 * 4);
         uint64_t x_index = qidx[k];
         for (size_t l = 0; l < n_layers; ++l) {
-            const int a = arities[l], depth = llog[l] - a - cfg.cap_height;
+            const int a = arities[l], depth = shape.depth[l];
             const size_t arity = (size_t)1 << a, within = x_index & (arity - 1);
             const uint64_t* leaf = q.data() + o_leaves[l] + k * 2 * arity;
+            uint64_t* out = rec.evals(l);
             for (size_t t = 0; t < arity; ++t)  // evals.remove(x_index & (arity - 1))
-                if (t != within) proof.push_back(leaf[2 * t]), proof.push_back(leaf[2 * t + 1]);
-            if (depth > 0) proof.insert(proof.end(), q.data() + o_sibs[l] + k * depth * 4, q.data() + o_sibs[l] + (k + 1) * depth * 4);
+                if (t != within) *out++ = leaf[2 * t], *out++ = leaf[2 * t + 1];
+            if (depth > 0) std::copy(q.data() + o_sibs[l] + k * depth * 4, q.data() + o_sibs[l] + (k + 1) * depth * 4, rec.sibs(l));
             x_index >>= a;
         }
     }
-    *proof_len = proof.size();
-    if (!proof_out || proof_cap < proof.size()) return vx_fail(ctx, VX_ERR_BUFSZ, "stark prove: proof needs %zu words, buffer has %zu", proof.size(), proof_cap);
-    memcpy(proof_out, proof.data(), proof.size() * 8);
+    *proof_len = shape.words();
+    if (!proof_out || proof_cap < shape.words()) return vx_fail(ctx, VX_ERR_BUFSZ, "stark prove: proof needs %zu words, buffer has %zu", shape.words(), proof_cap);
+    memcpy(proof_out, proof.pr, shape.words() * 8);
     return VX_OK;
 }

@@ -22,7 +22,7 @@
 
 #include "air_list.h"
 #include "air_program.h"
-#include "glh_poseidon.h"
+#include "stark_proof.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
 #include "vx_table_shapes.h"
@@ -30,60 +30,6 @@
 static_assert(VX_BLAKE_TABLE_LOG == blk::TABLE_LOG, "vx_table_shapes.h and air_blake.cuh disagree on the rows of the XOR lookup tables");
 
 namespace {
-inline void v_poseidon(uint64_t* s) { glh::poseidon(s); }
-void v_hash_or_noop(const uint64_t* in, size_t len, uint64_t* out4) {
-    uint64_t s[12] = {0};
-    if (len <= 4) {
-        memcpy(s, in, len * 8);
-    } else {
-        for (size_t off = 0; off < len; off += 8) {
-            const size_t k = len - off < 8 ? len - off : 8;
-            memcpy(s, in + off, k * 8);
-            v_poseidon(s);
-        }
-    }
-    memcpy(out4, s, 32);
-}
-bool v_merkle(const uint64_t* leaf, size_t leaf_len, size_t idx, const uint64_t* sib, size_t n_sib, const uint64_t* cap) {
-    uint64_t cur[4];
-    v_hash_or_noop(leaf, leaf_len, cur);
-    for (size_t k = 0; k < n_sib; ++k) {
-        uint64_t s[12] = {0};
-        if (idx & 1) {
-            memcpy(s, sib + 4 * k, 32);
-            memcpy(s + 4, cur, 32);
-        } else {
-            memcpy(s, cur, 32);
-            memcpy(s + 4, sib + 4 * k, 32);
-        }
-        v_poseidon(s);
-        memcpy(cur, s, 32);
-        idx >>= 1;
-    }
-    return memcmp(cur, cap + 4 * idx, 32) == 0;
-}
-struct VChallenger : glh::Challenger {
-    Fx ext() {
-        const uint64_t a = challenge(), b = challenge();
-        return {a, b};
-    }
-};
-Fx fx_inv(Fx x) {
-    const uint64_t n = glh::sub(glh::mul(x.a, x.a), glh::mul(7, glh::mul(x.b, x.b)));
-    const uint64_t ni = glh::inv(n);
-    return {glh::mul(x.a, ni), glh::mul(glh::sub(0, x.b), ni)};
-}
-Fx fx_pow(Fx x, uint64_t e) {
-    Fx r{1, 0};
-    while (e) {
-        if (e & 1) r = r * x;
-        x = x * x;
-        e >>= 1;
-    }
-    return r;
-}
-bool fx_eq(Fx x, Fx y) { return x.a == y.a && x.b == y.b; }
-
 struct AirV {
     int id, cols, pub, periodic, period_log, exact_log;
     void (*periodic_values)(std::vector<uint64_t>&);
@@ -285,24 +231,6 @@ int32_t vx_stark_verify(const vx_stark_config* cfg, const uint64_t* pr, size_t l
 }
 }  // extern "C"
 
-bool vx_stark_proof_peek(const uint64_t* pr, size_t len, int cap_height, const uint64_t** pub, size_t* n_pub, const uint64_t** cap) {
-    if (len < 12 || pr[9] > 16) return false;
-    const size_t pos = 10 + pr[9];
-    if (pos + 2 > len) return false;
-    const size_t np = pr[pos + 1];
-    if (np > 64 || cap_height < 0 || cap_height > 16 || pos + 2 + np + ((size_t)4 << cap_height) > len) return false;
-    *pub = pr + pos + 2, *n_pub = np, *cap = pr + pos + 2 + np;
-    return true;
-}
-void v_shared_challenges_n(const uint64_t* const* pubs, const size_t* n_pubs, const uint64_t* const* caps, size_t k, size_t cap_words, uint64_t* out, size_t n_out) {
-    VChallenger sc;
-    for (size_t t = 0; t < k; ++t) {
-        sc.observe(pubs[t], n_pubs[t]);
-        sc.observe(caps[t], cap_words);
-    }
-    for (size_t q = 0; q < n_out; ++q) out[q] = sc.challenge();
-}
-
 // what the query phase of a verified proof hands to vx_stark_fri_claims: the FRI side of every query, as FriFoldAir's claims
 struct FriClaims {
     int log_lde = 0;
@@ -319,256 +247,123 @@ int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size
                             size_t n_expect_public, const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen) {
     return stark_verify_impl(cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, nullptr, err, errlen);
 }
-static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen) {
-    if (!cfg || !pr) return VX_ERR_ARG;
-    // the configuration steers loops below (a circuit.json can carry it): the same ranges the prover accepts (vx_stark.hip)
-    if (cfg->rate_bits < 1 || cfg->rate_bits > 3 || cfg->arity_bits < 1 || cfg->arity_bits > 5 || cfg->final_poly_bits < 0 || cfg->final_poly_bits > 27 ||
-        cfg->num_queries < 1 || cfg->num_queries > 1024 || cfg->pow_bits < 0 || cfg->pow_bits > 32 || cfg->cap_height < 0 || cfg->cap_height > 27) {
-        if (err && errlen) snprintf(err, errlen, "stark verify: configuration out of range");
-        return VX_ERR_ARG;
-    }
-    size_t pos = 0;
-    auto have = [&](size_t k) { return pos + k <= len; };
-    NEED(have(10), "proof truncated (header)");
-    NEED(pr[0] == 0x314b524154535856ULL, "bad magic");
+namespace sp = stark_proof;
+static std::vector<Fx> fx_pairs(const uint64_t* w, size_t n) {
+    std::vector<Fx> v(n);
+    for (size_t j = 0; j < n; ++j) v[j] = {w[2 * j], w[2 * j + 1]};
+    return v;
+}
+// The head of an untrusted proof: the AIR it names and its degree bits, such that a Shape may be built from them.
+static int32_t proof_air(const uint64_t* pr, size_t len, int expect_air, AirV* air, char* err, size_t errlen) {
+    NEED(len >= 10, "proof truncated (header)");
+    NEED(pr[0] == sp::MAGIC, "bad magic");
     // (every narrow header field is compared as the 64-bit word it is: a proof has ONE encoding)
     NEED(((pr[1] | pr[2] | pr[5] | pr[6] | pr[7] | pr[8]) >> 31) == 0, "header word out of range");
-    const int air_id = (int)pr[1], L = (int)pr[2];
-    const size_t nq = pr[4];
-    const int r = (int)pr[5], cap_h = (int)pr[6];
-    const size_t n_queries = pr[7];
-    const int pow_bits = (int)pr[8];
-    const size_t n_layers = pr[9];
-    pos = 10;
-    NEED(r == cfg->rate_bits && cap_h == cfg->cap_height && (int)n_queries == cfg->num_queries && pow_bits == cfg->pow_bits, "config mismatch");
-    NEED(L >= 2 && L <= 26 && n_layers <= 16, "bad shape");
-    const AirV* air = nullptr;
+    const int air_id = (int)pr[1];
+    NEED(pr[2] >= 2 && pr[2] <= 26 && pr[9] <= 16, "bad shape");
     for (const AirV& a : AIRS_V)
-        if (a.id == air_id) air = &a;
-    AirV prog_air{};
-    if (!air && air_id >= VX_AIR_USER_BASE) {
-        if (const AirProgram* pg = vx_air_program_find(air_id)) {
-            prog_air = {air_id, (int)pg->cols, (int)pg->pub, (int)pg->plog.size(), pg->period_log, 0, nullptr, nullptr, (int)pg->aux, (int)pg->chal, (int)pg->auxpub, nullptr, pg};
-            air = &prog_air;
+        if (a.id == air_id) *air = a;
+    if (!air->id && air_id >= VX_AIR_USER_BASE)
+        if (const AirProgram* pg = vx_air_program_find(air_id))
+            *air = {air_id, (int)pg->cols, (int)pg->pub, (int)pg->plog.size(), pg->period_log, 0, nullptr, nullptr, (int)pg->aux, (int)pg->chal, (int)pg->auxpub, nullptr, pg};
+    NEED(air->id && (expect_air == 0 || expect_air == air_id), "unexpected AIR %d", air_id);
+    return VX_OK;
+}
+// The constraint identity at zeta: the AIR's constraints over the openings, combined under the two alphas, against Z_H(zeta) times
+// the quotient assembled from its two chunks per challenge.
+static int32_t constraints_at_zeta(const AirV& air, const sp::View& v, const uint64_t* chal, const uint64_t alphas[2], Fx zeta, char* err, size_t errlen) {
+    const sp::Shape& s = *v.s;
+    const size_t n = (size_t)1 << s.L;
+    const uint64_t last = glh::inv(glh::root(s.L)), ninv = glh::inv(n % glh::P);
+    const std::vector<Fx> o_local = fx_pairs(v.open_local(), s.c), o_next = fx_pairs(v.open_next(), s.c), o_quot = fx_pairs(v.open_quot(), sp::NQ);
+    const Fx zn = fx_pow(zeta, n), one{1, 0};
+    const Fx zh = zn - one;
+    Consumer<Fx> cons;
+    cons.acc[0] = cons.acc[1] = {0, 0};
+    cons.alpha[0] = {alphas[0], 0};
+    cons.alpha[1] = {alphas[1], 0};
+    cons.z_last = zeta - Fx{last, 0};
+    cons.l_first = zh * Fx{ninv, 0} * fx_inv(zeta - one);
+    cons.l_last = zh * Fx{glh::mul(ninv, last), 0} * fx_inv(zeta - Fx{last, 0});
+    std::vector<Fx> per(air.periodic ? air.periodic : 1), pubx(s.n_pub ? s.n_pub : 1), chalx(8), apubx(8);
+    if (air.periodic) {
+        std::vector<uint64_t> pv;
+        if (air.prog) pv = air.prog->periodic;
+        else air.periodic_values(pv);
+        size_t in_off = 0;
+        for (int j = 0; j < air.periodic; ++j) {
+            const int pl = air.prog ? air.prog->plog[j] : air.plog(j);
+            const size_t p = (size_t)1 << pl;
+            NEED(in_off + p <= pv.size(), "periodic table of AIR %d is short", air.id);
+            std::vector<uint64_t> coef(pv.begin() + in_off, pv.begin() + in_off + p);
+            host_intt(coef);
+            const Fx y = fx_pow(zeta, n >> pl);
+            Fx a{0, 0};
+            for (size_t k = p; k-- > 0;) a = a * y + Fx{coef[k], 0};
+            per[j] = a;
+            in_off += p;
         }
     }
-    NEED(air && (expect_air == 0 || expect_air == air_id), "unexpected AIR %d", air_id);
-    const size_t cm = air->cols, ca = air->aux, c = cm + ca;  // main ++ auxiliary columns
-    // FRI reduction plan (ConstantArityBits)
-    std::vector<int> arities;
-    {
-        int d = L;
-        while (d > cfg->final_poly_bits && d + r - cfg->arity_bits >= cap_h) {
-            arities.push_back(cfg->arity_bits);
-            d -= cfg->arity_bits;
-        }
+    for (size_t i = 0; i < s.n_pub; ++i) pubx[i] = {v.pub()[i], 0};
+    for (int q = 0; q < air.chal; ++q) chalx[q] = {chal[q], 0};
+    for (size_t q = 0; s.ca && q < 2 * s.auxpub; ++q) apubx[q] = {v.apub()[q], 0};
+    HostRow loc{o_local.data()}, nxt{o_next.data()};
+    if (air.prog) air_program_eval<Fx>(*air.prog, loc, nxt, per.data(), pubx.data(), chalx.data(), apubx.data(), cons);
+    else air.eval(loc, nxt, per.data(), pubx.data(), chalx.data(), apubx.data(), cons);
+    for (int k = 0; k < 2; ++k) {
+        const Fx q = o_quot[2 * k] + o_quot[2 * k + 1] * zn;
+        NEED(fx_eq(cons.acc[k], zh * q), "constraint identity fails at zeta (challenge %d)", k);
     }
-    NEED(have(n_layers + 2) && n_layers == arities.size(), "FRI plan mismatch");
-    for (size_t i = 0; i < n_layers; ++i) NEED(pr[pos + i] == (uint64_t)arities[i], "FRI plan mismatch");
-    pos += n_layers;
-    const size_t final_len = pr[pos], n_pub = pr[pos + 1];
-    pos += 2;
-    const int LN = L + r;
-    const size_t n = (size_t)1 << L, N = (size_t)1 << LN;
-    int final_log = LN;
-    for (int a : arities) final_log -= a;
-    NEED(pr[3] == (uint64_t)air->cols && n_pub == (size_t)air->pub && nq == 4 && final_len == (((size_t)1 << final_log) >> r), "shape mismatch");
-    // the proof is untrusted input: the shapes the prover refuses (vx_stark_prove_impl) are refused here too, so no
-    // Merkle depth below can go negative (a crafted L = 2 proof used to reach v_merkle with n_sib = SIZE_MAX)
-    NEED(r >= 1 && r <= 3 && cap_h >= 0 && LN >= cap_h && LN <= 27 && L >= air->period_log, "degree bits %d out of range for this AIR / cap height", L);
-    NEED(!air->exact_log || L == air->period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air->period_log, L);
-    {
-        int cur = LN;
-        for (int a : arities) {
-            NEED(cur - a - cap_h >= 0, "FRI layer below the cap height");
-            cur -= a;
-        }
-    }
-    for (size_t i = 0; i < len; ++i) NEED(pr[i] < glh::P || i < pos, "non-canonical element at word %zu", i);
-    NEED(have(n_pub), "proof truncated (public inputs)");
-    const uint64_t* pub = pr + pos;
-    pos += n_pub;
-    if (expect_public) {
-        NEED(n_expect_public == n_pub, "public input count differs");
-        for (size_t i = 0; i < n_pub; ++i) NEED(pub[i] == expect_public[i], "public input %zu differs", i);
-    }
-    const size_t cap_words = (size_t)4 << cap_h;
-    NEED(have((ca ? 3 : 2) * cap_words + 2 * (size_t)air->auxpub + 2 * (2 * c + nq)), "proof truncated (caps/openings)");
-    const uint64_t* cap_t = pr + pos;
-    pos += cap_words;
-    const uint64_t *apub = nullptr, *cap_a = nullptr;
-    if (ca) {
-        apub = pr + pos;
-        cap_a = pr + pos + 2 * (size_t)air->auxpub;
-        pos += 2 * (size_t)air->auxpub + cap_words;
-    }
-    const uint64_t* cap_q = pr + pos;
-    pos += cap_words;
-    std::vector<Fx> o_local(c), o_next(c), o_quot(nq);
-    for (size_t j = 0; j < c; ++j) o_local[j] = {pr[pos + 2 * j], pr[pos + 2 * j + 1]};
-    pos += 2 * c;
-    for (size_t j = 0; j < c; ++j) o_next[j] = {pr[pos + 2 * j], pr[pos + 2 * j + 1]};
-    pos += 2 * c;
-    for (size_t j = 0; j < nq; ++j) o_quot[j] = {pr[pos + 2 * j], pr[pos + 2 * j + 1]};
-    pos += 2 * nq;
-
-    VChallenger ch;
-    ch.observe(pub, n_pub);
-    ch.observe(cap_t, cap_words);
-    uint64_t chal[8] = {0};
-    if (ca) {  // auxiliary round: lookup challenges after the trace cap, then the published values and the second cap
-        NEED(air->chal <= 8 && 2 * air->auxpub <= 8, "AIR %d auxiliary round is misconfigured", air_id);
-        if (ext_chal) {
-            for (int q = 0; q < air->chal; ++q) chal[q] = ext_chal[q];
-            ch.observe(chal, (size_t)air->chal);
-        } else
-            for (int q = 0; q < air->chal; ++q) chal[q] = ch.challenge();
-        ch.observe(apub, 2 * (size_t)air->auxpub);
-        ch.observe(cap_a, cap_words);
-    }
-    const uint64_t alphas[2] = {ch.challenge(), ch.challenge()};
-    ch.observe(cap_q, cap_words);
-    const Fx zeta = ch.ext();
-    const uint64_t wn = glh::root(L), last = glh::inv(wn), ninv = glh::inv(n % glh::P);
-    const Fx zeta_next = zeta * Fx{wn, 0};
-    // ---- constraint identity at zeta
-    {
-        const Fx zn = fx_pow(zeta, n), one{1, 0};
-        const Fx zh = zn - one;
-        Consumer<Fx> cons;
-        cons.acc[0] = cons.acc[1] = {0, 0};
-        cons.alpha[0] = {alphas[0], 0};
-        cons.alpha[1] = {alphas[1], 0};
-        cons.z_last = zeta - Fx{last, 0};
-        cons.l_first = zh * Fx{ninv, 0} * fx_inv(zeta - one);
-        cons.l_last = zh * Fx{glh::mul(ninv, last), 0} * fx_inv(zeta - Fx{last, 0});
-        std::vector<Fx> per(air->periodic ? air->periodic : 1), pubx(n_pub ? n_pub : 1), chalx(8), apubx(8);
-        if (air->periodic) {
-            std::vector<uint64_t> pv;
-            if (air->prog) pv = air->prog->periodic;
-            else air->periodic_values(pv);
-            size_t in_off = 0;
-            for (int j = 0; j < air->periodic; ++j) {
-                const int pl = air->prog ? air->prog->plog[j] : air->plog(j);
-                const size_t p = (size_t)1 << pl;
-                NEED(in_off + p <= pv.size(), "periodic table of AIR %d is short", air_id);
-                std::vector<uint64_t> coef(pv.begin() + in_off, pv.begin() + in_off + p);
-                host_intt(coef);
-                const Fx y = fx_pow(zeta, n >> pl);
-                Fx a{0, 0};
-                for (size_t k = p; k-- > 0;) a = a * y + Fx{coef[k], 0};
-                per[j] = a;
-                in_off += p;
-            }
-        }
-        for (size_t i = 0; i < n_pub; ++i) pubx[i] = {pub[i], 0};
-        for (int q = 0; q < air->chal; ++q) chalx[q] = {chal[q], 0};
-        for (int q = 0; q < 2 * air->auxpub; ++q) apubx[q] = {apub[q], 0};
-        HostRow loc{o_local.data()}, nxt{o_next.data()};
-        if (air->prog) air_program_eval<Fx>(*air->prog, loc, nxt, per.data(), pubx.data(), chalx.data(), apubx.data(), cons);
-        else air->eval(loc, nxt, per.data(), pubx.data(), chalx.data(), apubx.data(), cons);
-        for (int k = 0; k < 2; ++k) {
-            const Fx q = o_quot[2 * k] + o_quot[2 * k + 1] * zn;
-            NEED(fx_eq(cons.acc[k], zh * q), "constraint identity fails at zeta (challenge %d)", k);
-        }
-    }
-    for (size_t j = 0; j < c; ++j) ch.observe(o_local[j].a), ch.observe(o_local[j].b);
-    for (size_t j = 0; j < nq; ++j) ch.observe(o_quot[j].a), ch.observe(o_quot[j].b);
-    for (size_t j = 0; j < c; ++j) ch.observe(o_next[j].a), ch.observe(o_next[j].b);
-    const Fx alpha = ch.ext();
-    std::vector<const uint64_t*> layer_caps;
-    std::vector<Fx> betas;
-    for (size_t l = 0; l < n_layers; ++l) {
-        NEED(have(cap_words), "proof truncated (FRI caps)");
-        layer_caps.push_back(pr + pos);
-        ch.observe(pr + pos, cap_words);
-        pos += cap_words;
-        betas.push_back(ch.ext());
-    }
-    NEED(have(2 * final_len + 1), "proof truncated (final poly)");
-    std::vector<Fx> fpoly(final_len);
-    for (size_t k = 0; k < final_len; ++k) {
-        fpoly[k] = {pr[pos + 2 * k], pr[pos + 2 * k + 1]};
-        ch.observe(fpoly[k].a), ch.observe(fpoly[k].b);
-    }
-    pos += 2 * final_len;
-    const uint64_t nonce = pr[pos++];
-    ch.observe(nonce);
-    const uint64_t resp = ch.challenge();
-    NEED(pow_bits == 0 || (resp >> (64 - pow_bits)) == 0, "proof of work invalid");
-    // reduced openings
-    Fx apow{1, 0}, y0{0, 0}, y1{0, 0};
-    for (size_t j = 0; j < c + nq; ++j) {
-        if (j < c) {
-            y0 = y0 + apow * o_local[j];
-            y1 = y1 + apow * o_next[j];
-        } else y0 = y0 + apow * o_quot[j - c];
-        apow = apow * alpha;
-    }
-    const Fx alpha_c = fx_pow(alpha, c);
-    const int depth0 = LN - cap_h;
-    const uint64_t wN = glh::root(LN);
-    if (fri) {
-        fri->log_lde = LN;
-        for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
-        for (const Fx& f : fpoly) fri->final_poly.push_back(f.a), fri->final_poly.push_back(f.b);
-        if (fri->want_combine) {
-            fri->cm = cm, fri->ca = ca, fri->nq = nq, fri->alpha[0] = alpha.a, fri->alpha[1] = alpha.b, fri->zeta[0] = zeta.a, fri->zeta[1] = zeta.b;
-            for (const std::vector<Fx>* o : {&o_local, &o_next, &o_quot})
-                for (const Fx& v : *o) fri->openings.push_back(v.a), fri->openings.push_back(v.b);
-        }
-    }
-    for (size_t qi = 0; qi < n_queries; ++qi) {
-        size_t x_index = ch.challenge() % N;
-        NEED(have(c + nq + (ca ? 12 : 8) * (size_t)depth0), "proof truncated (query %zu)", qi);
-        const uint64_t* row_t = pr + pos;
-        const uint64_t* sib_t = row_t + cm;
-        const uint64_t* row_a = sib_t + 4 * depth0;
-        const uint64_t* sib_a = row_a + ca;
-        const uint64_t* row_q = ca ? sib_a + 4 * depth0 : row_a;
-        const uint64_t* sib_q = row_q + nq;
-        pos += c + nq + (ca ? 12 : 8) * (size_t)depth0;
-        NEED(v_merkle(row_t, cm, x_index, sib_t, depth0, cap_t), "trace Merkle proof invalid (query %zu)", qi);
-        if (ca) NEED(v_merkle(row_a, ca, x_index, sib_a, depth0, cap_a), "auxiliary Merkle proof invalid (query %zu)", qi);
-        NEED(v_merkle(row_q, nq, x_index, sib_q, depth0, cap_q), "quotient Merkle proof invalid (query %zu)", qi);
-        uint64_t x = glh::mul(7, glh::pow(wN, brev(x_index, LN)));
+    return VX_OK;
+}
+// The FRI query phase (verify_fri_proof): per query the three rows under their caps, the combination of their words
+// (fri_combine_initial), and per layer the coset's leaf under its cap and its fold at beta (compute_evaluation), down to the
+// final polynomial.
+static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx zeta, const std::vector<Fx>& betas, FriClaims* fri, char* err, size_t errlen) {
+    const sp::Shape& s = *v.s;
+    const size_t c = s.c, nq = sp::NQ, N = (size_t)1 << s.LN, n_layers = s.arities.size();
+    const Fx zeta_next = fx_scale(zeta, glh::root(s.L));
+    const sp::Reduced red = sp::reduce_openings(alpha, v.open_local(), v.open_next(), v.open_quot(), c, nq);
+    const std::vector<Fx> fpoly = fx_pairs(v.final_poly(), s.final_len);
+    const uint64_t wN = glh::root(s.LN);
+    for (size_t qi = 0; qi < (size_t)s.num_queries; ++qi) {
+        size_t x_index = ch.query_index(N);
+        const sp::Query<const uint64_t> q = v.query(qi);
+        NEED(glh::merkle_path_ok(q.row_t(), s.cm, x_index, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
+        if (s.ca) NEED(glh::merkle_path_ok(q.row_a(), s.ca, x_index, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
+        NEED(glh::merkle_path_ok(q.row_q(), nq, x_index, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
+        uint64_t x = glh::mul(7, glh::pow(wN, brev(x_index, s.LN)));
         Fx s1{0, 0}, ap{1, 0};
         for (size_t j = 0; j < c; ++j) {
-            s1 = s1 + ap * Fx{j < cm ? row_t[j] : row_a[j - cm], 0};
+            s1 = s1 + ap * Fx{j < s.cm ? q.row_t()[j] : q.row_a()[j - s.cm], 0};
             ap = ap * alpha;
         }
         Fx s0 = s1;
         for (size_t j = 0; j < nq; ++j) {
-            s0 = s0 + ap * Fx{row_q[j], 0};
+            s0 = s0 + ap * Fx{q.row_q()[j], 0};
             ap = ap * alpha;
         }
-        Fx ev = alpha_c * (s0 - y0) * fx_inv(Fx{x, 0} - zeta) + (s1 - y1) * fx_inv(Fx{x, 0} - zeta_next);
+        Fx ev = red.alpha_c * (s0 - red.y0) * fx_inv(Fx{x, 0} - zeta) + (s1 - red.y1) * fx_inv(Fx{x, 0} - zeta_next);
         if (fri) fri->index.push_back(x_index), fri->ev0.push_back(ev.a), fri->ev0.push_back(ev.b);
         if (fri && fri->want_combine) {
-            fri->rows.insert(fri->rows.end(), row_t, row_t + cm);
-            fri->rows.insert(fri->rows.end(), row_a, row_a + ca);
-            fri->rows.insert(fri->rows.end(), row_q, row_q + nq);
+            fri->rows.insert(fri->rows.end(), q.row_t(), q.row_t() + s.cm);
+            fri->rows.insert(fri->rows.end(), q.row_a(), q.row_a() + s.ca);
+            fri->rows.insert(fri->rows.end(), q.row_q(), q.row_q() + nq);
         }
-        int cur_log = LN;
         for (size_t l = 0; l < n_layers; ++l) {
-            const int a = arities[l];
+            const int a = s.arities[l];
             const size_t arity = (size_t)1 << a, within = x_index & (arity - 1);
-            const int depth = cur_log - a - cap_h;
-            NEED(have(2 * (arity - 1) + 4 * (size_t)depth), "proof truncated (query %zu layer %zu)", qi, l);
             std::vector<uint64_t> leaf(2 * arity);
             for (size_t t = 0, src = 0; t < arity; ++t) {
                 if (t == within) {
                     leaf[2 * t] = ev.a, leaf[2 * t + 1] = ev.b;
                 } else {
-                    leaf[2 * t] = pr[pos + 2 * src], leaf[2 * t + 1] = pr[pos + 2 * src + 1];
+                    leaf[2 * t] = q.evals(l)[2 * src], leaf[2 * t + 1] = q.evals(l)[2 * src + 1];
                     ++src;
                 }
             }
-            pos += 2 * (arity - 1);
             if (fri) fri->leaves.insert(fri->leaves.end(), leaf.begin(), leaf.end());
-            NEED(v_merkle(leaf.data(), 2 * arity, x_index >> a, pr + pos, depth, layer_caps[l]), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
-            pos += 4 * (size_t)depth;
+            NEED(glh::merkle_path_ok(leaf.data(), 2 * arity, x_index >> a, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
             // compute_evaluation: interpolate the coset {x g^i} and evaluate at beta
             const uint64_t g = glh::root(a);
             std::vector<Fx> evn(arity);
@@ -594,24 +389,74 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
             ev = acc;
             x = glh::pow(x, arity);
             x_index >>= a;
-            cur_log -= a;
         }
         Fx fp{0, 0};
-        for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + fpoly[k];
+        for (size_t k = s.final_len; k-- > 0;) fp = fp * Fx{x, 0} + fpoly[k];
         NEED(fx_eq(fp, ev), "final polynomial evaluation mismatch (query %zu)", qi);
         if (fri) fri->ev_last.push_back(ev.a), fri->ev_last.push_back(ev.b);
     }
-    NEED(pos == len, "trailing data in proof (%zu of %zu words used)", pos, len);
-    if (ca && !ext_chal)  // a stand-alone proof has nobody to cancel a bus total against
-        for (int q = 0; q < 2 * air->auxpub; ++q) NEED(apub[q] == 0, "stand-alone proof publishes a non-zero bus total");
-    if (apub_out) *apub_out = apub;
-    if (log_n_out) *log_n_out = L;
     return VX_OK;
 }
-
-// host-side shared challenges for verifiers outside this file
-void vx_shared_challenges_host(const uint64_t* const* pubs, const size_t* n_pubs, const uint64_t* const* caps, size_t k, size_t cap_words, uint64_t* out, size_t n_out) {
-    v_shared_challenges_n(pubs, n_pubs, caps, k, cap_words, out, n_out);
+static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen) {
+    if (!cfg || !pr) return VX_ERR_ARG;
+    if (!sp::config_ok(*cfg)) {
+        if (err && errlen) snprintf(err, errlen, "stark verify: configuration out of range");
+        return VX_ERR_ARG;
+    }
+    AirV air{};
+    VX_TRY(proof_air(pr, len, expect_air, &air, err, errlen));
+    // the header is the one this AIR, these degree bits and the configuration imply, word for word
+    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)pr[2], *cfg);
+    const std::vector<uint64_t> hdr = shape.header_words();
+    for (size_t i = 0; i < hdr.size(); ++i)
+        NEED(i < len && pr[i] == hdr[i], "%s", i >= 5 && i <= 8 ? "config mismatch" : i >= 9 && i < hdr.size() - 2 ? "FRI plan mismatch" : "shape mismatch");
+    // the proof is untrusted input: the shapes the prover refuses (vx_stark_prove_impl) are refused here too, so no Merkle depth
+    // below can go negative (a crafted L = 2 proof used to reach the Merkle check with n_sib = SIZE_MAX)
+    NEED(shape.LN >= shape.cap_h && shape.LN <= 27 && shape.L >= air.period_log, "degree bits %d out of range for this AIR / cap height", shape.L);
+    NEED(!air.exact_log || shape.L == air.period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air.period_log, shape.L);
+    for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
+    sp::View v;
+    const char* bad_length = sp::View::parse(pr, len, shape, &v);
+    NEED(!bad_length, "%s (%zu words, this shape has %zu)", bad_length, len, shape.words());
+    if (expect_public) {
+        NEED(n_expect_public == shape.n_pub, "public input count differs");
+        for (size_t i = 0; i < shape.n_pub; ++i) NEED(v.pub()[i] == expect_public[i], "public input %zu differs", i);
+    }
+    sp::Transcript ch;
+    ch.trace(v);
+    uint64_t chal[8] = {0}, alphas[2];
+    if (shape.ca) {  // auxiliary round: lookup challenges after the trace cap, then the published values and the second cap
+        NEED(air.chal <= 8 && 2 * air.auxpub <= 8, "AIR %d auxiliary round is misconfigured", air.id);
+        ch.lookup_challenges(chal, (size_t)air.chal, ext_chal);
+        ch.aux(v);
+    }
+    ch.alphas(alphas);
+    const Fx zeta = ch.zeta(v);
+    VX_TRY(constraints_at_zeta(air, v, chal, alphas, zeta, err, errlen));
+    const Fx alpha = ch.alpha(v);
+    std::vector<Fx> betas;
+    for (size_t l = 0; l < shape.arities.size(); ++l) betas.push_back(ch.beta(v, l));
+    ch.final_poly(v);
+    NEED(ch.pow_ok(*v.nonce(), shape.pow_bits), "proof of work invalid");
+    if (fri) {
+        fri->log_lde = shape.LN;
+        for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
+        fri->final_poly.assign(v.final_poly(), v.final_poly() + 2 * shape.final_len);
+        if (fri->want_combine) {
+            fri->cm = shape.cm, fri->ca = shape.ca, fri->nq = sp::NQ, fri->alpha[0] = alpha.a, fri->alpha[1] = alpha.b, fri->zeta[0] = zeta.a, fri->zeta[1] = zeta.b;
+            fri->openings.assign(v.open_local(), v.open_local() + 2 * shape.c);
+            fri->openings.insert(fri->openings.end(), v.open_next(), v.open_next() + 2 * shape.c);
+            fri->openings.insert(fri->openings.end(), v.open_quot(), v.open_quot() + 2 * sp::NQ);
+        }
+    }
+    VX_TRY(fri_queries(v, ch, alpha, zeta, betas, fri, err, errlen));
+    const uint64_t* apub = shape.ca ? v.apub() : nullptr;
+    if (shape.ca && !ext_chal)  // a stand-alone proof has nobody to cancel a bus total against
+        for (size_t q = 0; q < 2 * shape.auxpub; ++q) NEED(apub[q] == 0, "stand-alone proof publishes a non-zero bus total");
+    if (apub_out) *apub_out = apub;
+    if (log_n_out) *log_n_out = shape.L;
+    return VX_OK;
 }
 
 // One table of a bus group: its serialised proof, what peek_tables reads from it (public inputs, trace cap), and what the
@@ -627,7 +472,7 @@ struct BusTable {
 };
 static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
     for (size_t i = 0; i < n; ++i)
-        if (!vx_stark_proof_peek(t[i].proof, t[i].len, cfg->cap_height, &t[i].pub, &t[i].n_pub, &t[i].cap)) return false;
+        if (!stark_proof::peek(t[i].proof, t[i].len, cfg->cap_height, &t[i].pub, &t[i].n_pub, &t[i].cap)) return false;
     return true;
 }
 // The messages a party outside the tables puts on their bus -- the verifier itself, in an aggregation proof: the denominator of
@@ -672,7 +517,7 @@ static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, s
     std::vector<size_t> n_pubs(n);
     for (size_t i = 0; i < n; ++i) pubs[i] = t[i].pub, n_pubs[i] = t[i].n_pub, caps[i] = t[i].cap;
     uint64_t chal[4];
-    v_shared_challenges_n(pubs.data(), n_pubs.data(), caps.data(), n, (size_t)4 << cfg->cap_height, chal, 4);
+    stark_proof::shared_challenges_n(pubs.data(), n_pubs.data(), caps.data(), n, (size_t)4 << cfg->cap_height, chal, 4);
     uint64_t bus[2] = {0, 0};
     for (size_t i = 0; i < n; ++i) {
         const uint64_t* apub = nullptr;
