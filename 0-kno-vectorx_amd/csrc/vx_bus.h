@@ -1,6 +1,6 @@
 // Host-side plumbing shared by every prover of "several tables on one logUp bus", implemented in vx_bus.hip: the circuit provers
 // (vx_header_range_prove in vx_header_range.hip, vx_rotate_prove in vx_rotate.hip) and the aggregation provers (vx_merkle_open_air.hip,
-// vx_leaf_sponge_air.hip, vx_fri_fold_air.hip, vx_fri_combine_air.hip, vx_fri_queries.hip).  The tables of one statement must use
+// vx_leaf_sponge_air.hip, vx_fri_fold_air.hip, vx_fri_combine_air.hip, vx_fri_queries.hip, vx_stark_openings.hip).  The tables of one statement must use
 // the same lookup challenges, drawn after every trace is committed: the rendezvous and the bookkeeping of such a group are
 // bus_meet.h (host-pure); TableGroup below is the group on the device -- a prover says which tables there are (TableSpec), which one
 // runs on the caller's context and thread, and in which order failures are reported.  What only the aggregation provers share --
@@ -47,6 +47,7 @@ struct TableShape {
 };
 // *n_words = hdr_words + the vx_stark_proof_bound of every table
 int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, std::initializer_list<TableShape> tables, size_t* n_words);
+int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, const TableShape* tables, size_t n_tables, size_t* n_words);
 // The tables of one statement on the device, in table order.  prove(): the table `here` (-1: none) is proven on the caller's
 // context and thread, every other local table on a host thread of its own and on the next of the chain of side contexts behind
 // `ctx`, in table order (every table has a context of its own: own stream, scratch, pool); they meet at their challenge hooks.
@@ -76,6 +77,9 @@ struct TableGroup {
 // writes the blob, or fails with VX_ERR_BUFSZ ("<what>: the blob needs N words, buffer has M") when blob_out cannot hold it.
 int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
                   size_t blob_cap, size_t* blob_len);
+// ... for a number of tables known only at run time (vx_stark_openings_prove)
+int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, const uint64_t* request, size_t n_request, const TableJob* const* jobs, size_t n_jobs, uint64_t* blob_out, size_t blob_cap,
+                  size_t* blob_len);
 
 // The three tables of a justification -- authority-set commitment (ShaChainAir, sends the chosen signers' keys), Ed25519
 // (EdAir) and SHA-512 (Sha512Air) -- added to `g` as the next three parties of `bus`; returns the index of the first.  The prover
@@ -151,6 +155,73 @@ int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
 // not end in the final polynomial; VX_ERR_ARG for claims out of range
 int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* ev0,
                               const uint64_t* leaves, size_t n_queries);
+
+// ---- STARK-openings blob (written by vx_stark_openings_prove in vx_stark_openings.hip, read by vx_stark_openings_verify in
+// vx_verify.hip): magic, the shape words of the inner proof (log_lde, cm, ca, arity_bits, fold layers, cap_height, queries), the
+// number of tables, one length per table, the proofs: MerkleOpenSetAir, then one LeafSpongeSetAir per leaf length above 4
+static const uint64_t VX_SOPEN_MAGIC = 0x314e45504f535856ULL;  // "VXSOPEN1"
+static constexpr size_t VX_SOPEN_HDR = 9;                       // before the lengths
+static constexpr uint64_t VX_SOPEN_TREE0 = 8;                   // main / auxiliary / quotient = TREE0 + 0 / 1 / 2; layer l = l
+// The Merkle side of a vx_stark_prove proof as claims: one per (query, tree), queries outermost in proof order, inside a query the
+// order of the query record -- main, auxiliary (ca > 0), quotient, layers 0..NL-1.  Filled by the verifier's own query phase in
+// its delegated mode (vx_stark_openings_claims, vx_verify.hip), which walks no path and reads no sibling word.
+struct StarkOpenings {
+    int LN = 0, a = 0, cap_h = 0;
+    size_t cm = 0, ca = 0, NL = 0, n_queries = 0;
+    std::vector<uint64_t> tree;   // the trees of a query, in record order
+    std::vector<uint64_t> caps;   // [tree.size()][4 << cap_h], in that order
+    std::vector<uint64_t> index;  // [n_queries]: x_index
+    struct Claim {
+        uint64_t tree, index;  // index: x_index for the commitment trees, x_index >> a (l + 1) for layer l
+        size_t leaf, leaf_len;  // the leaf words: leaves[leaf .. leaf + leaf_len), a layer leaf with its `within` slot filled
+        size_t sib;             // where the path's 4 (log_leaves - cap_h) sibling words start in the proof (prover mode)
+    };
+    std::vector<Claim> claims;
+    std::vector<uint64_t> leaves;
+    int log_leaves(uint64_t t) const { return t >= VX_SOPEN_TREE0 ? LN : LN - a * ((int)t + 1); }
+    std::array<uint64_t, 7> shape_words() const { return {{(uint64_t)LN, cm, ca, (uint64_t)a, NL, (uint64_t)cap_h, n_queries}}; }
+};
+// verifies `proof` as vx_stark_verify_ext does, every check except the Merkle paths, and fills *out; VX_ERR_ARG for more than 8
+// fold layers.  want_sibs: record where the siblings lie (the prover reads them, the verifier never does)
+int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, bool want_sibs, StarkOpenings* out, char* err, size_t errlen);
+// the two-to-one fold of a cap of canonical words down to one digest: the root the openings table proves paths to
+void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]);
+// the statement of a proof's openings, the four digest words of every table: hash_n_to_hash_no_pad(the shape words, the folded
+// root of every tree in record order, per query the index and the leaf words of every tree in record order).  roots: [tree.size()][4]
+void vx_stark_openings_statement(const StarkOpenings& so, const uint64_t* roots, uint64_t digest[4]);
+// The witness of MerkleOpenSetAir from authentication paths (vx_merkle_open_air.hip).  The levels of a path are a chain here:
+// _states_dev walks every path once on ctx->stream -- siblings below the cap from `siblings`, above it from the fold of the
+// tree's cap -- stores what enters every level and waits; *bad_out = the first opening that does not reach its root
+// (VX_ERR_STATEMENT), n_idx when all do.  _trace_dev only launches the trace kernel over those buffers, on any context of the
+// device.  Tree t (< n_trees <= 64) has 2^log_leaves[t] leaves (0: no such tree) and the cap caps[t][4 << cap_height]; opening
+// i enters with leaf_dev[i] (4 digest words on the device) when leaf_dev and leaf_dev[i] are set, else leaf_digests[4 i ..];
+// siblings: the 4 (log_leaves - cap_height) words of every opening, one after the other.
+struct MerklePathsWitness {
+    uint64_t* sc = nullptr;  // one pool block of the context that made it; freed by vx_merkle_paths_free
+    const void* trees_d = nullptr;
+    const uint64_t *path_d = nullptr, *nodes_d = nullptr, *leaf_d = nullptr;
+    const uint32_t* blk_d = nullptr;
+    uint64_t* claims_d = nullptr;
+    size_t n_idx = 0, n_active = 0;
+};
+int32_t vx_merkle_paths_states_dev(vx_ctx* ctx, const uint64_t* caps, int cap_height, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx,
+                                   const uint64_t* leaf_digests, const uint64_t* const* leaf_dev, const uint64_t* siblings, size_t n_idx, MerklePathsWitness* w, size_t* bad_out);
+int32_t vx_merkle_paths_trace_dev(vx_ctx* c, const MerklePathsWitness& w, int log_n, uint64_t* trace_d);
+void vx_merkle_paths_free(vx_ctx* ctx, MerklePathsWitness* w);
+// The witness of LeafSpongeSetAir from rows handed over directly (vx_leaf_sponge_air.hip): leaf i is the row rows[i][leaf_len]
+// (host, canonical words) of leaf leaf_idx[i] of tree tree_of[i]; all share leaf_len >= 5.  _states_dev enqueues the chains on
+// ctx->stream (no tree to compare a digest with: the path it enters is the check) and leaves digests_d [n_idx][4] for the paths;
+// _trace_dev only launches the trace kernel.
+struct SpongeRowsWitness {
+    uint64_t* sc = nullptr;
+    const uint64_t *states_d = nullptr, *idx_d = nullptr, *digests_d = nullptr;
+    const void* set_d = nullptr;
+    size_t n_idx = 0, n_blk = 0, leaf_len = 0;
+};
+int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, SpongeRowsWitness* w);
+int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* c, const SpongeRowsWitness& w, int log_n, uint64_t* trace_d);
+void vx_leaf_sponge_rows_free(vx_ctx* ctx, SpongeRowsWitness* w);
 
 // ---- FRI-combine blob (written by vx_fri_combine_prove in vx_fri_combine_air.hip, read by vx_fri_combine_verify in vx_verify.hip):
 // magic, log2 of the inner proof's LDE, main / auxiliary / quotient columns, queries, length of the FriCombineAir proof that follows

@@ -14,15 +14,18 @@ int32_t vx_one_table_hook(void*, const uint64_t* pub, size_t n_pub, const uint64
     return VX_OK;
 }
 
-int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, std::initializer_list<TableShape> tables, size_t* n_words) {
+int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, const TableShape* tables, size_t n_tables, size_t* n_words) {
     size_t total = hdr_words;
-    for (const TableShape& t : tables) {
+    for (size_t k = 0; k < n_tables; ++k) {
         size_t w = 0;
-        VX_TRY(vx_stark_proof_bound(t.air_id, cfg, t.log_n, &w));
+        VX_TRY(vx_stark_proof_bound(tables[k].air_id, cfg, tables[k].log_n, &w));
         total += w;
     }
     *n_words = total;
     return VX_OK;
+}
+int32_t vx_tables_proof_bound(const vx_stark_config* cfg, size_t hdr_words, std::initializer_list<TableShape> tables, size_t* n_words) {
+    return vx_tables_proof_bound(cfg, hdr_words, tables.begin(), tables.size(), n_words);
 }
 std::array<TableShape, 3> vx_justification_shapes(size_t n_authorities, size_t n_sig) {
     return {{{VX_AIR_SHA_CHAIN, sha_log_n(n_authorities)}, {ed_air_id(n_sig), ed_log_n(n_sig)}, {s512_air_id(n_sig), s512_log_n(n_sig)}}};
@@ -100,18 +103,22 @@ int32_t TableGroup::prove(int here, std::vector<int> order) {
     if (strncmp(msg, what, strlen(what)) == 0) return vx_fail(ctx, rc, "%s", msg);  // (it names the prover already)
     return vx_fail(ctx, rc, "%s: %s", what, msg);
 }
-int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
-                  size_t blob_cap, size_t* blob_len) {
-    size_t total = 1 + request.size() + jobs.size();
-    for (const TableJob* j : jobs) total += j->len;
+int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, const uint64_t* request, size_t n_request, const TableJob* const* jobs, size_t n_jobs, uint64_t* blob_out, size_t blob_cap,
+                  size_t* blob_len) {
+    size_t total = 1 + n_request + n_jobs;
+    for (size_t k = 0; k < n_jobs; ++k) total += jobs[k]->len;
     *blob_len = total;
     if (!blob_out || blob_cap < total) return vx_fail(ctx, VX_ERR_BUFSZ, "%s: the blob needs %zu words, buffer has %zu", what, total, blob_cap);
     uint64_t* w = blob_out;
     *w++ = magic;
-    for (uint64_t r : request) *w++ = r;
-    for (const TableJob* j : jobs) *w++ = j->len;
-    for (const TableJob* j : jobs) memcpy(w, j->proof.data(), j->len * 8), w += j->len;
+    for (size_t k = 0; k < n_request; ++k) *w++ = request[k];
+    for (size_t k = 0; k < n_jobs; ++k) *w++ = jobs[k]->len;
+    for (size_t k = 0; k < n_jobs; ++k) memcpy(w, jobs[k]->proof.data(), jobs[k]->len * 8), w += jobs[k]->len;
     return VX_OK;
+}
+int32_t pack_blob(vx_ctx* ctx, const char* what, uint64_t magic, std::initializer_list<uint64_t> request, std::initializer_list<const TableJob*> jobs, uint64_t* blob_out,
+                  size_t blob_cap, size_t* blob_len) {
+    return pack_blob(ctx, what, magic, request.begin(), request.size(), jobs.begin(), jobs.size(), blob_out, blob_cap, blob_len);
 }
 
 int vx_justification_add(TableGroup& g, const vx_justification* just, std::function<int32_t(vx_ctx*)> pre, int bus, unsigned mask) {

@@ -13,7 +13,9 @@
 // LeafSpongeSetAir (rows of several trees, the sponge table of vx_fri_queries_prove) runs the same three kernels: the states kernel
 // in a fourth layout -- the leaf of a FRI layer, 16 extension values at natural positions bitrev(16 j + t), what vx_fri_layer_tree
 // hashes -- with a per-leaf entry (tree, layer values, the tree's leaf digests, log2 of its leaves); trace and aux with the TREE
-// column written and used in the denominators.
+// column written and used in the denominators.  A fifth layout of the states kernel takes the rows themselves, handed over one per
+// opening (the sponge tables of vx_stark_openings_prove, whose rows come out of a proof: no tree exists to compare a digest with --
+// the path the digest enters is the check); any leaf length, one per table.
 // Parity: tests/test_gpu_leaf_sponge.py compares trace, auxiliary columns and both proofs with tests/leaf_sponge_ref.py and the
 // reference prover.
 #include <string.h>
@@ -31,8 +33,9 @@ namespace {
 using namespace lsp;
 
 constexpr int LAYOUT_FRI_LAYER = 3;  // behind the three vx_merkle_build layouts: the leaves of FRI layers, one entry per leaf
+constexpr int LAYOUT_ROWS = 4;       // ... and rows handed over directly, one entry per leaf: `data` is the row itself
 struct SetLeaf {
-    const uint64_t* data;         // the layer: 2^(log_leaves + 4) extension values (a, b) in natural order
+    const uint64_t* data;         // the layer: 2^(log_leaves + 4) extension values (a, b) in natural order; LAYOUT_ROWS: the row
     const uint64_t* tree_leaves;  // its tree's leaf digests, or nullptr
     uint64_t tree;
     int log_leaves;
@@ -48,7 +51,7 @@ struct SpongeArgs {
     uint64_t* claims;   // [n_idx][1 + leaf_len]: (index, row)
     uint64_t* digests;  // [n_idx][4]
     uint64_t* bad;      // 1 + the number of an opening whose digest is not the tree's (0: none)
-    const SetLeaf* set;  // LAYOUT_FRI_LAYER: [n_idx]; data, tree_leaves, n_leaves, log_leaves above are unused, leaf_len is 32
+    const SetLeaf* set;  // LAYOUT_FRI_LAYER / LAYOUT_ROWS: [n_idx]; data, tree_leaves, n_leaves, log_leaves above are unused, leaf_len is 32 / the rows' 
 };
 
 // (Tried: one lane per leaf with the tree builder's poseidon_permute -- 6.23 ms against 2.30 ms for 84 leaves x 128 blocks,
@@ -61,19 +64,19 @@ __global__ __launch_bounds__(256) void k_leaf_sponge_states(SpongeArgs a) {
     const bool live = t < a.n_idx;
     const size_t p = live ? t : a.n_idx - 1;  // surplus groups redo the last leaf and do not write
     const uint64_t j = a.idx[p];
-    constexpr bool FRI = LAYOUT == LAYOUT_FRI_LAYER;
-    constexpr size_t CLAIM_HDR = FRI ? 2 : 1;  // the set's claims name the tree: (tree, index, row)
+    constexpr bool FRI = LAYOUT == LAYOUT_FRI_LAYER, ROWS = LAYOUT == LAYOUT_ROWS;
+    constexpr size_t CLAIM_HDR = FRI || ROWS ? 2 : 1;  // the set's claims name the tree: (tree, index, row)
     int log_leaves = a.log_leaves;
     const uint64_t *data = a.data, *tree_leaves = a.tree_leaves;
     uint64_t* claim = a.claims + p * (a.leaf_len + CLAIM_HDR);
-    if constexpr (FRI) {
+    if constexpr (FRI || ROWS) {
         const SetLeaf sl = a.set[p];
         log_leaves = sl.log_leaves, data = sl.data, tree_leaves = sl.tree_leaves;
         if (live && l == 0) claim[0] = sl.tree;
     }
-    const size_t r = (LAYOUT == VX_LEAVES_COLS_BITREV || FRI) ? brev32((uint32_t)j, log_leaves) : j;
-    const size_t estride = LAYOUT == VX_LEAVES_ROW_MAJOR ? 1 : a.n_leaves;
-    const uint64_t* src = LAYOUT == VX_LEAVES_ROW_MAJOR ? data + r * a.leaf_len : FRI ? data + 2 * r : data + r;
+    const size_t r = ROWS ? 0 : (LAYOUT == VX_LEAVES_COLS_BITREV || FRI) ? brev32((uint32_t)j, log_leaves) : j;
+    const size_t estride = LAYOUT == VX_LEAVES_ROW_MAJOR || ROWS ? 1 : a.n_leaves;
+    const uint64_t* src = ROWS ? data : LAYOUT == VX_LEAVES_ROW_MAJOR ? data + r * a.leaf_len : FRI ? data + 2 * r : data + r;
     if (live && l == 0) claim[CLAIM_HDR - 1] = j;
     uint64_t s = 0;
     for (size_t k = 0; k < a.n_blk; ++k) {
@@ -262,6 +265,53 @@ int32_t vx_leaf_sponge_set_trace_dev(vx_ctx* ctx, const uint64_t* const* evals_d
     return VX_OK;
 }
 
+// ---- the witness of LeafSpongeSetAir from rows handed over directly (vx_bus.h)
+int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, SpongeRowsWitness* w) {
+    VX_CHECK(leaf_len >= 5 && leaf_len <= MAX_LEAF_LEN, "leaf sponge: leaf_len %zu (5..2^20; a row of at most 4 words is its own digest and has no sponge)", leaf_len);
+    VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "leaf sponge: %zu openings (1..2^21)", n_idx);
+    const size_t n_blk = sponge_blocks(leaf_len);
+    VX_CHECK(n_idx * n_blk <= ((size_t)1 << 21), "leaf sponge: %zu leaves of %zu blocks need more than 2^26 rows", n_idx, n_blk);
+    for (size_t i = 0; i < n_idx; ++i)
+        VX_CHECK(tree_of[i] >> 32 == 0 && leaf_idx[i] >> 40 == 0, "leaf sponge: opening %zu names leaf %llu of tree %llu (below 2^40 / 2^32)", i, (unsigned long long)leaf_idx[i],
+                 (unsigned long long)tree_of[i]);
+    for (size_t i = 0; i < n_idx * leaf_len; ++i) VX_CHECK(rows[i] < glh::P, "leaf sponge: opening %zu has a non-canonical word", i / leaf_len);
+    const size_t w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 2), w_set = n_idx * sizeof(SetLeaf) / 8, w_rows = n_idx * leaf_len;
+    // scratch: the entering states, the indices, the claims, the digests, the (unused) mismatch word, the per-leaf table, the rows
+    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1 + w_set + w_rows) * 8);
+    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
+    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx, *set_d = bad_d + 1, *rows_d = set_d + w_set;
+    std::vector<SetLeaf> set(n_idx);
+    for (size_t i = 0; i < n_idx; ++i) set[i] = SetLeaf{rows_d + i * leaf_len, nullptr, tree_of[i], 0};
+    hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(set_d, set.data(), w_set * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rows_d, rows, w_rows * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (`set` is pageable host memory of this frame)
+    if (e == hipSuccess) {
+        const SpongeArgs a{nullptr, idx_d, nullptr, 0, leaf_len, n_idx, n_blk, 0, states, claims_d, digests_d, bad_d, (const SetLeaf*)set_d};
+        hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_ROWS>, dim3((unsigned)((n_idx + 15) / 16)), dim3(256), 0, ctx->stream, a);  // 16 lanes per leaf
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        vx_pool_free(ctx, sc);
+        return vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
+    }
+    *w = SpongeRowsWitness{sc, states, idx_d, digests_d, set_d, n_idx, n_blk, leaf_len};
+    return VX_OK;
+}
+
+int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* ctx, const SpongeRowsWitness& w, int log_n, uint64_t* trace_d) {
+    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * w.n_idx * w.n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", w.n_idx, w.n_blk, log_n);
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_leaf_sponge_trace<true>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, w.states_d, w.idx_d, w.n_idx, w.n_blk, n, trace_d, (const SetLeaf*)w.set_d);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+void vx_leaf_sponge_rows_free(vx_ctx* ctx, SpongeRowsWitness* w) {
+    if (w->sc) vx_pool_free(ctx, w->sc);
+    *w = SpongeRowsWitness();
+}
+
 // The witness of LeafSpongeAir on the device.  data_d: the leaves of the whole tree ([n_leaves x leaf_len] words in `layout`; the
 // caller has checked that the buffer holds them).  tree_leaves (device, may be nullptr): the leaf digests of the tree the openings
 // are proven against -- a row that does not hash to its leaf digest is refused with VX_ERR_STATEMENT before anything is proven.
@@ -338,6 +388,29 @@ int32_t vx_leaf_sponge_set_air_trace(vx_ctx* ctx, const vx_buf* const* evals, co
     VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)SET_COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
              trace_out->n, SET_COLS, log_n);
     return vx_leaf_sponge_set_trace_dev(ctx, ev, log_leaves, nullptr, n_trees, tree_of, leaf_idx, n_idx, log_n, trace_out->d, public_out);
+}
+
+int32_t vx_leaf_sponge_rows_air_trace(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, int log_n, vx_buf* trace_out,
+                                      uint64_t public_out[14]) {
+    if (!ctx || !tree_of || !leaf_idx || !rows || !trace_out || !public_out) return VX_ERR_ARG;
+    VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)SET_COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
+             trace_out->n, SET_COLS, log_n);
+    SpongeRowsWitness w;
+    VX_TRY(vx_leaf_sponge_rows_states_dev(ctx, leaf_len, tree_of, leaf_idx, rows, n_idx, &w));
+    int32_t rc = vx_leaf_sponge_rows_trace_dev(ctx, w, log_n, trace_out->d);
+    if (rc == VX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: the witness kernels failed");
+    vx_leaf_sponge_rows_free(ctx, &w);
+    VX_TRY(rc);
+    std::vector<uint64_t> claims;  // (tree, index, row) of every opening: the set's claims digest
+    claims.reserve(n_idx * (leaf_len + 2));
+    for (size_t i = 0; i < n_idx; ++i) {
+        claims.push_back(tree_of[i]), claims.push_back(leaf_idx[i]);
+        claims.insert(claims.end(), rows + i * leaf_len, rows + (i + 1) * leaf_len);
+    }
+    uint64_t digest[4];
+    glh::hash_no_pad(claims.data(), claims.size(), digest);
+    vx_leaf_sponge_set_public(leaf_len, digest, public_out);
+    return VX_OK;
 }
 
 int32_t vx_merkle_rows_proof_bound(const vx_stark_config* cfg, size_t n_leaves, size_t leaf_len, size_t n_idx, size_t* n_words) {

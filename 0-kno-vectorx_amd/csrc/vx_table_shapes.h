@@ -1,6 +1,6 @@
 // Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers
 // (vx_bus.hip, vx_header_range.hip, vx_rotate.hip, the aggregation provers in vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
-// vx_fri_fold_air.hip and vx_fri_queries.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
+// vx_fri_fold_air.hip, vx_fri_queries.hip and vx_stark_openings.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
 // condition.  Host-only inline functions, no device code.
 #pragma once
 #include <stddef.h>
@@ -66,4 +66,40 @@ static inline int fri_queries_sponge_log_n(size_t n_queries, size_t n_layers) { 
 static inline int fri_combine_log_n(size_t n_queries, int log_lde, size_t cm, size_t ca, size_t nq) {
     const int l = ceil_log2(n_queries * (cm + ca + nq + (size_t)log_lde));
     return l < 5 ? 5 : l;
+}
+// The tables of a STARK proof's Merkle openings (vx_stark_openings_prove / vx_stark_openings_verify), in bus order: the openings
+// table (MerkleOpenSetAir, one path per (query, tree): main, auxiliary when ca > 0, quotient, the NL layer trees), then one
+// LeafSpongeSetAir table per distinct leaf length above 4 among {cm, ca, 2 2^a}, by ascending length (a row of at most 4 words is
+// its own digest: the quotient rows, and any other tree that short, have no sponge).  Rows: 32 per level of every path, 32 per 8
+// words of every leaf, each table at the smallest log_n >= 5.  false: a tree without a level, more than 8 layers, or a table of
+// more than 2^26 rows.
+struct StarkOpeningsTables {
+    int n = 0;
+    int air[4], log_n[4];
+    size_t leaf_len[4];  // [0] = 0: the openings table
+};
+static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, StarkOpeningsTables* t) {
+    if (LN < 1 || LN > 40 || a < 1 || a > 5 || NL > 8 || n_queries < 1 || n_queries > ((size_t)1 << 20) || cm < 1 || cm > ((size_t)1 << 20) || ca > ((size_t)1 << 20)) return false;
+    if (NL && (int)NL * a >= LN) return false;
+    size_t levels = (size_t)LN * (ca ? 3 : 2);
+    for (size_t l = 0; l < NL; ++l) levels += (size_t)(LN - a * ((int)l + 1));
+    const size_t lens[3] = {cm, ca, NL ? (size_t)2 << a : 0}, per_query[3] = {1, 1, NL};
+    t->n = 1, t->air[0] = VX_AIR_MERKLE_OPEN_SET, t->leaf_len[0] = 0;
+    t->log_n[0] = ceil_log2(32 * n_queries * levels);
+    for (;;) {  // the next length above the last one taken
+        size_t next = 0;
+        for (size_t L : lens)
+            if (L > 4 && L > t->leaf_len[t->n - 1] && (!next || L < next)) next = L;
+        if (!next) break;
+        size_t leaves = 0;
+        for (int k = 0; k < 3; ++k)
+            if (lens[k] == next) leaves += per_query[k];
+        t->air[t->n] = VX_AIR_LEAF_SPONGE_SET, t->leaf_len[t->n] = next, t->log_n[t->n] = ceil_log2(32 * n_queries * leaves * sponge_blocks(next));
+        ++t->n;
+    }
+    for (int k = 0; k < t->n; ++k) {
+        if (t->log_n[k] < 5) t->log_n[k] = 5;
+        if (t->log_n[k] > 26) return false;
+    }
+    return true;
 }

@@ -240,6 +240,10 @@ struct FriClaims {
     size_t cm = 0, ca = 0, nq = 0;
     uint64_t alpha[2] = {0, 0}, zeta[2] = {0, 0};
     std::vector<uint64_t> openings, rows;  // openings: local [c][2], next [c][2], quotient [nq][2]; rows: [query][c + nq]
+    // ... and, for vx_stark_openings_claims, the DELEGATED mode: no Merkle path is walked and no sibling word read -- every
+    // (query, tree) becomes a claim of *merkle instead (vx_bus.h), for a bus group to prove
+    StarkOpenings* merkle = nullptr;
+    bool want_sibs = false;  // prover mode: record where every path's siblings lie in the proof
 };
 static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
                                  const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen);
@@ -326,12 +330,25 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
     const sp::Reduced red = sp::reduce_openings(alpha, v.open_local(), v.open_next(), v.open_quot(), c, nq);
     const std::vector<Fx> fpoly = fx_pairs(v.final_poly(), s.final_len);
     const uint64_t wN = glh::root(s.LN);
+    StarkOpenings* const mk = fri ? fri->merkle : nullptr;
+    // delegated mode: the opening becomes a claim; of the path only its position in the proof is noted, no word of it is read
+    auto claim = [&](uint64_t tree, size_t index, const uint64_t* leaf, size_t leaf_len, const uint64_t* sib) {
+        mk->claims.push_back({tree, index, mk->leaves.size(), leaf_len, fri->want_sibs ? (size_t)(sib - v.pr) : 0});
+        mk->leaves.insert(mk->leaves.end(), leaf, leaf + leaf_len);
+    };
     for (size_t qi = 0; qi < (size_t)s.num_queries; ++qi) {
         size_t x_index = ch.query_index(N);
         const sp::Query<const uint64_t> q = v.query(qi);
-        NEED(glh::merkle_path_ok(q.row_t(), s.cm, x_index, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
-        if (s.ca) NEED(glh::merkle_path_ok(q.row_a(), s.ca, x_index, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
-        NEED(glh::merkle_path_ok(q.row_q(), nq, x_index, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
+        if (mk) {
+            mk->index.push_back(x_index);
+            claim(VX_SOPEN_TREE0, x_index, q.row_t(), s.cm, q.sib_t());
+            if (s.ca) claim(VX_SOPEN_TREE0 + 1, x_index, q.row_a(), s.ca, q.sib_a());
+            claim(VX_SOPEN_TREE0 + 2, x_index, q.row_q(), nq, q.sib_q());
+        } else {
+            NEED(glh::merkle_path_ok(q.row_t(), s.cm, x_index, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
+            if (s.ca) NEED(glh::merkle_path_ok(q.row_a(), s.ca, x_index, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
+            NEED(glh::merkle_path_ok(q.row_q(), nq, x_index, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
+        }
         uint64_t x = glh::mul(7, glh::pow(wN, brev(x_index, s.LN)));
         Fx s1{0, 0}, ap{1, 0};
         for (size_t j = 0; j < c; ++j) {
@@ -363,7 +380,8 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
                 }
             }
             if (fri) fri->leaves.insert(fri->leaves.end(), leaf.begin(), leaf.end());
-            NEED(glh::merkle_path_ok(leaf.data(), 2 * arity, x_index >> a, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
+            if (mk) claim(l, x_index >> a, leaf.data(), 2 * arity, q.sibs(l));
+            else NEED(glh::merkle_path_ok(leaf.data(), 2 * arity, x_index >> a, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
             // compute_evaluation: interpolate the coset {x g^i} and evaluate at beta
             const uint64_t g = glh::root(a);
             std::vector<Fx> evn(arity);
@@ -415,10 +433,28 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     // below can go negative (a crafted L = 2 proof used to reach the Merkle check with n_sib = SIZE_MAX)
     NEED(shape.LN >= shape.cap_h && shape.LN <= 27 && shape.L >= air.period_log, "degree bits %d out of range for this AIR / cap height", shape.L);
     NEED(!air.exact_log || shape.L == air.period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air.period_log, shape.L);
-    for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
+    const bool delegated = fri && fri->merkle;
+    if (!delegated)
+        for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
     sp::View v;
     const char* bad_length = sp::View::parse(pr, len, shape, &v);
     NEED(!bad_length, "%s (%zu words, this shape has %zu)", bad_length, len, shape.words());
+    if (delegated) {  // the same check over everything but the siblings: in this mode none of their words is read
+        auto canonical = [&](size_t from, size_t n) -> size_t {
+            for (size_t i = from; i < from + n; ++i)
+                if (pr[i] >= glh::P) return i;
+            return 0;
+        };
+        size_t bad = canonical(hdr.size(), shape.o_queries - hdr.size());
+        for (size_t k = 0; k < (size_t)shape.num_queries && !bad; ++k) {
+            const size_t at = shape.o_queries + k * shape.q_words;
+            bad = canonical(at, shape.cm);
+            if (!bad) bad = canonical(at + shape.q_row_a, shape.ca);
+            if (!bad) bad = canonical(at + shape.q_row_q, sp::NQ);
+            for (size_t l = 0; l < shape.arities.size() && !bad; ++l) bad = canonical(at + shape.q_layer[l], 2 * (((size_t)1 << shape.arities[l]) - 1));
+        }
+        NEED(!bad, "non-canonical element at word %zu", bad);
+    }
     if (expect_public) {
         NEED(n_expect_public == shape.n_pub, "public input count differs");
         for (size_t i = 0; i < shape.n_pub; ++i) NEED(v.pub()[i] == expect_public[i], "public input %zu differs", i);
@@ -439,6 +475,16 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     for (size_t l = 0; l < shape.arities.size(); ++l) betas.push_back(ch.beta(v, l));
     ch.final_poly(v);
     NEED(ch.pow_ok(*v.nonce(), shape.pow_bits), "proof of work invalid");
+    if (delegated) {
+        StarkOpenings& m = *fri->merkle;
+        m = StarkOpenings();
+        m.LN = shape.LN, m.a = cfg->arity_bits, m.cap_h = shape.cap_h, m.cm = shape.cm, m.ca = shape.ca, m.NL = shape.arities.size(), m.n_queries = (size_t)shape.num_queries;
+        auto tree = [&](uint64_t id, const uint64_t* cap) { m.tree.push_back(id), m.caps.insert(m.caps.end(), cap, cap + shape.cap_words); };
+        tree(VX_SOPEN_TREE0, v.cap_trace());
+        if (shape.ca) tree(VX_SOPEN_TREE0 + 1, v.cap_aux());
+        tree(VX_SOPEN_TREE0 + 2, v.cap_quot());
+        for (size_t l = 0; l < m.NL; ++l) tree(l, v.layer_cap(l));
+    }
     if (fri) {
         fri->log_lde = shape.LN;
         for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
@@ -982,6 +1028,149 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
     if (ev_last_out) memcpy(ev_last_out, fc.ev_last.data(), 2 * nq * 8);
     memcpy(leaves_out, fc.leaves.data(), fc.leaves.size() * 8);
     return VX_OK;
+}
+
+}  // extern "C"
+
+// The Merkle side of a vx_stark_prove proof as claims (vx_bus.h): the verifier's own code in its delegated mode -- transcript,
+// constraint identity at zeta, proof of work, combination, folds and the final polynomial are all checked; the paths are not.
+int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, bool want_sibs, StarkOpenings* out, char* err, size_t errlen) {
+    FriClaims fc;
+    fc.merkle = out, fc.want_sibs = want_sibs;
+    const int32_t rc = stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, &fc, err, errlen);
+    if (rc != VX_OK) return rc;
+    if (out->NL > (size_t)ffa::MAX_LAYERS) return ff_arg(err, errlen, "stark openings: a proof with %zu fold layers (at most 8: the layer trees are ids 0..7, the commitment trees 8..10)", out->NL);
+    return VX_OK;
+}
+void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]) {
+    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height));
+    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
+        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
+    memcpy(root, fold.data(), 32);
+}
+void vx_stark_openings_statement(const StarkOpenings& so, const uint64_t* roots, uint64_t digest[4]) {
+    std::vector<uint64_t> w;
+    w.reserve(7 + 4 * so.tree.size() + so.n_queries + so.leaves.size());
+    for (uint64_t x : so.shape_words()) w.push_back(x);
+    w.insert(w.end(), roots, roots + 4 * so.tree.size());
+    const size_t per_query = so.tree.size();
+    for (size_t i = 0; i < so.n_queries; ++i) {
+        w.push_back(so.index[i]);
+        for (size_t k = 0; k < per_query; ++k) {
+            const StarkOpenings::Claim& c = so.claims[i * per_query + k];
+            w.insert(w.end(), so.leaves.begin() + c.leaf, so.leaves.begin() + c.leaf + c.leaf_len);
+        }
+    }
+    glh::hash_no_pad(w.data(), w.size(), digest);
+}
+
+extern "C" {
+// The Merkle side of a vx_stark_prove proof (host only, prover-side): what vx_stark_openings_claims records, in caller-sized
+// arrays.  Every other check of the proof has run; the paths are for the caller to prove (vx_stark_openings_prove).
+int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, uint64_t shape_out[7], size_t* n_trees, uint64_t cap_tree_out[11],
+                               uint64_t* caps_out, size_t caps_cap, size_t* n_claims, uint64_t* tree_out, uint64_t* index_out, uint64_t* leaf_len_out, size_t claims_cap, size_t* leaves_len,
+                               uint64_t* leaves_out, size_t leaves_cap, size_t* siblings_len, uint64_t* siblings_out, size_t siblings_cap, char* err, size_t errlen) {
+    if (!cfg || !proof || !shape_out || !n_trees || !cap_tree_out || !caps_out || !n_claims || !tree_out || !index_out || !leaf_len_out || !leaves_len || !leaves_out || !siblings_len ||
+        !siblings_out)
+        return VX_ERR_ARG;
+    StarkOpenings so;
+    const int32_t rc = vx_stark_openings_claims(cfg, proof, len, 0, nullptr, 0, ext_chal, true, &so, err, errlen);
+    if (rc != VX_OK) return rc;
+    size_t sib_words = 0;
+    for (const StarkOpenings::Claim& c : so.claims) sib_words += 4 * (size_t)(so.log_leaves(c.tree) - so.cap_h);
+    const std::array<uint64_t, 7> sw = so.shape_words();
+    memcpy(shape_out, sw.data(), sizeof sw);
+    *n_trees = so.tree.size(), *n_claims = so.claims.size(), *leaves_len = so.leaves.size(), *siblings_len = sib_words;
+    if (caps_cap < so.caps.size() || claims_cap < so.claims.size() || leaves_cap < so.leaves.size() || siblings_cap < sib_words) {
+        if (err && errlen)
+            snprintf(err, errlen, "merkle claims: the buffers hold %zu / %zu / %zu / %zu words, %zu / %zu / %zu / %zu are needed", caps_cap, claims_cap, leaves_cap, siblings_cap, so.caps.size(),
+                     so.claims.size(), so.leaves.size(), sib_words);
+        return VX_ERR_BUFSZ;
+    }
+    memset(cap_tree_out, 0, 11 * 8);
+    memcpy(cap_tree_out, so.tree.data(), so.tree.size() * 8);
+    memcpy(caps_out, so.caps.data(), so.caps.size() * 8);
+    memcpy(leaves_out, so.leaves.data(), so.leaves.size() * 8);
+    uint64_t* sib = siblings_out;
+    for (size_t i = 0; i < so.claims.size(); ++i) {
+        const StarkOpenings::Claim& c = so.claims[i];
+        const size_t n = 4 * (size_t)(so.log_leaves(c.tree) - so.cap_h);
+        tree_out[i] = c.tree, index_out[i] = c.index, leaf_len_out[i] = c.leaf_len;
+        memcpy(sib, proof + c.sib, n * 8), sib += n;
+    }
+    return VX_OK;
+}
+
+// What vx_stark_openings_prove writes for this inner proof at most: read from the proof's head alone (AIR id and degree bits -> the
+// columns of the three trees, the fold layers), nothing is verified.
+int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
+    if (!cfg || !proof || !n_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
+    AirV air{};
+    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
+    StarkOpeningsTables ts;
+    if (shape.LN < shape.cap_h || shape.cap_h > 16 || !stark_openings_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, shape.arities.size(), (size_t)shape.num_queries, &ts)) return VX_ERR_ARG;
+    TableShape sh[4];
+    for (int k = 0; k < ts.n; ++k) sh[k] = {ts.air[k], ts.log_n[k]};
+    return vx_tables_proof_bound(cfg, VX_SOPEN_HDR + (size_t)ts.n, sh, (size_t)ts.n, n_words);
+}
+
+// STARK openings (the prover is vx_stark_openings.hip): the Merkle side of one inner vx_stark_prove proof on one bus -- the
+// openings table (MerkleOpenSetAir, one path per (query, tree)) and one LeafSpongeSetAir table per leaf length above 4, which
+// receive the openings of their trees (TAG_OPEN closes between them).  The inner proof is verified here in the delegated mode:
+// every check except the paths.  The verifier is the outside party: per (query, tree) it receives the root the path ended in with
+// the tree's depth -- the tables do not know which root belongs to which tree, the verifier does (vx_cap_fold of the proof's cap)
+// --, every word of a row longer than 4 words, and the opening itself of a row that is its own digest:
+//     sum over the tables of total x rows = sum over the claims of 1 / D_root(tree, lo) + 1 / D_root(tree, hi)
+//         + [leaf_len > 4] sum over j of 1 / D_row(tree, index, j, word_j)  +  [leaf_len <= 4] (1 / D_open(lo) + 1 / D_open(hi)).
+// EVERY public input of every table is rebuilt from the inner proof (the digest words are the statement digest, vx_bus.h).
+// No path is walked, no leaf hashed, no sibling read; the statement digest costs about what hashing the rows would.
+int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                                 size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    if (!cfg || !blob || !proof) return VX_ERR_ARG;
+    StarkOpenings so;
+    int32_t rc = vx_stark_openings_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, false, &so, err, errlen);
+    if (rc != VX_OK) return rc;
+    StarkOpeningsTables ts;
+    NEED(stark_openings_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, &ts), "stark openings: the proof's shape has no openings group (a tree without a level, or a table of more than 2^26 rows)");
+    NEED(so.cap_h <= 16, "stark openings: cap height %d (at most 16)", so.cap_h);
+    BusTable tab[4];
+    const std::array<uint64_t, 7> sw = so.shape_words();
+    rc = read_blob(blob, len, VX_SOPEN_MAGIC, "stark-openings", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
+    const size_t n_trees = so.tree.size();
+    std::vector<uint64_t> roots(4 * n_trees);
+    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
+    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB];
+    vx_stark_openings_statement(so, roots.data(), stmt);
+    vx_merkle_open_set_public(stmt, opub);
+    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
+    for (int k = 1; k < ts.n; ++k) {
+        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
+        tab[k].air = VX_AIR_LEAF_SPONGE_SET, tab[k].want = spub[k - 1], tab[k].n_want = lsp::PUB;
+    }
+    return verify_bus_group(cfg, tab, (size_t)ts.n, "the openings the tables prove are not the ones of this proof (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(2 * so.claims.size() + so.leaves.size());
+                                for (size_t i = 0; i < so.claims.size(); ++i) {
+                                    const StarkOpenings::Claim& c = so.claims[i];
+                                    const uint64_t* r = roots.data() + 4 * (i % n_trees);
+                                    const uint64_t* leaf = so.leaves.data() + c.leaf;
+                                    const Fx tree{c.tree, 0}, idx{c.index, 0}, depth{(uint64_t)so.log_leaves(c.tree), 0};
+                                    m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
+                                    m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
+                                    if (c.leaf_len > 4) {
+                                        for (size_t j = 0; j < c.leaf_len; ++j) m.receive(bus.row_of(tree, idx, Fx{(uint64_t)j, 0}, Fx{leaf[j], 0}));
+                                    } else {
+                                        uint64_t d[4] = {0, 0, 0, 0};
+                                        memcpy(d, leaf, c.leaf_len * 8);
+                                        m.receive(bus.open_of(tree, idx, Fx{d[0], 0}, Fx{d[1], 0}, bus::K<0>{}));
+                                        m.receive(bus.open_of(tree, idx, Fx{d[2], 0}, Fx{d[3], 0}, bus::K<1>{}));
+                                    }
+                                }
+                            });
 }
 
 // FRI combine (the prover is vx_fri_combine_air.hip), the fourth aggregation verifier: the claims are what a STARK verifier holds

@@ -35,6 +35,7 @@ SYMBOLS = [
     "vx_merkle_open_set_air_trace", "vx_leaf_sponge_set_air_trace", "vx_fri_queries_proof_bound", "vx_fri_queries_prove", "vx_fri_queries_verify",
     "vx_fri_combine_air_trace", "vx_fri_combine_proof_bound", "vx_fri_combine_prove", "vx_fri_combine_verify", "vx_stark_combine_claims",
     "vx_fri_combine_fold_proof_bound", "vx_fri_combine_fold_prove", "vx_fri_combine_fold_verify",
+    "vx_stark_merkle_claims", "vx_merkle_paths_air_trace", "vx_leaf_sponge_rows_air_trace", "vx_stark_openings_proof_bound", "vx_stark_openings_prove", "vx_stark_openings_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -200,6 +201,12 @@ def load_library():
         "vx_fri_combine_fold_prove": [vp, C.POINTER(StarkConfig), C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_fri_combine_fold_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, sz, sz, sz, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, C.c_char_p, sz],
         "vx_stark_fri_claims": [C.POINTER(StarkConfig), vp, sz, C.POINTER(C.c_int), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), vp, vp, sz, vp, vp, vp, sz, vp, sz, C.c_char_p, sz],
+        "vx_stark_merkle_claims": [C.POINTER(StarkConfig), vp, sz, vp, vp, C.POINTER(sz), vp, vp, sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz), vp, sz, C.c_char_p, sz],
+        "vx_merkle_paths_air_trace": [vp, vp, C.c_int, vp, sz, vp, vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_leaf_sponge_rows_air_trace": [vp, sz, vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_stark_openings_proof_bound": [C.POINTER(StarkConfig), vp, sz, C.POINTER(sz)],
+        "vx_stark_openings_prove": [vp, C.POINTER(StarkConfig), vp, sz, vp, vp, sz, C.POINTER(sz)],
+        "vx_stark_openings_verify": [C.POINTER(StarkConfig), vp, sz, vp, sz, C.c_int, vp, sz, vp, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -490,6 +497,56 @@ def stark_fri_claims(proof, cfg=None):
     NL, Q = nl.value, n.value
     return dict(log_lde=log_lde.value, betas=betas[: 2 * NL].reshape(NL, 2), final_poly=fpoly[: 2 * fl.value].reshape(-1, 2), index=index[:Q], ev0=ev0[: 2 * Q].reshape(Q, 2),
                 ev_last=ev_last[: 2 * Q].reshape(Q, 2), leaves=leaves[: Q * NL * 32].reshape(Q, NL, 32))
+
+
+SOPEN_MAGIC, SOPEN_HDR, SOPEN_TREE0 = 0x314E45504F535856, 9, 8  # "VXSOPEN1": magic, the 7 shape words, the table count; then one length per table, the proofs
+
+
+def stark_merkle_claims(proof, cfg=None, ext_chal=None):
+    """The Merkle side of a vx_stark_prove proof as claims (every check of the proof except the paths runs on the way; no GPU needed)
+    -> dict(shape (LN, cm, ca, a, NL, cap_height, n_queries), trees [n_trees] (the trees of a query in record order), caps
+    [n_trees][2^cap_height][4], tree / index / leaf_len [n_claims], leaves / siblings: one array per claim)."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+    shape, trees = np.zeros(7, dtype=np.uint64), np.zeros(11, dtype=np.uint64)
+    n_trees, n_claims, n_leaves, n_sibs = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    caps, tree, index, leaf_len = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    leaves, sibs = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    err = C.create_string_buffer(256)
+    for _ in range(2):  # the first call sizes the arrays (VX_ERR_BUFSZ with every size set)
+        rc = L.vx_stark_merkle_claims(C.byref(cfg), _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(shape), C.byref(n_trees), _ptr(trees), _ptr(caps), caps.size, C.byref(n_claims),
+                                      _ptr(tree), _ptr(index), _ptr(leaf_len), tree.size, C.byref(n_leaves), _ptr(leaves), leaves.size, C.byref(n_sibs), _ptr(sibs), sibs.size, err, 256)
+        if rc != -4:
+            break
+        caps = np.zeros(n_trees.value * (4 << int(shape[5])), dtype=np.uint64)
+        tree, index, leaf_len = (np.zeros(n_claims.value, dtype=np.uint64) for _ in range(3))
+        leaves, sibs = np.zeros(max(n_leaves.value, 1), dtype=np.uint64), np.zeros(max(n_sibs.value, 1), dtype=np.uint64)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+    LN, a, cap_h = int(shape[0]), int(shape[3]), int(shape[5])
+    depth = [LN - cap_h if t >= SOPEN_TREE0 else LN - a * (int(t) + 1) - cap_h for t in tree]
+    lcut, scut = np.cumsum([0] + [int(v) for v in leaf_len]), np.cumsum([0] + [4 * d for d in depth])
+    return dict(shape=[int(v) for v in shape], trees=[int(v) for v in trees[: n_trees.value]], caps=caps.reshape(n_trees.value, -1, 4), tree=tree, index=index, leaf_len=leaf_len,
+                leaves=[leaves[lcut[i]: lcut[i + 1]] for i in range(tree.size)], siblings=[sibs[scut[i]: scut[i + 1]].reshape(-1, 4) for i in range(tree.size)])
+
+
+def stark_openings_verify(blob, proof, cfg=None, expect_air=0, expect_public=None, ext_chal=None):
+    """Host-side check of a vx_stark_openings_prove blob together with the inner proof it belongs to: the proof is verified in
+    the delegated mode (every check except the Merkle paths) and the group proves the paths.  Walks no path, hashes no leaf,
+    reads no sibling; raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    pub = None if expect_public is None else np.ascontiguousarray(expect_public, dtype=np.uint64)
+    ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+    err = C.create_string_buffer(256)
+    rc = L.vx_stark_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size,
+                                    None if ch is None else _ptr(ch), err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
 
 
 FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
@@ -882,6 +939,50 @@ class Context:
                                 "fri queries: bad shape or configuration (arity_bits 4, 1..8 layers, at least one index bit left, 1..2^20 queries, tables of at most 2^26 rows)",
                                 lambda c, o, need: self.L.vx_fri_queries_prove(self.h, c, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], th, eh, _ptr(idx), idx.size,
                                                                                _ptr(o), o.size, need))
+
+    def merkle_paths_air_trace(self, caps, log_leaves, tree_of, leaf_idx, leaf_digests, siblings, log_n, out=None):
+        """The witness of MerkleOpenSetAir from authentication paths: tree t has 2^log_leaves[t] leaves (0: no such tree) and the cap
+        caps[t][2^cap_height][4]; opening i enters with leaf_digests[i][4] and siblings[i] = the [log_leaves - cap_height][4] words of
+        its path -> (Buffer [72][2^log_n], the 4 public inputs: the digest of the claims (tree, index, leaf digest))."""
+        cp = np.ascontiguousarray(caps, dtype=np.uint64).reshape(len(log_leaves), -1, 4)
+        cap_height = cp.shape[1].bit_length() - 1
+        to = np.ascontiguousarray(tree_of, dtype=np.uint64).reshape(-1)
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        dg = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1)
+        sb = np.concatenate([np.zeros(1, dtype=np.uint64)] + [np.ascontiguousarray(s, dtype=np.uint64).reshape(-1) for s in siblings])[1:]
+        want = sum(4 * (int(log_leaves[int(t)]) - cap_height) for t in to if int(t) < len(log_leaves))
+        if to.size != idx.size or dg.size != 4 * idx.size or cp.shape[1] != 1 << cap_height or sb.size != want:
+            raise ValueError("one tree, one digest [4] and one path [log_leaves - cap_height][4] for every opening")
+        sb = np.ascontiguousarray(np.concatenate([sb, np.zeros(1, dtype=np.uint64)]))  # (never empty)
+        ll = (C.c_int * len(log_leaves))(*[int(v) for v in log_leaves])
+        out = out or self.alloc(VX_MERKLE_OPEN_SET_AIR_COLS << log_n)
+        pub = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.vx_merkle_paths_air_trace(self.h, _ptr(cp), cap_height, ll, len(log_leaves), _ptr(to), _ptr(idx), _ptr(dg), _ptr(sb), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def leaf_sponge_rows_air_trace(self, tree_of, leaf_idx, rows, log_n, out=None):
+        """The witness of LeafSpongeSetAir from rows handed over directly: opening i is the row rows[i][L] (L >= 5) of leaf leaf_idx[i]
+        of tree tree_of[i] -> (Buffer [67][2^log_n], the 14 public inputs: L, B, the tail flags, the digest of the claims)."""
+        to = np.ascontiguousarray(tree_of, dtype=np.uint64).reshape(-1)
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        rw = np.ascontiguousarray(rows, dtype=np.uint64).reshape(idx.size, -1)
+        if to.size != idx.size:
+            raise ValueError("one tree for every opening")
+        out = out or self.alloc(VX_LEAF_SPONGE_SET_AIR_COLS << log_n)
+        pub = np.zeros(14, dtype=np.uint64)
+        self._ck(self.L.vx_leaf_sponge_rows_air_trace(self.h, rw.shape[1], _ptr(to), _ptr(idx), _ptr(rw), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
+    def stark_openings_prove(self, proof, cfg=None, ext_chal=None, out=None):
+        """Proves the Merkle openings of the vx_stark_prove proof `proof` from the paths it carries -> blob words
+        (lib.stark_openings_verify checks blob and proof together).  One openings table and one sponge table per leaf length above 4.
+        The proof is verified on the way and every path walked natively first: VxError(VX_ERR_STATEMENT) names query and tree.
+        out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        pr = np.ascontiguousarray(proof, dtype=np.uint64)
+        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_openings_proof_bound(c, _ptr(pr), pr.size, need),
+                                "stark openings: not a proof of a known AIR under this configuration, or a shape without an openings group (more than 8 fold layers, a table above 2^26 rows)",
+                                lambda c, o, need: self.L.vx_stark_openings_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

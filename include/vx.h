@@ -363,8 +363,9 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
  *   (index, ev0) per query -- NO leaves; walks no path, hashes no leaf, folds nothing.  Rebuilds every public input of all three
  *   tables from its arguments, sends (index, ev_0) of every query, receives (index, final_poly(x_NL)) and, per layer, the two
  *   halves of (root of caps[l], depth log_lde - 4 (l + 1)); accepts iff all three tables verify and the bus balances.
- * STILL OUTSIDE: the commitment trees' Merkle side (a per-tree leaf length), binding to the layer trees vx_stark_prove builds
- * itself; ev_0 comes from FriCombineAir (below), not yet on this three-table bus. */
+ * STILL OUTSIDE here: the commitment trees' Merkle side and binding to the layer trees vx_stark_prove builds itself -- both are
+ * vx_stark_openings_prove (below), which proves every tree's openings from the paths a proof carries; ev_0 comes from FriCombineAir
+ * (below), not yet on this three-table bus. */
 enum { VX_AIR_MERKLE_OPEN_SET = 19, VX_MERKLE_OPEN_SET_AIR_COLS = 72, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 6 };
 enum { VX_AIR_LEAF_SPONGE_SET = 20, VX_LEAF_SPONGE_SET_AIR_COLS = 67, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 12 };
 int32_t vx_merkle_open_set_air_trace(vx_ctx* ctx, const vx_tree* const* trees, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx, size_t n_idx, int log_n,
@@ -376,6 +377,57 @@ int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
                              const vx_tree* const* trees, const vx_buf* const* evals, const uint64_t* index, size_t n_queries, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
                               size_t final_len, const uint64_t* caps, int cap_height, const uint64_t* index, const uint64_t* ev0, size_t n_queries, char* err, size_t errlen);
+/* ---- A STARK proof's Merkle openings proven from the paths it carries (vx_stark_openings_prove).  Every Merkle-side prover above
+ * takes vx_tree handles and buffers resident on the device; an aggregator holds proof BYTES.  A vx_stark_prove proof carries, per
+ * query, the opened rows of its three commitment trees, the leaves of its FRI layers and every sibling up to the caps: that is
+ * the whole witness of MerkleOpenSetAir and LeafSpongeSetAir, no new AIR and no new bus tag.
+ * Conventions (prover, verifier and tests/stark_openings_ref.py alike): layer l is tree l, main / auxiliary / quotient are trees
+ *   8 / 9 / 10; inside a query the order of the query record -- main, auxiliary (only when the AIR has auxiliary columns),
+ *   quotient, layers 0..NL-1 --, queries outermost in proof order, duplicates included.  Leaf index: x_index for the commitment
+ *   trees, x_index >> a (l + 1) for layer l (a = arity_bits, any the configuration allows); log_leaves: LN resp. LN - a (l + 1);
+ *   leaf lengths cm, ca, 4 and 2 2^a, the `within` slot of a layer leaf filled with the verifier's running evaluation.
+ * vx_stark_merkle_claims (host only, prover-side): replays a proof with the verifier's own code in its DELEGATED mode -- every
+ *   check except the Merkle paths runs, no sibling word is read by it -- and hands out shape_out = (LN, cm, ca, a, NL, cap_height,
+ *   n_queries), the trees of a query cap_tree_out[*n_trees] with their caps caps_out[*n_trees][4 << cap_height], and per opening
+ *   (tree, index, leaf_len), the leaf words one after the other in leaves_out and the 4 (log_leaves - cap_height) sibling words
+ *   one after the other in siblings_out.  ext_chal (may be NULL) as in a bus group: the lookup challenges the proof was made
+ *   under.  caps_cap / leaves_cap / siblings_cap are in words, claims_cap in openings; VX_ERR_BUFSZ (all sizes set) when one is too
+ *   small; VX_ERR_ARG for more than 8 fold layers.
+ * vx_merkle_paths_air_trace: the witness of MerkleOpenSetAir from paths (test surface; mirrors vx_merkle_open_set_air_trace cell by
+ *   cell).  Tree t < n_trees <= 64 has 2^log_leaves[t] leaves (0: no such tree) and the cap caps[t][4 << cap_height]; opening i
+ *   enters with leaf_digests[i][4] and the 4 (log_leaves - cap_height) words of its path in `siblings`, one opening after the
+ *   other.  16 lanes per path walk the chain (siblings above the cap come from the fold of the cap) and store what enters every
+ *   level; a path that does not reach the folded root is VX_ERR_STATEMENT.
+ * vx_leaf_sponge_rows_air_trace: the witness of LeafSpongeSetAir from rows handed over directly (test surface): rows[i][leaf_len],
+ *   leaf_len >= 5, canonical words; public_out as vx_leaf_sponge_set_air_trace.
+ * vx_stark_openings_prove: extracts the claims (the inner proof is verified on the way), runs the sponge chains and the paths once
+ *   on the device -- a path that does not reach its root is VX_ERR_STATEMENT naming query and tree, nothing is proven then -- and
+ *   proves, under shared challenges and in this bus order, MerkleOpenSetAir (one path per claim) and one LeafSpongeSetAir table per
+ *   distinct leaf length above 4 among {cm, ca, 2 2^a}, by ascending length: 1 to 4 tables.  Rows: 32 per level of every path,
+ *   32 per 8 words of every leaf, each table at the smallest log_n >= 5; VX_ERR_ARG above 2^26.  The four digest words of every
+ *   table are the STATEMENT digest: hash_n_to_hash_no_pad(shape words, the folded root of every tree in record order, per query the
+ *   index and the leaf words of every tree in record order).  Blob: "VXSOPEN1", the 7 shape words, the table count, one length per
+ *   table, the proofs.  vx_stark_openings_proof_bound reads the head of the inner proof alone.
+ * vx_stark_openings_verify (host only): verifies the inner proof in the delegated mode against expect_air / expect_public (0 / NULL:
+ *   not checked) and the group with it as the outside party: per claim it receives root(tree, lo / hi) with depth log_leaves, every
+ *   word of a row longer than 4 words, and the opening itself of a row that is its own digest.  Walks no path, hashes no leaf, reads
+ *   no sibling: the siblings are dead weight in a proof verified this way.  The statement digest costs about as many permutations as
+ *   hashing the rows would; what disappears is everything per tree level.
+ * STILL OUTSIDE: the query arithmetic (FriCombineAir / FriFoldAir would take the verifier's place on the row bus), the constraint
+ * identity at zeta and the transcript. */
+int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t shape_out[7], size_t* n_trees,
+                               uint64_t cap_tree_out[11], uint64_t* caps_out, size_t caps_cap, size_t* n_claims, uint64_t* tree_out, uint64_t* index_out, uint64_t* leaf_len_out,
+                               size_t claims_cap, size_t* leaves_len, uint64_t* leaves_out, size_t leaves_cap, size_t* siblings_len, uint64_t* siblings_out, size_t siblings_cap,
+                               char* err, size_t errlen);
+int32_t vx_merkle_paths_air_trace(vx_ctx* ctx, const uint64_t* caps, int cap_height, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx,
+                                  const uint64_t* leaf_digests, const uint64_t* siblings, size_t n_idx, int log_n, vx_buf* trace_out, uint64_t public_out[4]);
+int32_t vx_leaf_sponge_rows_air_trace(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, int log_n,
+                                      vx_buf* trace_out, uint64_t public_out[14]);
+int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words);
+int32_t vx_stark_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t* blob_out, size_t blob_cap,
+                                size_t* blob_len);
+int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* proof, size_t proof_len, int expect_air,
+                                 const uint64_t* expect_public, size_t n_public, const uint64_t* ext_chal, char* err, size_t errlen);
 /* ---- FriCombineAir: the FRI combination of every query of one inner proof in one STARK table (AIR id VX_AIR_FRI_COMBINE; compiled:
  * csrc/air_fri_combine.cuh) -- what a STARK verifier computes per query before the fold loop (plonky2 v0.2.0 fri/verifier.rs
  * fri_combine_initial; vx_stark_verify does the same on the host), the fourth table of proof aggregation.
