@@ -190,38 +190,41 @@ void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]);
 // the statement of a proof's openings, the four digest words of every table: hash_n_to_hash_no_pad(the shape words, the folded
 // root of every tree in record order, per query the index and the leaf words of every tree in record order).  roots: [tree.size()][4]
 void vx_stark_openings_statement(const StarkOpenings& so, const uint64_t* roots, uint64_t digest[4]);
-// The witness of MerkleOpenSetAir from authentication paths (vx_merkle_open_air.hip).  The levels of a path are a chain here:
-// _states_dev walks every path once on ctx->stream -- siblings below the cap from `siblings`, above it from the fold of the
-// tree's cap -- stores what enters every level and waits; *bad_out = the first opening that does not reach its root
-// (VX_ERR_STATEMENT), n_idx when all do.  _trace_dev only launches the trace kernel over those buffers, on any context of the
-// device.  Tree t (< n_trees <= 64) has 2^log_leaves[t] leaves (0: no such tree) and the cap caps[t][4 << cap_height]; opening
-// i enters with leaf_dev[i] (4 digest words on the device) when leaf_dev and leaf_dev[i] are set, else leaf_digests[4 i ..];
-// siblings: the 4 (log_leaves - cap_height) words of every opening, one after the other.
-struct MerklePathsWitness {
-    uint64_t* sc = nullptr;  // one pool block of the context that made it; freed by vx_merkle_paths_free
-    const void* trees_d = nullptr;
-    const uint64_t *path_d = nullptr, *nodes_d = nullptr, *leaf_d = nullptr;
-    const uint32_t* blk_d = nullptr;
-    uint64_t* claims_d = nullptr;
+// The witness of the openings tables (MerkleOpenAir, MerkleOpenSetAir) on the device, made by vx_merkle_open_air.hip from one
+// description of a request for all its sources.  Without stored pairs (nodes_d == nullptr) the trace kernel reads the trees: their
+// node storage holds every node of every path.  From AUTHENTICATION PATHS no tree is in HBM and the levels of a path are a chain:
+// vx_merkle_paths_states_dev walks every path once on ctx->stream -- siblings below the cap from `siblings`, above it from the fold
+// of the tree's cap --, stores the pair entering every level and waits; *bad_out = the first opening that does not reach its root
+// (VX_ERR_STATEMENT), n_idx when all do.  Tree t (< n_trees <= 64) has 2^log_leaves[t] leaves (0: no such tree) and the cap
+// caps[t][4 << cap_height]; opening i enters with leaf_dev[i] (4 digest words on the device) when leaf_dev and leaf_dev[i] are
+// set, else leaf_digests[4 i ..]; siblings: the 4 (log_leaves - cap_height) words of every opening, one after the other.
+// vx_merkle_paths_trace_dev only launches the trace kernel over the witness, on any context of the device.  The witness owns its
+// pool block (of the context that made it) and returns it when it goes.
+struct MerkleOpenWitness {
+    Scratch sc;
+    std::vector<uint64_t> tables;  // the host's copy of the uploaded tables: alive until the uploads have been waited for
+    uint64_t *upper_d = nullptr, *trees_d = nullptr, *path_d = nullptr, *blk_d = nullptr, *claims_d = nullptr;
+    uint64_t *leaf_d = nullptr, *sibp_d = nullptr, *dig_d = nullptr, *sib_d = nullptr, *nodes_d = nullptr, *bad_d = nullptr;  // paths only
     size_t n_idx = 0, n_active = 0;
 };
 int32_t vx_merkle_paths_states_dev(vx_ctx* ctx, const uint64_t* caps, int cap_height, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx,
-                                   const uint64_t* leaf_digests, const uint64_t* const* leaf_dev, const uint64_t* siblings, size_t n_idx, MerklePathsWitness* w, size_t* bad_out);
-int32_t vx_merkle_paths_trace_dev(vx_ctx* c, const MerklePathsWitness& w, int log_n, uint64_t* trace_d);
-void vx_merkle_paths_free(vx_ctx* ctx, MerklePathsWitness* w);
-// The witness of LeafSpongeSetAir from rows handed over directly (vx_leaf_sponge_air.hip): leaf i is the row rows[i][leaf_len]
-// (host, canonical words) of leaf leaf_idx[i] of tree tree_of[i]; all share leaf_len >= 5.  _states_dev enqueues the chains on
-// ctx->stream (no tree to compare a digest with: the path it enters is the check) and leaves digests_d [n_idx][4] for the paths;
-// _trace_dev only launches the trace kernel.
-struct SpongeRowsWitness {
-    uint64_t* sc = nullptr;
-    const uint64_t *states_d = nullptr, *idx_d = nullptr, *digests_d = nullptr;
-    const void* set_d = nullptr;
+                                   const uint64_t* leaf_digests, const uint64_t* const* leaf_dev, const uint64_t* siblings, size_t n_idx, MerkleOpenWitness* w, size_t* bad_out);
+int32_t vx_merkle_paths_trace_dev(vx_ctx* c, const MerkleOpenWitness& w, int log_n, uint64_t* trace_d);
+// The witness of the sponge tables (LeafSpongeAir, LeafSpongeSetAir) on the device, made by vx_leaf_sponge_air.hip from one
+// tree's leaf data, from FRI layers or from ROWS handed over directly: leaf i is then the row rows[i][leaf_len] (host, canonical
+// words) of leaf leaf_idx[i] of tree tree_of[i]; all share leaf_len >= 5.  vx_leaf_sponge_rows_states_dev enqueues the chains on
+// ctx->stream and leaves digests_d [n_idx][4] for the paths; vx_leaf_sponge_rows_trace_dev only launches the trace kernel.  The
+// witness owns its pool block as above.
+struct LeafSpongeWitness {
+    Scratch sc;
+    uint64_t *states_d = nullptr, *idx_d = nullptr, *claims_d = nullptr, *digests_d = nullptr, *set_d = nullptr, *rows_d = nullptr;
+    // 1 + the first opening whose digest is not its tree's (~0: none).  The rows form has no tree to compare with (the path the
+    // digest enters is the check) and never reads the word.
+    uint64_t* bad_d = nullptr;
     size_t n_idx = 0, n_blk = 0, leaf_len = 0;
 };
-int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, SpongeRowsWitness* w);
-int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* c, const SpongeRowsWitness& w, int log_n, uint64_t* trace_d);
-void vx_leaf_sponge_rows_free(vx_ctx* ctx, SpongeRowsWitness* w);
+int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, LeafSpongeWitness* w);
+int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* c, const LeafSpongeWitness& w, int log_n, uint64_t* trace_d);
 
 // ---- FRI-combine blob (written by vx_fri_combine_prove in vx_fri_combine_air.hip, read by vx_fri_combine_verify in vx_verify.hip):
 // magic, log2 of the inner proof's LDE, main / auxiliary / quotient columns, queries, length of the FriCombineAir proof that follows

@@ -207,24 +207,22 @@ int32_t vx_fri_combine_trace_dev(vx_ctx* ctx, const FriCombineStmt& st, uint64_t
         for (size_t j = 0; j < absn; ++j, ap = ap * alpha) apow[2 * j] = ap.a, apow[2 * j + 1] = ap.b;
     }
     const size_t w_rows = n_queries * absn;
-    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (n_queries + w_rows + 2 * absn) * 8);
-    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "fri combine: out of device memory");
+    Scratch sc;
+    uint64_t *index_d, *rows_d, *apow_d;
+    sc.add(index_d, n_queries), sc.add(rows_d, w_rows), sc.add(apow_d, 2 * absn);
+    sc.alloc(ctx);
     CombArgs a{};
-    a.index = sc, a.rows = sc + n_queries, a.apow = (const gl2*)(sc + n_queries + w_rows), a.n_queries = n_queries, a.n = (size_t)1 << log_n;
+    a.index = index_d, a.rows = rows_d, a.apow = (const gl2*)apow_d, a.n_queries = n_queries, a.n = (size_t)1 << log_n;
     a.LN = st.log_lde, a.cm = (int)st.cm, a.c = (int)c, a.absn = (int)absn, a.rpq = (int)rpq, a.w = pub_out[PUB_W], a.tr = trace_d;
     a.alphac = gl2{pub_out[PUB_ALPHAC], pub_out[PUB_ALPHAC + 1]}, a.zeta = gl2{st.zeta[0], st.zeta[1]}, a.zetan = gl2{pub_out[PUB_ZETAN], pub_out[PUB_ZETAN + 1]};
     a.y0 = gl2{pub_out[PUB_Y0], pub_out[PUB_Y0 + 1]}, a.y1 = gl2{pub_out[PUB_Y1], pub_out[PUB_Y1 + 1]};
     const size_t idle = a.n - n_queries * rpq, idle_blocks = idle ? ((idle + BLOCK - 1) / BLOCK < 1024 ? (idle + BLOCK - 1) / BLOCK : 1024) : 0;
-    hipError_t e = hipMemcpyAsync(sc, index, n_queries * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sc + n_queries, rows, w_rows * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sc + n_queries + w_rows, apow.data(), 2 * absn * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    sc.up(index_d, index, n_queries * 8), sc.up(rows_d, rows, w_rows * 8), sc.up(apow_d, apow.data(), 2 * absn * 8);
+    if (sc.ok()) {
         hipLaunchKernelGGL(k_fri_combine_trace, dim3((unsigned)(n_queries + idle_blocks)), dim3(BLOCK), 0, ctx->stream, a);
-        e = hipGetLastError();
+        sc.launched();
     }
-    vx_pool_free(ctx, sc);
-    if (e != hipSuccess) return vx_fail(ctx, VX_ERR_DEVICE, "fri combine: %s", hipGetErrorString(e));
-    return VX_OK;
+    return sc.status("fri combine");
 }
 
 // the combination on the host (Fx), what the table proves: ev0_out [n_queries][2]; VX_ERR_STATEMENT when x = zeta or zeta w_n

@@ -160,20 +160,20 @@ int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
     VX_CHECK(log_n >= 5 && log_n <= 26 && n_queries * (size_t)rpq <= ((size_t)1 << log_n), "fri fold: %zu queries of %d rows do not fit 2^%d rows", n_queries, rpq, log_n);
     VX_CHECK(tree0 < ((uint64_t)1 << 32), "fri fold: TREE0 out of range");
     const size_t w_leaves = n_queries * n_layers * 32;
-    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (n_queries + w_leaves) * 8);
-    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "fri fold: out of device memory");
+    Scratch sc;
+    uint64_t *index_d, *leaves_d;
+    sc.add(index_d, n_queries), sc.add(leaves_d, w_leaves);
+    sc.alloc(ctx);
     FoldArgs a{};
-    a.index = sc, a.leaves = sc + n_queries, a.n_queries = n_queries, a.n = (size_t)1 << log_n, a.LN = log_lde, a.NL = (int)n_layers, a.rpq = rpq;
+    a.index = index_d, a.leaves = leaves_d, a.n_queries = n_queries, a.n = (size_t)1 << log_n, a.LN = log_lde, a.NL = (int)n_layers, a.rpq = rpq;
     a.winv = glh::inv(glh::root(log_lde)), a.tr = trace_d;
     memcpy(a.beta, betas, 2 * n_layers * 8);
-    hipError_t e = hipMemcpyAsync(sc, index, n_queries * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sc + n_queries, leaves, w_leaves * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    sc.up(index_d, index, n_queries * 8), sc.up(leaves_d, leaves, w_leaves * 8);
+    if (sc.ok()) {
         hipLaunchKernelGGL(k_fri_fold_trace, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, ctx->stream, a);
-        e = hipGetLastError();
+        sc.launched();
     }
-    vx_pool_free(ctx, sc);
-    if (e != hipSuccess) return vx_fail(ctx, VX_ERR_DEVICE, "fri fold: %s", hipGetErrorString(e));
+    VX_TRY(sc.status("fri fold"));
     vx_fri_fold_public(log_lde, betas, n_layers, tree0, index, ev0, leaves, n_queries, pub_out);
     return VX_OK;
 }

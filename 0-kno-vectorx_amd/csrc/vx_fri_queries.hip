@@ -78,13 +78,11 @@ int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
             for (int j = 0; j < 32; ++j) leaf[j] = got[32 * i + j] >= glh::P ? got[32 * i + j] - glh::P : got[32 * i + j];
         }
         const size_t n_cap = (size_t)1 << trees[l]->cap_height;
-        std::vector<uint64_t> fold(4 * n_cap);
-        VX_HIP(hipMemcpyAsync(fold.data(), trees[l]->levels + trees[l]->total - 4 * n_cap, 4 * n_cap * 8, hipMemcpyDeviceToHost, ctx->stream));
+        std::vector<uint64_t> cap(4 * n_cap);
+        VX_HIP(hipMemcpyAsync(cap.data(), trees[l]->levels + trees[l]->total - 4 * n_cap, 4 * n_cap * 8, hipMemcpyDeviceToHost, ctx->stream));
         VX_HIP(hipStreamSynchronize(ctx->stream));  // also: the trees and the layers are this stream's work, the side contexts read them
-        for (uint64_t& w : fold) w = w >= glh::P ? w - glh::P : w;
-        for (size_t nodes = n_cap; nodes > 1; nodes >>= 1)
-            for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
-        memcpy(roots.data() + 4 * l, fold.data(), 32);
+        for (uint64_t& w : cap) w = w >= glh::P ? w - glh::P : w;
+        vx_cap_fold(cap.data(), trees[l]->cap_height, roots.data() + 4 * l);
     }
     for (size_t i = 0; i < n_queries; ++i) memcpy(ev0.data() + 2 * i, leaves.data() + i * NL * 32 + 2 * (index[i] & 15), 16);
     // ---- the statement, natively: every chain holds and ends in the final polynomial (VX_ERR_STATEMENT names query and layer)

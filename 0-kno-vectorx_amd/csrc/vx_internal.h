@@ -61,6 +61,52 @@ vx_ctx* vx_side_ctx(vx_ctx* ctx);  // nullptr if it cannot be created
 void* vx_pool_alloc(vx_ctx* ctx, size_t bytes);
 void vx_pool_free(vx_ctx* ctx, void* p);
 void vx_pool_trim(vx_ctx* ctx);
+int32_t vx_fail(vx_ctx* ctx, int32_t code, const char* fmt, ...);
+
+// One pool block carved into word regions.  Every region is named once, with its size (add), before the block is taken (alloc):
+// the total and every offset come from that one list.  The copies go on ctx->stream and stop at the first error, which status()
+// reports.  The block returns to the pool with the object; a witness that outlives the function that made it holds the object.
+// add() keeps the ADDRESS of the caller's pointer until alloc() sets it: the pointers must not move in between, so the object
+// (and a witness that holds it) is neither copied nor moved, and add and alloc happen in one frame.  Before alloc() nothing is
+// copied and status() is the allocation's failure (vx_fail takes the null context).
+struct Scratch {
+    vx_ctx* ctx = nullptr;
+    uint64_t* base = nullptr;
+    size_t words = 0;
+    hipError_t err = hipSuccess;
+    std::vector<std::pair<uint64_t**, size_t>> regions;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        if (base) vx_pool_free(ctx, base);
+    }
+    void add(uint64_t*& p, size_t n) { regions.push_back({&p, words}), words += n; }
+    void alloc(vx_ctx* c) {
+        ctx = c, base = (uint64_t*)vx_pool_alloc(c, words * 8);
+        for (auto& r : regions) *r.first = base ? base + r.second : nullptr;
+    }
+    bool ok() const { return base && err == hipSuccess; }
+    void keep(hipError_t e) {
+        if (err == hipSuccess) err = e;
+    }
+    void copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+        if (ok()) err = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+    }
+    void up(void* dst, const void* src, size_t bytes) { copy(dst, src, bytes, hipMemcpyHostToDevice); }
+    void down(void* dst, const void* src, size_t bytes) { copy(dst, src, bytes, hipMemcpyDeviceToHost); }
+    void fill(void* dst, int byte, size_t bytes) {
+        if (ok()) err = hipMemsetAsync(dst, byte, bytes, ctx->stream);
+    }
+    void launched() { keep(hipGetLastError()); }  // after a kernel launch
+    void sync() {
+        if (ok()) err = hipStreamSynchronize(ctx->stream);
+    }
+    int32_t status(const char* what) const {
+        if (!base) return vx_fail(ctx, VX_ERR_OOM, "%s: out of device memory", what);
+        return err == hipSuccess ? VX_OK : vx_fail(ctx, VX_ERR_DEVICE, "%s: %s", what, hipGetErrorString(err));
+    }
+};
 
 struct vx_tree {
     uint64_t* levels;  // level 0 (leaf digests, 4*n) followed by each parent level up to the cap
@@ -69,7 +115,6 @@ struct vx_tree {
     size_t total;  // uint64 count
 };
 
-int32_t vx_fail(vx_ctx* ctx, int32_t code, const char* fmt, ...);
 #define VX_HIP(call)                                                                              \
     do {                                                                                          \
         hipError_t e_ = (call);                                                                   \

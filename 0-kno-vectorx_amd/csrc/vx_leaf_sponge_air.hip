@@ -1,21 +1,21 @@
-// Witness and prover of LeafSpongeAir (air_leaf_sponge.cuh): the opened leaf rows of one tree hashed in one table, and the
-// two-table proof vx_merkle_rows_prove (MerkleOpenAir + LeafSpongeAir on one logUp bus).
+// Witness and prover of the sponge tables (air_leaf_sponge.cuh): LeafSpongeAir, the opened leaf rows of one tree hashed in one
+// table, LeafSpongeSetAir, rows of several trees (the sponge tables of vx_fri_queries_prove and vx_stark_openings_prove), and the
+// two-table proof vx_merkle_rows_prove (MerkleOpenAir + LeafSpongeAir on one logUp bus).  One witness (LeafSpongeWitness, vx_bus.h),
+// made by sponge_states from any source and read by sponge_trace:
 //   k_leaf_sponge_states  the blocks of one leaf are a CHAIN (block k needs the output of block k - 1), and the workload has few
 //                         leaves and long chains (84 leaves x 128 permutations at leaf_len 1018): latency-bound.  16 lanes per
-//                         leaf run the cooperative permutation of the tree builder (poseidon.cuh), gather the row from the
-//                         leaf data in any of the three layouts, and store the state ENTERING every block, the row (the
-//                         claims the public inputs digest) and the digest, which is compared with the tree's leaf digest
+//                         leaf run the cooperative permutation of the tree builder (poseidon.cuh), gather the row from its
+//                         source, and store the state ENTERING every block, the row (the claims the public inputs digest) and the
+//                         digest, which is compared with the tree's leaf digest: the first opening that differs is reported
 //   k_leaf_sponge_trace   one lane per block: the blocks are independent once their entering states exist -- the lane writes
-//                         the shape columns and walks the 30 rounds (poseidon_air.cuh) over its 32 rows
+//                         the shape columns and walks the 30 rounds (poseidon_air.cuh) over its 32 rows; SET: with the TREE column
 //   k_leaf_sponge_aux     one lane per block: ONE extension inversion for the block's five helpers (Montgomery batch over the
 //                         products of its denominator pairs), written to its 32 rows, and the block's running-sum increment
-//                         on its first row (vx_bus_close_dev scans it)
-// LeafSpongeSetAir (rows of several trees, the sponge table of vx_fri_queries_prove) runs the same three kernels: the states kernel
-// in a fourth layout -- the leaf of a FRI layer, 16 extension values at natural positions bitrev(16 j + t), what vx_fri_layer_tree
-// hashes -- with a per-leaf entry (tree, layer values, the tree's leaf digests, log2 of its leaves); trace and aux with the TREE
-// column written and used in the denominators.  A fifth layout of the states kernel takes the rows themselves, handed over one per
-// opening (the sponge tables of vx_stark_openings_prove, whose rows come out of a proof: no tree exists to compare a digest with --
-// the path the digest enters is the check); any leaf length, one per table.
+//                         on its first row (vx_bus_close_dev scans it); SET: with the tree in the denominators
+// The sources of the states kernel: one tree's leaf data in any of the three vx_merkle_build layouts; the leaves of FRI layers -- 16
+// extension values at natural positions bitrev(16 j + t), what vx_fri_layer_tree hashes -- with a per-leaf entry (tree, layer
+// values, the tree's leaf digests, log2 of its leaves); and the rows themselves, handed over one per opening (their rows come out of
+// a proof: no tree exists to compare a digest with -- the path the digest enters is the check); any leaf length, one per table.
 // Parity: tests/test_gpu_leaf_sponge.py compares trace, auxiliary columns and both proofs with tests/leaf_sponge_ref.py and the
 // reference prover.
 #include <string.h>
@@ -50,8 +50,8 @@ struct SpongeArgs {
     uint64_t* states;   // [n_idx n_blk][12]: the state entering every block
     uint64_t* claims;   // [n_idx][1 + leaf_len]: (index, row)
     uint64_t* digests;  // [n_idx][4]
-    uint64_t* bad;      // 1 + the number of an opening whose digest is not the tree's (0: none)
-    const SetLeaf* set;  // LAYOUT_FRI_LAYER / LAYOUT_ROWS: [n_idx]; data, tree_leaves, n_leaves, log_leaves above are unused, leaf_len is 32 / the rows' 
+    unsigned long long* bad;  // LeafSpongeWitness::bad_d
+    const SetLeaf* set;  // LAYOUT_FRI_LAYER / LAYOUT_ROWS: [n_idx]; data, tree_leaves, n_leaves, log_leaves above are unused, leaf_len is 32 / the rows'
 };
 
 // (Tried: one lane per leaf with the tree builder's poseidon_permute -- 6.23 ms against 2.30 ms for 84 leaves x 128 blocks,
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_leaf_sponge_states(SpongeArgs a) {
     }
     if (live && l < 4) {
         a.digests[4 * p + l] = s;
-        if (tree_leaves && gl_canon(tree_leaves[4 * j + l]) != s) *a.bad = p + 1;
+        if (tree_leaves && gl_canon(tree_leaves[4 * j + l]) != s) atomicMin(a.bad, (unsigned long long)(p + 1));
     }
 }
 
@@ -173,7 +173,95 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restri
 }
 
 constexpr size_t MAX_LEAF_LEN = (size_t)1 << 20;
+
+// where the rows of a witness come from: what SpongeArgs distinguishes
+struct SpongeSource {
+    int layout;  // a vx_merkle_build layout: the data of one tree; LAYOUT_FRI_LAYER, LAYOUT_ROWS: one `set` entry per opening
+    size_t leaf_len;
+    const uint64_t *data = nullptr, *tree_leaves = nullptr;  // one tree (SpongeArgs)
+    size_t n_leaves = 0;
+    int log_leaves = 0;
+    const SetLeaf* set = nullptr;    // [n_idx]
+    const uint64_t* rows = nullptr;  // LAYOUT_ROWS: [n_idx][leaf_len] on the host; uploaded here, and the entries go up with `data` = their row
+};
+
+// The states of every opening's chain, enqueued on ctx->stream.  The requests' ranges are the caller's to check.
+int32_t sponge_states(vx_ctx* ctx, const SpongeSource& src, const uint64_t* leaf_idx, size_t n_idx, LeafSpongeWitness* w) {
+    const size_t leaf_len = src.leaf_len, n_blk = sponge_blocks(leaf_len), w_set = src.set ? n_idx * sizeof(SetLeaf) / 8 : 0;
+    static_assert(sizeof(SetLeaf) % 8 == 0, "SetLeaf is a whole number of words");
+    Scratch& sc = w->sc;
+    sc.add(w->states_d, 12 * n_idx * n_blk), sc.add(w->idx_d, n_idx), sc.add(w->claims_d, n_idx * (leaf_len + (src.set ? 2 : 1))), sc.add(w->digests_d, 4 * n_idx), sc.add(w->bad_d, 1);
+    sc.add(w->set_d, w_set), sc.add(w->rows_d, src.rows ? n_idx * leaf_len : 0);
+    sc.alloc(ctx);
+    VX_TRY(sc.status("leaf sponge"));
+    w->n_idx = n_idx, w->n_blk = n_blk, w->leaf_len = leaf_len;
+    sc.up(w->idx_d, leaf_idx, n_idx * 8), sc.fill(w->bad_d, 0xff, 8);
+    const SetLeaf* set = src.set;
+    std::vector<SetLeaf> row_set;
+    if (src.rows) {
+        row_set.assign(set, set + n_idx);
+        for (size_t i = 0; i < n_idx; ++i) row_set[i].data = w->rows_d + i * leaf_len;
+        set = row_set.data();
+        sc.up(w->rows_d, src.rows, n_idx * leaf_len * 8);
+    }
+    if (set) sc.up(w->set_d, set, w_set * 8);
+    if (src.rows) sc.sync();  // (`row_set` is pageable host memory of this frame)
+    if (sc.ok()) {
+        const SpongeArgs a{src.data,    w->idx_d,    src.tree_leaves, src.n_leaves, leaf_len, n_idx, n_blk, src.log_leaves,
+                           w->states_d, w->claims_d, w->digests_d, (unsigned long long*)w->bad_d, (const SetLeaf*)w->set_d};
+        const dim3 grid((unsigned)((n_idx + 15) / 16)), block(256);  // 16 lanes per leaf
+        if (src.layout == VX_LEAVES_ROW_MAJOR) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_ROW_MAJOR>, grid, block, 0, ctx->stream, a);
+        else if (src.layout == VX_LEAVES_COLS_BITREV) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS_BITREV>, grid, block, 0, ctx->stream, a);
+        else if (src.layout == VX_LEAVES_COLS) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS>, grid, block, 0, ctx->stream, a);
+        else if (src.layout == LAYOUT_FRI_LAYER) hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_FRI_LAYER>, grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_ROWS>, grid, block, 0, ctx->stream, a);
+        sc.launched();
+    }
+    return sc.status("leaf sponge");
+}
+
+// the trace kernel over a witness, on any context of the device
+template <bool SET>
+int32_t sponge_trace(vx_ctx* ctx, const LeafSpongeWitness& w, int log_n, uint64_t* trace_d) {
+    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * w.n_idx * w.n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", w.n_idx, w.n_blk, log_n);
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_leaf_sponge_trace<SET>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, w.states_d, w.idx_d, w.n_idx, w.n_blk, n, trace_d, (const SetLeaf*)w.set_d);
+    VX_HIP(hipGetLastError());
+    return VX_OK;
+}
+
+// A table made in one go: states, trace, then the claims and the mismatch word back -- the one wait.  *bad: the first opening that
+// does not hash to its tree's leaf digest, n_idx when all do (the caller words the refusal).
+template <bool SET>
+int32_t sponge_table(vx_ctx* ctx, const SpongeSource& src, const uint64_t* leaf_idx, size_t n_idx, int log_n, uint64_t* trace_d, std::vector<uint64_t>* claims, size_t* bad) {
+    LeafSpongeWitness w;
+    VX_TRY(sponge_states(ctx, src, leaf_idx, n_idx, &w));
+    VX_TRY(sponge_trace<SET>(ctx, w, log_n, trace_d));
+    claims->resize(n_idx * (src.leaf_len + (SET ? 2 : 1)));
+    uint64_t word = 0;
+    w.sc.down(claims->data(), w.claims_d, claims->size() * 8), w.sc.down(&word, w.bad_d, 8), w.sc.sync();
+    VX_TRY(w.sc.status("leaf sponge"));
+    *bad = word == ~0ULL ? n_idx : (size_t)(word - 1);
+    return VX_OK;
+}
+
+template <bool SET>
+int32_t sponge_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n, blocks = n / 32;
+    uint32_t wmask = 0;
+    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
+    hipLaunchKernelGGL(k_leaf_sponge_aux<SET>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
+    VX_HIP(hipGetLastError());
+    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+}
 }  // namespace
+
+int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    return sponge_gen_aux<false>(ctx, trace, log_n, chal, pub, aux, aux_pub);
+}
+int32_t LeafSpongeSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    return sponge_gen_aux<true>(ctx, trace, log_n, chal, pub, aux, aux_pub);
+}
 
 // L, B, the tail flags, the digest of the (index, row) claims: shared with the verifier (vx_verify.hip)
 void vx_leaf_sponge_public(size_t leaf_len, const uint64_t* claims, size_t n_idx, uint64_t pub[14]) {
@@ -181,24 +269,6 @@ void vx_leaf_sponge_public(size_t leaf_len, const uint64_t* claims, size_t n_idx
     pub[PUB_L] = leaf_len, pub[PUB_B] = sponge_blocks(leaf_len);
     for (size_t i = 0; i < 8; ++i) pub[PUB_W + i] = i < (t ? t : 8);
     glh::hash_no_pad(claims, n_idx * (leaf_len + 1), pub + PUB_DIGEST);
-}
-
-int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    uint32_t wmask = 0;
-    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
-    hipLaunchKernelGGL(k_leaf_sponge_aux<false>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
-}
-
-int32_t LeafSpongeSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    uint32_t wmask = 0;
-    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
-    hipLaunchKernelGGL(k_leaf_sponge_aux<true>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
 }
 
 // LeafSpongeSetAir's public inputs: L, B, the tail flags, a digest the table does not constrain (prover and verifier alike: vx_bus.h)
@@ -225,40 +295,14 @@ int32_t vx_leaf_sponge_set_trace_dev(vx_ctx* ctx, const uint64_t* const* evals_d
         VX_CHECK(leaf_idx[i] >> log_leaves[t] == 0, "leaf sponge: index %zu (%llu) is not a leaf of tree %zu", i, (unsigned long long)leaf_idx[i], t);
         set[i] = SetLeaf{evals_d[t], tree_leaves ? tree_leaves[t] : nullptr, tree_of[i], log_leaves[t]};
     }
-    const size_t n = (size_t)1 << log_n, w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 2), w_set = n_idx * sizeof(SetLeaf) / 8;
-    static_assert(sizeof(SetLeaf) % 8 == 0, "SetLeaf is a whole number of words");
-    // scratch: the entering states, the indices, the claims, the digests, the mismatch word, the per-leaf table
-    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1 + w_set) * 8);
-    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
-    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx, *set_d = bad_d + 1;
-    std::vector<uint64_t> claims(w_claims);
-    uint64_t bad = 0;
-    int32_t rc = VX_OK;
-    do {
-        hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(set_d, set.data(), w_set * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(bad_d, 0, 8, ctx->stream);
-        if (e != hipSuccess) {
-            rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
-            break;
-        }
-        const SpongeArgs a{nullptr, idx_d, nullptr, 0, leaf_len, n_idx, n_blk, 0, states, claims_d, digests_d, bad_d, (const SetLeaf*)set_d};
-        hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_FRI_LAYER>, dim3((unsigned)((n_idx + 15) / 16)), dim3(256), 0, ctx->stream, a);  // 16 lanes per leaf
-        e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_leaf_sponge_trace<true>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d, (const SetLeaf*)set_d);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, w_claims * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
-    } while (0);
-    vx_pool_free(ctx, sc);
-    VX_TRY(rc);
-    if (bad)
+    SpongeSource src{LAYOUT_FRI_LAYER, leaf_len};
+    src.set = set.data();
+    std::vector<uint64_t> claims;
+    size_t bad = 0;
+    VX_TRY(sponge_table<true>(ctx, src, leaf_idx, n_idx, log_n, trace_d, &claims, &bad));
+    if (bad < n_idx)
         return vx_fail(ctx, VX_ERR_STATEMENT, "leaf sponge: opening %llu (leaf %llu of tree %llu) does not hash to the tree's leaf digest -- the layer is not what the tree was built from",
-                       (unsigned long long)(bad - 1), (unsigned long long)leaf_idx[bad - 1], (unsigned long long)tree_of[bad - 1]);
+                       (unsigned long long)bad, (unsigned long long)leaf_idx[bad], (unsigned long long)tree_of[bad]);
     uint64_t digest[4];
     glh::hash_no_pad(claims.data(), claims.size(), digest);
     vx_leaf_sponge_set_public(leaf_len, digest, pub_out);
@@ -266,7 +310,7 @@ int32_t vx_leaf_sponge_set_trace_dev(vx_ctx* ctx, const uint64_t* const* evals_d
 }
 
 // ---- the witness of LeafSpongeSetAir from rows handed over directly (vx_bus.h)
-int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, SpongeRowsWitness* w) {
+int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, LeafSpongeWitness* w) {
     VX_CHECK(leaf_len >= 5 && leaf_len <= MAX_LEAF_LEN, "leaf sponge: leaf_len %zu (5..2^20; a row of at most 4 words is its own digest and has no sponge)", leaf_len);
     VX_CHECK(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "leaf sponge: %zu openings (1..2^21)", n_idx);
     const size_t n_blk = sponge_blocks(leaf_len);
@@ -275,42 +319,14 @@ int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint6
         VX_CHECK(tree_of[i] >> 32 == 0 && leaf_idx[i] >> 40 == 0, "leaf sponge: opening %zu names leaf %llu of tree %llu (below 2^40 / 2^32)", i, (unsigned long long)leaf_idx[i],
                  (unsigned long long)tree_of[i]);
     for (size_t i = 0; i < n_idx * leaf_len; ++i) VX_CHECK(rows[i] < glh::P, "leaf sponge: opening %zu has a non-canonical word", i / leaf_len);
-    const size_t w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 2), w_set = n_idx * sizeof(SetLeaf) / 8, w_rows = n_idx * leaf_len;
-    // scratch: the entering states, the indices, the claims, the digests, the (unused) mismatch word, the per-leaf table, the rows
-    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1 + w_set + w_rows) * 8);
-    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
-    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx, *set_d = bad_d + 1, *rows_d = set_d + w_set;
     std::vector<SetLeaf> set(n_idx);
-    for (size_t i = 0; i < n_idx; ++i) set[i] = SetLeaf{rows_d + i * leaf_len, nullptr, tree_of[i], 0};
-    hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(set_d, set.data(), w_set * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rows_d, rows, w_rows * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (`set` is pageable host memory of this frame)
-    if (e == hipSuccess) {
-        const SpongeArgs a{nullptr, idx_d, nullptr, 0, leaf_len, n_idx, n_blk, 0, states, claims_d, digests_d, bad_d, (const SetLeaf*)set_d};
-        hipLaunchKernelGGL(k_leaf_sponge_states<LAYOUT_ROWS>, dim3((unsigned)((n_idx + 15) / 16)), dim3(256), 0, ctx->stream, a);  // 16 lanes per leaf
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        vx_pool_free(ctx, sc);
-        return vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
-    }
-    *w = SpongeRowsWitness{sc, states, idx_d, digests_d, set_d, n_idx, n_blk, leaf_len};
-    return VX_OK;
+    for (size_t i = 0; i < n_idx; ++i) set[i] = SetLeaf{nullptr, nullptr, tree_of[i], 0};
+    SpongeSource src{LAYOUT_ROWS, leaf_len};
+    src.set = set.data(), src.rows = rows;
+    return sponge_states(ctx, src, leaf_idx, n_idx, w);
 }
 
-int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* ctx, const SpongeRowsWitness& w, int log_n, uint64_t* trace_d) {
-    VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * w.n_idx * w.n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", w.n_idx, w.n_blk, log_n);
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_leaf_sponge_trace<true>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, w.states_d, w.idx_d, w.n_idx, w.n_blk, n, trace_d, (const SetLeaf*)w.set_d);
-    VX_HIP(hipGetLastError());
-    return VX_OK;
-}
-
-void vx_leaf_sponge_rows_free(vx_ctx* ctx, SpongeRowsWitness* w) {
-    if (w->sc) vx_pool_free(ctx, w->sc);
-    *w = SpongeRowsWitness();
-}
+int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* ctx, const LeafSpongeWitness& w, int log_n, uint64_t* trace_d) { return sponge_trace<true>(ctx, w, log_n, trace_d); }
 
 // The witness of LeafSpongeAir on the device.  data_d: the leaves of the whole tree ([n_leaves x leaf_len] words in `layout`; the
 // caller has checked that the buffer holds them).  tree_leaves (device, may be nullptr): the leaf digests of the tree the openings
@@ -325,41 +341,13 @@ static int32_t leaf_sponge_trace_dev(vx_ctx* ctx, const uint64_t* data_d, size_t
     const size_t n_blk = sponge_blocks(leaf_len);
     VX_CHECK(log_n >= 5 && log_n <= 26 && 32 * n_idx * n_blk <= ((size_t)1 << log_n), "leaf sponge: %zu leaves of %zu blocks do not fit 2^%d rows", n_idx, n_blk, log_n);
     for (size_t i = 0; i < n_idx; ++i) VX_CHECK(leaf_idx[i] < n_leaves, "leaf sponge: index %zu (%llu) is not a leaf of the tree", i, (unsigned long long)leaf_idx[i]);
-    const size_t n = (size_t)1 << log_n, w_states = 12 * n_idx * n_blk, w_claims = n_idx * (leaf_len + 1);
-    // scratch: the entering states, the indices, the claims, the digests, the mismatch word
-    uint64_t* sc = (uint64_t*)vx_pool_alloc(ctx, (w_states + n_idx + w_claims + 4 * n_idx + 1) * 8);
-    if (!sc) return vx_fail(ctx, VX_ERR_OOM, "leaf sponge: out of device memory");
-    uint64_t *states = sc, *idx_d = states + w_states, *claims_d = idx_d + n_idx, *digests_d = claims_d + w_claims, *bad_d = digests_d + 4 * n_idx;
-    std::vector<uint64_t> claims(w_claims);
-    uint64_t bad = 0;
-    int32_t rc = VX_OK;
-    do {
-        hipError_t e = hipMemcpyAsync(idx_d, leaf_idx, n_idx * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(bad_d, 0, 8, ctx->stream);
-        if (e != hipSuccess) {
-            rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
-            break;
-        }
-        const SpongeArgs a{data_d, idx_d, tree_leaves, n_leaves, leaf_len, n_idx, n_blk, log_leaves, states, claims_d, digests_d, bad_d, nullptr};
-        const dim3 grid((unsigned)((n_idx + 15) / 16)), block(256);  // 16 lanes per leaf
-        if (layout == VX_LEAVES_ROW_MAJOR) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_ROW_MAJOR>, grid, block, 0, ctx->stream, a);
-        else if (layout == VX_LEAVES_COLS_BITREV) hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS_BITREV>, grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL(k_leaf_sponge_states<VX_LEAVES_COLS>, grid, block, 0, ctx->stream, a);
-        e = hipGetLastError();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_leaf_sponge_trace<false>, dim3((unsigned)((n / 32 + 63) / 64)), dim3(64), 0, ctx->stream, states, idx_d, n_idx, n_blk, n, trace_d, (const SetLeaf*)nullptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(claims.data(), claims_d, w_claims * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: %s", hipGetErrorString(e));
-    } while (0);
-    vx_pool_free(ctx, sc);
-    VX_TRY(rc);
-    if (bad)
+    SpongeSource src{layout, leaf_len, data_d, tree_leaves, n_leaves, log_leaves};
+    std::vector<uint64_t> claims;
+    size_t bad = 0;
+    VX_TRY(sponge_table<false>(ctx, src, leaf_idx, n_idx, log_n, trace_d, &claims, &bad));
+    if (bad < n_idx)
         return vx_fail(ctx, VX_ERR_STATEMENT, "merkle rows: opening %llu (leaf %llu) does not hash to the tree's leaf digest -- the leaf data is not what the tree was built from",
-                       (unsigned long long)(bad - 1), (unsigned long long)leaf_idx[bad - 1]);
+                       (unsigned long long)bad, (unsigned long long)leaf_idx[bad]);
     vx_leaf_sponge_public(leaf_len, claims.data(), n_idx, pub_out);
     return VX_OK;
 }
@@ -395,12 +383,11 @@ int32_t vx_leaf_sponge_rows_air_trace(vx_ctx* ctx, size_t leaf_len, const uint64
     if (!ctx || !tree_of || !leaf_idx || !rows || !trace_out || !public_out) return VX_ERR_ARG;
     VX_CHECK(log_n >= 5 && log_n <= 26 && trace_out->n >= ((size_t)SET_COLS << log_n), "leaf sponge: the trace buffer holds %zu elements, too few for %d columns of 2^%d rows (5 <= log_n <= 26)",
              trace_out->n, SET_COLS, log_n);
-    SpongeRowsWitness w;
+    LeafSpongeWitness w;
     VX_TRY(vx_leaf_sponge_rows_states_dev(ctx, leaf_len, tree_of, leaf_idx, rows, n_idx, &w));
-    int32_t rc = vx_leaf_sponge_rows_trace_dev(ctx, w, log_n, trace_out->d);
-    if (rc == VX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = vx_fail(ctx, VX_ERR_DEVICE, "leaf sponge: the witness kernels failed");
-    vx_leaf_sponge_rows_free(ctx, &w);
-    VX_TRY(rc);
+    VX_TRY(vx_leaf_sponge_rows_trace_dev(ctx, w, log_n, trace_out->d));
+    w.sc.sync();
+    VX_TRY(w.sc.status("leaf sponge"));
     std::vector<uint64_t> claims;  // (tree, index, row) of every opening: the set's claims digest
     claims.reserve(n_idx * (leaf_len + 2));
     for (size_t i = 0; i < n_idx; ++i) {

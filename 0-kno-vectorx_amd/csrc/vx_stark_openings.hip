@@ -18,16 +18,6 @@
 namespace {
 constexpr int N_TREE_IDS = (int)VX_SOPEN_TREE0 + 3;
 const char* tree_name(uint64_t t) { return t == VX_SOPEN_TREE0 ? "trace" : t == VX_SOPEN_TREE0 + 1 ? "auxiliary" : t == VX_SOPEN_TREE0 + 2 ? "quotient" : "FRI layer"; }
-// the witnesses live in pool blocks of the caller's context until the group has proven
-struct Witnesses {
-    vx_ctx* ctx;
-    MerklePathsWitness paths;
-    SpongeRowsWitness sponge[3];
-    ~Witnesses() {
-        vx_merkle_paths_free(ctx, &paths);
-        for (SpongeRowsWitness& s : sponge) vx_leaf_sponge_rows_free(ctx, &s);
-    }
-};
 }  // namespace
 
 extern "C" {
@@ -43,7 +33,9 @@ int32_t vx_stark_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const u
     VX_CHECK(so.cap_h <= 16 && stark_openings_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, &ts),
              "stark openings: the proof's shape has no openings group (cap height above 16, a tree without a level, or a table of more than 2^26 rows)");
     const size_t n_claims = so.claims.size(), n_trees = so.tree.size(), cap_words = (size_t)4 << so.cap_h;
-    Witnesses wit{ctx, {}, {}};
+    // the witnesses hold pool blocks of this context until the group has proven (declared before it: vx_bus.h)
+    MerkleOpenWitness paths;
+    LeafSpongeWitness sponge[3];
     // ---- the sponge chains of every leaf longer than 4 words, one launch per length; their digests enter the paths on the device
     std::vector<const uint64_t*> leaf_dev(n_claims, nullptr);
     std::vector<uint64_t> leaf_dig(4 * n_claims, 0);
@@ -57,8 +49,8 @@ int32_t vx_stark_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const u
             who.push_back(i), s_tree[k - 1].push_back(c.tree), s_idx[k - 1].push_back(c.index);
             s_rows[k - 1].insert(s_rows[k - 1].end(), so.leaves.begin() + c.leaf, so.leaves.begin() + c.leaf + L);
         }
-        VX_TRY(vx_leaf_sponge_rows_states_dev(ctx, L, s_tree[k - 1].data(), s_idx[k - 1].data(), s_rows[k - 1].data(), who.size(), &wit.sponge[k - 1]));
-        for (size_t j = 0; j < who.size(); ++j) leaf_dev[who[j]] = wit.sponge[k - 1].digests_d + 4 * j;
+        VX_TRY(vx_leaf_sponge_rows_states_dev(ctx, L, s_tree[k - 1].data(), s_idx[k - 1].data(), s_rows[k - 1].data(), who.size(), &sponge[k - 1]));
+        for (size_t j = 0; j < who.size(); ++j) leaf_dev[who[j]] = sponge[k - 1].digests_d + 4 * j;
     }
     // ---- the paths: a row of at most 4 words is its own digest, zero-padded; the siblings are read where the claims say they lie
     int log_leaves[N_TREE_IDS] = {0};
@@ -78,7 +70,7 @@ int32_t vx_stark_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const u
     // the native statement check: every path reaches the root of its tree (this also waits for the sponge chains)
     size_t bad = 0;
     const int32_t prc = vx_merkle_paths_states_dev(ctx, caps.data(), so.cap_h, log_leaves, (size_t)N_TREE_IDS, tree_of.data(), leaf_idx.data(), leaf_dig.data(), leaf_dev.data(), sibs.data(),
-                                                   n_claims, &wit.paths, &bad);
+                                                   n_claims, &paths, &bad);
     if (prc == VX_ERR_STATEMENT && bad < n_claims) {
         const uint64_t t = so.claims[bad].tree;
         if (t < VX_SOPEN_TREE0)
@@ -94,13 +86,13 @@ int32_t vx_stark_openings_prove(vx_ctx* ctx, const vx_stark_config* cfg, const u
     // host thread of its own; their gens only launch trace kernels over the buffers above, which nothing writes any more
     TableGroup g(ctx, cfg, "stark openings");
     const int open = g.add({"openings", VX_AIR_MERKLE_OPEN_SET, ts.log_n[0], mop::SET_COLS, mop::SET_PUB, 0, [&](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-                                VX_TRY(vx_merkle_paths_trace_dev(c, wit.paths, ts.log_n[0], trace->d));
+                                VX_TRY(vx_merkle_paths_trace_dev(c, paths, ts.log_n[0], trace->d));
                                 vx_merkle_open_set_public(stmt, pub);
                                 return (int32_t)VX_OK;
                             }});
     for (int k = 1; k < ts.n; ++k)
         g.add({"sponge", VX_AIR_LEAF_SPONGE_SET, ts.log_n[k], lsp::SET_COLS, lsp::PUB, 0, [&, k](vx_ctx* c, vx_buf* trace, uint64_t* pub) {
-                   VX_TRY(vx_leaf_sponge_rows_trace_dev(c, wit.sponge[k - 1], ts.log_n[k], trace->d));
+                   VX_TRY(vx_leaf_sponge_rows_trace_dev(c, sponge[k - 1], ts.log_n[k], trace->d));
                    vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, pub);
                    return (int32_t)VX_OK;
                }});

@@ -74,6 +74,25 @@ def test_witness_equals_the_reference(ctx, vx, oracle, name):
     tb.free(), ab.free(), gtree.free(), data.free()
 
 
+@pytest.mark.parametrize("n", [1, 17])  # 17: a second group of 16 lanes plus one
+@pytest.mark.parametrize("L", [5, 8, 9])  # one partial block, exactly one block, a one-word tail
+def test_the_rows_table_is_the_single_table(ctx, vx, L, n):
+    """LeafSpongeSetAir from rows handed over is LeafSpongeAir on the same rows with a trailing column: columns 0..65 agree"""
+    D = 5
+    leaves = np.random.default_rng(100 * L + n).integers(0, P, size=(1 << D, L), dtype=np.uint64)
+    idx = [int(v) for v in np.random.default_rng(n).permutation(1 << D)[:n]]
+    data = ctx.from_host(leaves)
+    log_n = R.log_rows(n, L)
+    single, _ = ctx.leaf_sponge_air_trace(data, 1 << D, L, vx.lib.VX_LEAVES_ROW_MAJOR, idx, log_n)
+    as_rows, _ = ctx.leaf_sponge_rows_air_trace([0] * n, idx, leaves[idx], log_n)
+    want = single.download().reshape(R.COLS, -1)
+    got = as_rows.download().reshape(vx.lib.VX_LEAF_SPONGE_SET_AIR_COLS, -1)
+    assert want.shape[1] == got.shape[1] == 1 << log_n
+    bad = np.argwhere(got[:R.COLS] != want)
+    assert bad.size == 0, "first differing (column, row): %s" % bad[:1]
+    single.free(), as_rows.free(), data.free()
+
+
 PROOFS = {
     "D3_cap0_L9_row_major": (3, 0, 9, "row_major", [1, 6, 3], {}),
     "D5_cap1_L21_cols_bitrev": (5, 1, 21, "cols_bitrev", [31, 4], {}),
@@ -168,6 +187,20 @@ def test_statement_refusal(ctx, vx, oracle):
     assert e.value.code == -5  # VX_ERR_STATEMENT
     blob = ctx.merkle_rows_prove(gtree, data2, 9, layout, [1, 3], cfg)  # the changed leaf is not opened: the rows agree
     vx.lib.merkle_rows_verify(blob, gtree.cap(), 3, [1, 3], leaves[[1, 3]], cfg)
+    gtree.free(), data.free(), data2.free()
+
+
+def test_the_first_mismatch_is_the_one_named(ctx, vx, oracle):
+    """two opened leaves differ from what the tree was built from: the refusal names the lower opening number"""
+    layout = vx.lib.VX_LEAVES_COLS_BITREV
+    leaves, data, gtree, _ = make(ctx, vx, oracle, 3, 9, layout, 0)
+    other = leaves.copy()
+    other[3, 0] ^= 1
+    other[6, 8] ^= 1
+    data2 = ctx.from_host(in_layout(vx, other, layout))
+    with pytest.raises(vx.VxError, match=r"opening 1 \(leaf 6\)") as e:  # openings 1 (leaf 6) and 2 (leaf 3) are wrong
+        ctx.merkle_rows_prove(gtree, data2, 9, layout, [1, 6, 3], ctx.stark_config(num_queries=8))
+    assert e.value.code == -5  # VX_ERR_STATEMENT
     gtree.free(), data.free(), data2.free()
 
 

@@ -41,6 +41,26 @@ def test_witness_equals_the_reference(ctx, vx, oracle, name):
     tb.free(), ab.free(), gtree.free()
 
 
+# depth 5 at cap heights 0, 2 and 5 (no level is read below the cap): both ends and a duplicate, 20 active blocks and 12 idle ones;
+# depth 4: eight paths fill the 32 blocks of 2^10 rows exactly
+ONE_TREE = {"D5_cap0": (5, 0, [0, 31, 31, 17]), "D5_cap2": (5, 2, [0, 31, 31, 17]), "D5_cap5": (5, 5, [0, 31, 31, 17]), "D4_full": (4, 1, [0, 15, 7, 8, 3, 3, 12, 1])}
+
+
+@pytest.mark.parametrize("name", list(ONE_TREE))
+def test_the_set_of_one_tree_is_the_single_table(ctx, vx, oracle, name):
+    """MerkleOpenSetAir over one tree is MerkleOpenAir with trailing columns: columns 0..65 agree over the whole table, idle blocks included"""
+    D, cap_height, idx = ONE_TREE[name]
+    gtree, _ = trees(ctx, vx, oracle, D, cap_height)
+    single, _ = ctx.merkle_open_air_trace(gtree, idx, 10)
+    as_set, _ = ctx.merkle_open_set_air_trace([gtree], [0] * len(idx), idx, 10)
+    want = single.download().reshape(M.COLS, -1)
+    got = as_set.download().reshape(vx.lib.VX_MERKLE_OPEN_SET_AIR_COLS, -1)
+    assert want.shape[1] == got.shape[1] == 1 << 10 and len(idx) * D <= 32
+    bad = np.argwhere(got[:M.COLS] != want)
+    assert bad.size == 0, "first differing (column, row): %s" % bad[:1]
+    single.free(), as_set.free(), gtree.free()
+
+
 @pytest.mark.parametrize("D,Q,over", [(3, 3, {}), (5, 7, {}), (3, 3, dict(rate_bits=3, num_queries=28))], ids=["D3_Q3", "D5_Q7", "D3_Q3_rate3"])
 def test_proof_equals_the_reference_prover(ctx, vx, oracle, D, Q, over):
     gtree, rtree = trees(ctx, vx, oracle, D, 1)
