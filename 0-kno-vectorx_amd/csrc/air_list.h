@@ -8,6 +8,7 @@
 #include "air_epoch.cuh"
 #include "air_fri_combine.cuh"
 #include "air_fri_fold.cuh"
+#include "air_leaf_noop.cuh"
 #include "air_leaf_sponge.cuh"
 #include "air_merkle_open.cuh"
 #include "air_sha.cuh"
@@ -18,7 +19,7 @@
 template <class... Airs>
 struct AirList {};
 using VxAirs = AirList<ShaAir, BlakeAir, FibAir, MixAir, LookupAir, ShaTreeAir256, ShaTreeAir512, ShaTreeAir16, EdAir17, EdAir16, Sha512Air16, Sha512Air10, Sha512Air15,
-                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir, MerkleOpenSetAir, LeafSpongeSetAir, FriCombineAir>;
+                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir, MerkleOpenSetAir, LeafSpongeSetAir, FriCombineAir, LeafNoopAir>;
 
 template <class... Airs>
 constexpr bool air_list_ok(AirList<Airs...>) {

@@ -134,6 +134,13 @@ struct View : Proof<const uint64_t> {
         out->pr = pr, out->s = &shape;
         return nullptr;
     }
+    // ... of the HEAD of a proof, everything before the query records: for a reader that never calls query().  The words are the
+    // whole proof (the records are there and are not read) or the head alone; no other length is a proof of this shape.
+    static const char* parse_head(const uint64_t* pr, size_t len, const Shape& shape, View* out) {
+        if (len != shape.o_queries) return parse(pr, len, shape, out);
+        out->pr = pr, out->s = &shape;
+        return nullptr;
+    }
 };
 struct Writer : Proof<uint64_t> {
     std::vector<uint64_t> words;

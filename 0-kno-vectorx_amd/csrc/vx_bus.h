@@ -226,6 +226,14 @@ struct LeafSpongeWitness {
 int32_t vx_leaf_sponge_rows_states_dev(vx_ctx* ctx, size_t leaf_len, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* rows, size_t n_idx, LeafSpongeWitness* w);
 int32_t vx_leaf_sponge_rows_trace_dev(vx_ctx* c, const LeafSpongeWitness& w, int log_n, uint64_t* trace_d);
 
+// LeafNoopAir (vx_leaf_noop_air.hip): the openings of leaves of at most 4 words, which are their own digest.  Opening i is leaf
+// leaf_idx[i] of tree tree_of[i] with leaf_len[i] in 1..4 words, rows[i][4] zero-padded (host, canonical).  Its public inputs are
+// the four words of a digest it does not constrain, prover and verifier alike.  vx_leaf_noop_check: the ranges, VX_ERR_ARG on `ctx`;
+// vx_leaf_noop_trace_dev uploads the openings and launches the trace kernel on ctx->stream.
+void vx_leaf_noop_public(const uint64_t digest[4], uint64_t pub[4]);
+int32_t vx_leaf_noop_check(vx_ctx* ctx, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* leaf_len, const uint64_t* rows, size_t n_idx);
+int32_t vx_leaf_noop_trace_dev(vx_ctx* ctx, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* leaf_len, const uint64_t* rows, size_t n_idx, int log_n, uint64_t* trace_d);
+
 // ---- FRI-combine blob (written by vx_fri_combine_prove in vx_fri_combine_air.hip, read by vx_fri_combine_verify in vx_verify.hip):
 // magic, log2 of the inner proof's LDE, main / auxiliary / quotient columns, queries, length of the FriCombineAir proof that follows
 static const uint64_t VX_FCOMB_MAGIC = 0x31424d4f43465856ULL;  // "VXFCOMB1"
@@ -260,6 +268,36 @@ int32_t vx_fri_combine_host(vx_ctx* ctx, const FriCombineStmt& st, const uint64_
 // the statement digest of vx_fri_combine_fold_prove: both tables' four digest words
 void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index,
                                    const uint64_t* rows, const uint64_t* leaves, size_t n_queries, uint64_t digest[4]);
+
+// ---- STARK-queries blob (written by vx_stark_queries_prove in vx_stark_queries.hip, read by vx_stark_queries_verify in
+// vx_verify.hip): magic, the 7 shape words of the inner proof (as VXSOPEN1), the number of tables, one length per table, the proofs
+// in bus order: MerkleOpenSetAir, one LeafSpongeSetAir per leaf length above 4, LeafNoopAir, FriCombineAir, FriFoldAir
+static const uint64_t VX_SQRY_MAGIC = 0x3130595251535856ULL;  // "VXSQRY01"
+static constexpr size_t VX_SQRY_HDR = 9;                      // before the lengths
+// The whole query phase of a vx_stark_prove proof as claims: the Merkle side (`so`: trees 0..7 the layers, 8 / 9 / 10 main / auxiliary /
+// quotient) and the arithmetic side, from ONE replay of the verifier's code.  In the verifier's query-free mode only the head is
+// filled: so.claims / so.leaves / rows / leaves / ev0 stay empty, so.index holds the derived indices.
+struct StarkQueries {
+    StarkOpenings so;
+    int rate_bits = 0;
+    size_t nq = 0;
+    uint64_t alpha[2] = {0, 0}, zeta[2] = {0, 0};
+    std::vector<uint64_t> openings;  // local [c][2], next [c][2], quotient [nq][2]
+    std::vector<uint64_t> betas, final_poly;
+    std::vector<uint64_t> rows, leaves, ev0;  // [query][c + nq], [query][layer][32], [query][2]
+    FriCombineStmt stmt() const {
+        const size_t c = so.cm + so.ca;
+        return FriCombineStmt{so.LN, rate_bits, so.cm, so.ca, nq, alpha, zeta, openings.data(), openings.data() + 2 * c, openings.data() + 4 * c};
+    }
+};
+// query_free = false: the prover's replay of the whole proof (every check except the paths; where the siblings lie is recorded);
+// true: the verifier's, which reads no word at or behind the query records and accepts the proof whole or as its head alone
+int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                const uint64_t* ext_chal, bool query_free, StarkQueries* out, char* err, size_t errlen);
+// the statement of a proof's query phase, the four digest words of every table: hash_n_to_hash_no_pad(the 7 shape words, alpha, zeta,
+// the openings local / next / quotient, betas, the final polynomial, the folded root of every tree in record order, the index of
+// every query).  No row word and no leaf word: they are in committed traces.  roots: [so.tree.size()][4]
+void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, uint64_t digest[4]);
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

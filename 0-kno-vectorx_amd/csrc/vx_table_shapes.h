@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "stark_proof.h"
 #include "vx_internal.h"
 
 // BlakeChainAir (hash chain / header hash): 16 rows per compression, at least one copy of the 2^16-row XOR tables
@@ -67,6 +68,11 @@ static inline int fri_combine_log_n(size_t n_queries, int log_lde, size_t cm, si
     const int l = ceil_log2(n_queries * (cm + ca + nq + (size_t)log_lde));
     return l < 5 ? 5 : l;
 }
+// LeafNoopAir: one row per opening of a leaf of at most 4 words, at least 2^5 rows
+static inline int leaf_noop_log_n(size_t n_idx) {
+    const int l = ceil_log2(n_idx);
+    return l < 5 ? 5 : l;
+}
 // The tables of a STARK proof's Merkle openings (vx_stark_openings_prove / vx_stark_openings_verify), in bus order: the openings
 // table (MerkleOpenSetAir, one path per (query, tree): main, auxiliary when ca > 0, quotient, the NL layer trees), then one
 // LeafSpongeSetAir table per distinct leaf length above 4 among {cm, ca, 2 2^a}, by ascending length (a row of at most 4 words is
@@ -99,6 +105,43 @@ static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, si
     }
     for (int k = 0; k < t->n; ++k) {
         if (t->log_n[k] < 5) t->log_n[k] = 5;
+        if (t->log_n[k] > 26) return false;
+    }
+    return true;
+}
+// The tables of a STARK proof's whole query phase (vx_stark_queries_prove / vx_stark_queries_verify), in bus order: the tables of
+// stark_openings_tables (FriFoldAir needs a = 4 and at least one layer: the layer leaves have 32 words), then LeafNoopAir (one row
+// per opening of a leaf of at most 4 words: the quotient tree always, main and auxiliary when that narrow), FriCombineAir and
+// FriFoldAir.  The tables are proven under the configuration of the inner proof, and a FRI plan can overshoot: with arity 4,
+// final_poly_bits 0 and cap height 0 a table of 2^7 rows would be folded twice, below degree one (plonky2's ConstantArityBits
+// asserts there) -- no final polynomial is left and no proof of that size exists.  Such a table is proven at the next size that
+// has a plan (its rows behind the claims are idle), prover and proof bound alike; the verifier reads a table's size from its proof.
+// false: what stark_openings_tables refuses, a != 4, no layer, no index bit left, or a table of more than 2^26 rows.
+static inline bool fri_plan_ok(int log_n, const vx_stark_config& cfg) {
+    int d = log_n;
+    for (int a : stark_proof::fri_arity_plan(log_n, cfg)) d -= a;
+    return d >= 0;
+}
+struct StarkQueriesTables {
+    int n = 0, n_sponge = 0;
+    int air[7], log_n[7];
+    size_t leaf_len[7];  // of the sponge tables, 0 elsewhere
+    size_t noop_per_query = 0;
+};
+static inline bool stark_queries_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, const vx_stark_config& cfg, StarkQueriesTables* t) {
+    StarkOpeningsTables o;
+    if (a != 4 || NL < 1 || LN - 4 * (int)NL < 1 || !stark_openings_tables(LN, cm, ca, a, NL, n_queries, &o)) return false;
+    for (int k = 0; k < o.n; ++k) t->air[k] = o.air[k], t->log_n[k] = o.log_n[k], t->leaf_len[k] = o.leaf_len[k];
+    t->n = o.n, t->n_sponge = o.n - 1;
+    t->noop_per_query = 1 + (cm <= 4) + (ca && ca <= 4);
+    const int extra_air[3] = {VX_AIR_LEAF_NOOP, VX_AIR_FRI_COMBINE, VX_AIR_FRI_FOLD};
+    const int extra_log[3] = {leaf_noop_log_n(n_queries * t->noop_per_query), fri_combine_log_n(n_queries, LN, cm, ca, 4), fri_fold_log_n(n_queries, LN, NL)};
+    for (int k = 0; k < 3; ++k) {
+        if (extra_log[k] > 26) return false;
+        t->air[t->n] = extra_air[k], t->log_n[t->n] = extra_log[k], t->leaf_len[t->n] = 0, ++t->n;
+    }
+    for (int k = 0; k < t->n; ++k) {
+        while (t->log_n[k] <= 26 && !fri_plan_ok(t->log_n[k], cfg)) ++t->log_n[k];
         if (t->log_n[k] > 26) return false;
     }
     return true;

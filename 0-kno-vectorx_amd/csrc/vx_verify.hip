@@ -244,6 +244,9 @@ struct FriClaims {
     // (query, tree) becomes a claim of *merkle instead (vx_bus.h), for a bus group to prove
     StarkOpenings* merkle = nullptr;
     bool want_sibs = false;  // prover mode: record where every path's siblings lie in the proof
+    // ... and, for vx_stark_queries_verify, the QUERY-FREE mode, the third state of the delegated sink (`merkle` is set as well): the
+    // query phase derives the indices and nothing else -- no word at or behind Shape::o_queries is read, and the proof may end there
+    bool query_free = false;
 };
 static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
                                  const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen);
@@ -331,6 +334,13 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
     const std::vector<Fx> fpoly = fx_pairs(v.final_poly(), s.final_len);
     const uint64_t wN = glh::root(s.LN);
     StarkOpenings* const mk = fri ? fri->merkle : nullptr;
+    if (fri && fri->query_free) {  // the indices alone: every other step of a query is proven by the tables of vx_stark_queries_prove
+        for (size_t qi = 0; qi < (size_t)s.num_queries; ++qi) {
+            const size_t x_index = ch.query_index(N);
+            fri->index.push_back(x_index), mk->index.push_back(x_index);
+        }
+        return VX_OK;
+    }
     // delegated mode: the opening becomes a claim; of the path only its position in the proof is noted, no word of it is read
     auto claim = [&](uint64_t tree, size_t index, const uint64_t* leaf, size_t leaf_len, const uint64_t* sib) {
         mk->claims.push_back({tree, index, mk->leaves.size(), leaf_len, fri->want_sibs ? (size_t)(sib - v.pr) : 0});
@@ -433,13 +443,16 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     // below can go negative (a crafted L = 2 proof used to reach the Merkle check with n_sib = SIZE_MAX)
     NEED(shape.LN >= shape.cap_h && shape.LN <= 27 && shape.L >= air.period_log, "degree bits %d out of range for this AIR / cap height", shape.L);
     NEED(!air.exact_log || shape.L == air.period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air.period_log, shape.L);
-    const bool delegated = fri && fri->merkle;
+    const bool delegated = fri && fri->merkle, query_free = delegated && fri->query_free;
     if (!delegated)
         for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
     sp::View v;
-    const char* bad_length = sp::View::parse(pr, len, shape, &v);
+    const char* bad_length = query_free ? sp::View::parse_head(pr, len, shape, &v) : sp::View::parse(pr, len, shape, &v);
+    if (query_free) NEED(!bad_length, "%s (%zu words, this shape has %zu and its head %zu)", bad_length, len, shape.words(), shape.o_queries);
     NEED(!bad_length, "%s (%zu words, this shape has %zu)", bad_length, len, shape.words());
-    if (delegated) {  // the same check over everything but the siblings: in this mode none of their words is read
+    if (query_free) {  // the head alone is read
+        for (size_t i = hdr.size(); i < shape.o_queries; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
+    } else if (delegated) {  // the same check over everything but the siblings: in this mode none of their words is read
         auto canonical = [&](size_t from, size_t n) -> size_t {
             for (size_t i = from; i < from + n; ++i)
                 if (pr[i] >= glh::P) return i;
@@ -1301,4 +1314,122 @@ int32_t vx_stark_combine_claims(const vx_stark_config* cfg, const uint64_t* proo
     return VX_OK;
 }
 
+}
+
+// The whole query phase of a vx_stark_prove proof as claims (vx_bus.h), from ONE run of the verifier's code: the Merkle side and
+// the arithmetic side of every query in the prover's mode, the head alone in the query-free mode.
+int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                const uint64_t* ext_chal, bool query_free, StarkQueries* out, char* err, size_t errlen) {
+    FriClaims fc;
+    fc.merkle = &out->so, fc.want_sibs = !query_free, fc.want_combine = true, fc.query_free = query_free;
+    const int32_t rc = stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, &fc, err, errlen);
+    if (rc != VX_OK) return rc;
+    out->rate_bits = cfg->rate_bits, out->nq = fc.nq;
+    memcpy(out->alpha, fc.alpha, 16), memcpy(out->zeta, fc.zeta, 16);
+    out->openings = std::move(fc.openings), out->betas = std::move(fc.betas), out->final_poly = std::move(fc.final_poly);
+    out->rows = std::move(fc.rows), out->leaves = std::move(fc.leaves), out->ev0 = std::move(fc.ev0);
+    return VX_OK;
+}
+void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, uint64_t digest[4]) {
+    const StarkOpenings& so = sq.so;
+    std::vector<uint64_t> w;
+    w.reserve(11 + sq.openings.size() + sq.betas.size() + sq.final_poly.size() + 4 * so.tree.size() + so.n_queries);
+    for (uint64_t x : so.shape_words()) w.push_back(x);
+    w.insert(w.end(), sq.alpha, sq.alpha + 2), w.insert(w.end(), sq.zeta, sq.zeta + 2);
+    w.insert(w.end(), sq.openings.begin(), sq.openings.end());
+    w.insert(w.end(), sq.betas.begin(), sq.betas.end());
+    w.insert(w.end(), sq.final_poly.begin(), sq.final_poly.end());
+    w.insert(w.end(), roots, roots + 4 * so.tree.size());
+    w.insert(w.end(), so.index.begin(), so.index.end());
+    glh::hash_no_pad(w.data(), w.size(), digest);
+}
+
+extern "C" {
+// What vx_stark_queries_prove writes for this inner proof at most: read from the proof's head alone, nothing is verified.
+int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
+    if (!cfg || !proof || !n_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
+    AirV air{};
+    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
+    StarkQueriesTables ts;
+    if (shape.LN < shape.cap_h || shape.cap_h > 16 || !stark_queries_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, shape.arities.size(), (size_t)shape.num_queries, *cfg, &ts)) return VX_ERR_ARG;
+    TableShape sh[7];
+    for (int k = 0; k < ts.n; ++k) sh[k] = {ts.air[k], ts.log_n[k]};
+    return vx_tables_proof_bound(cfg, VX_SQRY_HDR + (size_t)ts.n, sh, (size_t)ts.n, n_words);
+}
+
+// The whole query phase of a proof (the prover is vx_stark_queries.hip): MerkleOpenSetAir, the sponge tables, LeafNoopAir,
+// FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0) on one bus.  TAG_OPEN closes between the openings and the leaf tables,
+// TAG_ROW between the leaf tables and the arithmetic, TAG_FRI end 0 between combination and fold.  The inner proof is verified in
+// the QUERY-FREE mode: transcript, proof of work, the constraint identity at zeta, reduce_openings and the query indices, from the
+// head of the proof alone -- it may be handed over whole or without its query records.  The verifier is the outside party: per query
+// it receives root(tree, lo / hi) with the tree's depth for every tree of the record and fri(index, final_poly(x_NL), 1), and sends
+// nothing:
+//     sum over the tables of total x rows = sum over the queries of sum over the trees (1 / D_root(lo) + 1 / D_root(hi)) + 1 / D_fri(exit).
+// EVERY public input of every table is rebuilt from the head; per query one exponentiation and one Horner evaluation remain.
+int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                                size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    if (!cfg || !blob || !proof) return VX_ERR_ARG;
+    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return ff_arg(err, errlen, "stark queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    StarkQueries sq;
+    int32_t rc = vx_stark_queries_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, true, &sq, err, errlen);
+    if (rc != VX_OK) return rc;
+    const StarkOpenings& so = sq.so;
+    StarkQueriesTables ts;
+    if (so.cap_h > 16 || !stark_queries_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, *cfg, &ts))
+        return ff_arg(err, errlen, "stark queries: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
+    BusTable tab[7];
+    const std::array<uint64_t, 7> sw = so.shape_words();
+    rc = read_blob(blob, len, VX_SQRY_MAGIC, "stark-queries", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen);
+    if (rc != VX_OK) return rc;
+    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
+    const size_t n_trees = so.tree.size(), final_len = sq.final_poly.size() / 2;
+    std::vector<uint64_t> roots(4 * n_trees);
+    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
+    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB], npub[lnp::PUB], cpub[fca::PUB], fpub[ffa::PUB];
+    vx_stark_queries_statement(sq, roots.data(), stmt);
+    vx_merkle_open_set_public(stmt, opub);
+    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
+    int k = 1;
+    for (; k <= ts.n_sponge; ++k) {
+        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
+        tab[k].air = VX_AIR_LEAF_SPONGE_SET, tab[k].want = spub[k - 1], tab[k].n_want = lsp::PUB;
+    }
+    vx_leaf_noop_public(stmt, npub);
+    tab[k].air = VX_AIR_LEAF_NOOP, tab[k].want = npub, tab[k].n_want = lnp::PUB, ++k;
+    vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, cpub);
+    tab[k].air = VX_AIR_FRI_COMBINE, tab[k].want = cpub, tab[k].n_want = fca::PUB, ++k;
+    vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, fpub);
+    tab[k].air = VX_AIR_FRI_FOLD, tab[k].want = fpub, tab[k].n_want = ffa::PUB;
+    return verify_bus_group(cfg, tab, (size_t)ts.n, "the query phase the tables prove is not the one of this proof (the lookup bus does not balance)", err, errlen,
+                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                                m.reserve(so.n_queries * (2 * n_trees + 1));
+                                const uint64_t w = glh::root(so.LN);
+                                for (size_t i = 0; i < so.n_queries; ++i) {
+                                    for (size_t t = 0; t < n_trees; ++t) {
+                                        const uint64_t* r = roots.data() + 4 * t;
+                                        const Fx tree{so.tree[t], 0}, depth{(uint64_t)so.log_leaves(so.tree[t]), 0};
+                                        m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
+                                        m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
+                                    }
+                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(so.index[i], so.LN))), (uint64_t)1 << (4 * so.NL));  // x_NL = x_0^(16^NL)
+                                    Fx fp{0, 0};
+                                    for (size_t j = final_len; j-- > 0;) fp = fp * Fx{x, 0} + Fx{sq.final_poly[2 * j], sq.final_poly[2 * j + 1]};
+                                    m.receive(bus.fri(Fx{so.index[i], 0}, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                }
+                            });
+}
+}
+
+extern "C" {
+// Where the query records of a vx_stark_prove proof start: the length of its head, all vx_stark_queries_verify reads.  Read from the
+// proof's header alone (AIR id, degree bits) and the configuration; nothing is verified.
+int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* head_words) {
+    if (!cfg || !proof || !head_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
+    AirV air{};
+    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
+    *head_words = shape.o_queries;
+    return VX_OK;
+}
 }

@@ -36,6 +36,7 @@ SYMBOLS = [
     "vx_fri_combine_air_trace", "vx_fri_combine_proof_bound", "vx_fri_combine_prove", "vx_fri_combine_verify", "vx_stark_combine_claims",
     "vx_fri_combine_fold_proof_bound", "vx_fri_combine_fold_prove", "vx_fri_combine_fold_verify",
     "vx_stark_merkle_claims", "vx_merkle_paths_air_trace", "vx_leaf_sponge_rows_air_trace", "vx_stark_openings_proof_bound", "vx_stark_openings_prove", "vx_stark_openings_verify",
+    "vx_leaf_noop_air_trace", "vx_stark_queries_proof_bound", "vx_stark_queries_prove", "vx_stark_queries_verify", "vx_stark_proof_head_words",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -53,6 +54,7 @@ VX_AIR_FRI_FOLD, VX_FRI_FOLD_AIR_COLS, VX_FRI_FOLD_AIR_AUX_COLS = 18, 120, 36
 VX_AIR_MERKLE_OPEN_SET, VX_MERKLE_OPEN_SET_AIR_COLS, VX_MERKLE_OPEN_SET_AIR_AUX_COLS = 19, 72, 6
 VX_AIR_LEAF_SPONGE_SET, VX_LEAF_SPONGE_SET_AIR_COLS, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 20, 67, 12
 VX_AIR_FRI_COMBINE, VX_FRI_COMBINE_AIR_COLS, VX_FRI_COMBINE_AIR_AUX_COLS = 21, 28, 4
+VX_AIR_LEAF_NOOP, VX_LEAF_NOOP_AIR_COLS, VX_LEAF_NOOP_AIR_AUX_COLS = 22, 11, 8
 
 
 class JustificationStruct(C.Structure):
@@ -207,6 +209,11 @@ def load_library():
         "vx_stark_openings_proof_bound": [C.POINTER(StarkConfig), vp, sz, C.POINTER(sz)],
         "vx_stark_openings_prove": [vp, C.POINTER(StarkConfig), vp, sz, vp, vp, sz, C.POINTER(sz)],
         "vx_stark_openings_verify": [C.POINTER(StarkConfig), vp, sz, vp, sz, C.c_int, vp, sz, vp, C.c_char_p, sz],
+        "vx_leaf_noop_air_trace": [vp, vp, vp, vp, vp, sz, C.c_int, vp, vp],
+        "vx_stark_queries_proof_bound": [C.POINTER(StarkConfig), vp, sz, C.POINTER(sz)],
+        "vx_stark_proof_head_words": [C.POINTER(StarkConfig), vp, sz, C.POINTER(sz)],
+        "vx_stark_queries_prove": [vp, C.POINTER(StarkConfig), vp, sz, vp, vp, sz, C.POINTER(sz)],
+        "vx_stark_queries_verify": [C.POINTER(StarkConfig), vp, sz, vp, sz, C.c_int, vp, sz, vp, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -545,6 +552,36 @@ def stark_openings_verify(blob, proof, cfg=None, expect_air=0, expect_public=Non
     err = C.create_string_buffer(256)
     rc = L.vx_stark_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size,
                                     None if ch is None else _ptr(ch), err, 256)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+
+
+def stark_proof_head(proof, cfg=None):
+    """The head of a vx_stark_prove proof: everything before its first query record, all lib.stark_queries_verify reads."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    n = C.c_size_t(0)
+    rc = L.vx_stark_proof_head_words(C.byref(cfg), _ptr(pr), pr.size, C.byref(n))
+    if rc != 0:
+        raise VxError(rc, "stark proof head: not a proof of a known AIR under this configuration")
+    return pr[: n.value].copy()
+
+
+def stark_queries_verify(blob, proof, cfg=None, expect_air=0, expect_public=None, ext_chal=None):
+    """Host-side check of a vx_stark_queries_prove blob together with the inner proof it belongs to -- the whole proof or its HEAD
+    alone (everything before the first query record; lib.stark_proof_head cuts it): the proof's transcript, proof of work and
+    constraint identity at zeta are checked in the query-free mode, which reads no query record, and the group proves the query phase.
+    Raises VxError with the reason."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    pr = np.ascontiguousarray(proof, dtype=np.uint64)
+    pub = None if expect_public is None else np.ascontiguousarray(expect_public, dtype=np.uint64)
+    ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+    err = C.create_string_buffer(256)
+    rc = L.vx_stark_queries_verify(C.byref(cfg), _ptr(b), b.size, _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size,
+                                   None if ch is None else _ptr(ch), err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
 
@@ -973,6 +1010,22 @@ class Context:
         self._ck(self.L.vx_leaf_sponge_rows_air_trace(self.h, rw.shape[1], _ptr(to), _ptr(idx), _ptr(rw), idx.size, log_n, out.h, _ptr(pub)))
         return out, pub
 
+    def leaf_noop_air_trace(self, tree_of, leaf_idx, rows, log_n, out=None):
+        """The witness of LeafNoopAir: opening i is the row rows[i] (1..4 words: its own digest) of leaf leaf_idx[i] of tree tree_of[i];
+        the rows may differ in length -> (Buffer [11][2^log_n], the 4 public inputs: the digest of the claims)."""
+        to = np.ascontiguousarray(tree_of, dtype=np.uint64).reshape(-1)
+        idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
+        if to.size != idx.size or len(rows) != idx.size:
+            raise ValueError("one tree and one row for every opening")
+        ln = np.array([len(r) for r in rows], dtype=np.uint64)
+        rw = np.zeros((idx.size, 4), dtype=np.uint64)
+        for i, r in enumerate(rows):
+            rw[i, :min(len(r), 4)] = np.asarray(r, dtype=np.uint64)[:4]
+        out = out or self.alloc(VX_LEAF_NOOP_AIR_COLS << log_n)
+        pub = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.vx_leaf_noop_air_trace(self.h, _ptr(to), _ptr(idx), _ptr(ln), _ptr(rw), idx.size, log_n, out.h, _ptr(pub)))
+        return out, pub
+
     def stark_openings_prove(self, proof, cfg=None, ext_chal=None, out=None):
         """Proves the Merkle openings of the vx_stark_prove proof `proof` from the paths it carries -> blob words
         (lib.stark_openings_verify checks blob and proof together).  One openings table and one sponge table per leaf length above 4.
@@ -983,6 +1036,18 @@ class Context:
         return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_openings_proof_bound(c, _ptr(pr), pr.size, need),
                                 "stark openings: not a proof of a known AIR under this configuration, or a shape without an openings group (more than 8 fold layers, a table above 2^26 rows)",
                                 lambda c, o, need: self.L.vx_stark_openings_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
+
+    def stark_queries_prove(self, proof, cfg=None, ext_chal=None, out=None):
+        """Proves the whole query phase of the vx_stark_prove proof `proof` on one bus -> blob words (lib.stark_queries_verify checks
+        blob and the proof's head together).  Five to seven tables: the openings, one sponge table per leaf length above 4, the no-op
+        leaves, the FRI combination, the fold chains.  The proof is verified on the way and paths, combinations and folds are checked
+        natively first: VxError(VX_ERR_STATEMENT) names query and tree or layer.  out: a caller's uint64 buffer; when it is too small
+        the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        pr = np.ascontiguousarray(proof, dtype=np.uint64)
+        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_queries_proof_bound(c, _ptr(pr), pr.size, need),
+                                "stark queries: not a proof of a known AIR under this configuration, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)",
+                                lambda c, o, need: self.L.vx_stark_queries_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

@@ -168,7 +168,8 @@ typedef struct vx_stark_config {
  * 17 (VX_AIR_LEAF_SPONGE) hashes the opened leaf rows to those openings' digests: the second one, see vx_merkle_rows_prove.
  * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove.
  * 19 (VX_AIR_MERKLE_OPEN_SET) / 20 (VX_AIR_LEAF_SPONGE_SET) are 16 / 17 for several trees in one table: see vx_fri_queries_prove.
- * 21 (VX_AIR_FRI_COMBINE) proves the FRI combination of every query, the value the fold chain starts from: see vx_fri_combine_prove. */
+ * 21 (VX_AIR_FRI_COMBINE) proves the FRI combination of every query, the value the fold chain starts from: see vx_fri_combine_prove.
+ * 22 (VX_AIR_LEAF_NOOP) turns the openings of leaves of at most 4 words, which are their own digest, into row words: see LeafNoopAir. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -413,8 +414,8 @@ int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, 
  *   word of a row longer than 4 words, and the opening itself of a row that is its own digest.  Walks no path, hashes no leaf, reads
  *   no sibling: the siblings are dead weight in a proof verified this way.  The statement digest costs about as many permutations as
  *   hashing the rows would; what disappears is everything per tree level.
- * STILL OUTSIDE: the query arithmetic (FriCombineAir / FriFoldAir would take the verifier's place on the row bus), the constraint
- * identity at zeta and the transcript. */
+ * The query arithmetic on this same bus: vx_stark_queries_prove (below), where FriCombineAir / FriFoldAir take the verifier's place.
+ * STILL OUTSIDE: the constraint identity at zeta and the transcript. */
 int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t shape_out[7], size_t* n_trees,
                                uint64_t cap_tree_out[11], uint64_t* caps_out, size_t caps_cap, size_t* n_claims, uint64_t* tree_out, uint64_t* index_out, uint64_t* leaf_len_out,
                                size_t claims_cap, size_t* leaves_len, uint64_t* leaves_out, size_t leaves_cap, size_t* siblings_len, uint64_t* siblings_out, size_t siblings_cap,
@@ -490,6 +491,49 @@ int32_t vx_fri_combine_fold_verify(const vx_stark_config* cfg, const uint64_t* b
                                    const uint64_t zeta[2], const uint64_t* open_local, const uint64_t* open_next, const uint64_t* open_quot, const uint64_t* betas, size_t n_layers,
                                    const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* rows, const uint64_t* leaves, size_t n_queries, char* err,
                                    size_t errlen);
+/* ---- LeafNoopAir: the openings of leaves that are their own digest in one STARK table (AIR id VX_AIR_LEAF_NOOP; compiled:
+ * csrc/air_leaf_noop.cuh) -- a Poseidon tree whose leaves have at most 4 words does not hash them (plonky2 v0.2.0 hash_or_noop): the
+ * leaf digest is the zero-padded row.  That is the quotient tree of every vx_stark_prove proof and any commitment tree of at most 4
+ * columns.  One row per opening: ACT, TREE, IDX, the four words W and four flags E (word j exists); E_0 = ACT, the flags only fall,
+ * a word that does not exist is zero.  The row RECEIVES the opening's two open_of(TREE, IDX, ., ., half) messages (what
+ * MerkleOpenSetAir sends) and SENDS row_of(TREE, IDX, j, W_j) for every word that exists (what FriCombineAir receives): the no-op
+ * counterpart of LeafSpongeSetAir.  The length of a leaf is NOT a public input -- one table carries leaves of several lengths; the
+ * receiver's public column counts decide which words must arrive, so the balance of the bus forces the flags.  Public inputs: four
+ * digest words the table does not constrain.  Any log_n >= 5; idle rows are zero.
+ * vx_leaf_noop_air_trace: the witness on its own (test surface) -- opening i is leaf leaf_idx[i] of tree tree_of[i] with
+ *   leaf_len[i] in 1..4 words, rows[i][4] zero-padded; trace_out: [VX_LEAF_NOOP_AIR_COLS][2^log_n] with 2^log_n >= n_idx;
+ *   public_out: hash_n_to_hash_no_pad of (tree, index, length, the four words) of every opening.  VX_ERR_ARG: a length outside
+ *   1..4, a non-canonical word, a non-zero word behind the length, a table that is too small. */
+enum { VX_AIR_LEAF_NOOP = 22, VX_LEAF_NOOP_AIR_COLS = 11, VX_LEAF_NOOP_AIR_AUX_COLS = 8 };
+int32_t vx_leaf_noop_air_trace(vx_ctx* ctx, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* leaf_len, const uint64_t* rows, size_t n_idx, int log_n,
+                               vx_buf* trace_out, uint64_t public_out[4]);
+/* ---- The whole query phase of a vx_stark_prove proof on ONE bus (csrc/vx_stark_queries.hip): the group of
+ * vx_stark_openings_prove with LeafNoopAir, FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0) in the verifier's place on the row
+ * bus, five to seven tables in this order: MerkleOpenSetAir (one path per claim), one LeafSpongeSetAir per distinct leaf length above
+ * 4 among {cm, ca, 32} ascending, LeafNoopAir (one row per claim of a leaf of at most 4 words: the quotient tree always),
+ * FriCombineAir, FriFoldAir.  Conventions as vx_stark_openings_prove: layer l is tree l, main / auxiliary / quotient are trees 8 / 9 /
+ * 10, the record order inside a query and duplicate indices are kept, the `within` slot of a layer leaf holds the running evaluation.
+ * vx_stark_queries_prove: the claims come from ONE replay of the verifier's code; the native checks run first -- a path that misses
+ *   its root, an ev_0 or a fold that differs, an inner proof the verifier refuses: VX_ERR_STATEMENT naming query and tree or layer,
+ *   nothing is proven.  VX_ERR_ARG: arity_bits != 4, no FRI layer or more than 8, log_lde - 4 layers < 1, a table above 2^26 rows.
+ *   The four digest words of every table are ONE statement digest: hash_n_to_hash_no_pad(the 7 shape words, alpha, zeta, the openings
+ *   local / next / quotient, betas, the final polynomial, the folded root of every tree in record order, the index of every query) --
+ *   no row word and no leaf word.  Blob: "VXSQRY01", the 7 shape words, the table count, one length per table, the proofs.
+ * vx_stark_queries_verify (host only): runs the inner proof's transcript, proof of work, constraint identity at zeta,
+ *   reduce_openings and the query-index derivation in the verifier's QUERY-FREE mode, which reads no word at or behind the query
+ *   records: `proof` is the whole proof or its head alone (everything before the first query record); any other length is refused.
+ *   It rebuilds every public input of every table from the head and is the outside party of the bus: per query it RECEIVES
+ *   root(tree, lo / hi) with depth log_leaves for every tree of the record and fri(index, final_poly(x_NL), 1); it sends nothing.  Per
+ *   query one exponentiation and one Horner evaluation remain; the query records (over 90 % of a proof) are dead weight.
+ * vx_stark_proof_head_words: where the query records of a proof start -- the length of the head vx_stark_queries_verify accepts --
+ *   from the proof's header and the configuration alone; nothing is verified.
+ * STILL OUTSIDE: the transcript, the constraint identity at zeta and the final-polynomial evaluation. */
+int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* head_words);
+int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words);
+int32_t vx_stark_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t* blob_out, size_t blob_cap,
+                               size_t* blob_len);
+int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* proof, size_t proof_len, int expect_air,
+                                const uint64_t* expect_public, size_t n_public, const uint64_t* ext_chal, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */
