@@ -209,6 +209,20 @@ inline bool peek(const uint64_t* pr, size_t len, int cap_height, const uint64_t*
     return true;
 }
 
+// What the query phase and every party outside a table of it derive from an index: the low `bits` bits of x reversed, the point of
+// a query index on the LDE coset, 7 w_LN^brev(index), and the value of a final polynomial given as word pairs at a base-field point.
+inline size_t brev(size_t x, int bits) {
+    size_t r = 0;
+    for (int i = 0; i < bits; ++i) r = (r << 1) | ((x >> i) & 1);
+    return r;
+}
+inline uint64_t query_point(uint64_t index, int LN) { return glh::mul(7, glh::pow(glh::root(LN), brev(index, LN))); }
+inline Fx final_poly_at(const uint64_t* final_poly, size_t final_len, uint64_t x) {
+    Fx fp{0, 0};
+    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+    return fp;
+}
+
 // fri_combine_initial's reduced openings: with the c trace columns' openings at zeta (local) and zeta w (next) and the nq quotient
 // openings at zeta, as word pairs, y0 = sum_j alpha^j (local ++ quot)[j], y1 = sum_j alpha^j next[j].  apow (optional) receives
 // alpha^0 .. alpha^(c + nq - 1) as word pairs.

@@ -1,11 +1,10 @@
 // Host-side plumbing shared by every prover of "several tables on one logUp bus", implemented in vx_bus.hip: the circuit provers
-// (vx_header_range_prove in vx_header_range.hip, vx_rotate_prove in vx_rotate.hip) and the aggregation provers (vx_merkle_open_air.hip,
-// vx_leaf_sponge_air.hip, vx_fri_fold_air.hip, vx_fri_combine_air.hip, vx_fri_queries.hip, vx_stark_openings.hip).  The tables of one statement must use
-// the same lookup challenges, drawn after every trace is committed: the rendezvous and the bookkeeping of such a group are
-// bus_meet.h (host-pure); TableGroup below is the group on the device -- a prover says which tables there are (TableSpec), which one
-// runs on the caller's context and thread, and in which order failures are reported.  What only the aggregation provers share --
-// the hook of a table alone on its bus, the blob writer, the blob formats and the public inputs of their AIRs, which the verifier
-// (vx_verify.hip) rebuilds with the same functions -- is declared here as well.
+// and the aggregation provers.  The tables of one statement must use the same lookup challenges, drawn after every trace is
+// committed: the rendezvous and the bookkeeping of such a group are bus_meet.h (host-pure); TableGroup below is the group on the
+// device -- a prover says which tables there are (TableSpec), which one runs on the caller's context and thread, and in which order
+// failures are reported.  What only the aggregation provers share -- the hook of a table alone on its bus, the blob writer, the blob
+// formats and the public inputs of their AIRs, which the verifier (vx_verify.hip) rebuilds with the same functions -- is declared
+// here as well.
 #pragma once
 #include <array>
 #include <functional>
@@ -163,8 +162,8 @@ static const uint64_t VX_SOPEN_MAGIC = 0x314e45504f535856ULL;  // "VXSOPEN1"
 static constexpr size_t VX_SOPEN_HDR = 9;                       // before the lengths
 static constexpr uint64_t VX_SOPEN_TREE0 = 8;                   // main / auxiliary / quotient = TREE0 + 0 / 1 / 2; layer l = l
 // The Merkle side of a vx_stark_prove proof as claims: one per (query, tree), queries outermost in proof order, inside a query the
-// order of the query record -- main, auxiliary (ca > 0), quotient, layers 0..NL-1.  Filled by the verifier's own query phase in
-// its delegated mode (vx_stark_openings_claims, vx_verify.hip), which walks no path and reads no sibling word.
+// order of the query record -- main, auxiliary (ca > 0), quotient, layers 0..NL-1.  Filled by the verifier's own query phase
+// (vx_verify.hip) whenever it has a sink (StarkQueries below).
 struct StarkOpenings {
     int LN = 0, a = 0, cap_h = 0;
     size_t cm = 0, ca = 0, NL = 0, n_queries = 0;
@@ -174,17 +173,13 @@ struct StarkOpenings {
     struct Claim {
         uint64_t tree, index;  // index: x_index for the commitment trees, x_index >> a (l + 1) for layer l
         size_t leaf, leaf_len;  // the leaf words: leaves[leaf .. leaf + leaf_len), a layer leaf with its `within` slot filled
-        size_t sib;             // where the path's 4 (log_leaves - cap_h) sibling words start in the proof (prover mode)
+        size_t sib;             // where the path's 4 (log_leaves - cap_h) sibling words start in the proof
     };
     std::vector<Claim> claims;
     std::vector<uint64_t> leaves;
     int log_leaves(uint64_t t) const { return t >= VX_SOPEN_TREE0 ? LN : LN - a * ((int)t + 1); }
     std::array<uint64_t, 7> shape_words() const { return {{(uint64_t)LN, cm, ca, (uint64_t)a, NL, (uint64_t)cap_h, n_queries}}; }
 };
-// verifies `proof` as vx_stark_verify_ext does, every check except the Merkle paths, and fills *out; VX_ERR_ARG for more than 8
-// fold layers.  want_sibs: record where the siblings lie (the prover reads them, the verifier never does)
-int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                 const uint64_t* ext_chal, bool want_sibs, StarkOpenings* out, char* err, size_t errlen);
 // the two-to-one fold of a cap of canonical words down to one digest: the root the openings table proves paths to
 void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]);
 // the statement of a proof's openings, the four digest words of every table: hash_n_to_hash_no_pad(the shape words, the folded
@@ -274,9 +269,14 @@ void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* bet
 // in bus order: MerkleOpenSetAir, one LeafSpongeSetAir per leaf length above 4, LeafNoopAir, FriCombineAir, FriFoldAir
 static const uint64_t VX_SQRY_MAGIC = 0x3130595251535856ULL;  // "VXSQRY01"
 static constexpr size_t VX_SQRY_HDR = 9;                      // before the lengths
-// The whole query phase of a vx_stark_prove proof as claims: the Merkle side (`so`: trees 0..7 the layers, 8 / 9 / 10 main / auxiliary /
-// quotient) and the arithmetic side, from ONE replay of the verifier's code.  In the verifier's query-free mode only the head is
-// filled: so.claims / so.leaves / rows / leaves / ev0 stay empty, so.index holds the derived indices.
+// What the verifier's query phase does with the openings of a proof.  Walked: it walks every path itself (vx_stark_verify).
+// Delegated: the paths are left to the tables of a bus group -- none is walked and no sibling word is read.  QueryFree: the whole
+// query phase is left to them -- only the indices are derived, no word at or behind the query records is read, and the proof may
+// end there.
+enum class QueryPhase { Walked, Delegated, QueryFree };
+// The whole query phase of a vx_stark_prove proof as claims, the ONE sink of the verifier's query phase: the Merkle side (`so`: trees
+// 0..7 the layers, 8 / 9 / 10 main / auxiliary / quotient) and the arithmetic side, from one replay of the verifier's code.  Query-free
+// only the head is filled: so.claims / so.leaves / rows / leaves / ev0 / ev_last stay empty, so.index holds the derived indices.
 struct StarkQueries {
     StarkOpenings so;
     int rate_bits = 0;
@@ -284,20 +284,54 @@ struct StarkQueries {
     uint64_t alpha[2] = {0, 0}, zeta[2] = {0, 0};
     std::vector<uint64_t> openings;  // local [c][2], next [c][2], quotient [nq][2]
     std::vector<uint64_t> betas, final_poly;
-    std::vector<uint64_t> rows, leaves, ev0;  // [query][c + nq], [query][layer][32], [query][2]
+    std::vector<uint64_t> rows, leaves, ev0, ev_last;  // [query][c + nq], [query][layer][2 arity] (`within` filled), [query][2]: ev_0, the accepted ev_NL
     FriCombineStmt stmt() const {
         const size_t c = so.cm + so.ca;
         return FriCombineStmt{so.LN, rate_bits, so.cm, so.ca, nq, alpha, zeta, openings.data(), openings.data() + 2 * c, openings.data() + 4 * c};
     }
 };
-// query_free = false: the prover's replay of the whole proof (every check except the paths; where the siblings lie is recorded);
-// true: the verifier's, which reads no word at or behind the query records and accepts the proof whole or as its head alone
+// verifies `proof` as vx_stark_verify_ext does with its query phase in `mode`, and fills *out
 int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                const uint64_t* ext_chal, bool query_free, StarkQueries* out, char* err, size_t errlen);
+                                const uint64_t* ext_chal, QueryPhase mode, StarkQueries* out, char* err, size_t errlen);
+// ... delegated, for the openings group: VX_ERR_ARG for more than 8 fold layers
+int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, StarkQueries* out, char* err, size_t errlen);
 // the statement of a proof's query phase, the four digest words of every table: hash_n_to_hash_no_pad(the 7 shape words, alpha, zeta,
 // the openings local / next / quotient, betas, the final polynomial, the folded root of every tree in record order, the index of
 // every query).  No row word and no leaf word: they are in committed traces.  roots: [so.tree.size()][4]
 void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, uint64_t digest[4]);
+
+// The Merkle side of the two proof-sourced group provers (vx_stark_openings_prove, vx_stark_queries_prove; defined in
+// vx_stark_openings.hip): everything their tables read, gathered from the claims and the proof that carries the paths.  It holds
+// pool blocks of `ctx` until the group has proven, so it is declared before the TableGroup.
+struct StarkMerkleSide {
+    static constexpr int N_TREE_IDS = (int)VX_SOPEN_TREE0 + 3;
+    // sponge_len: the leaf lengths of the n_sponge (<= 3) sponge tables, in table order (vx_table_shapes.h)
+    StarkMerkleSide(vx_ctx* ctx, const char* prefix, const StarkOpenings& so, const uint64_t* proof, const size_t* sponge_len, int n_sponge);
+    // the sponge chains of every leaf longer than 4 words, one launch per length (their digests enter the paths on the device),
+    // then every path walked once: "<prefix> query Q: the path of ... does not reach the root of its tree" (VX_ERR_STATEMENT) otherwise
+    int32_t launch();
+    // the openings table and the sponge tables as the next 1 + n_sponge tables of `g`, with log_n[k] rows (log2) and the statement
+    // digest in their public inputs (stmt outlives the group); returns the index of the openings table
+    int add_tables(TableGroup& g, const int* log_n, const uint64_t* stmt);
+
+    vx_ctx* ctx;
+    const char* prefix;
+    const StarkOpenings& so;
+    int n_sponge;
+    size_t sponge_len[3] = {0, 0, 0};
+    MerkleOpenWitness paths;
+    LeafSpongeWitness sponge[3];
+    int log_leaves[N_TREE_IDS] = {0};
+    std::vector<uint64_t> caps, roots;                            // [N_TREE_IDS][4 << cap_h] by tree id; [so.tree.size()][4] in record order
+    std::vector<uint64_t> tree_of, leaf_idx, leaf_dig, sibs;      // per claim; leaf_dig: a row of at most 4 words is its own digest, zero-padded
+    std::vector<const uint64_t*> leaf_dev;                        // per claim: where the sponge leaves its digest (nullptr: leaf_dig)
+    std::vector<uint64_t> s_tree[3], s_idx[3], s_rows[3];         // per sponge table: its openings as rows
+    std::vector<size_t> s_who[3];                                 // ... and which claims they are
+    std::vector<uint64_t> n_tree, n_idx, n_len, n_rows;           // the openings of the leaves of at most 4 words, rows [.][4] (LeafNoopAir's)
+};
+// the blob of such a group: magic, the 7 shape words, the number of tables, one length per table, the proofs of g.job[0 .. n_tables)
+int32_t vx_stark_group_blob(TableGroup& g, int n_tables, uint64_t magic, const StarkOpenings& so, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

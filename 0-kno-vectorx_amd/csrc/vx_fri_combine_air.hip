@@ -231,11 +231,8 @@ int32_t vx_fri_combine_host(vx_ctx* ctx, const FriCombineStmt& st, const uint64_
     uint64_t ac[2], zn[2], y0[2], y1[2];
     vx_fri_combine_reduced(st, ac, zn, y0, y1);
     const Fx alpha{st.alpha[0], st.alpha[1]}, zeta{st.zeta[0], st.zeta[1]};
-    const uint64_t w = glh::root(st.log_lde);
     for (size_t i = 0; i < n_queries; ++i) {
-        size_t rev = 0;
-        for (int b = 0; b < st.log_lde; ++b) rev = (rev << 1) | ((index[i] >> b) & 1);
-        const Fx x{glh::mul(7, glh::pow(w, rev)), 0}, e0 = x - zeta, e1 = x - Fx{zn[0], zn[1]};
+        const Fx x{stark_proof::query_point(index[i], st.log_lde), 0}, e0 = x - zeta, e1 = x - Fx{zn[0], zn[1]};
         if ((e0.a | e0.b) == 0 || (e1.a | e1.b) == 0) return vx_fail(ctx, VX_ERR_STATEMENT, "fri combine: query %zu: the point of the index is zeta or zeta w_n", i);
         Fx s1{0, 0}, s0{0, 0}, ap{1, 0};
         for (size_t j = 0; j < absn; ++j) {

@@ -223,11 +223,8 @@ int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
     VX_CHECK(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
     for (size_t i = 0; i < 2 * final_len; ++i) VX_CHECK(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
     // the statement, natively: leaf_l[within_l] = ev_l, ev_(l+1) = the fold, final_poly(x_NL) = ev_NL
-    const uint64_t w = glh::root(log_lde);
     for (size_t i = 0; i < n_queries; ++i) {
-        size_t rev = 0;
-        for (int b = 0; b < log_lde; ++b) rev = (rev << 1) | ((index[i] >> b) & 1);
-        uint64_t x = glh::mul(7, glh::pow(w, rev)), xi = glh::inv(x);
+        uint64_t x = stark_proof::query_point(index[i], log_lde), xi = glh::inv(x);
         Fx ev{ev0[2 * i], ev0[2 * i + 1]};
         for (size_t l = 0; l < n_layers; ++l) {
             const uint64_t* leaf = leaves + (i * n_layers + l) * 32;
@@ -237,8 +234,7 @@ int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
             ev = fold16_host(leaf, within, Fx{betas[2 * l], betas[2 * l + 1]}, xi);
             x = glh::pow(x, 16), xi = glh::pow(xi, 16);
         }
-        Fx fp{0, 0};
-        for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
+        const Fx fp = stark_proof::final_poly_at(final_poly, final_len, x);
         if (fp.a != ev.a || fp.b != ev.b)
             return vx_fail(ctx, VX_ERR_STATEMENT, "fri fold: query %zu, layer %zu: the folded value is not the final polynomial's at x^(16^%zu)", i, n_layers, n_layers);
     }

@@ -1,7 +1,6 @@
-// Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers
-// (vx_bus.hip, vx_header_range.hip, vx_rotate.hip, the aggregation provers in vx_merkle_open_air.hip, vx_leaf_sponge_air.hip,
-// vx_fri_fold_air.hip, vx_fri_queries.hip and vx_stark_openings.hip) and the host verifier (vx_verify.hip): that both sides size a table the same way is a soundness
-// condition.  Host-only inline functions, no device code.
+// Rows (log2) and AIR id of every table of the circuits as a function of the request -- stated once, for the provers and the host
+// verifier (vx_verify.hip): that both sides size a table the same way is a soundness condition.  Host-only inline functions, no
+// device code.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -79,12 +78,14 @@ static inline int leaf_noop_log_n(size_t n_idx) {
 // its own digest: the quotient rows, and any other tree that short, have no sponge).  Rows: 32 per level of every path, 32 per 8
 // words of every leaf, each table at the smallest log_n >= 5.  false: a tree without a level, more than 8 layers, or a table of
 // more than 2^26 rows.
-struct StarkOpeningsTables {
-    int n = 0;
-    int air[4], log_n[4];
-    size_t leaf_len[4];  // [0] = 0: the openings table
+// The tables of either group: the openings table, n_sponge sponge tables and, in the query-phase group, three more.
+struct StarkGroupTables {
+    int n = 0, n_sponge = 0;
+    int air[7], log_n[7];
+    size_t leaf_len[7];  // of the sponge tables, 0 elsewhere
+    size_t noop_per_query = 0;  // query-phase group
 };
-static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, StarkOpeningsTables* t) {
+static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, StarkGroupTables* t) {
     if (LN < 1 || LN > 40 || a < 1 || a > 5 || NL > 8 || n_queries < 1 || n_queries > ((size_t)1 << 20) || cm < 1 || cm > ((size_t)1 << 20) || ca > ((size_t)1 << 20)) return false;
     if (NL && (int)NL * a >= LN) return false;
     size_t levels = (size_t)LN * (ca ? 3 : 2);
@@ -103,6 +104,7 @@ static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, si
         t->air[t->n] = VX_AIR_LEAF_SPONGE_SET, t->leaf_len[t->n] = next, t->log_n[t->n] = ceil_log2(32 * n_queries * leaves * sponge_blocks(next));
         ++t->n;
     }
+    t->n_sponge = t->n - 1;
     for (int k = 0; k < t->n; ++k) {
         if (t->log_n[k] < 5) t->log_n[k] = 5;
         if (t->log_n[k] > 26) return false;
@@ -122,17 +124,8 @@ static inline bool fri_plan_ok(int log_n, const vx_stark_config& cfg) {
     for (int a : stark_proof::fri_arity_plan(log_n, cfg)) d -= a;
     return d >= 0;
 }
-struct StarkQueriesTables {
-    int n = 0, n_sponge = 0;
-    int air[7], log_n[7];
-    size_t leaf_len[7];  // of the sponge tables, 0 elsewhere
-    size_t noop_per_query = 0;
-};
-static inline bool stark_queries_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, const vx_stark_config& cfg, StarkQueriesTables* t) {
-    StarkOpeningsTables o;
-    if (a != 4 || NL < 1 || LN - 4 * (int)NL < 1 || !stark_openings_tables(LN, cm, ca, a, NL, n_queries, &o)) return false;
-    for (int k = 0; k < o.n; ++k) t->air[k] = o.air[k], t->log_n[k] = o.log_n[k], t->leaf_len[k] = o.leaf_len[k];
-    t->n = o.n, t->n_sponge = o.n - 1;
+static inline bool stark_queries_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, const vx_stark_config& cfg, StarkGroupTables* t) {
+    if (a != 4 || NL < 1 || LN - 4 * (int)NL < 1 || !stark_openings_tables(LN, cm, ca, a, NL, n_queries, t)) return false;
     t->noop_per_query = 1 + (cm <= 4) + (ca && ca <= 4);
     const int extra_air[3] = {VX_AIR_LEAF_NOOP, VX_AIR_FRI_COMBINE, VX_AIR_FRI_FOLD};
     const int extra_log[3] = {leaf_noop_log_n(n_queries * t->noop_per_query), fri_combine_log_n(n_queries, LN, cm, ca, 4), fri_fold_log_n(n_queries, LN, NL)};

@@ -5,9 +5,8 @@
 // Cargo.lock:4848-4905, not vendored.  Verification is cheap scalar work (a few thousand
 // Poseidon permutations) and stays on the host, as in the reference.
 // Every host verifier of a statement lives here too, and all of them end in ONE sequence, verify_bus_group: the tables of a logUp
-// bus under their shared challenges, and the balance of the bus against the messages of a party outside the tables -- nobody
-// (vx_header_range_verify, vx_rotate_verify) or the verifier itself (the aggregation verifiers vx_merkle_openings_verify,
-// vx_merkle_rows_verify, vx_fri_fold_verify, which are argument checks, read_blob, their tables and their message list).
+// bus under their shared challenges, and the balance of the bus against the messages of a party outside the tables -- nobody (the
+// circuit verifiers) or the verifier itself (the aggregation verifiers: argument checks, read_blob, their tables, their messages).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -17,6 +16,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 
 #include <array>
 
@@ -56,8 +56,7 @@ void host_intt(std::vector<uint64_t>& a) {
     int lg = 0;
     while (((size_t)1 << lg) < p) ++lg;
     for (size_t i = 0; i < p; ++i) {
-        size_t j = 0;
-        for (int b = 0; b < lg; ++b) j |= ((i >> b) & 1) << (lg - 1 - b);
+        const size_t j = stark_proof::brev(i, lg);
         if (j > i) std::swap(a[i], a[j]);
     }
     for (int st = 1; st <= lg; ++st) {
@@ -76,23 +75,19 @@ void host_intt(std::vector<uint64_t>& a) {
     const uint64_t pinv = glh::inv(p % glh::P);
     for (uint64_t& x : a) x = glh::mul(x, pinv);
 }
-size_t brev(size_t x, int bits) {
-    size_t r = 0;
-    for (int i = 0; i < bits; ++i) r = (r << 1) | ((x >> i) & 1);
-    return r;
-}
-int32_t v_fail(char* err, size_t errlen, const char* fmt, ...) {
+// every refusal of this file: the reason into the caller's buffer, the code back
+int32_t v_fail(int32_t code, char* err, size_t errlen, const char* fmt, ...) {
     if (err && errlen) {
         va_list ap;
         va_start(ap, fmt);
         vsnprintf(err, errlen, fmt, ap);
         va_end(ap);
     }
-    return VX_ERR_STATEMENT;
+    return code;
 }
 #define NEED(cond, ...) \
     do {                \
-        if (!(cond)) return v_fail(err, errlen, __VA_ARGS__); \
+        if (!(cond)) return v_fail(VX_ERR_STATEMENT, err, errlen, __VA_ARGS__); \
     } while (0)
 }  // namespace
 
@@ -103,18 +98,9 @@ std::mutex g_airp_mu;
 std::map<int, std::shared_ptr<const AirProgram>> g_airp;       // live ids
 std::vector<std::shared_ptr<const AirProgram>> g_airp_retired;  // kept alive: a prover may still hold the pointer
 int g_airp_next = VX_AIR_USER_BASE;
-int32_t airp_fail(char* err, size_t errlen, const char* fmt, ...) {
-    if (err && errlen) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(err, errlen, fmt, ap);
-        va_end(ap);
-    }
-    return VX_ERR_ARG;
-}
 #define AIRP_NEED(cond, ...) \
     do {                     \
-        if (!(cond)) return airp_fail(err, errlen, __VA_ARGS__); \
+        if (!(cond)) return v_fail(VX_ERR_ARG, err, errlen, __VA_ARGS__); \
     } while (0)
 }  // namespace
 const AirProgram* vx_air_program_find(int id) {
@@ -231,28 +217,13 @@ int32_t vx_stark_verify(const vx_stark_config* cfg, const uint64_t* pr, size_t l
 }
 }  // extern "C"
 
-// what the query phase of a verified proof hands to vx_stark_fri_claims: the FRI side of every query, as FriFoldAir's claims
-struct FriClaims {
-    int log_lde = 0;
-    std::vector<uint64_t> betas, final_poly, index, ev0, leaves, ev_last;  // leaves: [query][layer][2 arity], the `within` slot filled
-    // ... and, for vx_stark_combine_claims, what the FRI combination reads: FriCombineAir's claims
-    bool want_combine = false;
-    size_t cm = 0, ca = 0, nq = 0;
-    uint64_t alpha[2] = {0, 0}, zeta[2] = {0, 0};
-    std::vector<uint64_t> openings, rows;  // openings: local [c][2], next [c][2], quotient [nq][2]; rows: [query][c + nq]
-    // ... and, for vx_stark_openings_claims, the DELEGATED mode: no Merkle path is walked and no sibling word read -- every
-    // (query, tree) becomes a claim of *merkle instead (vx_bus.h), for a bus group to prove
-    StarkOpenings* merkle = nullptr;
-    bool want_sibs = false;  // prover mode: record where every path's siblings lie in the proof
-    // ... and, for vx_stark_queries_verify, the QUERY-FREE mode, the third state of the delegated sink (`merkle` is set as well): the
-    // query phase derives the indices and nothing else -- no word at or behind Shape::o_queries is read, and the proof may end there
-    bool query_free = false;
-};
+// The verifier with its query phase in one of the three states of QueryPhase (vx_bus.h) and an optional sink: what the query
+// phase saw, as the claims of the tables that prove it.
 static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen);
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen);
 int32_t vx_stark_verify_ext(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public,
                             size_t n_expect_public, const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen) {
-    return stark_verify_impl(cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, nullptr, err, errlen);
+    return stark_verify_impl(cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, QueryPhase::Walked, nullptr, err, errlen);
 }
 namespace sp = stark_proof;
 static std::vector<Fx> fx_pairs(const uint64_t* w, size_t n) {
@@ -260,8 +231,14 @@ static std::vector<Fx> fx_pairs(const uint64_t* w, size_t n) {
     for (size_t j = 0; j < n; ++j) v[j] = {w[2 * j], w[2 * j + 1]};
     return v;
 }
-// The head of an untrusted proof: the AIR it names and its degree bits, such that a Shape may be built from them.
-static int32_t proof_air(const uint64_t* pr, size_t len, int expect_air, AirV* air, char* err, size_t errlen) {
+// The head of an untrusted proof: header -> the AIR it names -> the Shape that AIR, the degree bits and the configuration imply
+// (config_ok(cfg) is the caller's).
+struct ProofHead {
+    AirV air{};
+    std::optional<sp::Shape> shape;
+};
+static int32_t proof_head(const vx_stark_config& cfg, const uint64_t* pr, size_t len, int expect_air, ProofHead* head, char* err, size_t errlen) {
+    AirV* const air = &head->air;
     NEED(len >= 10, "proof truncated (header)");
     NEED(pr[0] == sp::MAGIC, "bad magic");
     // (every narrow header field is compared as the 64-bit word it is: a proof has ONE encoding)
@@ -274,6 +251,7 @@ static int32_t proof_air(const uint64_t* pr, size_t len, int expect_air, AirV* a
         if (const AirProgram* pg = vx_air_program_find(air_id))
             *air = {air_id, (int)pg->cols, (int)pg->pub, (int)pg->plog.size(), pg->period_log, 0, nullptr, nullptr, (int)pg->aux, (int)pg->chal, (int)pg->auxpub, nullptr, pg};
     NEED(air->id && (expect_air == 0 || expect_air == air_id), "unexpected AIR %d", air_id);
+    head->shape.emplace(air->id, air->cols, air->aux, air->pub, air->auxpub, (int)pr[2], cfg);
     return VX_OK;
 }
 // The constraint identity at zeta: the AIR's constraints over the openings, combined under the two alphas, against Z_H(zeta) times
@@ -325,41 +303,31 @@ static int32_t constraints_at_zeta(const AirV& air, const sp::View& v, const uin
 }
 // The FRI query phase (verify_fri_proof): per query the three rows under their caps, the combination of their words
 // (fri_combine_initial), and per layer the coset's leaf under its cap and its fold at beta (compute_evaluation), down to the
-// final polynomial.
-static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx zeta, const std::vector<Fx>& betas, FriClaims* fri, char* err, size_t errlen) {
+// final polynomial.  The arithmetic of a query is stated once; the modes differ in what happens to an OPENING: walked here,
+// left to the tables of a bus group (with a sink it is recorded as their claim either way: of the path only its position in the
+// proof is noted, no word of it is read), or -- query-free -- skipped with the whole record: the indices alone are derived.
+static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx zeta, const std::vector<Fx>& betas, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
     const sp::Shape& s = *v.s;
     const size_t c = s.c, nq = sp::NQ, N = (size_t)1 << s.LN, n_layers = s.arities.size();
     const Fx zeta_next = fx_scale(zeta, glh::root(s.L));
     const sp::Reduced red = sp::reduce_openings(alpha, v.open_local(), v.open_next(), v.open_quot(), c, nq);
-    const std::vector<Fx> fpoly = fx_pairs(v.final_poly(), s.final_len);
-    const uint64_t wN = glh::root(s.LN);
-    StarkOpenings* const mk = fri ? fri->merkle : nullptr;
-    if (fri && fri->query_free) {  // the indices alone: every other step of a query is proven by the tables of vx_stark_queries_prove
-        for (size_t qi = 0; qi < (size_t)s.num_queries; ++qi) {
-            const size_t x_index = ch.query_index(N);
-            fri->index.push_back(x_index), mk->index.push_back(x_index);
+    auto opening = [&](uint64_t tree, size_t index, const uint64_t* leaf, size_t leaf_len, const uint64_t* sib, int depth, const uint64_t* cap) {
+        if (sink) {
+            StarkOpenings& so = sink->so;
+            so.claims.push_back({tree, index, so.leaves.size(), leaf_len, (size_t)(sib - v.pr)});
+            so.leaves.insert(so.leaves.end(), leaf, leaf + leaf_len);
         }
-        return VX_OK;
-    }
-    // delegated mode: the opening becomes a claim; of the path only its position in the proof is noted, no word of it is read
-    auto claim = [&](uint64_t tree, size_t index, const uint64_t* leaf, size_t leaf_len, const uint64_t* sib) {
-        mk->claims.push_back({tree, index, mk->leaves.size(), leaf_len, fri->want_sibs ? (size_t)(sib - v.pr) : 0});
-        mk->leaves.insert(mk->leaves.end(), leaf, leaf + leaf_len);
+        return mode != QueryPhase::Walked || glh::merkle_path_ok(leaf, leaf_len, index, sib, depth, cap);
     };
     for (size_t qi = 0; qi < (size_t)s.num_queries; ++qi) {
         size_t x_index = ch.query_index(N);
+        if (sink) sink->so.index.push_back(x_index);
+        if (mode == QueryPhase::QueryFree) continue;  // every other step of a query is proven by the tables of vx_stark_queries_prove
         const sp::Query<const uint64_t> q = v.query(qi);
-        if (mk) {
-            mk->index.push_back(x_index);
-            claim(VX_SOPEN_TREE0, x_index, q.row_t(), s.cm, q.sib_t());
-            if (s.ca) claim(VX_SOPEN_TREE0 + 1, x_index, q.row_a(), s.ca, q.sib_a());
-            claim(VX_SOPEN_TREE0 + 2, x_index, q.row_q(), nq, q.sib_q());
-        } else {
-            NEED(glh::merkle_path_ok(q.row_t(), s.cm, x_index, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
-            if (s.ca) NEED(glh::merkle_path_ok(q.row_a(), s.ca, x_index, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
-            NEED(glh::merkle_path_ok(q.row_q(), nq, x_index, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
-        }
-        uint64_t x = glh::mul(7, glh::pow(wN, brev(x_index, s.LN)));
+        NEED(opening(VX_SOPEN_TREE0, x_index, q.row_t(), s.cm, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
+        if (s.ca) NEED(opening(VX_SOPEN_TREE0 + 1, x_index, q.row_a(), s.ca, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
+        NEED(opening(VX_SOPEN_TREE0 + 2, x_index, q.row_q(), nq, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
+        uint64_t x = sp::query_point(x_index, s.LN);
         Fx s1{0, 0}, ap{1, 0};
         for (size_t j = 0; j < c; ++j) {
             s1 = s1 + ap * Fx{j < s.cm ? q.row_t()[j] : q.row_a()[j - s.cm], 0};
@@ -371,11 +339,11 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
             ap = ap * alpha;
         }
         Fx ev = red.alpha_c * (s0 - red.y0) * fx_inv(Fx{x, 0} - zeta) + (s1 - red.y1) * fx_inv(Fx{x, 0} - zeta_next);
-        if (fri) fri->index.push_back(x_index), fri->ev0.push_back(ev.a), fri->ev0.push_back(ev.b);
-        if (fri && fri->want_combine) {
-            fri->rows.insert(fri->rows.end(), q.row_t(), q.row_t() + s.cm);
-            fri->rows.insert(fri->rows.end(), q.row_a(), q.row_a() + s.ca);
-            fri->rows.insert(fri->rows.end(), q.row_q(), q.row_q() + nq);
+        if (sink) {
+            sink->ev0.push_back(ev.a), sink->ev0.push_back(ev.b);
+            sink->rows.insert(sink->rows.end(), q.row_t(), q.row_t() + s.cm);
+            sink->rows.insert(sink->rows.end(), q.row_a(), q.row_a() + s.ca);
+            sink->rows.insert(sink->rows.end(), q.row_q(), q.row_q() + nq);
         }
         for (size_t l = 0; l < n_layers; ++l) {
             const int a = s.arities[l];
@@ -389,14 +357,13 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
                     ++src;
                 }
             }
-            if (fri) fri->leaves.insert(fri->leaves.end(), leaf.begin(), leaf.end());
-            if (mk) claim(l, x_index >> a, leaf.data(), 2 * arity, q.sibs(l));
-            else NEED(glh::merkle_path_ok(leaf.data(), 2 * arity, x_index >> a, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
+            if (sink) sink->leaves.insert(sink->leaves.end(), leaf.begin(), leaf.end());
+            NEED(opening(l, x_index >> a, leaf.data(), 2 * arity, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
             // compute_evaluation: interpolate the coset {x g^i} and evaluate at beta
             const uint64_t g = glh::root(a);
             std::vector<Fx> evn(arity);
-            for (size_t t = 0; t < arity; ++t) evn[brev(t, a)] = {leaf[2 * t], leaf[2 * t + 1]};
-            const uint64_t start = glh::mul(x, glh::pow(g, arity - brev(within, a)));
+            for (size_t t = 0; t < arity; ++t) evn[sp::brev(t, a)] = {leaf[2 * t], leaf[2 * t + 1]};
+            const uint64_t start = glh::mul(x, glh::pow(g, arity - sp::brev(within, a)));
             std::vector<uint64_t> pts(arity);
             uint64_t gp = 1;
             for (size_t t = 0; t < arity; ++t) {
@@ -418,24 +385,20 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
             x = glh::pow(x, arity);
             x_index >>= a;
         }
-        Fx fp{0, 0};
-        for (size_t k = s.final_len; k-- > 0;) fp = fp * Fx{x, 0} + fpoly[k];
-        NEED(fx_eq(fp, ev), "final polynomial evaluation mismatch (query %zu)", qi);
-        if (fri) fri->ev_last.push_back(ev.a), fri->ev_last.push_back(ev.b);
+        NEED(fx_eq(sp::final_poly_at(v.final_poly(), s.final_len, x), ev), "final polynomial evaluation mismatch (query %zu)", qi);
+        if (sink) sink->ev_last.push_back(ev.a), sink->ev_last.push_back(ev.b);
     }
     return VX_OK;
 }
 static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, FriClaims* fri, char* err, size_t errlen) {
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
     if (!cfg || !pr) return VX_ERR_ARG;
-    if (!sp::config_ok(*cfg)) {
-        if (err && errlen) snprintf(err, errlen, "stark verify: configuration out of range");
-        return VX_ERR_ARG;
-    }
-    AirV air{};
-    VX_TRY(proof_air(pr, len, expect_air, &air, err, errlen));
+    if (!sp::config_ok(*cfg)) return v_fail(VX_ERR_ARG, err, errlen, "stark verify: configuration out of range");
+    ProofHead head;
+    VX_TRY(proof_head(*cfg, pr, len, expect_air, &head, err, errlen));
     // the header is the one this AIR, these degree bits and the configuration imply, word for word
-    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)pr[2], *cfg);
+    const AirV& air = head.air;
+    const sp::Shape& shape = *head.shape;
     const std::vector<uint64_t> hdr = shape.header_words();
     for (size_t i = 0; i < hdr.size(); ++i)
         NEED(i < len && pr[i] == hdr[i], "%s", i >= 5 && i <= 8 ? "config mismatch" : i >= 9 && i < hdr.size() - 2 ? "FRI plan mismatch" : "shape mismatch");
@@ -443,8 +406,9 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     // below can go negative (a crafted L = 2 proof used to reach the Merkle check with n_sib = SIZE_MAX)
     NEED(shape.LN >= shape.cap_h && shape.LN <= 27 && shape.L >= air.period_log, "degree bits %d out of range for this AIR / cap height", shape.L);
     NEED(!air.exact_log || shape.L == air.period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air.period_log, shape.L);
-    const bool delegated = fri && fri->merkle, query_free = delegated && fri->query_free;
-    if (!delegated)
+    // every word that is read is canonical -- the whole proof, everything but the siblings, or the head alone
+    const bool query_free = mode == QueryPhase::QueryFree;
+    if (mode == QueryPhase::Walked)
         for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
     sp::View v;
     const char* bad_length = query_free ? sp::View::parse_head(pr, len, shape, &v) : sp::View::parse(pr, len, shape, &v);
@@ -452,7 +416,7 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     NEED(!bad_length, "%s (%zu words, this shape has %zu)", bad_length, len, shape.words());
     if (query_free) {  // the head alone is read
         for (size_t i = hdr.size(); i < shape.o_queries; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
-    } else if (delegated) {  // the same check over everything but the siblings: in this mode none of their words is read
+    } else if (mode == QueryPhase::Delegated) {  // everything but the siblings: in this mode none of their words is read
         auto canonical = [&](size_t from, size_t n) -> size_t {
             for (size_t i = from; i < from + n; ++i)
                 if (pr[i] >= glh::P) return i;
@@ -488,28 +452,23 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     for (size_t l = 0; l < shape.arities.size(); ++l) betas.push_back(ch.beta(v, l));
     ch.final_poly(v);
     NEED(ch.pow_ok(*v.nonce(), shape.pow_bits), "proof of work invalid");
-    if (delegated) {
-        StarkOpenings& m = *fri->merkle;
-        m = StarkOpenings();
+    if (sink) {
+        *sink = StarkQueries();
+        StarkOpenings& m = sink->so;
         m.LN = shape.LN, m.a = cfg->arity_bits, m.cap_h = shape.cap_h, m.cm = shape.cm, m.ca = shape.ca, m.NL = shape.arities.size(), m.n_queries = (size_t)shape.num_queries;
         auto tree = [&](uint64_t id, const uint64_t* cap) { m.tree.push_back(id), m.caps.insert(m.caps.end(), cap, cap + shape.cap_words); };
         tree(VX_SOPEN_TREE0, v.cap_trace());
         if (shape.ca) tree(VX_SOPEN_TREE0 + 1, v.cap_aux());
         tree(VX_SOPEN_TREE0 + 2, v.cap_quot());
         for (size_t l = 0; l < m.NL; ++l) tree(l, v.layer_cap(l));
+        sink->rate_bits = cfg->rate_bits, sink->nq = sp::NQ, sink->alpha[0] = alpha.a, sink->alpha[1] = alpha.b, sink->zeta[0] = zeta.a, sink->zeta[1] = zeta.b;
+        sink->openings.assign(v.open_local(), v.open_local() + 2 * shape.c);
+        sink->openings.insert(sink->openings.end(), v.open_next(), v.open_next() + 2 * shape.c);
+        sink->openings.insert(sink->openings.end(), v.open_quot(), v.open_quot() + 2 * sp::NQ);
+        for (const Fx& b : betas) sink->betas.push_back(b.a), sink->betas.push_back(b.b);
+        sink->final_poly.assign(v.final_poly(), v.final_poly() + 2 * shape.final_len);
     }
-    if (fri) {
-        fri->log_lde = shape.LN;
-        for (const Fx& b : betas) fri->betas.push_back(b.a), fri->betas.push_back(b.b);
-        fri->final_poly.assign(v.final_poly(), v.final_poly() + 2 * shape.final_len);
-        if (fri->want_combine) {
-            fri->cm = shape.cm, fri->ca = shape.ca, fri->nq = sp::NQ, fri->alpha[0] = alpha.a, fri->alpha[1] = alpha.b, fri->zeta[0] = zeta.a, fri->zeta[1] = zeta.b;
-            fri->openings.assign(v.open_local(), v.open_local() + 2 * shape.c);
-            fri->openings.insert(fri->openings.end(), v.open_next(), v.open_next() + 2 * shape.c);
-            fri->openings.insert(fri->openings.end(), v.open_quot(), v.open_quot() + 2 * sp::NQ);
-        }
-    }
-    VX_TRY(fri_queries(v, ch, alpha, zeta, betas, fri, err, errlen));
+    VX_TRY(fri_queries(v, ch, alpha, zeta, betas, mode, sink, err, errlen));
     const uint64_t* apub = shape.ca ? v.apub() : nullptr;
     if (shape.ca && !ext_chal)  // a stand-alone proof has nobody to cancel a bus total against
         for (size_t q = 0; q < 2 * shape.auxpub; ++q) NEED(apub[q] == 0, "stand-alone proof publishes a non-zero bus total");
@@ -528,6 +487,7 @@ struct BusTable {
     int air = 0;
     const uint64_t* want = nullptr;
     size_t n_want = 0;
+    void expect(int air_id, const uint64_t* public_inputs, size_t n) { air = air_id, want = public_inputs, n_want = n; }
 };
 static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
     for (size_t i = 0; i < n; ++i)
@@ -536,14 +496,31 @@ static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
 }
 // The messages a party outside the tables puts on their bus -- the verifier itself, in an aggregation proof: the denominator of
 // each, and whether the verifier receives it (+) or sends it (-).
+using VBus = bus::Bus<X2<Fx>>;
 struct BusMessages {
     std::vector<X2<Fx>> den;
     std::vector<uint8_t> sent;
     void reserve(size_t n) { den.reserve(n), sent.reserve(n); }
     void receive(const X2<Fx>& d) { den.push_back(d), sent.push_back(0); }
     void send(const X2<Fx>& d) { den.push_back(d), sent.push_back(1); }
+    // What the aggregation verifiers say about a query phase, each stated once.  The root a path ended in with the tree's depth,
+    // in its two halves: the tables do not know which root belongs to which tree, the verifier does
+    void receive_root(const VBus& bus, uint64_t tree, const uint64_t root[4], int depth) {
+        const Fx t{tree, 0}, d{(uint64_t)depth, 0};
+        receive(bus.root(t, Fx{root[0], 0}, Fx{root[1], 0}, bus::K<0>{}, d));
+        receive(bus.root(t, Fx{root[2], 0}, Fx{root[3], 0}, bus::K<1>{}, d));
+    }
+    // the 32 words of the leaf a query opens in layer tree `layer` (arity 16)
+    void send_layer_leaf(const VBus& bus, size_t layer, uint64_t index, const uint64_t leaf[32]) {
+        for (size_t j = 0; j < 32; ++j) send(bus.row_of(Fx{(uint64_t)layer, 0}, Fx{index >> (4 * (layer + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaf[j], 0}));
+    }
+    // the exit of a fold chain: the final polynomial at x_NL = x_0^(16^NL)
+    void receive_exit(const VBus& bus, uint64_t index, int log_lde, size_t n_layers, const uint64_t* final_poly, size_t final_len) {
+        const Fx fp = stark_proof::final_poly_at(final_poly, final_len, glh::pow(stark_proof::query_point(index, log_lde), (uint64_t)1 << (4 * n_layers)));
+        receive(bus.fri(Fx{index, 0}, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+    }
 };
-using BusOutside = std::function<void(const bus::Bus<X2<Fx>>&, BusMessages&)>;
+using BusOutside = std::function<void(const VBus&, BusMessages&)>;
 // sum over the messages of +- 1 / D with ONE inversion (Montgomery batch: prefix products, one inverse, walked back); false when
 // the product of the denominators is zero
 static bool bus_messages_sum(const BusMessages& m, X2<Fx>* sum) {
@@ -586,7 +563,7 @@ static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, s
         for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
     }
     BusMessages msgs;
-    if (outside) outside(bus::Bus<X2<Fx>>(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0}), msgs);
+    if (outside) outside(VBus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0}), msgs);
     X2<Fx> sum;
     NEED(bus_messages_sum(msgs, &sum), "a message of the verifier has a zero denominator under the challenges");
     NEED(sum.a.b == 0 && sum.b.b == 0 && bus[0] == sum.a.a && bus[1] == sum.b.a, "%s", unbalanced);
@@ -613,11 +590,8 @@ static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const
 }
 // the root of a tree known by its cap (a table proves paths to ONE root): the two-to-one fold of the cap
 static int32_t cap_root(const uint64_t* cap, int cap_height, const char* what, uint64_t root[4], char* err, size_t errlen) {
-    std::vector<uint64_t> fold(cap, cap + ((size_t)4 << cap_height));
-    for (uint64_t w : fold) NEED(w < glh::P, "%s: non-canonical cap word", what);
-    for (size_t nodes = (size_t)1 << cap_height; nodes > 1; nodes >>= 1)
-        for (size_t i = 0; i < nodes / 2; ++i) glh::two_to_one(fold.data() + 8 * i, fold.data() + 8 * i + 4, fold.data() + 4 * i);
-    memcpy(root, fold.data(), 32);
+    for (size_t i = 0; i < ((size_t)4 << cap_height); ++i) NEED(cap[i] < glh::P, "%s: non-canonical cap word", what);
+    vx_cap_fold(cap, cap_height, root);
     return VX_OK;
 }
 
@@ -723,8 +697,8 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     be_limbs(out96 + 32, tpub), be_limbs(out96 + 64, tpub + 8);  // state_root_merkle_root || data_root_merkle_root as big-endian words
     tpub[16] = (uint64_t)target_block - trusted_block;  // the number of headers = of enabled leaves: the Merkle table MUST take every header's roots from the bus
     NEED(tpub[16] <= max_headers, "the block range exceeds max_headers");
-    for (size_t s = 0; s < S; ++s) tab[s].air = VX_AIR_BLAKE_CHAIN, tab[s].want = spubs.data() + 20 * s, tab[s].n_want = 20;
-    tab[S].air = tree_id, tab[S].want = tpub, tab[S].n_want = 17;
+    for (size_t s = 0; s < S; ++s) tab[s].expect(VX_AIR_BLAKE_CHAIN, spubs.data() + 20 * s, 20);
+    tab[S].expect(tree_id, tpub, 17);
     if (justified) {
         int jair[3];
         const int32_t rc = vx_justification_expect(tab[S + 1].pub, tab[S + 1].n_pub, tab[S + 2].pub, tab[S + 2].n_pub, tab[S + 3].n_pub, authority_set_hash, authority_set_id, out96,
@@ -732,7 +706,7 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
         if (rc != VX_OK) return rc;
         const uint64_t* jwant[3] = {cpub, epub, hpub};
         const size_t jn[3] = {10, 2, 15};
-        for (int q = 0; q < 3; ++q) tab[S + 1 + q].air = jair[q], tab[S + 1 + q].want = jwant[q], tab[S + 1 + q].n_want = jn[q];
+        for (int q = 0; q < 3; ++q) tab[S + 1 + q].expect(jair[q], jwant[q], jn[q]);
     }
     // the bus closes: state roots and data roots of the hashed headers = the leaves of the Merkle trees; the keys of the signed
     // authorities = the keys the signatures verify under; R || A and H between the curve table and the SHA-512 table
@@ -754,11 +728,10 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
          log_leaves);
     NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle openings: %zu openings (1..2^21)", n_idx);
     BusTable tab[1];
-    int32_t rc = read_blob(blob, len, VX_MOPEN_MAGIC, "merkle-openings", {(uint64_t)log_leaves, n_idx}, tab, 1, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_MOPEN_MAGIC, "merkle-openings", {(uint64_t)log_leaves, n_idx}, tab, 1, err, errlen));
     NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
     uint64_t root[4], pub[mop::PUB];
-    if ((rc = cap_root(cap, cap_height, "merkle openings", root, err, errlen)) != VX_OK) return rc;
+    VX_TRY(cap_root(cap, cap_height, "merkle openings", root, err, errlen));
     std::vector<uint64_t> claims(5 * n_idx);
     for (size_t i = 0; i < n_idx; ++i) {
         NEED(leaf_idx[i] >> log_leaves == 0, "merkle openings: claim %zu names a leaf outside the tree", i);
@@ -769,9 +742,9 @@ int32_t vx_merkle_openings_verify(const vx_stark_config* cfg, const uint64_t* bl
         }
     }
     vx_merkle_open_public(root, log_leaves, claims.data(), n_idx, pub);
-    tab[0].air = VX_AIR_MERKLE_OPEN, tab[0].want = pub, tab[0].n_want = mop::PUB;
+    tab[0].expect(VX_AIR_MERKLE_OPEN, pub, mop::PUB);
     return verify_bus_group(cfg, tab, 1, "the openings the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(2 * n_idx);
                                 for (const uint64_t* c = claims.data(); c < claims.data() + 5 * n_idx; c += 5) {
                                     m.receive(bus.open(Fx{c[0], 0}, Fx{c[1], 0}, Fx{c[2], 0}, bus::K<0>{}));
@@ -798,11 +771,10 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
     NEED(n_idx >= 1 && n_idx <= ((size_t)1 << 21), "merkle rows: %zu openings (1..2^21)", n_idx);
     NEED(leaf_len >= 5 && leaf_len <= ((size_t)1 << 20), "merkle rows: leaf_len %zu (5..2^20)", leaf_len);
     BusTable tab[2];
-    int32_t rc = read_blob(blob, len, VX_MROWS_MAGIC, "merkle-rows", {(uint64_t)log_leaves, leaf_len, n_idx}, tab, 2, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_MROWS_MAGIC, "merkle-rows", {(uint64_t)log_leaves, leaf_len, n_idx}, tab, 2, err, errlen));
     NEED(peek_tables(cfg, tab, 2), "a proof is too short to hold a trace cap");
     uint64_t root[4], opub[mop::PUB], spub[lsp::PUB];
-    if ((rc = cap_root(cap, cap_height, "merkle rows", root, err, errlen)) != VX_OK) return rc;
+    VX_TRY(cap_root(cap, cap_height, "merkle rows", root, err, errlen));
     vx_merkle_open_public(root, log_leaves, nullptr, 0, opub);
     NEED(tab[0].n_pub == (size_t)mop::PUB, "merkle rows: the openings table has %zu public inputs", tab[0].n_pub);
     for (int j = 5; j < mop::PUB; ++j) {
@@ -820,10 +792,10 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
         }
     }
     vx_leaf_sponge_public(leaf_len, claims.data(), n_idx, spub);
-    tab[0].air = VX_AIR_MERKLE_OPEN, tab[0].want = opub, tab[0].n_want = mop::PUB;
-    tab[1].air = VX_AIR_LEAF_SPONGE, tab[1].want = spub, tab[1].n_want = lsp::PUB;
+    tab[0].expect(VX_AIR_MERKLE_OPEN, opub, mop::PUB);
+    tab[1].expect(VX_AIR_LEAF_SPONGE, spub, lsp::PUB);
     return verify_bus_group(cfg, tab, 2, "the rows the tables prove are not the claimed ones (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(n_idx * leaf_len);
                                 for (size_t i = 0; i < n_idx; ++i)
                                     for (size_t j = 0; j < leaf_len; ++j) m.receive(bus.row(Fx{leaf_idx[i], 0}, Fx{(uint64_t)j, 0}, Fx{rows[i * leaf_len + j], 0}));
@@ -851,9 +823,9 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
     {
         uint64_t bpub[20], epub[10], spub[10];
         BusTable tab[3] = {{p0, l0}, {p0 + l0 + l1 + l2 + l3 + l4, l5}, {p0 + l0 + l1, l2}};
-        tab[0].air = VX_AIR_BLAKE_CHAIN, tab[0].want = bpub, tab[0].n_want = 20;
-        tab[1].air = VX_AIR_EPOCH_END, tab[1].want = epub, tab[1].n_want = 10;
-        tab[2].air = VX_AIR_SHA_CHAIN, tab[2].want = spub, tab[2].n_want = 10;
+        tab[0].expect(VX_AIR_BLAKE_CHAIN, bpub, 20);
+        tab[1].expect(VX_AIR_EPOCH_END, epub, 10);
+        tab[2].expect(VX_AIR_SHA_CHAIN, spub, 10);
         NEED(peek_tables(cfg, tab, 3), "epoch-end proofs are too short to hold a trace cap");
         for (int j = 0; j < 8; ++j) {
             uint32_t a, b;
@@ -890,9 +862,9 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
     const int32_t rc = vx_justification_expect(tab[0].pub, tab[0].n_pub, tab[1].pub, tab[1].n_pub, tab[2].n_pub, authority_set_hash, authority_set_id, (const uint8_t*)(blob + 4),
                                                (uint32_t)blob[2], blob[25], spub, epub, hpub, air, err, errlen);
     if (rc != VX_OK) return rc;
-    tab[0].air = air[0], tab[0].want = spub, tab[0].n_want = 10;
-    tab[1].air = air[1], tab[1].want = epub, tab[1].n_want = 2;
-    tab[2].air = air[2], tab[2].want = hpub, tab[2].n_want = 15;
+    tab[0].expect(air[0], spub, 10);
+    tab[1].expect(air[1], epub, 2);
+    tab[2].expect(air[2], hpub, 15);
     return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen);
 }
 
@@ -903,51 +875,41 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
 //     published total x rows = sum over the queries of  - sum over the layers l, j < 32 of 1 / D_row(tree l, index >> 4 (l + 1), j, leaf_l[j])
 //                                                        - 1 / D_fri(index, ev_0, 0)  +  1 / D_fri(index, final_poly(x_NL), 1).
 // NOTHING IS FOLDED here: per query one exponentiation for x_NL = x_0^(16^NL) and one Horner evaluation remain.
-static int32_t ff_arg(char* err, size_t errlen, const char* fmt, ...) {
-    if (err && errlen) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(err, errlen, fmt, ap);
-        va_end(ap);
+// The fold-side claims of an aggregation verifier, `what` its name in the messages: the ranges, then every word canonical and every
+// index inside the LDE.  ev0 / leaves: nullptr where the verifier holds none.
+static int32_t fold_claims_check(const char* what, int max_log_lde, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len,
+                                 const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, char* err, size_t errlen) {
+    NEED(log_lde >= 5 && log_lde <= max_log_lde && n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "%s: log_lde %d / %zu layers out of range", what,
+         log_lde, n_layers);
+    NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "%s: %zu queries (1..2^20)", what, n_queries);
+    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "%s: a final polynomial of %zu coefficients", what, final_len);
+    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "%s: non-canonical beta word %zu", what, i);
+    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "%s: non-canonical final-polynomial word %zu", what, i);
+    for (size_t i = 0; i < n_queries; ++i) {
+        NEED(index[i] >> log_lde == 0, "%s: claim %zu names an index outside the LDE", what, i);
+        NEED(!ev0 || (ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P), "%s: claim %zu has a non-canonical ev_0", what, i);
     }
-    return VX_ERR_ARG;
+    for (size_t i = 0; leaves && i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "%s: claim %zu has a non-canonical leaf word", what, i / (32 * n_layers));
+    return VX_OK;
 }
 int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
                            size_t final_len, const uint64_t* index, const uint64_t* ev0, const uint64_t* leaves, size_t n_queries, char* err, size_t errlen) {
     if (!cfg || !blob || !betas || !final_poly || !index || !ev0 || !leaves) return VX_ERR_ARG;
-    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
-    NEED(log_lde >= 5 && log_lde <= 32 && n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri fold: log_lde %d / %zu layers out of range", log_lde,
-         n_layers);
-    NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "fri fold: %zu queries (1..2^20)", n_queries);
-    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri fold: a final polynomial of %zu coefficients", final_len);
+    if (cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "fri fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    VX_TRY(fold_claims_check("fri fold", 32, log_lde, betas, n_layers, final_poly, final_len, index, ev0, leaves, n_queries, err, errlen));
     BusTable tab[1];
-    const int32_t rc = read_blob(blob, len, VX_FFOLD_MAGIC, "fri-fold", {(uint64_t)log_lde, n_layers, n_queries}, tab, 1, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_FFOLD_MAGIC, "fri-fold", {(uint64_t)log_lde, n_layers, n_queries}, tab, 1, err, errlen));
     NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
-    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri fold: non-canonical beta word %zu", i);
-    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri fold: non-canonical final-polynomial word %zu", i);
-    for (size_t i = 0; i < n_queries; ++i) {
-        NEED(index[i] >> log_lde == 0, "fri fold: claim %zu names an index outside the LDE", i);
-        NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri fold: claim %zu has a non-canonical ev_0", i);
-    }
-    for (size_t i = 0; i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "fri fold: claim %zu has a non-canonical leaf word", i / (32 * n_layers));
     uint64_t pub[ffa::PUB];
     vx_fri_fold_public(log_lde, betas, n_layers, 0, index, ev0, leaves, n_queries, pub);
-    tab[0].air = VX_AIR_FRI_FOLD, tab[0].want = pub, tab[0].n_want = ffa::PUB;
+    tab[0].expect(VX_AIR_FRI_FOLD, pub, ffa::PUB);
     return verify_bus_group(cfg, tab, 1, "the fold chains the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(n_queries * (32 * n_layers + 2));
-                                const uint64_t w = glh::root(log_lde);
                                 for (size_t i = 0; i < n_queries; ++i) {
-                                    const Fx idx{index[i], 0};
-                                    for (size_t l = 0; l < n_layers; ++l)
-                                        for (size_t j = 0; j < 32; ++j)
-                                            m.send(bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0}));
-                                    m.send(bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
-                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
-                                    Fx fp{0, 0};
-                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
-                                    m.receive(bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                    for (size_t l = 0; l < n_layers; ++l) m.send_layer_leaf(bus, l, index[i], leaves + (i * n_layers + l) * 32);
+                                    m.send(bus.fri(Fx{index[i], 0}, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
+                                    m.receive_exit(bus, index[i], log_lde, n_layers, final_poly, final_len);
                                 }
                             });
 }
@@ -964,52 +926,31 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
 int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly,
                               size_t final_len, const uint64_t* caps, int cap_height, const uint64_t* index, const uint64_t* ev0, size_t n_queries, char* err, size_t errlen) {
     if (!cfg || !blob || !betas || !final_poly || !caps || !index || !ev0) return VX_ERR_ARG;
-    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
-    NEED(log_lde >= 5 && log_lde <= 30 && n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri queries: log_lde %d / %zu layers out of range", log_lde,
-         n_layers);
+    if (cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "fri queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    VX_TRY(fold_claims_check("fri queries", 30, log_lde, betas, n_layers, final_poly, final_len, index, ev0, nullptr, n_queries, err, errlen));
     NEED(cap_height >= 0 && cap_height <= 16 && cap_height <= log_lde - 4 * (int)n_layers, "fri queries: cap height %d out of range (at most log_lde - 4 layers)", cap_height);
-    NEED(n_queries >= 1 && n_queries <= ((size_t)1 << 20), "fri queries: %zu queries (1..2^20)", n_queries);
-    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri queries: a final polynomial of %zu coefficients", final_len);
     const int log_open = fri_queries_open_log_n(n_queries, log_lde, n_layers), log_sponge = fri_queries_sponge_log_n(n_queries, n_layers);
     NEED(log_open <= 26 && log_sponge <= 26, "fri queries: the request needs a table of more than 2^26 rows");
     BusTable tab[3];
-    int32_t rc = read_blob(blob, len, VX_FQRY_MAGIC, "fri-queries", {(uint64_t)log_lde, n_layers, n_queries}, tab, 3, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_FQRY_MAGIC, "fri-queries", {(uint64_t)log_lde, n_layers, n_queries}, tab, 3, err, errlen));
     NEED(peek_tables(cfg, tab, 3), "a proof is too short to hold a trace cap");
-    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri queries: non-canonical beta word %zu", i);
-    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri queries: non-canonical final-polynomial word %zu", i);
-    for (size_t i = 0; i < n_queries; ++i) {
-        NEED(index[i] >> log_lde == 0, "fri queries: claim %zu names an index outside the LDE", i);
-        NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri queries: claim %zu has a non-canonical ev_0", i);
-    }
     std::vector<uint64_t> roots(4 * n_layers);
-    for (size_t l = 0; l < n_layers; ++l)
-        if ((rc = cap_root(caps + l * ((size_t)4 << cap_height), cap_height, "fri queries", roots.data() + 4 * l, err, errlen)) != VX_OK) return rc;
+    for (size_t l = 0; l < n_layers; ++l) VX_TRY(cap_root(caps + l * ((size_t)4 << cap_height), cap_height, "fri queries", roots.data() + 4 * l, err, errlen));
     uint64_t stmt[4], opub[mop::SET_PUB], spub[lsp::PUB], fpub[ffa::PUB];
     vx_fri_queries_statement(log_lde, betas, n_layers, final_poly, final_len, roots.data(), index, ev0, n_queries, stmt);
     vx_merkle_open_set_public(stmt, opub);
     vx_leaf_sponge_set_public(32, stmt, spub);
     vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, fpub);
-    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
-    tab[1].air = VX_AIR_LEAF_SPONGE_SET, tab[1].want = spub, tab[1].n_want = lsp::PUB;
-    tab[2].air = VX_AIR_FRI_FOLD, tab[2].want = fpub, tab[2].n_want = ffa::PUB;
+    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
+    tab[1].expect(VX_AIR_LEAF_SPONGE_SET, spub, lsp::PUB);
+    tab[2].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB);
     return verify_bus_group(cfg, tab, 3, "the query phase the tables prove is not the claimed one (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(n_queries * (2 + 2 * n_layers));
-                                const uint64_t w = glh::root(log_lde);
                                 for (size_t i = 0; i < n_queries; ++i) {
-                                    const Fx idx{index[i], 0};
-                                    m.send(bus.fri(idx, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
-                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
-                                    Fx fp{0, 0};
-                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
-                                    m.receive(bus.fri(idx, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
-                                    for (size_t l = 0; l < n_layers; ++l) {
-                                        const uint64_t* r = roots.data() + 4 * l;
-                                        const Fx tree{(uint64_t)l, 0}, depth{(uint64_t)(log_lde - 4 * ((int)l + 1)), 0};
-                                        m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
-                                        m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
-                                    }
+                                    m.send(bus.fri(Fx{index[i], 0}, Fx{ev0[2 * i], 0}, Fx{ev0[2 * i + 1], 0}, bus::K<0>{}));
+                                    m.receive_exit(bus, index[i], log_lde, n_layers, final_poly, final_len);
+                                    for (size_t l = 0; l < n_layers; ++l) m.receive_root(bus, l, roots.data() + 4 * l, log_lde - 4 * ((int)l + 1));
                                 }
                             });
 }
@@ -1021,22 +962,20 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
                             uint64_t* final_poly_out, size_t final_cap, uint64_t* index_out, uint64_t* ev0_out, uint64_t* ev_last_out, size_t query_cap, uint64_t* leaves_out,
                             size_t leaves_cap, char* err, size_t errlen) {
     if (!cfg || !proof || !log_lde || !n_layers || !final_len || !n_queries || !betas_out || !final_poly_out || !index_out || !ev0_out || !leaves_out) return VX_ERR_ARG;
-    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri claims: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
-    FriClaims fc;
-    const int32_t rc = stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, &fc, err, errlen);
-    if (rc != VX_OK) return rc;
-    const size_t nl = fc.betas.size() / 2, nq = fc.index.size();
-    if (nl < 1 || nl > (size_t)ffa::MAX_LAYERS || 4 * (int)nl >= fc.log_lde)
-        return ff_arg(err, errlen, "fri claims: a proof with %zu fold layers over an LDE of 2^%d has no FriFoldAir statement (1..8 layers, one index bit left)", nl, fc.log_lde);
-    *log_lde = fc.log_lde, *n_layers = nl, *final_len = fc.final_poly.size() / 2, *n_queries = nq;
-    if (final_cap < fc.final_poly.size() || query_cap < nq || leaves_cap < fc.leaves.size()) {
-        if (err && errlen) snprintf(err, errlen, "fri claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", final_cap, query_cap, leaves_cap, fc.final_poly.size(), nq, fc.leaves.size());
-        return VX_ERR_BUFSZ;
-    }
+    if (cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "fri claims: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    StarkQueries fc;
+    VX_TRY(stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, QueryPhase::Walked, &fc, err, errlen));
+    const size_t nl = fc.so.NL, nq = fc.so.n_queries;
+    if (nl < 1 || nl > (size_t)ffa::MAX_LAYERS || 4 * (int)nl >= fc.so.LN)
+        return v_fail(VX_ERR_ARG, err, errlen, "fri claims: a proof with %zu fold layers over an LDE of 2^%d has no FriFoldAir statement (1..8 layers, one index bit left)", nl, fc.so.LN);
+    *log_lde = fc.so.LN, *n_layers = nl, *final_len = fc.final_poly.size() / 2, *n_queries = nq;
+    if (final_cap < fc.final_poly.size() || query_cap < nq || leaves_cap < fc.leaves.size())
+        return v_fail(VX_ERR_BUFSZ, err, errlen, "fri claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", final_cap, query_cap, leaves_cap, fc.final_poly.size(), nq,
+                      fc.leaves.size());
     memset(betas_out, 0, 16 * 8);
     memcpy(betas_out, fc.betas.data(), fc.betas.size() * 8);
     memcpy(final_poly_out, fc.final_poly.data(), fc.final_poly.size() * 8);
-    memcpy(index_out, fc.index.data(), nq * 8);
+    memcpy(index_out, fc.so.index.data(), nq * 8);
     memcpy(ev0_out, fc.ev0.data(), 2 * nq * 8);
     if (ev_last_out) memcpy(ev_last_out, fc.ev_last.data(), 2 * nq * 8);
     memcpy(leaves_out, fc.leaves.data(), fc.leaves.size() * 8);
@@ -1045,15 +984,17 @@ int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, s
 
 }  // extern "C"
 
-// The Merkle side of a vx_stark_prove proof as claims (vx_bus.h): the verifier's own code in its delegated mode -- transcript,
-// constraint identity at zeta, proof of work, combination, folds and the final polynomial are all checked; the paths are not.
+// The query phase of a vx_stark_prove proof as claims (vx_bus.h), from ONE run of the verifier's own code -- transcript, constraint
+// identity at zeta, proof of work and, unless query-free, combination, folds and the final polynomial are all checked.
+int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                const uint64_t* ext_chal, QueryPhase mode, StarkQueries* out, char* err, size_t errlen) {
+    return stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, mode, out, err, errlen);
+}
 int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                 const uint64_t* ext_chal, bool want_sibs, StarkOpenings* out, char* err, size_t errlen) {
-    FriClaims fc;
-    fc.merkle = out, fc.want_sibs = want_sibs;
-    const int32_t rc = stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, &fc, err, errlen);
-    if (rc != VX_OK) return rc;
-    if (out->NL > (size_t)ffa::MAX_LAYERS) return ff_arg(err, errlen, "stark openings: a proof with %zu fold layers (at most 8: the layer trees are ids 0..7, the commitment trees 8..10)", out->NL);
+                                 const uint64_t* ext_chal, StarkQueries* out, char* err, size_t errlen) {
+    VX_TRY(vx_stark_queries_claims(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, QueryPhase::Delegated, out, err, errlen));
+    if (out->so.NL > (size_t)ffa::MAX_LAYERS)
+        return v_fail(VX_ERR_ARG, err, errlen, "stark openings: a proof with %zu fold layers (at most 8: the layer trees are ids 0..7, the commitment trees 8..10)", out->so.NL);
     return VX_OK;
 }
 void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]) {
@@ -1087,20 +1028,17 @@ int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof
     if (!cfg || !proof || !shape_out || !n_trees || !cap_tree_out || !caps_out || !n_claims || !tree_out || !index_out || !leaf_len_out || !leaves_len || !leaves_out || !siblings_len ||
         !siblings_out)
         return VX_ERR_ARG;
-    StarkOpenings so;
-    const int32_t rc = vx_stark_openings_claims(cfg, proof, len, 0, nullptr, 0, ext_chal, true, &so, err, errlen);
-    if (rc != VX_OK) return rc;
+    StarkQueries sq;
+    VX_TRY(vx_stark_openings_claims(cfg, proof, len, 0, nullptr, 0, ext_chal, &sq, err, errlen));
+    const StarkOpenings& so = sq.so;
     size_t sib_words = 0;
     for (const StarkOpenings::Claim& c : so.claims) sib_words += 4 * (size_t)(so.log_leaves(c.tree) - so.cap_h);
     const std::array<uint64_t, 7> sw = so.shape_words();
     memcpy(shape_out, sw.data(), sizeof sw);
     *n_trees = so.tree.size(), *n_claims = so.claims.size(), *leaves_len = so.leaves.size(), *siblings_len = sib_words;
-    if (caps_cap < so.caps.size() || claims_cap < so.claims.size() || leaves_cap < so.leaves.size() || siblings_cap < sib_words) {
-        if (err && errlen)
-            snprintf(err, errlen, "merkle claims: the buffers hold %zu / %zu / %zu / %zu words, %zu / %zu / %zu / %zu are needed", caps_cap, claims_cap, leaves_cap, siblings_cap, so.caps.size(),
-                     so.claims.size(), so.leaves.size(), sib_words);
-        return VX_ERR_BUFSZ;
-    }
+    if (caps_cap < so.caps.size() || claims_cap < so.claims.size() || leaves_cap < so.leaves.size() || siblings_cap < sib_words)
+        return v_fail(VX_ERR_BUFSZ, err, errlen, "merkle claims: the buffers hold %zu / %zu / %zu / %zu words, %zu / %zu / %zu / %zu are needed", caps_cap, claims_cap, leaves_cap, siblings_cap,
+                      so.caps.size(), so.claims.size(), so.leaves.size(), sib_words);
     memset(cap_tree_out, 0, 11 * 8);
     memcpy(cap_tree_out, so.tree.data(), so.tree.size() * 8);
     memcpy(caps_out, so.caps.data(), so.caps.size() * 8);
@@ -1115,18 +1053,27 @@ int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof
     return VX_OK;
 }
 
-// What vx_stark_openings_prove writes for this inner proof at most: read from the proof's head alone (AIR id and degree bits -> the
-// columns of the three trees, the fold layers), nothing is verified.
-int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
+// What vx_stark_openings_prove / vx_stark_queries_prove write for this inner proof at most: read from the proof's head alone (AIR id
+// and degree bits -> the columns of the three trees, the fold layers), nothing is verified.
+static int32_t stark_group_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, bool queries, size_t* n_words) {
     if (!cfg || !proof || !n_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
-    AirV air{};
-    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
-    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
-    StarkOpeningsTables ts;
-    if (shape.LN < shape.cap_h || shape.cap_h > 16 || !stark_openings_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, shape.arities.size(), (size_t)shape.num_queries, &ts)) return VX_ERR_ARG;
-    TableShape sh[4];
+    ProofHead head;
+    if (proof_head(*cfg, proof, proof_len, 0, &head, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+    const sp::Shape& shape = *head.shape;
+    const size_t NL = shape.arities.size(), n_q = (size_t)shape.num_queries;
+    StarkGroupTables ts;
+    if (shape.LN < shape.cap_h || shape.cap_h > 16) return VX_ERR_ARG;
+    if (!(queries ? stark_queries_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, NL, n_q, *cfg, &ts) : stark_openings_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, NL, n_q, &ts)))
+        return VX_ERR_ARG;
+    TableShape sh[7];
     for (int k = 0; k < ts.n; ++k) sh[k] = {ts.air[k], ts.log_n[k]};
-    return vx_tables_proof_bound(cfg, VX_SOPEN_HDR + (size_t)ts.n, sh, (size_t)ts.n, n_words);
+    return vx_tables_proof_bound(cfg, (queries ? VX_SQRY_HDR : VX_SOPEN_HDR) + (size_t)ts.n, sh, (size_t)ts.n, n_words);
+}
+int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
+    return stark_group_proof_bound(cfg, proof, proof_len, false, n_words);
+}
+int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
+    return stark_group_proof_bound(cfg, proof, proof_len, true, n_words);
 }
 
 // STARK openings (the prover is vx_stark_openings.hip): the Merkle side of one inner vx_stark_prove proof on one bus -- the
@@ -1142,16 +1089,15 @@ int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t
 int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
                                  size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
     if (!cfg || !blob || !proof) return VX_ERR_ARG;
-    StarkOpenings so;
-    int32_t rc = vx_stark_openings_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, false, &so, err, errlen);
-    if (rc != VX_OK) return rc;
-    StarkOpeningsTables ts;
+    StarkQueries sq;
+    VX_TRY(vx_stark_openings_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, &sq, err, errlen));
+    const StarkOpenings& so = sq.so;
+    StarkGroupTables ts;
     NEED(stark_openings_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, &ts), "stark openings: the proof's shape has no openings group (a tree without a level, or a table of more than 2^26 rows)");
     NEED(so.cap_h <= 16, "stark openings: cap height %d (at most 16)", so.cap_h);
     BusTable tab[4];
     const std::array<uint64_t, 7> sw = so.shape_words();
-    rc = read_blob(blob, len, VX_SOPEN_MAGIC, "stark-openings", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_SOPEN_MAGIC, "stark-openings", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen));
     NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
     const size_t n_trees = so.tree.size();
     std::vector<uint64_t> roots(4 * n_trees);
@@ -1159,21 +1105,19 @@ int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blo
     uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB];
     vx_stark_openings_statement(so, roots.data(), stmt);
     vx_merkle_open_set_public(stmt, opub);
-    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
+    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
     for (int k = 1; k < ts.n; ++k) {
         vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
-        tab[k].air = VX_AIR_LEAF_SPONGE_SET, tab[k].want = spub[k - 1], tab[k].n_want = lsp::PUB;
+        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
     }
     return verify_bus_group(cfg, tab, (size_t)ts.n, "the openings the tables prove are not the ones of this proof (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(2 * so.claims.size() + so.leaves.size());
                                 for (size_t i = 0; i < so.claims.size(); ++i) {
                                     const StarkOpenings::Claim& c = so.claims[i];
-                                    const uint64_t* r = roots.data() + 4 * (i % n_trees);
                                     const uint64_t* leaf = so.leaves.data() + c.leaf;
-                                    const Fx tree{c.tree, 0}, idx{c.index, 0}, depth{(uint64_t)so.log_leaves(c.tree), 0};
-                                    m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
-                                    m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
+                                    const Fx tree{c.tree, 0}, idx{c.index, 0};
+                                    m.receive_root(bus, c.tree, roots.data() + 4 * (i % n_trees), so.log_leaves(c.tree));
                                     if (c.leaf_len > 4) {
                                         for (size_t j = 0; j < c.leaf_len; ++j) m.receive(bus.row_of(tree, idx, Fx{(uint64_t)j, 0}, Fx{leaf[j], 0}));
                                     } else {
@@ -1207,7 +1151,7 @@ static int32_t fc_stmt_check(const FriCombineStmt& st, const uint64_t* index, co
     return VX_OK;
 }
 // the row words of one query as the verifier sends them: tree TREE0 + t, position within the tree's row
-static void fc_send_rows(const bus::Bus<X2<Fx>>& bus, BusMessages& m, const FriCombineStmt& st, uint64_t index, const uint64_t* row) {
+static void fc_send_rows(const VBus& bus, BusMessages& m, const FriCombineStmt& st, uint64_t index, const uint64_t* row) {
     const size_t c = st.cm + st.ca, absn = c + st.nq;
     for (size_t j = 0; j < absn; ++j) {
         const uint64_t t = j < st.cm ? 0 : j < c ? 1 : 2, pos = j < st.cm ? j : j < c ? j - st.cm : j - c;
@@ -1219,20 +1163,18 @@ int32_t vx_fri_combine_verify(const vx_stark_config* cfg, const uint64_t* blob, 
                               size_t n_queries, char* err, size_t errlen) {
     if (!cfg || !blob || !alpha || !zeta || !open_local || !open_next || !open_quot || !index || !rows || !ev0) return VX_ERR_ARG;
     const FriCombineStmt st{log_lde, cfg->rate_bits, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot};
-    int32_t rc = fc_stmt_check(st, index, rows, n_queries, "fri combine", err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(fc_stmt_check(st, index, rows, n_queries, "fri combine", err, errlen));
     for (size_t i = 0; i < n_queries; ++i) NEED(ev0[2 * i] < glh::P && ev0[2 * i + 1] < glh::P, "fri combine: claim %zu has a non-canonical ev_0", i);
     NEED(fri_combine_log_n(n_queries, log_lde, cm, ca, nq) <= 26, "fri combine: the request needs a table of more than 2^26 rows");
     BusTable tab[1];
-    rc = read_blob(blob, len, VX_FCOMB_MAGIC, "fri-combine", {(uint64_t)log_lde, cm, ca, nq, n_queries}, tab, 1, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_FCOMB_MAGIC, "fri-combine", {(uint64_t)log_lde, cm, ca, nq, n_queries}, tab, 1, err, errlen));
     NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
     uint64_t pub[fca::PUB];
     vx_fri_combine_public(st, fca::TREE0, index, rows, ev0, n_queries, pub);
-    tab[0].air = VX_AIR_FRI_COMBINE, tab[0].want = pub, tab[0].n_want = fca::PUB;
+    tab[0].expect(VX_AIR_FRI_COMBINE, pub, fca::PUB);
     const size_t absn = cm + ca + nq;
     return verify_bus_group(cfg, tab, 1, "the combinations the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(n_queries * (absn + 1));
                                 for (size_t i = 0; i < n_queries; ++i) {
                                     fc_send_rows(bus, m, st, index[i], rows + i * absn);
@@ -1250,40 +1192,28 @@ int32_t vx_fri_combine_fold_verify(const vx_stark_config* cfg, const uint64_t* b
                                    const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* rows, const uint64_t* leaves, size_t n_queries, char* err,
                                    size_t errlen) {
     if (!cfg || !blob || !alpha || !zeta || !open_local || !open_next || !open_quot || !betas || !final_poly || !index || !rows || !leaves) return VX_ERR_ARG;
-    if (cfg->arity_bits != 4) return ff_arg(err, errlen, "fri combine-fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    if (cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "fri combine-fold: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
     const FriCombineStmt st{log_lde, cfg->rate_bits, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot};
-    int32_t rc = fc_stmt_check(st, index, rows, n_queries, "fri combine-fold", err, errlen);
-    if (rc != VX_OK) return rc;
-    NEED(n_layers >= 1 && n_layers <= (size_t)ffa::MAX_LAYERS && 4 * (int)n_layers < log_lde, "fri combine-fold: log_lde %d / %zu layers out of range", log_lde, n_layers);
-    NEED(final_len >= 1 && final_len <= ((size_t)1 << 27), "fri combine-fold: a final polynomial of %zu coefficients", final_len);
+    VX_TRY(fc_stmt_check(st, index, rows, n_queries, "fri combine-fold", err, errlen));
+    VX_TRY(fold_claims_check("fri combine-fold", 32, log_lde, betas, n_layers, final_poly, final_len, index, nullptr, leaves, n_queries, err, errlen));
     NEED(fri_combine_log_n(n_queries, log_lde, cm, ca, nq) <= 26 && fri_fold_log_n(n_queries, log_lde, n_layers) <= 26, "fri combine-fold: the request needs a table of more than 2^26 rows");
-    for (size_t i = 0; i < 2 * n_layers; ++i) NEED(betas[i] < glh::P, "fri combine-fold: non-canonical beta word %zu", i);
-    for (size_t i = 0; i < 2 * final_len; ++i) NEED(final_poly[i] < glh::P, "fri combine-fold: non-canonical final-polynomial word %zu", i);
-    for (size_t i = 0; i < n_queries * n_layers * 32; ++i) NEED(leaves[i] < glh::P, "fri combine-fold: claim %zu has a non-canonical leaf word", i / (32 * n_layers));
     BusTable tab[2];
-    rc = read_blob(blob, len, VX_FCFLD_MAGIC, "fri-combine-fold", {(uint64_t)log_lde, cm, ca, nq, n_layers, n_queries}, tab, 2, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_FCFLD_MAGIC, "fri-combine-fold", {(uint64_t)log_lde, cm, ca, nq, n_layers, n_queries}, tab, 2, err, errlen));
     NEED(peek_tables(cfg, tab, 2), "a proof is too short to hold a trace cap");
     uint64_t stmt[4], cpub[fca::PUB], fpub[ffa::PUB];
     vx_fri_combine_fold_statement(st, betas, n_layers, final_poly, final_len, index, rows, leaves, n_queries, stmt);
     vx_fri_combine_public_digest(st, fca::TREE0, stmt, cpub);
     vx_fri_fold_public_digest(log_lde, betas, n_layers, 0, stmt, fpub);
-    tab[0].air = VX_AIR_FRI_COMBINE, tab[0].want = cpub, tab[0].n_want = fca::PUB;
-    tab[1].air = VX_AIR_FRI_FOLD, tab[1].want = fpub, tab[1].n_want = ffa::PUB;
+    tab[0].expect(VX_AIR_FRI_COMBINE, cpub, fca::PUB);
+    tab[1].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB);
     const size_t absn = cm + ca + nq;
     return verify_bus_group(cfg, tab, 2, "the query-phase arithmetic the tables prove is not the claimed one (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(n_queries * (absn + 32 * n_layers + 1));
-                                const uint64_t w = glh::root(log_lde);
                                 for (size_t i = 0; i < n_queries; ++i) {
                                     fc_send_rows(bus, m, st, index[i], rows + i * absn);
-                                    for (size_t l = 0; l < n_layers; ++l)
-                                        for (size_t j = 0; j < 32; ++j)
-                                            m.send(bus.row_of(Fx{(uint64_t)l, 0}, Fx{index[i] >> (4 * (l + 1)), 0}, Fx{(uint64_t)j, 0}, Fx{leaves[(i * n_layers + l) * 32 + j], 0}));
-                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(index[i], log_lde))), (uint64_t)1 << (4 * n_layers));  // x_NL = x_0^(16^NL)
-                                    Fx fp{0, 0};
-                                    for (size_t k = final_len; k-- > 0;) fp = fp * Fx{x, 0} + Fx{final_poly[2 * k], final_poly[2 * k + 1]};
-                                    m.receive(bus.fri(Fx{index[i], 0}, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                    for (size_t l = 0; l < n_layers; ++l) m.send_layer_leaf(bus, l, index[i], leaves + (i * n_layers + l) * 32);
+                                    m.receive_exit(bus, index[i], log_lde, n_layers, final_poly, final_len);
                                 }
                             });
 }
@@ -1295,20 +1225,16 @@ int32_t vx_stark_combine_claims(const vx_stark_config* cfg, const uint64_t* proo
                                 uint64_t zeta_out[2], uint64_t* openings_out, size_t openings_cap, uint64_t* index_out, uint64_t* ev0_out, size_t query_cap, uint64_t* rows_out,
                                 size_t rows_cap, char* err, size_t errlen) {
     if (!cfg || !proof || !log_lde || !cm || !ca || !nq || !n_queries || !alpha_out || !zeta_out || !openings_out || !index_out || !ev0_out || !rows_out) return VX_ERR_ARG;
-    FriClaims fc;
-    fc.want_combine = true;
-    const int32_t rc = stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, &fc, err, errlen);
-    if (rc != VX_OK) return rc;
-    const size_t n = fc.index.size();
-    *log_lde = fc.log_lde, *cm = fc.cm, *ca = fc.ca, *nq = fc.nq, *n_queries = n;
-    if (openings_cap < fc.openings.size() || query_cap < n || rows_cap < fc.rows.size()) {
-        if (err && errlen)
-            snprintf(err, errlen, "combine claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", openings_cap, query_cap, rows_cap, fc.openings.size(), n, fc.rows.size());
-        return VX_ERR_BUFSZ;
-    }
+    StarkQueries fc;
+    VX_TRY(stark_verify_impl(cfg, proof, len, 0, nullptr, 0, nullptr, nullptr, nullptr, QueryPhase::Walked, &fc, err, errlen));
+    const size_t n = fc.so.n_queries;
+    *log_lde = fc.so.LN, *cm = fc.so.cm, *ca = fc.so.ca, *nq = fc.nq, *n_queries = n;
+    if (openings_cap < fc.openings.size() || query_cap < n || rows_cap < fc.rows.size())
+        return v_fail(VX_ERR_BUFSZ, err, errlen, "combine claims: the buffers hold %zu / %zu / %zu words, %zu / %zu / %zu are needed", openings_cap, query_cap, rows_cap, fc.openings.size(), n,
+                      fc.rows.size());
     memcpy(alpha_out, fc.alpha, 16), memcpy(zeta_out, fc.zeta, 16);
     memcpy(openings_out, fc.openings.data(), fc.openings.size() * 8);
-    memcpy(index_out, fc.index.data(), n * 8);
+    memcpy(index_out, fc.so.index.data(), n * 8);
     memcpy(ev0_out, fc.ev0.data(), 2 * n * 8);
     memcpy(rows_out, fc.rows.data(), fc.rows.size() * 8);
     return VX_OK;
@@ -1316,20 +1242,6 @@ int32_t vx_stark_combine_claims(const vx_stark_config* cfg, const uint64_t* proo
 
 }
 
-// The whole query phase of a vx_stark_prove proof as claims (vx_bus.h), from ONE run of the verifier's code: the Merkle side and
-// the arithmetic side of every query in the prover's mode, the head alone in the query-free mode.
-int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
-                                const uint64_t* ext_chal, bool query_free, StarkQueries* out, char* err, size_t errlen) {
-    FriClaims fc;
-    fc.merkle = &out->so, fc.want_sibs = !query_free, fc.want_combine = true, fc.query_free = query_free;
-    const int32_t rc = stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, &fc, err, errlen);
-    if (rc != VX_OK) return rc;
-    out->rate_bits = cfg->rate_bits, out->nq = fc.nq;
-    memcpy(out->alpha, fc.alpha, 16), memcpy(out->zeta, fc.zeta, 16);
-    out->openings = std::move(fc.openings), out->betas = std::move(fc.betas), out->final_poly = std::move(fc.final_poly);
-    out->rows = std::move(fc.rows), out->leaves = std::move(fc.leaves), out->ev0 = std::move(fc.ev0);
-    return VX_OK;
-}
 void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, uint64_t digest[4]) {
     const StarkOpenings& so = sq.so;
     std::vector<uint64_t> w;
@@ -1345,19 +1257,6 @@ void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, u
 }
 
 extern "C" {
-// What vx_stark_queries_prove writes for this inner proof at most: read from the proof's head alone, nothing is verified.
-int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
-    if (!cfg || !proof || !n_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
-    AirV air{};
-    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
-    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
-    StarkQueriesTables ts;
-    if (shape.LN < shape.cap_h || shape.cap_h > 16 || !stark_queries_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, shape.arities.size(), (size_t)shape.num_queries, *cfg, &ts)) return VX_ERR_ARG;
-    TableShape sh[7];
-    for (int k = 0; k < ts.n; ++k) sh[k] = {ts.air[k], ts.log_n[k]};
-    return vx_tables_proof_bound(cfg, VX_SQRY_HDR + (size_t)ts.n, sh, (size_t)ts.n, n_words);
-}
-
 // The whole query phase of a proof (the prover is vx_stark_queries.hip): MerkleOpenSetAir, the sponge tables, LeafNoopAir,
 // FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0) on one bus.  TAG_OPEN closes between the openings and the leaf tables,
 // TAG_ROW between the leaf tables and the arithmetic, TAG_FRI end 0 between combination and fold.  The inner proof is verified in
@@ -1370,18 +1269,16 @@ int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t*
 int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
                                 size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
     if (!cfg || !blob || !proof) return VX_ERR_ARG;
-    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return ff_arg(err, errlen, "stark queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "stark queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
     StarkQueries sq;
-    int32_t rc = vx_stark_queries_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, true, &sq, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(vx_stark_queries_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, QueryPhase::QueryFree, &sq, err, errlen));
     const StarkOpenings& so = sq.so;
-    StarkQueriesTables ts;
+    StarkGroupTables ts;
     if (so.cap_h > 16 || !stark_queries_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, *cfg, &ts))
-        return ff_arg(err, errlen, "stark queries: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
+        return v_fail(VX_ERR_ARG, err, errlen, "stark queries: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
     BusTable tab[7];
     const std::array<uint64_t, 7> sw = so.shape_words();
-    rc = read_blob(blob, len, VX_SQRY_MAGIC, "stark-queries", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen);
-    if (rc != VX_OK) return rc;
+    VX_TRY(read_blob(blob, len, VX_SQRY_MAGIC, "stark-queries", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen));
     NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
     const size_t n_trees = so.tree.size(), final_len = sq.final_poly.size() / 2;
     std::vector<uint64_t> roots(4 * n_trees);
@@ -1389,33 +1286,24 @@ int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob
     uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB], npub[lnp::PUB], cpub[fca::PUB], fpub[ffa::PUB];
     vx_stark_queries_statement(sq, roots.data(), stmt);
     vx_merkle_open_set_public(stmt, opub);
-    tab[0].air = VX_AIR_MERKLE_OPEN_SET, tab[0].want = opub, tab[0].n_want = mop::SET_PUB;
+    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
     int k = 1;
     for (; k <= ts.n_sponge; ++k) {
         vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
-        tab[k].air = VX_AIR_LEAF_SPONGE_SET, tab[k].want = spub[k - 1], tab[k].n_want = lsp::PUB;
+        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
     }
     vx_leaf_noop_public(stmt, npub);
-    tab[k].air = VX_AIR_LEAF_NOOP, tab[k].want = npub, tab[k].n_want = lnp::PUB, ++k;
+    tab[k].expect(VX_AIR_LEAF_NOOP, npub, lnp::PUB), ++k;
     vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, cpub);
-    tab[k].air = VX_AIR_FRI_COMBINE, tab[k].want = cpub, tab[k].n_want = fca::PUB, ++k;
+    tab[k].expect(VX_AIR_FRI_COMBINE, cpub, fca::PUB), ++k;
     vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, fpub);
-    tab[k].air = VX_AIR_FRI_FOLD, tab[k].want = fpub, tab[k].n_want = ffa::PUB;
+    tab[k].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB);
     return verify_bus_group(cfg, tab, (size_t)ts.n, "the query phase the tables prove is not the one of this proof (the lookup bus does not balance)", err, errlen,
-                            [&](const bus::Bus<X2<Fx>>& bus, BusMessages& m) {
+                            [&](const VBus& bus, BusMessages& m) {
                                 m.reserve(so.n_queries * (2 * n_trees + 1));
-                                const uint64_t w = glh::root(so.LN);
                                 for (size_t i = 0; i < so.n_queries; ++i) {
-                                    for (size_t t = 0; t < n_trees; ++t) {
-                                        const uint64_t* r = roots.data() + 4 * t;
-                                        const Fx tree{so.tree[t], 0}, depth{(uint64_t)so.log_leaves(so.tree[t]), 0};
-                                        m.receive(bus.root(tree, Fx{r[0], 0}, Fx{r[1], 0}, bus::K<0>{}, depth));
-                                        m.receive(bus.root(tree, Fx{r[2], 0}, Fx{r[3], 0}, bus::K<1>{}, depth));
-                                    }
-                                    const uint64_t x = glh::pow(glh::mul(7, glh::pow(w, brev(so.index[i], so.LN))), (uint64_t)1 << (4 * so.NL));  // x_NL = x_0^(16^NL)
-                                    Fx fp{0, 0};
-                                    for (size_t j = final_len; j-- > 0;) fp = fp * Fx{x, 0} + Fx{sq.final_poly[2 * j], sq.final_poly[2 * j + 1]};
-                                    m.receive(bus.fri(Fx{so.index[i], 0}, Fx{fp.a, 0}, Fx{fp.b, 0}, bus::K<1>{}));
+                                    for (size_t t = 0; t < n_trees; ++t) m.receive_root(bus, so.tree[t], roots.data() + 4 * t, so.log_leaves(so.tree[t]));
+                                    m.receive_exit(bus, so.index[i], so.LN, so.NL, sq.final_poly.data(), final_len);
                                 }
                             });
 }
@@ -1426,10 +1314,9 @@ extern "C" {
 // proof's header alone (AIR id, degree bits) and the configuration; nothing is verified.
 int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* head_words) {
     if (!cfg || !proof || !head_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
-    AirV air{};
-    if (proof_air(proof, proof_len, 0, &air, nullptr, 0) != VX_OK) return VX_ERR_ARG;
-    const sp::Shape shape(air.id, air.cols, air.aux, air.pub, air.auxpub, (int)proof[2], *cfg);
-    *head_words = shape.o_queries;
+    ProofHead head;
+    if (proof_head(*cfg, proof, proof_len, 0, &head, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+    *head_words = head.shape->o_queries;
     return VX_OK;
 }
 }

@@ -238,16 +238,25 @@ def default_stark_config(**over):
     return cfg
 
 
-def stark_verify(proof, cfg=None, expect_air=0, expect_public=None):
-    """Host-side verification (no GPU needed).  Raises VxError(VX_ERR_STATEMENT) with the reason."""
-    L = load_library()
+def _words(x):
+    """contiguous uint64 words, or None for an argument that is left out"""
+    return None if x is None else np.ascontiguousarray(x, dtype=np.uint64)
+
+
+def _host_verify(name, cfg, *args):
+    """One call of a host `vx_*_verify`: the configuration (None: the default), then `args` -- an array goes as its pointer, None as
+    NULL --, then a 256-byte buffer for the reason.  Raises VxError(rc, reason) unless it returns VX_OK."""
     cfg = cfg or default_stark_config()
-    pr = np.ascontiguousarray(proof, dtype=np.uint64)
-    pub = None if expect_public is None else np.ascontiguousarray(expect_public, dtype=np.uint64)
     err = C.create_string_buffer(256)
-    rc = L.vx_stark_verify(C.byref(cfg), _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size, err, 256)
+    rc = getattr(load_library(), name)(C.byref(cfg), *[_ptr(a) if isinstance(a, np.ndarray) else a for a in args], err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
+
+
+def stark_verify(proof, cfg=None, expect_air=0, expect_public=None):
+    """Host-side verification (no GPU needed).  Raises VxError(VX_ERR_STATEMENT) with the reason."""
+    pr, pub = _words(proof), _words(expect_public)
+    _host_verify("vx_stark_verify", cfg, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size)
 
 
 def air_register(cols, n_public, code, consts=(), periodic=(), n_regs=None, aux_cols=0, n_challenges=0, n_aux_public=0, gen_aux=None):
@@ -356,29 +365,18 @@ def merge_blobs(blobs):
 
 
 def header_range_verify(blob, max_headers, trusted_block, trusted_hash, target_block, out96, cfg=None, authority_set_hash=None, authority_set_id=0):
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     th = np.frombuffer(bytes(trusted_hash), dtype=np.uint8).copy()
     o = np.frombuffer(bytes(out96), dtype=np.uint8).copy()
     ah = None if authority_set_hash is None else np.frombuffer(bytes(authority_set_hash), dtype=np.uint8).copy()
-    err = C.create_string_buffer(256)
-    rc = L.vx_header_range_verify(C.byref(cfg), _ptr(b), b.size, max_headers, trusted_block, _ptr(th), authority_set_id, None if ah is None else _ptr(ah), target_block,
-                                  _ptr(o), err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_header_range_verify", cfg, b, b.size, max_headers, trusted_block, th, authority_set_id, ah, target_block, o)
 
 
 def rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg=None):
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     ah = np.frombuffer(bytes(authority_set_hash), dtype=np.uint8).copy()
     o = np.frombuffer(bytes(out32), dtype=np.uint8).copy()
-    err = C.create_string_buffer(256)
-    rc = L.vx_rotate_verify(C.byref(cfg), _ptr(b), b.size, authority_set_id, _ptr(ah), _ptr(o), err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_rotate_verify", cfg, b, b.size, authority_set_id, ah, o)
 
 
 MOPEN_MAGIC, MOPEN_HDR = 0x314E45504F4D5856, 4  # "VXMOPEN1": magic, log2(n_leaves), number of openings, proof length; then the MerkleOpenAir proof
@@ -396,18 +394,13 @@ def _cap(cap):
 def merkle_openings_verify(blob, cap, log_leaves, leaf_idx, leaf_digests, cfg=None):
     """Host-side check of a vx_merkle_openings_prove blob against the verifier's own claims: the tree's cap [2^cap_height][4],
     log2(n_leaves), and the openings (leaf_idx[i], leaf_digests[i][4]) in order.  Walks no Merkle path; raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     cp, cap_height = _cap(cap)
-    idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
-    dig = np.ascontiguousarray(leaf_digests, dtype=np.uint64).reshape(-1)
+    idx = _words(leaf_idx).reshape(-1)
+    dig = _words(leaf_digests).reshape(-1)
     if dig.size != 4 * idx.size:
         raise ValueError("one 4-word digest per opening")
-    err = C.create_string_buffer(256)
-    rc = L.vx_merkle_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, _ptr(idx), _ptr(dig), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_merkle_openings_verify", cfg, b, b.size, cp, cap_height, log_leaves, idx, dig, idx.size)
 
 
 MROWS_MAGIC, MROWS_HDR = 0x3153574F524D5856, 6  # "VXMROWS1": magic, log2(n_leaves), leaf_len, openings, two proof lengths; then the MerkleOpenAir and the LeafSpongeAir proof
@@ -417,18 +410,13 @@ def merkle_rows_verify(blob, cap, log_leaves, leaf_idx, rows, cfg=None):
     """Host-side check of a vx_merkle_rows_prove blob against the verifier's own claims: the tree's cap [2^cap_height][4],
     log2(n_leaves), and the opened rows (leaf_idx[i], rows[i][leaf_len]) in order.  Walks no Merkle path and hashes no leaf; raises
     VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     cp, cap_height = _cap(cap)
-    idx = np.ascontiguousarray(leaf_idx, dtype=np.uint64).reshape(-1)
-    rw = np.ascontiguousarray(rows, dtype=np.uint64)
+    idx = _words(leaf_idx).reshape(-1)
+    rw = _words(rows)
     if rw.ndim != 2 or rw.shape[0] != idx.size:
         raise ValueError("one row [leaf_len] per opening")
-    err = C.create_string_buffer(256)
-    rc = L.vx_merkle_rows_verify(C.byref(cfg), _ptr(b), b.size, _ptr(cp), cap_height, log_leaves, rw.shape[1], _ptr(idx), _ptr(rw), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_merkle_rows_verify", cfg, b, b.size, cp, cap_height, log_leaves, rw.shape[1], idx, rw, idx.size)
 
 
 FFOLD_MAGIC, FFOLD_HDR = 0x31444C4F46465856, 5  # "VXFFOLD1": magic, log2 of the inner LDE, fold layers, queries, proof length; then the FriFoldAir proof
@@ -449,14 +437,9 @@ def _fri_claims(betas, final_poly, index, ev0, leaves):
 def fri_fold_verify(blob, log_lde, betas, final_poly, index, ev0, leaves, cfg=None):
     """Host-side check of a vx_fri_fold_prove blob against the verifier's own claims: the inner proof's LDE size, betas [NL][2] and
     final polynomial [len][2], and per query (index, ev0 [2], leaves [NL][32]) in order.  Folds nothing; raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
-    err = C.create_string_buffer(256)
-    rc = L.vx_fri_fold_verify(C.byref(cfg), _ptr(b), b.size, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(idx), _ptr(ev), _ptr(lv), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_fri_fold_verify", cfg, b, b.size, log_lde, be, be.shape[0], fp, fp.shape[0], idx, ev, lv, idx.size)
 
 
 FQRY_MAGIC, FQRY_HDR = 0x3130595251465856, 7  # "VXFQRY01": magic, log2 of the inner LDE, fold layers, queries, three proof lengths; then the proofs
@@ -466,21 +449,16 @@ def fri_queries_verify(blob, log_lde, betas, final_poly, caps, index, ev0, cfg=N
     """Host-side check of a vx_fri_queries_prove blob against what a succinct verifier holds: the inner proof's LDE size, betas
     [NL][2], the final polynomial [len][2], the layer caps [NL][2^cap_height][4] and per query (index, ev0 [2]) in order.  Holds no
     leaves, walks no path, folds nothing; raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
-    be = np.ascontiguousarray(betas, dtype=np.uint64).reshape(-1, 2)
-    fp = np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
-    cp = np.ascontiguousarray(caps, dtype=np.uint64).reshape(be.shape[0], -1, 4)
-    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
-    ev = np.ascontiguousarray(ev0, dtype=np.uint64).reshape(-1)
+    b = _words(blob)
+    be = _words(betas).reshape(-1, 2)
+    fp = _words(final_poly).reshape(-1, 2)
+    cp = _words(caps).reshape(be.shape[0], -1, 4)
+    idx = _words(index).reshape(-1)
+    ev = _words(ev0).reshape(-1)
     cap_height = cp.shape[1].bit_length() - 1
     if ev.size != 2 * idx.size or cp.shape[1] != 1 << cap_height:
         raise ValueError("one ev_0 [2] for every query and one cap of 2^cap_height digests for every layer")
-    err = C.create_string_buffer(256)
-    rc = L.vx_fri_queries_verify(C.byref(cfg), _ptr(b), b.size, log_lde, _ptr(be), be.shape[0], _ptr(fp), fp.shape[0], _ptr(cp), cap_height, _ptr(idx), _ptr(ev), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_fri_queries_verify", cfg, b, b.size, log_lde, be, be.shape[0], fp, fp.shape[0], cp, cap_height, idx, ev, idx.size)
 
 
 def stark_fri_claims(proof, cfg=None):
@@ -543,17 +521,8 @@ def stark_openings_verify(blob, proof, cfg=None, expect_air=0, expect_public=Non
     """Host-side check of a vx_stark_openings_prove blob together with the inner proof it belongs to: the proof is verified in
     the delegated mode (every check except the Merkle paths) and the group proves the paths.  Walks no path, hashes no leaf,
     reads no sibling; raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
-    pr = np.ascontiguousarray(proof, dtype=np.uint64)
-    pub = None if expect_public is None else np.ascontiguousarray(expect_public, dtype=np.uint64)
-    ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
-    err = C.create_string_buffer(256)
-    rc = L.vx_stark_openings_verify(C.byref(cfg), _ptr(b), b.size, _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size,
-                                    None if ch is None else _ptr(ch), err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
+    _host_verify("vx_stark_openings_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
 
 
 def stark_proof_head(proof, cfg=None):
@@ -573,17 +542,8 @@ def stark_queries_verify(blob, proof, cfg=None, expect_air=0, expect_public=None
     alone (everything before the first query record; lib.stark_proof_head cuts it): the proof's transcript, proof of work and
     constraint identity at zeta are checked in the query-free mode, which reads no query record, and the group proves the query phase.
     Raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
-    pr = np.ascontiguousarray(proof, dtype=np.uint64)
-    pub = None if expect_public is None else np.ascontiguousarray(expect_public, dtype=np.uint64)
-    ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
-    err = C.create_string_buffer(256)
-    rc = L.vx_stark_queries_verify(C.byref(cfg), _ptr(b), b.size, _ptr(pr), pr.size, expect_air, None if pub is None else _ptr(pub), 0 if pub is None else pub.size,
-                                   None if ch is None else _ptr(ch), err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
+    _host_verify("vx_stark_queries_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
 
 
 FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
@@ -610,29 +570,18 @@ def _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, i
 def fri_combine_verify(blob, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0, cfg=None):
     """Host-side check of a vx_fri_combine_prove blob against the verifier's own claims: the inner proof's shape, alpha, zeta, the
     openings at zeta and per query (index, rows [cm + ca + nq], ev0 [2]) in order.  Combines nothing per query; raises VxError."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     al, ze, ol, on, oq, idx, rw, ev = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows, ev0)
-    err = C.create_string_buffer(256)
-    rc = L.vx_fri_combine_verify(C.byref(cfg), _ptr(b), b.size, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(idx), _ptr(rw), _ptr(ev), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_fri_combine_verify", cfg, b, b.size, log_lde, cm, ca, nq, al, ze, ol, on, oq, idx, rw, ev, idx.size)
 
 
 def fri_combine_fold_verify(blob, log_lde, cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, betas, final_poly, index, rows, leaves, cfg=None):
     """Host-side check of a vx_fri_combine_fold_prove blob: the combine claims WITHOUT ev_0 and the fold claims (betas [NL][2], the
     final polynomial [len][2], leaves [n][NL][32]).  Combines and folds nothing; raises VxError with the reason."""
-    L = load_library()
-    cfg = cfg or default_stark_config()
-    b = np.ascontiguousarray(blob, dtype=np.uint64)
+    b = _words(blob)
     al, ze, ol, on, oq, idx, rw, _ = _combine_claims(cm, ca, nq, alpha, zeta, open_local, open_next, open_quot, index, rows)
     be, fp, _, _, lv = _fri_claims(betas, final_poly, index, np.zeros(2 * idx.size, dtype=np.uint64), leaves)
-    err = C.create_string_buffer(256)
-    rc = L.vx_fri_combine_fold_verify(C.byref(cfg), _ptr(b), b.size, log_lde, cm, ca, nq, _ptr(al), _ptr(ze), _ptr(ol), _ptr(on), _ptr(oq), _ptr(be), be.shape[0], _ptr(fp), fp.shape[0],
-                                      _ptr(idx), _ptr(rw), _ptr(lv), idx.size, err, 256)
-    if rc != 0:
-        raise VxError(rc, err.value.decode())
+    _host_verify("vx_fri_combine_fold_verify", cfg, b, b.size, log_lde, cm, ca, nq, al, ze, ol, on, oq, be, be.shape[0], fp, fp.shape[0], idx, rw, lv, idx.size)
 
 
 def stark_combine_claims(proof, cfg=None):

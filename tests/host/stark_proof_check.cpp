@@ -2,7 +2,8 @@
 // shapes.  The layout is restated here ONCE more, as the order in which `sections` visits a proof: a proof of counter words written
 // through Writer in that order must be the counter itself (the sections tile the proof, in order, without gap or overlap), View must
 // hand the same words back, every strict prefix must be refused, the transcript must reach the same query indices in the prover's
-// and in the verifier's call order, and reduce_openings must agree with a naive Horner evaluation.  A hang ends in SIGALRM.
+// and in the verifier's call order, and reduce_openings must agree with a naive Horner evaluation.  The point of a query index and
+// the value of a final polynomial are restated on 128-bit remainders and compared exactly.  A hang ends in SIGALRM.
 #include <unistd.h>
 
 #include <cstdio>
@@ -176,6 +177,53 @@ void check_reduce() {
                 CHECK(fx_eq(r2.y0, r.y0) && fx_eq(r2.y1, r.y1) && fx_eq(r2.alpha_c, r.alpha_c));
             }
 }
+
+// ---- the point of a query index, 7 w_LN^brev(index), and the final polynomial at a base-field point, restated: w_LN by squaring
+// the 2^32-th root of unity 7^((p - 1) / 2^32), the power bit by bit from the index's LOW bit (which weighs 2^(LN - 1) reversed)
+uint64_t powmod(uint64_t x, uint64_t e) {
+    uint64_t r = 1;
+    for (; e; e >>= 1, x = mulmod(x, x))
+        if (e & 1) r = mulmod(r, x);
+    return r;
+}
+uint64_t point_restated(uint64_t index, int LN) {
+    uint64_t w = powmod(7, (glh::P - 1) >> 32);
+    for (int i = 32; i > LN; --i) w = mulmod(w, w);
+    uint64_t x = 7;
+    for (int b = 0; b < LN; ++b)
+        if ((index >> b) & 1) x = mulmod(x, powmod(w, (uint64_t)1 << (LN - 1 - b)));
+    return x;
+}
+void check_query_point_and_final_poly() {
+    snprintf(shape_name, sizeof shape_name, "query_point");
+    CHECK(sp::brev(0, 0) == 0 && sp::brev(1, 1) == 1 && sp::brev(1, 5) == 16 && sp::brev(0b10110, 5) == 0b01101 && sp::brev(((size_t)1 << 21) - 2, 21) == ((size_t)1 << 20) - 1);
+    for (uint64_t i = 0; i < 32; ++i) CHECK(sp::query_point(i, 5) == point_restated(i, 5));
+    CHECK(sp::query_point(0, 5) == 7 && sp::query_point(1, 5) == glh::P - 7);  // w^(N / 2) = -1
+    uint64_t seed = 0x2545f4914f6cdd1dULL;
+    auto rnd = [&seed]() {
+        seed = seed * 6364136223846793005ULL + 1442695040888963407ULL;
+        return (seed ^ (seed >> 29)) % glh::P;
+    };
+    const uint64_t N21 = (uint64_t)1 << 21;
+    for (uint64_t i : {(uint64_t)0, (uint64_t)1, N21 - 1, N21 - 2, N21 >> 1}) CHECK(sp::query_point(i, 21) == point_restated(i, 21));
+    for (int rep = 0; rep < 64; ++rep) {
+        const uint64_t i = rnd() % N21, x = sp::query_point(i, 21);
+        CHECK(x == point_restated(i, 21) && powmod(mulmod(x, powmod(7, glh::P - 2)), N21) == 1);  // x / 7 lies in the subgroup of order 2^21
+    }
+    snprintf(shape_name, sizeof shape_name, "final_poly_at");
+    for (size_t len : {1, 2, 8})
+        for (int rep = 0; rep < 20; ++rep) {
+            std::vector<uint64_t> words(2 * len);
+            for (uint64_t& w : words) w = rep == 0 ? glh::P - 1 : rnd();
+            const uint64_t x = rep == 1 ? 0 : rep == 2 ? glh::P - 1 : rnd();
+            std::vector<E> coef;
+            for (size_t k = 0; k < len; ++k) coef.push_back({words[2 * k], words[2 * k + 1]});
+            const E want = horner(coef, E{x, 0});
+            const Fx got = sp::final_poly_at(words.data(), len, x);
+            CHECK(got.a == want.a && got.b == want.b);
+            if (len == 1) CHECK(got.a == words[0] && got.b == words[1]);
+        }
+}
 }  // namespace
 
 int main() {
@@ -205,6 +253,7 @@ int main() {
     snprintf(shape_name, sizeof shape_name, "the grid");
     CHECK(deepest_cap > 0 && no_layers > 0 && with_layers > 0);
     check_reduce();
+    check_query_point_and_final_poly();
     printf("ok %zu %zu\n", n_shapes, n_transcripts);
     return 0;
 }

@@ -45,6 +45,38 @@ def test_reference_blobs_pass_the_product_verifier_in_all_three_forms(vx, oracle
             vx.lib.stark_verify(p, cfg)
 
 
+@pytest.mark.parametrize("name", ["fib8", "lookup8"])
+def test_every_claim_extractor_reads_what_the_reference_reads(vx, oracle, name):
+    """vx_stark_fri_claims, vx_stark_combine_claims and vx_stark_merkle_claims fill from ONE sink of the verifier's query phase: each
+    must hand out, word for word, what the reference reads from the same proof, and they must agree on index and ev_0."""
+    g = Z.group(name)
+    cl, hd, rows, leaves, cfg = g["cl"], g["hd"], g["rows"], g["leaves"], pcfg(vx, g["cfg"])
+    LN, cm, ca, a, NL, cap_h, n_q = cl["shape"]
+    index = np.array(cl["index"], dtype=np.uint64)
+    ev0 = np.array([leaves[q, 0, 2 * (int(i) & 15): 2 * (int(i) & 15) + 2] for q, i in enumerate(index)], dtype=np.uint64)  # the slot the chain enters layer 0 with
+    ev_last = np.array([[e.a, e.b] for e in (Z.F.final_eval(hd["fpoly"], int(i), LN, NL) for i in index)], dtype=np.uint64)
+    f, c, m = vx.lib.stark_fri_claims(g["proof"], cfg), vx.lib.stark_combine_claims(g["proof"], cfg), vx.lib.stark_merkle_claims(g["proof"], cfg)
+    same = lambda got, want: np.array_equal(np.asarray(got, dtype=np.uint64), np.asarray(want, dtype=np.uint64))  # noqa: E731
+    # the fold side
+    assert f["log_lde"] == LN and f["leaves"].shape == (n_q, NL, 32)
+    assert same(f["betas"], hd["betas"]) and same(f["final_poly"], hd["fpoly"]) and same(f["index"], index) and same(f["ev0"], ev0)
+    assert same(f["leaves"], leaves) and same(f["ev_last"], ev_last)
+    # the combination side
+    assert (c["log_lde"], c["cm"], c["ca"], c["nq"]) == (LN, cm, ca, Z.NQ) and c["rows"].shape == (n_q, cm + ca + Z.NQ)
+    assert same(c["alpha"], hd["alpha"]) and same(c["zeta"], hd["zeta"])
+    assert same(c["open_local"], hd["ol"]) and same(c["open_next"], hd["on"]) and same(c["open_quot"], hd["oq"])
+    assert same(c["index"], index) and same(c["ev0"], ev0) and same(c["rows"], rows)
+    # the Merkle side: one claim per (query, tree), in record order
+    assert m["shape"] == list(cl["shape"]) and m["trees"] == list(cl["trees"]) and len(cl["claims"]) == n_q * len(cl["trees"]) == m["tree"].size
+    for k, t in enumerate(cl["trees"]):
+        assert same(m["caps"][k], cl["caps"][t])
+    for i, want in enumerate(cl["claims"]):
+        assert (int(m["tree"][i]), int(m["index"][i]), int(m["leaf_len"][i])) == (want["tree"], want["index"], len(want["leaf"]))
+        assert same(m["leaves"][i], want["leaf"]) and same(m["siblings"][i], want["sib"])
+    # ... and with each other
+    assert same(f["index"], c["index"]) and same(f["ev0"], c["ev0"]) and same(m["index"][::len(cl["trees"])], f["index"])
+
+
 def test_the_statement_digest_holds_no_row_and_no_leaf_word(oracle):
     g = Z.group("fib8")
     words = len(g["cl"]["shape"]) + 4 + 2 * (2 * 2 + 4) + 2 * 1 + 2 * len(g["hd"]["fpoly"]) + 4 * len(g["cl"]["trees"]) + 5
