@@ -11,7 +11,7 @@
 #include "gl.cuh"
 
 namespace bus {
-enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10, TAG_ROOT = 11 };
+enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10, TAG_ROOT = 11, TAG_OBS = 12, TAG_CHAL = 13 };
 
 // a slot known at compile time: 0 leaves its term out, 1 adds the bare power of gamma, so a kind that does not use a slot
 // (or whose tag is 0 or 1) costs what the hand-written sum cost
@@ -104,5 +104,11 @@ struct Bus {
     // evaluates the final polynomial (the verifier)
     template <class E>
     VX_HD X fri(const S& index, const S& va, const S& vb, const E& end) const { return denom(beta, index, va, vb, end, K<TAG_FRI>{}); }
+    // a word a Fiat-Shamir transcript absorbs (chain, position among the chain's absorbed words, word): whoever holds the proof (the
+    // verifier of vx_stark_transcripts_verify) -> TranscriptAir
+    VX_HD X obs(const S& chain, const S& position, const S& word) const { return denom(beta, chain, position, word, None{}, K<TAG_OBS>{}); }
+    // a challenge a transcript yields (chain, ordinal among the chain's challenges, words absorbed when it was drawn, value):
+    // TranscriptAir -> whoever uses the challenges (the verifier).  `absorbed` binds WHEN: without it the absorptions could be regrouped
+    VX_HD X chal(const S& chain, const S& ordinal, const S& absorbed, const S& word) const { return denom(beta, chain, ordinal, absorbed, word, K<TAG_CHAL>{}); }
 };
 }  // namespace bus

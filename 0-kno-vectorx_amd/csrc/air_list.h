@@ -14,12 +14,13 @@
 #include "air_sha.cuh"
 #include "air_sha512.cuh"
 #include "air_sha_tree.cuh"
+#include "air_transcript.cuh"
 #include "vx_internal.h"
 
 template <class... Airs>
 struct AirList {};
 using VxAirs = AirList<ShaAir, BlakeAir, FibAir, MixAir, LookupAir, ShaTreeAir256, ShaTreeAir512, ShaTreeAir16, EdAir17, EdAir16, Sha512Air16, Sha512Air10, Sha512Air15,
-                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir, MerkleOpenSetAir, LeafSpongeSetAir, FriCombineAir, LeafNoopAir>;
+                       EpochEndAir, MerkleOpenAir, LeafSpongeAir, FriFoldAir, MerkleOpenSetAir, LeafSpongeSetAir, FriCombineAir, LeafNoopAir, TranscriptAir>;
 
 template <class... Airs>
 constexpr bool air_list_ok(AirList<Airs...>) {

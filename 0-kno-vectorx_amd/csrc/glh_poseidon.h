@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "glh.h"
 #include "poseidon_constants.h"
 
@@ -62,10 +64,19 @@ inline bool merkle_path_ok(const uint64_t* leaf, size_t leaf_len, size_t idx, co
     }
     return memcmp(cur, cap + 4 * idx, 32) == 0;
 }
-struct Challenger {
+// The duplex challenger, stated once over a recorder R: what it is told about every duplex, absorbed word and drawn challenge.
+// Challenger records nothing; RecordingChallenger (the prover of TranscriptAir, air_transcript.cuh) keeps the chain's witness.
+struct NoRecord {
+    void duplexed(int) {}
+    void observed(uint64_t) {}
+    void drawn(uint64_t) {}
+};
+template <class R>
+struct ChallengerOf : R {
     uint64_t st[12] = {0}, in[8], out[8];
     int n_in = 0, n_out = 0;
     void duplex() {
+        R::duplexed(n_in);
         for (int i = 0; i < n_in; ++i) st[i] = in[i];
         n_in = 0;
         poseidon(st);
@@ -73,6 +84,7 @@ struct Challenger {
         n_out = 8;
     }
     void observe(uint64_t x) {
+        R::observed(x);
         n_out = 0;
         in[n_in++] = x;
         if (n_in == 8) duplex();
@@ -82,7 +94,38 @@ struct Challenger {
     }
     uint64_t challenge() {
         if (n_in > 0 || n_out == 0) duplex();
+        R::drawn(out[n_out - 1]);
         return out[--n_out];
+    }
+};
+using Challenger = ChallengerOf<NoRecord>;
+// What a transcript did, as TranscriptAir's chain: the absorbed words in order, every challenge as (words absorbed when it was drawn,
+// value), and per duplex (k, q) = words absorbed by it, challenges popped from its output.
+struct TranscriptRecord {
+    std::vector<uint64_t> words, chal;
+    std::vector<uint8_t> plan;
+    void duplexed(int k) { plan.push_back((uint8_t)k), plan.push_back(0); }
+    void observed(uint64_t x) { words.push_back(x); }
+    void drawn(uint64_t v) { ++plan.back(), chal.push_back(words.size()), chal.push_back(v); }
+    size_t n_chal() const { return chal.size() / 2; }
+    size_t n_blocks() const { return plan.size() / 2; }
+};
+using RecordingChallenger = ChallengerOf<TranscriptRecord>;
+// The verifier's side of a transcript somebody else proves: it hashes NOTHING.  observe appends to the words it will send,
+// challenge returns the next claimed value -- claims: n_claims pairs (absorbed, value) -- and notes how many words were absorbed
+// by then.  A run that asks for more challenges than are claimed is answered with zeros and `short_of` is set: the caller checks
+// next == n_claims && !short_of before it believes anything the run concluded.
+struct ClaimedChallenger {
+    const uint64_t* claims = nullptr;
+    size_t n_claims = 0, next = 0;
+    bool short_of = false;
+    std::vector<uint64_t> words, absorbed;
+    void observe(uint64_t x) { words.push_back(x); }
+    void observe(const uint64_t* x, size_t n) { words.insert(words.end(), x, x + n); }
+    uint64_t challenge() {
+        absorbed.push_back(words.size());
+        if (next >= n_claims) return short_of = true, 0;
+        return claims[2 * next++ + 1];
     }
 };
 }  // namespace glh

@@ -153,7 +153,12 @@ struct Writer : Proof<uint64_t> {
 };
 
 // The transcript: one method per protocol step, in the order both sides call them (plonky2 iop/challenger.rs, starky prover.rs).
-struct Transcript : glh::Challenger {
+// Stated over the challenger C: glh::Challenger hashes (prover and verifier), glh::RecordingChallenger hashes and keeps what
+// TranscriptAir proves of it, glh::ClaimedChallenger hashes nothing and answers with claimed challenges (vx_stark_transcripts_verify).
+template <class C>
+struct TranscriptOf : C {
+    using C::challenge;
+    using C::observe;
     Fx ext() {
         const uint64_t a = challenge(), b = challenge();
         return {a, b};
@@ -182,9 +187,9 @@ struct Transcript : glh::Challenger {
     void final_poly(const Proof<W>& p) { observe(p.final_poly(), 2 * p.s->final_len); }
     // the sponge state the proof of work grinds on: a nonce absorbed at position n_in must make pow_ok
     int grind_state(uint64_t st_out[12]) const {
-        memcpy(st_out, st, sizeof st);
-        memcpy(st_out, in, n_in * 8);
-        return n_in;
+        memcpy(st_out, this->st, sizeof this->st);
+        memcpy(st_out, this->in, this->n_in * 8);
+        return this->n_in;
     }
     bool pow_ok(uint64_t nonce, int pow_bits) {
         observe(nonce);
@@ -193,6 +198,7 @@ struct Transcript : glh::Challenger {
     }
     size_t query_index(size_t N) { return challenge() % N; }
 };
+using Transcript = TranscriptOf<glh::Challenger>;
 
 // Lookup challenges shared by the k tables of a bus: a transcript of every table's public inputs and trace cap, in bus order.
 inline void shared_challenges_n(const uint64_t* const* pubs, const size_t* n_pubs, const uint64_t* const* caps, size_t k, size_t cap_words, uint64_t* out, size_t n_out) {

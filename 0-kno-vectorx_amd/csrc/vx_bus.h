@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "bus_meet.h"
+#include "glh_poseidon.h"
 #include "vx_internal.h"
 
 // the hook of a table that is alone on its bus (the other party is the verifier): the lookup challenges are the shared-challenge
@@ -332,6 +333,31 @@ struct StarkMerkleSide {
 };
 // the blob of such a group: magic, the 7 shape words, the number of tables, one length per table, the proofs of g.job[0 .. n_tables)
 int32_t vx_stark_group_blob(TableGroup& g, int n_tables, uint64_t magic, const StarkOpenings& so, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+
+// ---- STARK-transcripts blob (written by vx_stark_transcripts_prove in vx_transcript_air.hip, read by vx_stark_transcripts_verify in
+// vx_verify.hip): magic, the request -- n chains, then per chain n_obs, n_chal and the n_chal claimed challenges as (absorbed, value)
+// --, the length of the TranscriptAir proof that follows
+static const uint64_t VX_STRN_MAGIC = 0x31304e5254535856ULL;  // "VXSTRN01"
+// One chain of TranscriptAir as claims: the words its transcript absorbs, in order, and every challenge it yields as (words absorbed
+// when it was drawn, value).  The prover takes them from a glh::TranscriptRecord, the verifier from its own replay over the claimed
+// challenger (the words) and from the blob (the challenges).
+struct TranscriptClaim {
+    const uint64_t* words;
+    size_t n_obs;
+    const uint64_t* chal;  // [n_chal][2]
+    size_t n_chal;
+};
+// the statement of a group of transcripts, TranscriptAir's four digest words, prover and verifier alike: hash_n_to_hash_no_pad(n, per
+// chain n_obs and n_chal, per chain the observed words, per chain (absorbed, value) of every challenge)
+void vx_stark_transcripts_statement(const TranscriptClaim* chains, size_t n, uint64_t digest[4]);
+void vx_transcript_public(const uint64_t digest[4], uint64_t pub[4]);
+// The witness of TranscriptAir on the device (vx_transcript_air.hip): chain c is the record of a transcript -- words, block plan,
+// challenges -- made by the ONE challenger (glh::RecordingChallenger).  Uploads the words and the plan, walks every chain
+// (k_transcript_states), writes the trace and, when chal_out is set, hands back the challenges the DEVICE drew, chain after chain.
+int32_t vx_transcript_trace_dev(vx_ctx* ctx, const glh::TranscriptRecord* chains, size_t n_chains, int log_n, uint64_t* trace_d, uint64_t* chal_out);
+// verifies `proof` as vx_stark_verify_ext does over the recording challenger and hands out what its transcript did: the whole proof
+// (the query phase is walked) or its head alone (the indices are derived, no record is read)
+int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen);
 
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {

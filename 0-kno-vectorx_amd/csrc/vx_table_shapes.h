@@ -139,3 +139,11 @@ static inline bool stark_queries_tables(int LN, size_t cm, size_t ca, int a, siz
     }
     return true;
 }
+// TranscriptAir (vx_stark_transcripts_prove): one 32-row block per duplex of every chain, at least 2^5 rows, proven at the next size
+// that has a FRI plan under the configuration (as above; the rows behind the chains are idle).  Above 26: the callers refuse.
+static inline int transcript_log_n(size_t blocks, const vx_stark_config& cfg) {
+    int l = ceil_log2(32 * blocks);
+    if (l < 5) l = 5;
+    while (l <= 26 && !fri_plan_ok(l, cfg)) ++l;
+    return l;
+}

@@ -306,7 +306,8 @@ static int32_t constraints_at_zeta(const AirV& air, const sp::View& v, const uin
 // final polynomial.  The arithmetic of a query is stated once; the modes differ in what happens to an OPENING: walked here,
 // left to the tables of a bus group (with a sink it is recorded as their claim either way: of the path only its position in the
 // proof is noted, no word of it is read), or -- query-free -- skipped with the whole record: the indices alone are derived.
-static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx zeta, const std::vector<Fx>& betas, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
+template <class T>  // T: the transcript, over whichever challenger (stark_proof.h)
+static int32_t fri_queries(const sp::View& v, T& ch, Fx alpha, Fx zeta, const std::vector<Fx>& betas, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
     const sp::Shape& s = *v.s;
     const size_t c = s.c, nq = sp::NQ, N = (size_t)1 << s.LN, n_layers = s.arities.size();
     const Fx zeta_next = fx_scale(zeta, glh::root(s.L));
@@ -390,7 +391,11 @@ static int32_t fri_queries(const sp::View& v, sp::Transcript& ch, Fx alpha, Fx z
     }
     return VX_OK;
 }
-static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+// The verifier, stated once over the transcript `ch` (sp::TranscriptOf<C>): C hashes (every verifier so far), hashes and records
+// (the prover of TranscriptAir), or answers with claimed challenges and hashes nothing (vx_stark_transcripts_verify).  head_ok: a
+// proof that ends at its head is accepted and read query-free whatever `mode` says (a whole proof is read in `mode`).
+template <class T>
+static int32_t stark_verify_over(T& ch, bool head_ok, const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
                                  const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
     if (!cfg || !pr) return VX_ERR_ARG;
     if (!sp::config_ok(*cfg)) return v_fail(VX_ERR_ARG, err, errlen, "stark verify: configuration out of range");
@@ -407,6 +412,7 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
     NEED(shape.LN >= shape.cap_h && shape.LN <= 27 && shape.L >= air.period_log, "degree bits %d out of range for this AIR / cap height", shape.L);
     NEED(!air.exact_log || shape.L == air.period_log, "this AIR has positional columns of period 2^%d: a trace of 2^%d rows is not acceptable", air.period_log, shape.L);
     // every word that is read is canonical -- the whole proof, everything but the siblings, or the head alone
+    if (head_ok && len == shape.o_queries) mode = QueryPhase::QueryFree;
     const bool query_free = mode == QueryPhase::QueryFree;
     if (mode == QueryPhase::Walked)
         for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
@@ -436,7 +442,6 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
         NEED(n_expect_public == shape.n_pub, "public input count differs");
         for (size_t i = 0; i < shape.n_pub; ++i) NEED(v.pub()[i] == expect_public[i], "public input %zu differs", i);
     }
-    sp::Transcript ch;
     ch.trace(v);
     uint64_t chal[8] = {0}, alphas[2];
     if (shape.ca) {  // auxiliary round: lookup challenges after the trace cap, then the published values and the second cap
@@ -474,6 +479,18 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
         for (size_t q = 0; q < 2 * shape.auxpub; ++q) NEED(apub[q] == 0, "stand-alone proof publishes a non-zero bus total");
     if (apub_out) *apub_out = apub;
     if (log_n_out) *log_n_out = shape.L;
+    return VX_OK;
+}
+static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                                 const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
+    sp::Transcript ch;
+    return stark_verify_over(ch, false, cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, mode, sink, err, errlen);
+}
+// ... over the recording challenger (vx_bus.h): what the transcript of a valid proof did, as TranscriptAir's chain
+int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen) {
+    sp::TranscriptOf<glh::RecordingChallenger> ch;
+    VX_TRY(stark_verify_over(ch, true, cfg, proof, len, 0, nullptr, 0, ext_chal, nullptr, nullptr, QueryPhase::Walked, nullptr, err, errlen));
+    *out = static_cast<const glh::TranscriptRecord&>(ch);
     return VX_OK;
 }
 
@@ -572,11 +589,11 @@ static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, s
 
 // An aggregation blob (vx_bus.h: magic, the request words, one length per proof, the proofs) as the tables of its bus group: the
 // blob must be for this request, every proof present and the lengths must add up to the blob.
-static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const char* what, std::initializer_list<uint64_t> request, BusTable* t, size_t n, char* err,
+static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const char* what, const uint64_t* request, size_t n_request, BusTable* t, size_t n, char* err,
                          size_t errlen) {
-    const size_t hdr = 1 + request.size() + n;
+    const size_t hdr = 1 + n_request + n;
     NEED(len > hdr && blob[0] == magic, "bad %s blob", what);
-    NEED(std::equal(request.begin(), request.end(), blob + 1), "blob is for a different request");
+    NEED(std::equal(request, request + n_request, blob + 1), "blob is for a different request");
     size_t body = len - hdr;
     const uint64_t* p = blob + hdr;
     for (size_t i = 0; i < n; ++i) {
@@ -587,6 +604,10 @@ static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const
     }
     NEED(body == 0, "blob lengths are inconsistent");
     return VX_OK;
+}
+static int32_t read_blob(const uint64_t* blob, size_t len, uint64_t magic, const char* what, std::initializer_list<uint64_t> request, BusTable* t, size_t n, char* err,
+                         size_t errlen) {
+    return read_blob(blob, len, magic, what, request.begin(), request.size(), t, n, err, errlen);
 }
 // the root of a tree known by its cap (a table proves paths to ONE root): the two-to-one fold of the cap
 static int32_t cap_root(const uint64_t* cap, int cap_height, const char* what, uint64_t root[4], char* err, size_t errlen) {
@@ -1318,5 +1339,83 @@ int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* pr
     if (proof_head(*cfg, proof, proof_len, 0, &head, nullptr, 0) != VX_OK) return VX_ERR_ARG;
     *head_words = head.shape->o_queries;
     return VX_OK;
+}
+}
+
+extern "C" {
+// The transcript of one proof as TranscriptAir's claims (include/vx.h): one replay of the verifier's code over the recording challenger.
+int32_t vx_stark_transcript_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, size_t* n_obs, uint64_t* obs_out, size_t obs_cap,
+                                   size_t* n_chal, uint64_t* chal_out, size_t chal_cap, char* err, size_t errlen) {
+    if (!cfg || !proof || !n_obs || !n_chal) return VX_ERR_ARG;
+    glh::TranscriptRecord r;
+    VX_TRY(vx_stark_transcript_record(cfg, proof, proof_len, ext_chal, &r, err, errlen));
+    *n_obs = r.words.size(), *n_chal = r.n_chal();
+    if (!obs_out || !chal_out || obs_cap < r.words.size() || chal_cap < r.chal.size())
+        return v_fail(VX_ERR_BUFSZ, err, errlen, "transcript claims: the buffers hold %zu / %zu words, %zu / %zu are needed", obs_out ? obs_cap : (size_t)0, chal_out ? chal_cap : (size_t)0,
+                      r.words.size(), r.chal.size());
+    memcpy(obs_out, r.words.data(), r.words.size() * 8);
+    memcpy(chal_out, r.chal.data(), r.chal.size() * 8);
+    return VX_OK;
+}
+
+// The transcripts of n inner proofs (the prover is vx_transcript_air.hip): ONE TranscriptAir table, alone on its bus.  Every inner proof
+// is verified in the TRANSCRIPT-FREE state: the verifier's own code over the claimed challenger, which hashes nothing -- every
+// challenge is the blob's claim, every absorbed word is noted.  Proof of work (the response has pow_bits leading zero bits), query
+// indices (value mod N), the constraint identity at zeta and, for a whole proof, the walked query phase use the claimed values; a
+// head alone is read query-free.  The claims must be canonical, as many as the shape draws, each drawn after as many words as the
+// blob says.  The verifier is the outside party: per chain it SENDS obs(c, i, w_i) and RECEIVES chal(c, j, A_j, v_j):
+//     total x rows of the table = sum over the chains of  sum_j 1 / D_chal(c, j, A_j, v_j)  -  sum_i 1 / D_obs(c, i, w_i).
+// What forces what: DESIGN.md 5m.  Stand-alone the statement digest hashes the words the transcripts would have hashed.
+int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* const* proofs, const size_t* lens, size_t n,
+                                    const uint64_t* const* ext_chals, char* err, size_t errlen) {
+    if (!cfg || !blob || !proofs || !lens) return VX_ERR_ARG;
+    if (n < 1 || n > (size_t)tsc::MAX_CHAINS) return v_fail(VX_ERR_ARG, err, errlen, "stark transcripts: %zu proofs (1..%d)", n, tsc::MAX_CHAINS);
+    // ---- the request inside the blob: n, then per chain n_obs, n_chal and the claims
+    NEED(len >= 2 && blob[0] == VX_STRN_MAGIC, "bad stark-transcripts blob");
+    NEED(blob[1] == n, "blob is for a different request (%llu chains, %zu proofs)", (unsigned long long)blob[1], n);
+    std::vector<TranscriptClaim> claims(n);
+    size_t at = 2;
+    for (size_t c = 0; c < n; ++c) {
+        NEED(len - at >= 2 && blob[at + 1] <= (len - at - 2) / 2, "blob truncated (the claims of chain %zu)", c);
+        claims[c] = {nullptr, (size_t)blob[at], blob + at + 2, (size_t)blob[at + 1]};
+        at += 2 + 2 * claims[c].n_chal;
+        for (size_t j = 0; j < claims[c].n_chal; ++j) {
+            NEED(claims[c].chal[2 * j + 1] < glh::P, "chain %zu: claimed challenge %zu is not canonical", c, j);
+            NEED(claims[c].chal[2 * j] <= claims[c].n_obs, "chain %zu: challenge %zu claims %llu absorbed words of %zu", c, j, (unsigned long long)claims[c].chal[2 * j], claims[c].n_obs);
+        }
+    }
+    const size_t n_request = at - 1;
+    // ---- every inner proof under its claimed transcript
+    std::vector<sp::TranscriptOf<glh::ClaimedChallenger>> ch(n);
+    for (size_t c = 0; c < n; ++c) {
+        if (!proofs[c]) return VX_ERR_ARG;
+        ch[c].claims = claims[c].chal, ch[c].n_claims = claims[c].n_chal;
+        char inner[200] = "";
+        const int32_t rc = stark_verify_over(ch[c], true, cfg, proofs[c], lens[c], 0, nullptr, 0, ext_chals ? ext_chals[c] : nullptr, nullptr, nullptr, QueryPhase::Walked, nullptr, inner, sizeof inner);
+        // what the claims got wrong comes first: a run on too few claims was answered with zeros
+        NEED(!ch[c].short_of, "chain %zu: the blob claims %zu challenges, the proof's shape draws more", c, claims[c].n_chal);
+        if (rc != VX_OK) return v_fail(rc, err, errlen, "chain %zu: %s", c, inner);
+        NEED(ch[c].next == claims[c].n_chal, "chain %zu: the blob claims %zu challenges, the proof's shape draws %zu", c, claims[c].n_chal, ch[c].next);
+        NEED(ch[c].words.size() == claims[c].n_obs, "chain %zu: the blob claims %zu absorbed words, the proof's shape absorbs %zu", c, claims[c].n_obs, ch[c].words.size());
+        for (size_t j = 0; j < claims[c].n_chal; ++j)
+            NEED(claims[c].chal[2 * j] == ch[c].absorbed[j], "chain %zu: challenge %zu is claimed after %llu absorbed words, the proof's shape draws it after %llu", c, j,
+                 (unsigned long long)claims[c].chal[2 * j], (unsigned long long)ch[c].absorbed[j]);
+        claims[c].words = ch[c].words.data();
+    }
+    // ---- the table, and the verifier as the outside party of its bus
+    BusTable tab[1];
+    VX_TRY(read_blob(blob, len, VX_STRN_MAGIC, "stark-transcripts", blob + 1, n_request, tab, 1, err, errlen));
+    NEED(peek_tables(cfg, tab, 1), "the proof is too short to hold a trace cap");
+    uint64_t stmt[4], pub[tsc::PUB];
+    vx_stark_transcripts_statement(claims.data(), n, stmt);
+    vx_transcript_public(stmt, pub);
+    tab[0].expect(VX_AIR_TRANSCRIPT, pub, tsc::PUB);
+    return verify_bus_group(cfg, tab, 1, "the transcripts the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen, [&](const VBus& bus, BusMessages& m) {
+        for (size_t c = 0; c < n; ++c) {
+            const Fx chain{(uint64_t)c, 0};
+            for (size_t i = 0; i < claims[c].n_obs; ++i) m.send(bus.obs(chain, Fx{(uint64_t)i, 0}, Fx{claims[c].words[i], 0}));
+            for (size_t j = 0; j < claims[c].n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claims[c].chal[2 * j], 0}, Fx{claims[c].chal[2 * j + 1], 0}));
+        }
+    });
 }
 }

@@ -37,6 +37,7 @@ SYMBOLS = [
     "vx_fri_combine_fold_proof_bound", "vx_fri_combine_fold_prove", "vx_fri_combine_fold_verify",
     "vx_stark_merkle_claims", "vx_merkle_paths_air_trace", "vx_leaf_sponge_rows_air_trace", "vx_stark_openings_proof_bound", "vx_stark_openings_prove", "vx_stark_openings_verify",
     "vx_leaf_noop_air_trace", "vx_stark_queries_proof_bound", "vx_stark_queries_prove", "vx_stark_queries_verify", "vx_stark_proof_head_words",
+    "vx_transcript_air_trace", "vx_stark_transcript_claims", "vx_stark_transcripts_proof_bound", "vx_stark_transcripts_prove", "vx_stark_transcripts_verify",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -55,6 +56,7 @@ VX_AIR_MERKLE_OPEN_SET, VX_MERKLE_OPEN_SET_AIR_COLS, VX_MERKLE_OPEN_SET_AIR_AUX_
 VX_AIR_LEAF_SPONGE_SET, VX_LEAF_SPONGE_SET_AIR_COLS, VX_LEAF_SPONGE_SET_AIR_AUX_COLS = 20, 67, 12
 VX_AIR_FRI_COMBINE, VX_FRI_COMBINE_AIR_COLS, VX_FRI_COMBINE_AIR_AUX_COLS = 21, 28, 4
 VX_AIR_LEAF_NOOP, VX_LEAF_NOOP_AIR_COLS, VX_LEAF_NOOP_AIR_AUX_COLS = 22, 11, 8
+VX_AIR_TRANSCRIPT, VX_TRANSCRIPT_AIR_COLS, VX_TRANSCRIPT_AIR_AUX_COLS, VX_TRANSCRIPT_MAX_CHAINS = 23, 93, 18, 64
 
 
 class JustificationStruct(C.Structure):
@@ -214,6 +216,11 @@ def load_library():
         "vx_stark_proof_head_words": [C.POINTER(StarkConfig), vp, sz, C.POINTER(sz)],
         "vx_stark_queries_prove": [vp, C.POINTER(StarkConfig), vp, sz, vp, vp, sz, C.POINTER(sz)],
         "vx_stark_queries_verify": [C.POINTER(StarkConfig), vp, sz, vp, sz, C.c_int, vp, sz, vp, C.c_char_p, sz],
+        "vx_transcript_air_trace": [vp, sz, vp, vp, vp, sz, C.c_int, vp, vp, vp],
+        "vx_stark_transcript_claims": [C.POINTER(StarkConfig), vp, sz, vp, C.POINTER(sz), vp, sz, C.POINTER(sz), vp, sz, C.c_char_p, sz],
+        "vx_stark_transcripts_proof_bound": [C.POINTER(StarkConfig), vp, vp, sz, vp, C.POINTER(sz)],
+        "vx_stark_transcripts_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, vp, vp, sz, C.POINTER(sz)],
+        "vx_stark_transcripts_verify": [C.POINTER(StarkConfig), vp, sz, vp, vp, sz, vp, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -544,6 +551,49 @@ def stark_queries_verify(blob, proof, cfg=None, expect_air=0, expect_public=None
     Raises VxError with the reason."""
     b, pr, pub = _words(blob), _words(proof), _words(expect_public)
     _host_verify("vx_stark_queries_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
+
+
+class _ProofList:
+    """n proofs (and their optional external lookup challenges) as the pointer arrays the transcripts entry points take; the arrays
+    they point into are kept alive here"""
+
+    def __init__(self, proofs, ext_chals=None):
+        self.proofs = [np.ascontiguousarray(p, dtype=np.uint64) for p in proofs]
+        ext = list(ext_chals) if ext_chals is not None else [None] * len(self.proofs)
+        if len(ext) != len(self.proofs):
+            raise ValueError("one entry of ext_chals (None: drawn challenges) for every proof")
+        self.ext = [_words(e) for e in ext]
+        self.n = len(self.proofs)
+        self.ptrs = (C.c_void_p * max(self.n, 1))(*[p.ctypes.data for p in self.proofs])
+        self.lens = (C.c_size_t * max(self.n, 1))(*[p.size for p in self.proofs])
+        self.exts = (C.c_void_p * max(self.n, 1))(*[None if e is None else e.ctypes.data for e in self.ext])
+
+
+def stark_transcript_claims(proof, cfg=None, ext_chal=None):
+    """The Fiat-Shamir transcript of a vx_stark_prove proof (whole, or its head alone) as TranscriptAir's claims, from one replay of
+    the verifier's code over a recording challenger (no GPU needed) -> (the absorbed words, the challenges [n][2] as (words absorbed
+    when it was drawn, value)).  Raises VxError with the reason when the proof is refused."""
+    L = load_library()
+    cfg = cfg or default_stark_config()
+    pr, ch = _words(proof), _words(ext_chal)
+    n_obs, n_chal, err = C.c_size_t(0), C.c_size_t(0), C.create_string_buffer(256)
+    obs, chal = np.zeros(1, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    for _ in range(2):  # the first call sizes the arrays (VX_ERR_BUFSZ with both counts set)
+        rc = L.vx_stark_transcript_claims(C.byref(cfg), _ptr(pr), pr.size, None if ch is None else _ptr(ch), C.byref(n_obs), _ptr(obs), obs.size, C.byref(n_chal), _ptr(chal), chal.size, err, 256)
+        if rc != -4:
+            break
+        obs, chal = np.zeros(max(n_obs.value, 1), dtype=np.uint64), np.zeros(max(2 * n_chal.value, 2), dtype=np.uint64)
+    if rc != 0:
+        raise VxError(rc, err.value.decode())
+    return obs[: n_obs.value], chal[: 2 * n_chal.value].reshape(-1, 2)
+
+
+def stark_transcripts_verify(blob, proofs, cfg=None, ext_chals=None):
+    """Host-side check of a vx_stark_transcripts_prove blob together with the inner proofs it belongs to (each whole, or its head
+    alone): every proof is verified with its transcript answered from the blob's claims -- no Poseidon permutation runs for an inner
+    transcript -- and the TranscriptAir table proves the claims.  Raises VxError with the reason; it names the chain."""
+    b, pl = _words(blob), _ProofList(proofs, ext_chals)
+    _host_verify("vx_stark_transcripts_verify", cfg, b, b.size, pl.ptrs, pl.lens, pl.n, pl.exts)
 
 
 FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
@@ -997,6 +1047,33 @@ class Context:
         return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_queries_proof_bound(c, _ptr(pr), pr.size, need),
                                 "stark queries: not a proof of a known AIR under this configuration, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)",
                                 lambda c, o, need: self.L.vx_stark_queries_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
+
+    def transcript_air_trace(self, ops, words, log_n, out=None):
+        """The witness of TranscriptAir: chain c has the run lengths ops[c] = [observe count, challenge count, observe count, ...] and
+        absorbs words[c] in order -> (Buffer [93][2^log_n], the 4 public inputs: the statement digest, the challenges the device drew
+        per chain)."""
+        if len(ops) != len(words):
+            raise ValueError("one list of words for every chain")
+        n_ops = (C.c_size_t * max(len(ops), 1))(*[len(o) for o in ops])
+        op = np.ascontiguousarray([int(v) for o in ops for v in o] + [0], dtype=np.uint64)
+        wd = np.ascontiguousarray([int(v) for w in words for v in w] + [0], dtype=np.uint64)
+        drawn = [sum(int(v) for v in o[1::2]) for o in ops]
+        chal = np.zeros(sum(drawn) + 1, dtype=np.uint64)
+        out = out or self.alloc(VX_TRANSCRIPT_AIR_COLS << log_n)
+        pub = np.zeros(4, dtype=np.uint64)
+        self._ck(self.L.vx_transcript_air_trace(self.h, len(ops), n_ops, _ptr(op), _ptr(wd), wd.size - 1, log_n, out.h, _ptr(pub), _ptr(chal)))
+        cut = np.cumsum([0] + drawn)
+        return out, pub, [chal[cut[c]: cut[c + 1]].copy() for c in range(len(ops))]
+
+    def stark_transcripts_prove(self, proofs, cfg=None, ext_chals=None, out=None):
+        """Proves the Fiat-Shamir transcripts of the vx_stark_prove proofs `proofs` (each whole, or its head alone) in one TranscriptAir
+        table -> blob words (lib.stark_transcripts_verify checks blob and proofs together).  ext_chals: per proof the external lookup
+        challenges it was made under, or None.  Every proof is verified natively first: VxError(VX_ERR_STATEMENT) names the proof.
+        out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        pl = _ProofList(proofs, ext_chals)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_transcripts_proof_bound(c, pl.ptrs, pl.lens, pl.n, pl.exts, need),
+                                "stark transcripts: 1..64 proofs of known AIRs under this configuration, every one acceptable, in a table of at most 2^26 rows",
+                                lambda c, o, need: self.L.vx_stark_transcripts_prove(self.h, c, pl.ptrs, pl.lens, pl.n, pl.exts, _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

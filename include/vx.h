@@ -169,7 +169,8 @@ typedef struct vx_stark_config {
  * 18 (VX_AIR_FRI_FOLD) proves the FRI fold chain of every query: the third one, see vx_fri_fold_prove.
  * 19 (VX_AIR_MERKLE_OPEN_SET) / 20 (VX_AIR_LEAF_SPONGE_SET) are 16 / 17 for several trees in one table: see vx_fri_queries_prove.
  * 21 (VX_AIR_FRI_COMBINE) proves the FRI combination of every query, the value the fold chain starts from: see vx_fri_combine_prove.
- * 22 (VX_AIR_LEAF_NOOP) turns the openings of leaves of at most 4 words, which are their own digest, into row words: see LeafNoopAir. */
+ * 22 (VX_AIR_LEAF_NOOP) turns the openings of leaves of at most 4 words, which are their own digest, into row words: see LeafNoopAir.
+ * 23 (VX_AIR_TRANSCRIPT) proves the Fiat-Shamir transcripts of up to 64 inner proofs: see vx_stark_transcripts_prove. */
 enum { VX_AIR_FIBONACCI = 1, VX_AIR_MIX = 2, VX_AIR_LOOKUP = 5 };
 int32_t vx_stark_default_config(vx_stark_config* cfg);
 /* Run-time AIR descriptor (SURVEY 8b `vx_air_desc`): the constraint system of a starky-style AIR as a straight-line program over a
@@ -527,13 +528,50 @@ int32_t vx_leaf_noop_air_trace(vx_ctx* ctx, const uint64_t* tree_of, const uint6
  *   query one exponentiation and one Horner evaluation remain; the query records (over 90 % of a proof) are dead weight.
  * vx_stark_proof_head_words: where the query records of a proof start -- the length of the head vx_stark_queries_verify accepts --
  *   from the proof's header and the configuration alone; nothing is verified.
- * STILL OUTSIDE: the transcript, the constraint identity at zeta and the final-polynomial evaluation. */
+ * STILL OUTSIDE: the transcript (proven on a bus of its own by vx_stark_transcripts_prove below; joining the two groups is not built),
+ * the constraint identity at zeta and the final-polynomial evaluation. */
 int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* head_words);
 int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words);
 int32_t vx_stark_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t* blob_out, size_t blob_cap,
                                size_t* blob_len);
 int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* proof, size_t proof_len, int expect_air,
                                 const uint64_t* expect_public, size_t n_public, const uint64_t* ext_chal, char* err, size_t errlen);
+/* ---- TranscriptAir: the Fiat-Shamir transcripts of 1..64 inner proofs -- chains -- in one STARK table (AIR id VX_AIR_TRANSCRIPT;
+ * compiled: csrc/air_transcript.cuh): the duplex challenger of plonky2 v0.2.0 iop/challenger.rs, one 32-row PoseidonAir
+ * block per duplex.  A block RECEIVES obs(chain, position, word) for every word it absorbs and SENDS chal(chain, ordinal, absorbed,
+ * value) for every challenge popped from its output; `absorbed` = the words the chain had absorbed when the challenge was drawn.
+ * Public inputs: four statement-digest words the table does not constrain.  Any log_n >= 5; idle blocks permute the zero state.
+ * vx_transcript_air_trace: the witness on its own (test surface).  Chain c has n_ops[c] run lengths in `ops` (the chains' lists one
+ *   after the other): observe count, challenge count, observe count, ... starting with an observe count, zero allowed; `words`: the
+ *   observed words of all chains in order (n_words = the sum of the observe counts).  trace_out: [VX_TRANSCRIPT_AIR_COLS][2^log_n];
+ *   public_out: the statement digest below; chal_out: one word per challenge drawn, chain after chain (the caller sizes it by the sum
+ *   of the challenge counts).  VX_ERR_ARG: a non-canonical word, no chain or more than 64, an empty chain, a chain whose first
+ *   operation draws from an empty sponge, a table that is too small ("do not fit").
+ * vx_stark_transcript_claims (host only): replays one vx_stark_prove proof -- the whole proof, or its head alone as
+ *   vx_stark_proof_head_words cuts it -- with the verifier's own code over a recording challenger and hands out the words its
+ *   transcript absorbs (obs_out) and every challenge as (absorbed, value) (chal_out: 2 words each).  ext_chal as vx_stark_verify_ext.
+ *   *n_obs / *n_chal are always set on VX_OK and VX_ERR_BUFSZ (a buffer too small; the buffers may be NULL to ask for the sizes).
+ * vx_stark_transcripts_prove: proofs[i] (lens[i] words; ext_chals may be NULL, ext_chals[i] NULL: drawn lookup challenges) is chain i.
+ *   Every inner proof is verified natively first: a refusal is VX_ERR_STATEMENT naming the proof, nothing is proven.  One
+ *   TranscriptAir table at the smallest log_n >= 5 that holds the chains and has a FRI plan; VX_ERR_ARG above 2^26 rows or 64 proofs.
+ *   Statement digest: hash_n_to_hash_no_pad(n, per chain n_obs and n_chal, per chain the observed words, per chain (absorbed, value)
+ *   of every challenge).  Blob: "VXSTRN01", n, per chain n_obs, n_chal and the claimed challenges as (absorbed, value), the length
+ *   of the table's proof, the proof.
+ * vx_stark_transcripts_verify (host only): verifies every inner proof with its transcript answered from the blob's claims -- NO
+ *   Poseidon permutation runs for an inner transcript; proof of work, query indices, the constraint identity at zeta and (for a whole
+ *   proof) the walked query phase use the claimed values; a head alone is read query-free.  Then it is the outside party of the bus:
+ *   per chain it SENDS obs(c, i, w_i) for the words it absorbed and RECEIVES chal(c, j, A_j, v_j).  Error texts name the chain.
+ * Stand-alone this does not lower the verifier's permutation count: the statement digest hashes the same words. */
+enum { VX_AIR_TRANSCRIPT = 23, VX_TRANSCRIPT_AIR_COLS = 93, VX_TRANSCRIPT_AIR_AUX_COLS = 18, VX_TRANSCRIPT_MAX_CHAINS = 64 };
+int32_t vx_transcript_air_trace(vx_ctx* ctx, size_t n_chains, const size_t* n_ops, const uint64_t* ops, const uint64_t* words, size_t n_words, int log_n, vx_buf* trace_out,
+                                uint64_t public_out[4], uint64_t* chal_out);
+int32_t vx_stark_transcript_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, size_t* n_obs, uint64_t* obs_out, size_t obs_cap,
+                                   size_t* n_chal, uint64_t* chal_out, size_t chal_cap, char* err, size_t errlen);
+int32_t vx_stark_transcripts_proof_bound(const vx_stark_config* cfg, const uint64_t* const* proofs, const size_t* lens, size_t n, const uint64_t* const* ext_chals, size_t* n_words);
+int32_t vx_stark_transcripts_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* const* proofs, const size_t* lens, size_t n, const uint64_t* const* ext_chals,
+                                   uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
+int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* const* proofs, const size_t* lens, size_t n,
+                                    const uint64_t* const* ext_chals, char* err, size_t errlen);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */
