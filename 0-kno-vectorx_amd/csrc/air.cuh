@@ -226,6 +226,46 @@ struct RowViewN {  // column-major LDE, rows i[0..R) of it
     }
 };
 
+// ---- the bus of a table whose helpers hold two messages each (the Merkle-opening, leaf, FRI and transcript tables) ----
+// Such an AIR states its messages ONCE, for its constraints (bus_constraints below) and for its witness (bus_aux.cuh):
+//   N_HELP     helpers: helper e, an extension cell at COLS + 2 e, holds m_a / D_a + m_b / D_b of message pair e; the running
+//              sum z sits behind them at COLS + 2 N_HELP and the table publishes total / rows (AUX = 2 N_HELP + 2, AUXPUB = 1)
+//   BUS_ROWS   rows that share one set of helpers: 1, or 32 (a Poseidon block)
+//   BUS_STEP   the periodic column on whose rows the sum advances (a block's first row), -1: on every row
+//   BUS_BLOCK  lanes per workgroup of the witness kernel
+//   template <class F, class Row, class Sink> static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s)
+//              walks the pairs in helper order and hands pair e to s.put(m_a, D_a, m_b, D_b), or to s.pair(m, D_a, D_b) where
+//              both messages share a multiplicity.  A multiplicity is a signed field value: sent m, received zero - m.  Only
+//              + - * and F::from, so it instantiates for every field type of this file.  A loop over pairs is marked
+//              `#pragma unroll Sink::UNROLL`: rolled in the quotient kernel, unrolled in the witness kernel (arrays in registers)
+template <class F, class Row, class Cn>
+struct BusConstraints {  // the sink of eval: h D_a D_b - m_a D_b - m_b D_a per pair, in helper order
+    static constexpr int UNROLL = 1;
+    const Row& loc;
+    Cn& c;
+    int at;  // the column of the next helper
+    X2<F> hsum;
+    VX_HD X2<F> helper() {
+        const X2<F> h{loc[at], loc[at + 1]};
+        at += 2, hsum = hsum + h;
+        return h;
+    }
+    VX_HD void put(const F& ma, const X2<F>& da, const F& mb, const X2<F>& db) { c.constraint_x2(helper() * da * db - db * ma - da * mb); }
+    VX_HD void pair(const F& m, const X2<F>& da, const X2<F>& db) { c.constraint_x2(helper() * da * db - (da + db) * m); }
+};
+// the bus block of such an AIR's eval: the N_HELP helper constraints, then z' - z - sum h [* step] + total / rows
+template <class Air, class F, class Row, class Cn>
+VX_HD void bus_constraints(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
+    static_assert(Air::AUX == 2 * Air::N_HELP + 2 && Air::AUXPUB == 1 && Air::CHAL == 4, "air.cuh: helpers, then one running sum");
+    constexpr int Z = Air::COLS + 2 * Air::N_HELP;
+    const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
+    BusConstraints<F, Row, Cn> s{loc, c, Air::COLS, X2<F>{F::from(0), F::from(0)}};
+    Air::template messages<F>(loc, pub, bus, s);
+    const X2<F> z{loc[Z], loc[Z + 1]}, zn{nxt[Z], nxt[Z + 1]}, total{apub[0], apub[1]};
+    if constexpr (Air::BUS_STEP >= 0) c.constraint_x2(zn - z - s.hsum * per[Air::BUS_STEP] + total);
+    else c.constraint_x2(zn - z - s.hsum + total);
+}
+
 // ---- AIR 1: Fibonacci (the canonical starky example; used to pin the generic prover) ----
 // columns (x0, x1); public inputs (x0[0], x1[0], x1[n-1]); next.x0 = x1, next.x1 = x0 + x1.
 struct FibAir {

@@ -3,8 +3,9 @@
 //     D = beta + t0 + gamma t1 + gamma^2 t2 + gamma^3 t3 + gamma^4 tag        (beta, gamma: extension-field challenges)
 // and the tables' published totals cancel when every message sent is received.  What a slot MEANS is a contract between the
 // table that sends a kind and the table that receives it, so each kind is one named function here and both sides -- in `eval`
-// (X = X2<F>: device FpN<R>, host Fx, CountF) and in the witness kernel (X = gl2) -- call that name.  The oracle
-// (oracle/*.py: one fp(tag, tuple)) restates tags and slot orders independently on purpose.
+// (X = X2<F>: device FpN<R>, host Fx, CountF) and in the witness kernel (X = gl2; X2<Fp> in bus_aux.cuh, which reads a table's
+// whole message list from the AIR: air.cuh "the bus of a table ...") -- call that name.  The oracle (oracle/*.py: one
+// fp(tag, tuple)) restates tags and slot orders independently on purpose.
 #pragma once
 #include <type_traits>
 

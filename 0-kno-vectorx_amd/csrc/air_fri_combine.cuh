@@ -47,6 +47,16 @@ struct FriCombineAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
+    static constexpr int N_HELP = fca::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256;
+
+    // a row word received on an absorb row, the entry of the fold chain sent on the last row
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace fca;
+        const F ta = loc[TA], tq = loc[TQ], idx = loc[IDX];
+        s.put(F::from(0) - (loc[TM] + ta + tq), bus.row_of(pub[PUB_TREE0] + ta + tq + tq, idx, loc[POS], loc[W]), loc[LAST], bus.fri(idx, loc[EV], loc[EV + 1], bus::K<0>{}));
+    }
+
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F*, const F* pub, const F* chal, const F* apub, Cn& c) {
         using namespace fca;
@@ -123,15 +133,7 @@ struct FriCombineAir {
             c.constraint_x2((d1 * xzn - one) * last);
             c.constraint_x2((ev - alphac * (s - y0) * d0 - (s1 - y1) * d1) * last);
         }
-        // ---- 9. the bus: a row word received on an absorb row, the entry of the fold chain sent on the last row
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F tree = pub[PUB_TREE0] + ta + tq + tq;
-            const X2<F> dr = bus.row_of(tree, idx, pos, w), df = bus.fri(idx, ev.a, ev.b, bus::K<0>{});
-            const X2<F> h{loc[COLS], loc[COLS + 1]};
-            c.constraint_x2(h * dr * df + df * abs - dr * last);
-            const X2<F> z{loc[COLS + 2], loc[COLS + 3]}, zn{nxt[COLS + 2], nxt[COLS + 3]};
-            c.constraint_x2(zn - z - h + X2<F>{apub[0], apub[1]});
-        }
+        // ---- 9. the bus (messages above): no row does both, so one helper carries both messages
+        bus_constraints<FriCombineAir>(loc, nxt, (const F*)nullptr, pub, chal, apub, c);
     }
 };

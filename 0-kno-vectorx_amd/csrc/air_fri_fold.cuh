@@ -76,6 +76,19 @@ struct FriFoldAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
+    static constexpr int N_HELP = ffa::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 64;
+
+    // 32 leaf words received on a fold row; the entry received on the first row, the exit sent on the first bit row
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace ffa;
+        const F zero = F::from(0), tree = pub[PUB_TREE0] + loc[CNT], q = loc[Q], idx = loc[IDX], received = zero - loc[FOLD];
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 16; ++e)
+            s.pair(received, bus.row_of(tree, q, F::from((uint64_t)(2 * e)), loc[LEAF + 2 * e]), bus.row_of(tree, q, F::from((uint64_t)(2 * e + 1)), loc[LEAF + 2 * e + 1]));
+        s.put(zero - loc[FIRST], bus.fri(idx, loc[EV], loc[EV + 1], bus::K<0>{}), loc[FBIT], bus.fri(idx, loc[EV], loc[EV + 1], bus::K<1>{}));
+    }
+
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F*, const F* pub, const F* chal, const F* apub, Cn& c) {
         using namespace ffa;
@@ -177,27 +190,7 @@ struct FriFoldAir {
                 c.constraint_x2(X2<F>{loc[out], loc[out + 1]} - (u + w) * F::from(HALF) - bj * (u - w) * (sj * F::from(T.fc[j][k])));
             }
         }
-        // ---- 10. the bus: 32 leaf words received on a fold row, the entry received on the first row, the exit sent on the
-        // first bit row; two messages per helper, the running sum advances on every row
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F tree = pub[PUB_TREE0] + cnt;
-            X2<F> hsum{zero, zero};
-#pragma unroll 1
-            for (int e = 0; e < 16; ++e) {
-                const X2<F> da = bus.row_of(tree, q, F::from((uint64_t)(2 * e)), loc[LEAF + 2 * e]), db = bus.row_of(tree, q, F::from((uint64_t)(2 * e + 1)), loc[LEAF + 2 * e + 1]);
-                const X2<F> h{loc[COLS + 2 * e], loc[COLS + 2 * e + 1]};
-                c.constraint_x2(h * da * db + (da + db) * fold);
-                hsum = hsum + h;
-            }
-            {
-                const X2<F> de = bus.fri(idx, loc[EV], loc[EV + 1], bus::K<0>{}), dx = bus.fri(idx, loc[EV], loc[EV + 1], bus::K<1>{});
-                const X2<F> h{loc[COLS + 32], loc[COLS + 33]};
-                c.constraint_x2(h * de * dx - de * loc[FBIT] + dx * first);
-                hsum = hsum + h;
-            }
-            const X2<F> z{loc[COLS + 34], loc[COLS + 35]}, zn{nxt[COLS + 34], nxt[COLS + 35]};
-            c.constraint_x2(zn - z - hsum + X2<F>{apub[0], apub[1]});
-        }
+        // ---- 10. the bus (messages above): two messages per helper, the running sum advances on every row
+        bus_constraints<FriFoldAir>(loc, nxt, (const F*)nullptr, pub, chal, apub, c);
     }
 };

@@ -36,6 +36,19 @@ struct LeafNoopAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
+    static constexpr int N_HELP = lnp::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256;
+
+    // the two halves of the digest received, the words that exist sent
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace lnp;
+        const F tree = loc[TREE], idx = loc[IDX];
+        s.pair(F::from(0) - loc[ACT], bus.open_of(tree, idx, loc[W], loc[W + 1], bus::K<0>{}), bus.open_of(tree, idx, loc[W + 2], loc[W + 3], bus::K<1>{}));
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            s.put(loc[E + 2 * e], bus.row_of(tree, idx, F::from((uint64_t)(2 * e)), loc[W + 2 * e]), loc[E + 2 * e + 1], bus.row_of(tree, idx, F::from((uint64_t)(2 * e + 1)), loc[W + 2 * e + 1]));
+    }
+
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F*, const F*, const F* chal, const F* apub, Cn& c) {
         using namespace lnp;
@@ -50,23 +63,7 @@ struct LeafNoopAir {
         for (int j = 0; j < 3; ++j) c.constraint(loc[E + j + 1] * (one - loc[E + j]));
 #pragma unroll
         for (int j = 0; j < 4; ++j) c.constraint((one - loc[E + j]) * loc[W + j]);
-        // ---- 3. the bus: the two halves of the digest received, the words that exist sent
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F tree = loc[TREE], idx = loc[IDX];
-            const X2<F> dlo = bus.open_of(tree, idx, loc[W], loc[W + 1], bus::K<0>{}), dhi = bus.open_of(tree, idx, loc[W + 2], loc[W + 3], bus::K<1>{});
-            const X2<F> h0{loc[COLS], loc[COLS + 1]};
-            c.constraint_x2(h0 * dlo * dhi + (dlo + dhi) * act);
-            X2<F> hsum = h0;
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const X2<F> da = bus.row_of(tree, idx, F::from((uint64_t)(2 * e)), loc[W + 2 * e]), db = bus.row_of(tree, idx, F::from((uint64_t)(2 * e + 1)), loc[W + 2 * e + 1]);
-                const X2<F> h{loc[COLS + 2 + 2 * e], loc[COLS + 3 + 2 * e]};
-                c.constraint_x2(h * da * db - db * loc[E + 2 * e] - da * loc[E + 2 * e + 1]);
-                hsum = hsum + h;
-            }
-            const X2<F> z{loc[COLS + 6], loc[COLS + 7]}, zn{nxt[COLS + 6], nxt[COLS + 7]};
-            c.constraint_x2(zn - z - hsum + X2<F>{apub[0], apub[1]});
-        }
+        // ---- 3. the bus (messages below)
+        bus_constraints<LeafNoopAir>(loc, nxt, (const F*)nullptr, (const F*)nullptr, chal, apub, c);
     }
 };

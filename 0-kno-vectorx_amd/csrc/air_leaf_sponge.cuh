@@ -53,10 +53,32 @@ inline void periodic_values(std::vector<uint64_t>& v) {
 }
 
 
-// the constraints of both AIRs: SET = false is LeafSpongeAir, SET = true LeafSpongeSetAir
-template <bool SET, class F, class Row, class Cn>
+// the messages of both AIRs (air.cuh): eight row words sent, the two halves of the digest received; the set's messages name their tree
+template <bool SET, class F, class Row, class Sink>
+VX_HD void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    const F idx = loc[IDX], last = loc[LASTB], cont = loc[ACT] - last, pos8 = loc[POS] * F::from(8);
+    auto d_row = [&](const F& position, const F& word) {
+        if constexpr (SET) return bus.row_of(loc[TREE], idx, position, word);
+        else return bus.row(idx, position, word);
+    };
+    auto d_open = [&](const F& da, const F& db, auto half) {
+        if constexpr (SET) return bus.open_of(loc[TREE], idx, da, db, half);
+        else return bus.open(idx, da, db, half);
+    };
+#pragma unroll Sink::UNROLL
+    for (int e = 0; e < 4; ++e) {  // multiplicity ACT - LASTB (1 - w_i): the words a tail keeps are not sent
+        const F ma = cont + last * pub[PUB_W + 2 * e], mb = cont + last * pub[PUB_W + 2 * e + 1];
+        const F pa = pos8 + F::from((uint64_t)(2 * e)), pb = pos8 + F::from((uint64_t)(2 * e + 1));
+        s.put(ma, d_row(pa, loc[MSG + 2 * e]), mb, d_row(pb, loc[MSG + 2 * e + 1]));
+    }
+    s.pair(F::from(0) - last, d_open(loc[DIG], loc[DIG + 1], bus::K<0>{}), d_open(loc[DIG + 2], loc[DIG + 3], bus::K<1>{}));
+}
+
+// the constraints of both AIRs: Air::SET = false is LeafSpongeAir, true LeafSpongeSetAir
+template <class Air, class F, class Row, class Cn>
 VX_HD void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-    constexpr int NC = SET ? SET_COLS : COLS;  // the auxiliary columns follow the main ones
+    constexpr bool SET = Air::SET;
+    constexpr int NC = Air::COLS;
     const F one = F::from(1), full = per[P_FULL], round = per[P_ROUND], out = per[P_OUT], spare = per[P_SPARE], first = per[P_FIRST];
     // ---- 1. the permutation (PoseidonAir, as in MerkleOpenAir): x = s + round constant, a = x^2, b = a^2, t = x a b; y = t in
     // full rounds and for word 0, x otherwise; next s = MDS y on the round rows, next s = s on the output row
@@ -125,38 +147,8 @@ VX_HD void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, cons
 #pragma unroll 1
         for (int i = 0; i < 8; ++i) c.constraint(fl * (loc[MSG + i] * (one - pub[PUB_W + i])));
     }
-    // ---- 7. the bus: eight row words sent, the two halves of the digest received; two messages per helper, the running sum
-    // advances once per block
-    {
-        const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-        const F zero = F::from(0), pos8 = pos * F::from(8);
-        auto d_row = [&](const F& position, const F& word) {  // the set's messages name their tree
-            if constexpr (SET) return bus.row_of(loc[TREE], idx, position, word);
-            else return bus.row(idx, position, word);
-        };
-        auto d_open = [&](const F& da, const F& db, auto half) {
-            if constexpr (SET) return bus.open_of(loc[TREE], idx, da, db, half);
-            else return bus.open(idx, da, db, half);
-        };
-        X2<F> hsum{zero, zero};
-#pragma unroll 1
-        for (int e = 0; e < 4; ++e) {
-            const F ma = cont + last * pub[PUB_W + 2 * e], mb = cont + last * pub[PUB_W + 2 * e + 1];
-            const F pa = pos8 + F::from((uint64_t)(2 * e)), pb = pos8 + F::from((uint64_t)(2 * e + 1));
-            const X2<F> da = d_row(pa, loc[MSG + 2 * e]), db = d_row(pb, loc[MSG + 2 * e + 1]);
-            const X2<F> h{loc[NC + 2 * e], loc[NC + 2 * e + 1]};
-            c.constraint_x2(h * da * db - db * ma - da * mb);
-            hsum = hsum + h;
-        }
-        {
-            const X2<F> dlo = d_open(loc[DIG], loc[DIG + 1], bus::K<0>{}), dhi = d_open(loc[DIG + 2], loc[DIG + 3], bus::K<1>{});
-            const X2<F> h{loc[NC + 8], loc[NC + 9]};
-            c.constraint_x2(h * dlo * dhi + (dlo + dhi) * last);
-            hsum = hsum + h;
-        }
-        const X2<F> z{loc[NC + 10], loc[NC + 11]}, zn{nxt[NC + 10], nxt[NC + 11]};
-        c.constraint_x2(zn - z - hsum * first + X2<F>{apub[0], apub[1]});
-    }
+    // ---- 7. the bus (messages above): two messages per helper, the running sum advances once per block
+    bus_constraints<Air>(loc, nxt, per, pub, chal, apub, c);
 }
 }  // namespace lsp
 
@@ -167,7 +159,13 @@ struct LeafSpongeAir {
     static void periodic_values(std::vector<uint64_t>& v) { lsp::periodic_values(v); }
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-        lsp::eval<false>(loc, nxt, per, pub, chal, apub, c);
+        lsp::eval<LeafSpongeAir>(loc, nxt, per, pub, chal, apub, c);
+    }
+    static constexpr bool SET = false;
+    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64;
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        lsp::messages<SET>(loc, pub, bus, s);
     }
 };
 
@@ -178,6 +176,12 @@ struct LeafSpongeSetAir {
     static void periodic_values(std::vector<uint64_t>& v) { lsp::periodic_values(v); }
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-        lsp::eval<true>(loc, nxt, per, pub, chal, apub, c);
+        lsp::eval<LeafSpongeSetAir>(loc, nxt, per, pub, chal, apub, c);
+    }
+    static constexpr bool SET = true;
+    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64;
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        lsp::messages<SET>(loc, pub, bus, s);
     }
 };

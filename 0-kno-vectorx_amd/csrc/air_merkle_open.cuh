@@ -50,10 +50,24 @@ inline void periodic_values(std::vector<uint64_t>& v) {
 }
 
 
-// the constraints of both AIRs: SET = false is MerkleOpenAir, SET = true MerkleOpenSetAir
-template <bool SET, class F, class Row, class Cn>
+// the messages of both AIRs (air.cuh): the first block of a path sends its opening; the set's END block the root it ended in as well
+template <bool SET, class F, class Row, class Sink>
+VX_HD void messages(const Row& loc, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+    const F r = loc[R];
+    if constexpr (SET) {
+        const F tree = loc[TREE], depth = loc[DEPTH];
+        s.pair(loc[FIRSTB], bus.open_of(tree, r, loc[LEAF], loc[LEAF + 1], bus::K<0>{}), bus.open_of(tree, r, loc[LEAF + 2], loc[LEAF + 3], bus::K<1>{}));
+        s.pair(loc[END], bus.root(tree, loc[ROOT], loc[ROOT + 1], bus::K<0>{}, depth), bus.root(tree, loc[ROOT + 2], loc[ROOT + 3], bus::K<1>{}, depth));
+    } else {
+        s.pair(loc[FIRSTB], bus.open(r, loc[LEAF], loc[LEAF + 1], bus::K<0>{}), bus.open(r, loc[LEAF + 2], loc[LEAF + 3], bus::K<1>{}));
+    }
+}
+
+// the constraints of both AIRs: Air::SET = false is MerkleOpenAir, true MerkleOpenSetAir
+template <class Air, class F, class Row, class Cn>
 VX_HD void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-    constexpr int NC = SET ? SET_COLS : COLS;  // the auxiliary columns follow the main ones
+    constexpr bool SET = Air::SET;
+    constexpr int NC = Air::COLS;
     const F one = F::from(1), full = per[P_FULL], round = per[P_ROUND], out = per[P_OUT], spare = per[P_SPARE], first = per[P_FIRST];
     // ---- 1. the permutation (PoseidonAir): x = s + round constant, a = x^2, b = a^2, t = x a b; y = t in full rounds and for
     // word 0, x otherwise; next s = MDS y on the round rows, next s = s on the output row
@@ -126,25 +140,8 @@ VX_HD void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, cons
 #pragma unroll 1
         for (int i = 0; i < 4; ++i) c.constraint(spare * end * (loc[i] - pub[i]));
     }
-    // ---- 7. the bus: the first block of a path sends its opening (the set: its END block the root it ended in as well); one
-    // helper each, the running sum advances once per block
-    {
-        const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-        if constexpr (SET) {
-            const F tree = loc[TREE];
-            const X2<F> dlo = bus.open_of(tree, r, loc[LEAF], loc[LEAF + 1], bus::K<0>{}), dhi = bus.open_of(tree, r, loc[LEAF + 2], loc[LEAF + 3], bus::K<1>{});
-            const X2<F> rlo = bus.root(tree, loc[ROOT], loc[ROOT + 1], bus::K<0>{}, loc[DEPTH]), rhi = bus.root(tree, loc[ROOT + 2], loc[ROOT + 3], bus::K<1>{}, loc[DEPTH]);
-            const X2<F> h{loc[NC], loc[NC + 1]}, h2{loc[NC + 2], loc[NC + 3]}, z{loc[NC + 4], loc[NC + 5]}, zn{nxt[NC + 4], nxt[NC + 5]};
-            c.constraint_x2(h * dlo * dhi - (dlo + dhi) * loc[FIRSTB]);
-            c.constraint_x2(h2 * rlo * rhi - (rlo + rhi) * end);
-            c.constraint_x2(zn - z - (h + h2) * first + X2<F>{apub[0], apub[1]});
-        } else {
-            const X2<F> dlo = bus.open(r, loc[LEAF], loc[LEAF + 1], bus::K<0>{}), dhi = bus.open(r, loc[LEAF + 2], loc[LEAF + 3], bus::K<1>{});
-            const X2<F> h{loc[COLS], loc[COLS + 1]}, z{loc[COLS + 2], loc[COLS + 3]}, zn{nxt[COLS + 2], nxt[COLS + 3]};
-            c.constraint_x2(h * dlo * dhi - (dlo + dhi) * loc[FIRSTB]);
-            c.constraint_x2(zn - z - h * first + X2<F>{apub[0], apub[1]});
-        }
-    }
+    // ---- 7. the bus (messages above): one helper per message pair, the running sum advances once per block
+    bus_constraints<Air>(loc, nxt, per, pub, chal, apub, c);
 }
 }  // namespace mop
 
@@ -155,7 +152,13 @@ struct MerkleOpenAir {
     static void periodic_values(std::vector<uint64_t>& v) { mop::periodic_values(v); }
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-        mop::eval<false>(loc, nxt, per, pub, chal, apub, c);
+        mop::eval<MerkleOpenAir>(loc, nxt, per, pub, chal, apub, c);
+    }
+    static constexpr bool SET = false;
+    static constexpr int N_HELP = 1, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64;
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        mop::messages<SET>(loc, pub, bus, s);
     }
 };
 
@@ -166,6 +169,12 @@ struct MerkleOpenSetAir {
     static void periodic_values(std::vector<uint64_t>& v) { mop::periodic_values(v); }
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
-        mop::eval<true>(loc, nxt, per, pub, chal, apub, c);
+        mop::eval<MerkleOpenSetAir>(loc, nxt, per, pub, chal, apub, c);
+    }
+    static constexpr bool SET = true;
+    static constexpr int N_HELP = 2, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64;
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        mop::messages<SET>(loc, pub, bus, s);
     }
 };

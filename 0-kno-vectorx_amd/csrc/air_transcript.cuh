@@ -48,6 +48,27 @@ struct TranscriptAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { lsp::periodic_values(v); }
 
+    static constexpr int N_HELP = tsc::N_HELP, BUS_ROWS = 32, BUS_STEP = tsc::P_FIRST, BUS_BLOCK = 64;
+
+    // eight absorbed words received with multiplicity W_i, eight outputs sent with multiplicity Q_i
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace tsc;
+        const F zero = F::from(0), chain = loc[CHAIN], nabs = loc[NABS], nch = loc[NCH];
+        F sw = loc[W];  // (the sum eval has: one expression, one computation)
+#pragma unroll
+        for (int i = 1; i < 8; ++i) sw = sw + loc[W + i];
+        const F absorbed = nabs + sw;
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 4; ++e)
+            s.put(zero - loc[W + 2 * e], bus.obs(chain, nabs + F::from((uint64_t)(2 * e)), loc[MSG + 2 * e]), zero - loc[W + 2 * e + 1],
+                  bus.obs(chain, nabs + F::from((uint64_t)(2 * e + 1)), loc[MSG + 2 * e + 1]));
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 4; ++e)
+            s.put(loc[Q + 2 * e], bus.chal(chain, nch + F::from((uint64_t)(7 - 2 * e)), absorbed, loc[OUT + 2 * e]), loc[Q + 2 * e + 1],
+                  bus.chal(chain, nch + F::from((uint64_t)(6 - 2 * e)), absorbed, loc[OUT + 2 * e + 1]));
+    }
+
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F*, const F* chal, const F* apub, Cn& c) {
         using namespace tsc;
@@ -131,27 +152,8 @@ struct TranscriptAir {
             c.constraint(sc * (nxt[NCH] - nch - sq));
             // a block that absorbs nothing follows one that was squeezed dry
             c.constraint(spare * (nxt[ACT] - nxt[W]) * (one - loc[Q]));
-            // ---- 7. the bus: eight absorbed words received, eight outputs sent; two messages per helper, the running sum advances
-            // once per block
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F zero = F::from(0), absorbed = nabs + sw;
-            X2<F> hsum{zero, zero};
-#pragma unroll 1
-            for (int e = 0; e < 4; ++e) {
-                const X2<F> da = bus.obs(chain, nabs + F::from((uint64_t)(2 * e)), loc[MSG + 2 * e]), db = bus.obs(chain, nabs + F::from((uint64_t)(2 * e + 1)), loc[MSG + 2 * e + 1]);
-                const X2<F> h{loc[COLS + 2 * e], loc[COLS + 2 * e + 1]};
-                c.constraint_x2(h * da * db + db * loc[W + 2 * e] + da * loc[W + 2 * e + 1]);
-                hsum = hsum + h;
-            }
-#pragma unroll 1
-            for (int e = 0; e < 4; ++e) {
-                const X2<F> da = bus.chal(chain, nch + F::from((uint64_t)(7 - 2 * e)), absorbed, loc[OUT + 2 * e]), db = bus.chal(chain, nch + F::from((uint64_t)(6 - 2 * e)), absorbed, loc[OUT + 2 * e + 1]);
-                const X2<F> h{loc[COLS + 8 + 2 * e], loc[COLS + 9 + 2 * e]};
-                c.constraint_x2(h * da * db - db * loc[Q + 2 * e] - da * loc[Q + 2 * e + 1]);
-                hsum = hsum + h;
-            }
-            const X2<F> z{loc[COLS + 16], loc[COLS + 17]}, zn{nxt[COLS + 16], nxt[COLS + 17]};
-            c.constraint_x2(zn - z - hsum * first + X2<F>{apub[0], apub[1]});
         }
+        // ---- 7. the bus (messages above): two messages per helper, the running sum advances once per block
+        bus_constraints<TranscriptAir>(loc, nxt, per, (const F*)nullptr, chal, apub, c);
     }
 };

@@ -247,7 +247,7 @@ __device__ __forceinline__ gl2 gl2_inv(gl2 x) {
     return {gl_mul(x.a, ni), gl_mul(gl_neg(x.b), ni)};
 }
 // h[e] = num[e] / den[e] for e < N with ONE inversion (Montgomery batch: the products of den[0..e], their inverse, walked back).
-// The helpers of a row or block of a logUp witness (k_leaf_sponge_aux, k_fri_fold_aux); every den[e] is non-zero.
+// The helpers of a row or block of a logUp witness (k_bus_aux, bus_aux.cuh); every den[e] is non-zero.
 template <int N>
 __device__ __forceinline__ void gl2_batch_div(const gl2 (&num)[N], const gl2 (&den)[N], gl2 (&h)[N]) {
     gl2 pre[N];

@@ -9,8 +9,8 @@
 //                        stores it, and the last row's lane computes D0, D1 and EV.  A bit row recomputes its accumulator from
 //                        (index, bit position).  Blocks behind the queries zero the idle rows.  The table is store-bound (28
 //                        columns) and small; nothing else is tuned
-//   k_fri_combine_aux    one lane per row: ONE extension inversion for the row's helper, which is also the row's running-sum
-//                        increment (vx_bus_close_dev scans it)
+// The auxiliary columns are bus_aux.cuh's, from the AIR's own message list: one lane per row; the one helper is also the row's
+// running-sum increment.
 // vx_fri_combine_prove combines every query natively on the host first and refuses a claimed ev_0 that differs, or x = zeta, with
 // VX_ERR_STATEMENT before anything is proven.
 // vx_fri_combine_fold_prove: FriCombineAir + FriFoldAir on one bus, TAG_FRI end 0 closing between them.
@@ -19,6 +19,7 @@
 
 #include "air_fri_combine.cuh"
 #include "air_fri_fold.cuh"
+#include "bus_aux.cuh"
 #include "stark_proof.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
@@ -114,22 +115,6 @@ __global__ __launch_bounds__(BLOCK) void k_fri_combine_trace(CombArgs a) {
         }
         put(S1, s1.a), put(S1 + 1, s1.b), put(D0, d0.a), put(D0 + 1, d0.b), put(D1, d1.a), put(D1 + 1, d1.b), put(EV, ev.a), put(EV + 1, ev.b);
     }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_fri_combine_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint64_t tree0) {
-    const size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x;
-    if (i >= n) return;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + i]; };
-    gl2 h{0, 0};
-    const uint64_t ta = cell(TA), tq = cell(TQ), abs = cell(TM) | ta | tq, last = cell(LAST);
-    if (abs | last) {  // h = (-abs D_fri + last D_row) / (D_row D_fri): a row word received, or the entry sent
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t idx = cell(IDX);
-        const gl2 dr = bus.row_of(gl_add(tree0, ta + 2 * tq), idx, cell(POS), cell(W)), df = bus.fri(idx, cell(EV), cell(EV + 1), bus::K<0>{});
-        h = gl2_mul(abs ? gl2{gl_neg(df.a), gl_neg(df.b)} : dr, gl2_inv(gl2_mul(dr, df)));
-    }
-    aux[i] = h.a, aux[n + i] = h.b;
-    aux[2 * n + i] = h.a, aux[3 * n + i] = h.b;  // the increment; the scan makes it the running sum
 }
 
 constexpr size_t MAX_QUERIES = (size_t)1 << 20, MAX_ROW = (size_t)1 << 20;
@@ -277,10 +262,7 @@ void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* bet
 }
 
 int32_t FriCombineAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_fri_combine_aux, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[PUB_TREE0]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+    return bus_gen_aux<FriCombineAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 extern "C" {

@@ -5,14 +5,14 @@
 //                     the square-and-multiply accumulator -- and stores its cells itself (adjacent lanes = adjacent rows of a
 //                     column).  A bit row refolds the last leaf: it carries ev_NL.  Fold rows and bit rows run the same code;
 //                     the table is a few hundred rows and latency-bound, so nothing here is tuned
-//   k_fri_fold_aux    one lane per row: ONE extension inversion for the row's 17 helpers (Montgomery batch over the products of
-//                     its denominator pairs) and the row's running-sum increment (vx_bus_close_dev scans it)
+// The auxiliary columns are bus_aux.cuh's, from the AIR's own message list: one lane per row, 17 helpers.
 // vx_fri_fold_prove folds every query natively on the host first (the same level algebra in Fx) and refuses a chain that does
 // not hold, or does not end in the final polynomial, with VX_ERR_STATEMENT before anything is proven.
 // Parity: tests/test_gpu_fri_fold.py compares trace, auxiliary columns and proof with tests/fri_fold_ref.py and the reference prover.
 #include <string.h>
 
 #include "air_fri_fold.cuh"
+#include "bus_aux.cuh"
 #include "glh_poseidon.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
@@ -99,38 +99,6 @@ __global__ __launch_bounds__(64) void k_fri_fold_trace(FoldArgs a) {
     // a fold row: the value entering the layer and 1 / x_l; a bit row: ev_NL and 1 / x_NL (s is (1 / x_l)^16 by now: g^16 = 1)
     const gl2 ev = is_fold ? ev_in : v[0];
     put(EV, ev.a), put(EV + 1, ev.b), put(Y, is_fold ? yl : s);
-}
-
-__global__ __launch_bounds__(64) void k_fri_fold_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint64_t tree0) {
-    const size_t i = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (i >= n) return;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + i]; };
-    gl2 h[N_HELP];
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
-    const uint64_t fold = cell(FOLD), first = cell(FIRST), fbit = cell(FBIT);
-    if (fold | first | fbit) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the 17 message pairs, with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t q = cell(Q), tree = gl_add(tree0, cell(CNT));
-        gl2 num[N_HELP], den[N_HELP];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {  // received: multiplicity -FOLD
-            const gl2 da = bus.row_of(tree, q, (uint64_t)(2 * e), cell(LEAF + 2 * e)), db = bus.row_of(tree, q, (uint64_t)(2 * e + 1), cell(LEAF + 2 * e + 1));
-            num[e] = gl2_scale(gl2_add(da, db), fold ? GL_P - 1 : 0), den[e] = gl2_mul(da, db);
-        }
-        {  // the entry (received on the first row), the exit (sent on the first bit row)
-            const uint64_t idx = cell(IDX), va = cell(EV), vb = cell(EV + 1);
-            const gl2 de = bus.fri(idx, va, vb, bus::K<0>{}), dx = bus.fri(idx, va, vb, bus::K<1>{});
-            num[16] = gl2_sub(gl2_scale(de, fbit), gl2_scale(dx, first)), den[16] = gl2_mul(de, dx);
-        }
-        gl2_batch_div(num, den, h);
-    }
-    gl2 sum = h[0];
-#pragma unroll
-    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) aux[(size_t)(2 * e) * n + i] = h[e].a, aux[(size_t)(2 * e + 1) * n + i] = h[e].b;
-    aux[(size_t)(2 * N_HELP) * n + i] = sum.a, aux[(size_t)(2 * N_HELP + 1) * n + i] = sum.b;  // increments; the scan makes them the running sum
 }
 
 constexpr size_t MAX_QUERIES = (size_t)1 << 20;
@@ -242,10 +210,7 @@ int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
 }
 
 int32_t FriFoldAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_fri_fold_aux, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[PUB_TREE0]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+    return bus_gen_aux<FriFoldAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 extern "C" {

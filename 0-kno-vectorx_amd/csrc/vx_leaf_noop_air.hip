@@ -3,12 +3,12 @@
 //                      loads) and stores its eleven cells; rows behind the openings are zero.  Column-major stores: a wave writes
 //                      one run of 64 words of a column, every store is coalesced.  The table is small (one row per opening of a
 //                      commitment tree of at most 4 columns) and store-bound; nothing else is tuned
-//   k_leaf_noop_aux    one lane per row: ONE extension inversion for the row's three helpers (Montgomery batch over the products
-//                      of its denominator pairs) and the row's running-sum increment (vx_bus_close_dev scans it)
+// The auxiliary columns are bus_aux.cuh's, from the AIR's own message list: one lane per row.
 // Parity: tests/test_gpu_leaf_noop.py compares trace, auxiliary columns and public inputs with tests/leaf_noop_ref.py.
 #include <string.h>
 
 #include "air_leaf_noop.cuh"
+#include "bus_aux.cuh"
 #include "glh_poseidon.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
@@ -37,38 +37,6 @@ __global__ __launch_bounds__(BLOCK) void k_leaf_noop_trace(const ulonglong2* __r
     for (int j = 0; j < COLS; ++j) tr[(size_t)j * n + i] = cell[j];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_leaf_noop_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
-    const size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x;
-    if (i >= n) return;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + i]; };
-    gl2 h[N_HELP];
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
-    if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the three message pairs, with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t tree = cell(TREE), idx = cell(IDX);
-        uint64_t w[4], e[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = cell(W + j), e[j] = cell(E + j);
-        gl2 num[N_HELP], den[N_HELP];
-        {
-            const gl2 dlo = bus.open_of(tree, idx, w[0], w[1], bus::K<0>{}), dhi = bus.open_of(tree, idx, w[2], w[3], bus::K<1>{});
-            num[0] = gl2_scale(gl2_add(dlo, dhi), GL_P - 1), den[0] = gl2_mul(dlo, dhi);  // received: multiplicity -ACT
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const gl2 da = bus.row_of(tree, idx, (uint64_t)(2 * k), w[2 * k]), db = bus.row_of(tree, idx, (uint64_t)(2 * k + 1), w[2 * k + 1]);
-            num[1 + k] = gl2_add(gl2_scale(db, e[2 * k]), gl2_scale(da, e[2 * k + 1])), den[1 + k] = gl2_mul(da, db);
-        }
-        gl2_batch_div(num, den, h);
-    }
-    gl2 sum = h[0];
-#pragma unroll
-    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) aux[(size_t)(2 * e) * n + i] = h[e].a, aux[(size_t)(2 * e + 1) * n + i] = h[e].b;
-    aux[(size_t)(2 * N_HELP) * n + i] = sum.a, aux[(size_t)(2 * N_HELP + 1) * n + i] = sum.b;  // the increment; the scan makes it the running sum
-}
 }  // namespace
 
 void vx_leaf_noop_public(const uint64_t digest[4], uint64_t pub[4]) { memcpy(pub + PUB_DIGEST, digest, 32); }
@@ -105,11 +73,8 @@ int32_t vx_leaf_noop_trace_dev(vx_ctx* ctx, const uint64_t* tree_of, const uint6
     return sc.status("leaf noop");
 }
 
-int32_t LeafNoopAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_leaf_noop_aux, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+int32_t LeafNoopAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    return bus_gen_aux<LeafNoopAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 extern "C" {

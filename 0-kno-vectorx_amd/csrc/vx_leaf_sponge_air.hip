@@ -9,9 +9,7 @@
 //                         digest, which is compared with the tree's leaf digest: the first opening that differs is reported
 //   k_leaf_sponge_trace   one lane per block: the blocks are independent once their entering states exist -- the lane writes
 //                         the shape columns and walks the 30 rounds (poseidon_air.cuh) over its 32 rows; SET: with the TREE column
-//   k_leaf_sponge_aux     one lane per block: ONE extension inversion for the block's five helpers (Montgomery batch over the
-//                         products of its denominator pairs), written to its 32 rows, and the block's running-sum increment
-//                         on its first row (vx_bus_close_dev scans it); SET: with the tree in the denominators
+// The auxiliary columns of both tables are bus_aux.cuh's, from the AIRs' own message list: one lane per block.
 // The sources of the states kernel: one tree's leaf data in any of the three vx_merkle_build layouts; the leaves of FRI layers -- 16
 // extension values at natural positions bitrev(16 j + t), what vx_fri_layer_tree hashes -- with a per-leaf entry (tree, layer
 // values, the tree's leaf digests, log2 of its leaves); and the rows themselves, handed over one per opening (their rows come out of
@@ -22,6 +20,7 @@
 
 #include "air_leaf_sponge.cuh"
 #include "air_merkle_open.cuh"
+#include "bus_aux.cuh"
 #include "glh_poseidon.h"
 #include "poseidon.cuh"
 #include "poseidon_air.cuh"
@@ -122,56 +121,6 @@ __global__ __launch_bounds__(64) void k_leaf_sponge_trace(const uint64_t* __rest
     poseidon_air_block_cols(shape, tr, n, MSG, 32 * b);
 }
 
-template <bool SET>
-__global__ __launch_bounds__(64) void k_leaf_sponge_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma, uint32_t wmask) {
-    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (b >= n / 32) return;
-    const size_t row = 32 * b;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
-    gl2 h[N_HELP];
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
-    if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the five message pairs, with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t idx = cell(IDX), pos8 = 8 * cell(POS), last = cell(LASTB);
-        uint64_t tree = 0;
-        if constexpr (SET) tree = cell(TREE);
-        auto d_row = [&](uint64_t position, uint64_t word) {
-            if constexpr (SET) return bus.row_of(tree, idx, position, word);
-            else return bus.row(idx, position, word);
-        };
-        auto d_open = [&](uint64_t da, uint64_t db, auto half) {
-            if constexpr (SET) return bus.open_of(tree, idx, da, db, half);
-            else return bus.open(idx, da, db, half);
-        };
-        gl2 num[N_HELP], den[N_HELP];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint64_t ma = last ? (wmask >> (2 * e)) & 1 : 1, mb = last ? (wmask >> (2 * e + 1)) & 1 : 1;
-            const gl2 da = d_row(pos8 + 2 * e, cell(MSG + 2 * e)), db = d_row(pos8 + 2 * e + 1, cell(MSG + 2 * e + 1));
-            num[e] = gl2_add(gl2_scale(db, ma), gl2_scale(da, mb)), den[e] = gl2_mul(da, db);
-        }
-        {
-            const gl2 dlo = d_open(cell(DIG), cell(DIG + 1), bus::K<0>{}), dhi = d_open(cell(DIG + 2), cell(DIG + 3), bus::K<1>{});
-            num[4] = gl2_scale(gl2_add(dlo, dhi), last ? GL_P - 1 : 0), den[4] = gl2_mul(dlo, dhi);  // received: multiplicity -LASTB
-        }
-        gl2_batch_div(num, den, h);
-    }
-    gl2 sum = h[0];
-#pragma unroll
-    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) {
-        uint64_t *ca = aux + (size_t)(2 * e) * n + row, *cb = aux + (size_t)(2 * e + 1) * n + row;
-        const gl2 v = h[e];
-#pragma unroll 8
-        for (int r = 0; r < 32; ++r) ca[r] = v.a, cb[r] = v.b;
-    }
-    uint64_t *za = aux + (size_t)(2 * N_HELP) * n + row, *zb = aux + (size_t)(2 * N_HELP + 1) * n + row;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
-}
-
 constexpr size_t MAX_LEAF_LEN = (size_t)1 << 20;
 
 // where the rows of a witness come from: what SpongeArgs distinguishes
@@ -245,22 +194,13 @@ int32_t sponge_table(vx_ctx* ctx, const SpongeSource& src, const uint64_t* leaf_
     return VX_OK;
 }
 
-template <bool SET>
-int32_t sponge_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    uint32_t wmask = 0;
-    for (int i = 0; i < 8; ++i) wmask |= (uint32_t)(pub[PUB_W + i] & 1) << i;
-    hipLaunchKernelGGL(k_leaf_sponge_aux<SET>, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, wmask);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
-}
 }  // namespace
 
 int32_t LeafSpongeAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    return sponge_gen_aux<false>(ctx, trace, log_n, chal, pub, aux, aux_pub);
+    return bus_gen_aux<LeafSpongeAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 int32_t LeafSpongeSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    return sponge_gen_aux<true>(ctx, trace, log_n, chal, pub, aux, aux_pub);
+    return bus_gen_aux<LeafSpongeSetAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 // L, B, the tail flags, the digest of the (index, row) claims: shared with the verifier (vx_verify.hip)

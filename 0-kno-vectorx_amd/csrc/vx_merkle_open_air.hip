@@ -10,10 +10,8 @@
 //                                different depths), the tree of a path one entry of a small device table (node storage, the fold of
 //                                its cap, depth, root): three dependent loads, no search.  MerkleOpenAir (SET = false) is the set
 //                                of one tree without the trailing TREE, ROOT and DEPTH columns: root and depth are public inputs
-//   k_merkle_open_aux            one lane per block: one extension inversion for the helper of the block's two TAG_OPEN messages,
-//                                written to its 32 rows, and the block's running-sum increment on its first row (vx_bus_close_dev
-//                                scans it)
-//   k_merkle_open_set_aux        ... for both helpers of the set (the opening, the root)
+// The auxiliary columns of both tables are bus_aux.cuh's, from the AIRs' own message list: one lane per block, one helper for the
+// opening and, in the set, one for the root.
 // The sources: one tree or several trees in HBM (PATHS = false) -- the node storage already holds every node of every path, so the
 // levels of a path are independent -- and AUTHENTICATION PATHS (vx_merkle_paths_air_trace, PATHS = true): no tree is in HBM, a path is
 // what a proof carries -- the leaf digest and one sibling per level up to the cap -- so its levels are a chain:
@@ -25,6 +23,7 @@
 #include <string.h>
 
 #include "air_merkle_open.cuh"
+#include "bus_aux.cuh"
 #include "glh_poseidon.h"
 #include "poseidon.cuh"
 #include "poseidon_air.cuh"
@@ -98,25 +97,6 @@ __global__ __launch_bounds__(64) void k_merkle_open_trace(OpenArgs a) {
     poseidon_air_block_cols(shape, a.tr, a.n, BIT, 32 * b);
 }
 
-__global__ __launch_bounds__(64) void k_merkle_open_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
-    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (b >= n / 32) return;
-    const size_t row = 32 * b;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
-    gl2 h{0, 0};
-    const uint64_t firstb = cell(FIRSTB);
-    if (firstb) {  // h = FIRSTB (1 / D_lo + 1 / D_hi) with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const gl2 dlo = bus.open(cell(R), cell(LEAF), cell(LEAF + 1), bus::K<0>{}), dhi = bus.open(cell(R), cell(LEAF + 2), cell(LEAF + 3), bus::K<1>{});
-        h = gl2_scale(gl2_mul(gl2_add(dlo, dhi), gl2_inv(gl2_mul(dlo, dhi))), firstb);
-    }
-#pragma unroll
-    for (int r = 0; r < 32; ++r) {
-        aux[row + r] = h.a, aux[n + row + r] = h.b;
-        aux[2 * n + row + r] = r == 0 ? h.a : 0, aux[3 * n + row + r] = r == 0 ? h.b : 0;  // increments; the scan makes them the running sum
-    }
-}
-
 // The chain of every path.  Lanes 0..3 of a group hold the node the path has reached; every level the group loads the sibling
 // (lanes 0..7, word l & 3), stores the pair, orders it by the index bit and permutes.  Every group of a launch runs max_depth
 // levels -- the DPP exchange of the permutation wants whole waves in step -- and a path shorter than that keeps its node from its
@@ -160,34 +140,6 @@ __global__ __launch_bounds__(256) void k_merkle_path_states(PathArgs a) {
         if (on) cur = s;
     }
     if (live && l < 4 && cur != gl_canon(tr.root[l])) atomicMin(a.bad, (unsigned long long)(p + 1));
-}
-
-__global__ __launch_bounds__(64) void k_merkle_open_set_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
-    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (b >= n / 32) return;
-    const size_t row = 32 * b;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
-    gl2 h[2] = {gl2{0, 0}, gl2{0, 0}};
-    const uint64_t firstb = cell(FIRSTB), end = cell(END);
-    if (firstb | end) {  // h = FIRSTB (1 / D_lo + 1 / D_hi) of the opening, h2 = END (...) of the root, with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t tree = cell(TREE), r = cell(R), depth = cell(DEPTH);
-        const gl2 dlo = bus.open_of(tree, r, cell(LEAF), cell(LEAF + 1), bus::K<0>{}), dhi = bus.open_of(tree, r, cell(LEAF + 2), cell(LEAF + 3), bus::K<1>{});
-        const gl2 rlo = bus.root(tree, cell(ROOT), cell(ROOT + 1), bus::K<0>{}, depth), rhi = bus.root(tree, cell(ROOT + 2), cell(ROOT + 3), bus::K<1>{}, depth);
-        const gl2 num[2] = {gl2_scale(gl2_add(dlo, dhi), firstb), gl2_scale(gl2_add(rlo, rhi), end)}, den[2] = {gl2_mul(dlo, dhi), gl2_mul(rlo, rhi)};
-        gl2_batch_div(num, den, h);
-    }
-    const gl2 sum = gl2_add(h[0], h[1]);
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        uint64_t *ca = aux + (size_t)(2 * e) * n + row, *cb = aux + (size_t)(2 * e + 1) * n + row;
-        const gl2 v = h[e];
-#pragma unroll 8
-        for (int r = 0; r < 32; ++r) ca[r] = v.a, cb[r] = v.b;
-    }
-    uint64_t *za = aux + 4 * n + row, *zb = aux + 5 * n + row;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
 }
 
 // ---- a request, as every source states it
@@ -356,22 +308,14 @@ int32_t open_trees_trace(vx_ctx* ctx, const OpenTree* trees, size_t n_trees, con
 }  // namespace
 
 int32_t MerkleOpenSetAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    (void)pub;
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    hipLaunchKernelGGL(k_merkle_open_set_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 4 * n, log_n, aux_pub);
+    return bus_gen_aux<MerkleOpenSetAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 // MerkleOpenSetAir's public inputs: the digest the table does not constrain (prover and verifier alike: vx_bus.h)
 void vx_merkle_open_set_public(const uint64_t digest[4], uint64_t pub[4]) { memcpy(pub, digest, 32); }
 
 int32_t MerkleOpenAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    (void)pub;
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    hipLaunchKernelGGL(k_merkle_open_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 2 * n, log_n, aux_pub);
+    return bus_gen_aux<MerkleOpenAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 // root, depth, the digest of the (index, leaf digest) claims: shared with the verifier (vx_verify.hip)

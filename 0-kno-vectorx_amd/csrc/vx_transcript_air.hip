@@ -9,13 +9,13 @@
 //                        it are stored, and the q challenges popped from the end of the output go to the chain's challenge list
 //   k_transcript_trace   one lane per block: the blocks are independent once their entering states exist -- the lane writes the
 //                        shape columns and walks the 30 rounds (poseidon_air.cuh) over its 32 rows; idle blocks start from zero
-//   k_transcript_aux     one lane per block: ONE extension inversion for the block's eight helpers (Montgomery batch) and the
-//                        block's running-sum increment on its first row (vx_bus_close_dev scans it)
+// The auxiliary columns are bus_aux.cuh's, from the AIR's own message list: one lane per block, eight helpers.
 // Parity: tests/test_gpu_transcript.py compares trace, auxiliary columns, challenges, the table's proof and the group's blob with
 // tests/transcript_ref.py and the reference prover.
 #include <string.h>
 
 #include "air_transcript.cuh"
+#include "bus_aux.cuh"
 #include "glh_poseidon.h"
 #include "poseidon.cuh"
 #include "poseidon_air.cuh"
@@ -87,49 +87,6 @@ __global__ __launch_bounds__(64) void k_transcript_trace(const uint64_t* __restr
     poseidon_air_block_cols(shape, tr, n, MSG, 32 * b);
 }
 
-__global__ __launch_bounds__(64) void k_transcript_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, size_t n, gl2 beta, gl2 gamma) {
-    const size_t b = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (b >= n / 32) return;
-    const size_t row = 32 * b;
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
-    gl2 h[N_HELP];
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) h[e] = gl2{0, 0};
-    if (cell(ACT)) {  // h_e = (m_a D_b + m_b D_a) / (D_a D_b) for the eight message pairs, with one inversion
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t chain = cell(CHAIN), nabs = cell(NABS), nch = cell(NCH);
-        uint64_t absorbed = nabs;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) absorbed += cell(W + i);
-        gl2 num[N_HELP], den[N_HELP];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {  // received: multiplicity -W_i
-            const uint64_t ma = cell(W + 2 * e) ? GL_P - 1 : 0, mb = cell(W + 2 * e + 1) ? GL_P - 1 : 0;
-            const gl2 da = bus.obs(chain, nabs + 2 * e, cell(MSG + 2 * e)), db = bus.obs(chain, nabs + 2 * e + 1, cell(MSG + 2 * e + 1));
-            num[e] = gl2_add(gl2_scale(db, ma), gl2_scale(da, mb)), den[e] = gl2_mul(da, db);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {  // sent: multiplicity Q_i
-            const gl2 da = bus.chal(chain, nch + (7 - 2 * e), absorbed, cell(OUT + 2 * e)), db = bus.chal(chain, nch + (6 - 2 * e), absorbed, cell(OUT + 2 * e + 1));
-            num[4 + e] = gl2_add(gl2_scale(db, cell(Q + 2 * e)), gl2_scale(da, cell(Q + 2 * e + 1))), den[4 + e] = gl2_mul(da, db);
-        }
-        gl2_batch_div(num, den, h);
-    }
-    gl2 sum = h[0];
-#pragma unroll
-    for (int e = 1; e < N_HELP; ++e) sum = gl2_add(sum, h[e]);
-#pragma unroll
-    for (int e = 0; e < N_HELP; ++e) {
-        uint64_t *ca = aux + (size_t)(2 * e) * n + row, *cb = aux + (size_t)(2 * e + 1) * n + row;
-        const gl2 v = h[e];
-#pragma unroll 8
-        for (int r = 0; r < 32; ++r) ca[r] = v.a, cb[r] = v.b;
-    }
-    uint64_t *za = aux + (size_t)(2 * N_HELP) * n + row, *zb = aux + (size_t)(2 * N_HELP + 1) * n + row;
-#pragma unroll 8
-    for (int r = 0; r < 32; ++r) za[r] = r == 0 ? sum.a : 0, zb[r] = r == 0 ? sum.b : 0;  // increments; the scan makes them the running sum
-}
-
 size_t total_blocks(const glh::TranscriptRecord* chains, size_t n_chains) {
     size_t blocks = 0;
     for (size_t c = 0; c < n_chains; ++c) blocks += chains[c].n_blocks();
@@ -138,11 +95,8 @@ size_t total_blocks(const glh::TranscriptRecord* chains, size_t n_chains) {
 TranscriptClaim claim_of(const glh::TranscriptRecord& r) { return {r.words.data(), r.words.size(), r.chal.data(), r.n_chal()}; }
 }  // namespace
 
-int32_t TranscriptAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n, blocks = n / 32;
-    hipLaunchKernelGGL(k_transcript_aux, dim3((unsigned)((blocks + 63) / 64)), dim3(64), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + (size_t)(2 * N_HELP) * n, log_n, aux_pub);
+int32_t TranscriptAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    return bus_gen_aux<TranscriptAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 void vx_transcript_public(const uint64_t digest[4], uint64_t pub[4]) { memcpy(pub + PUB_DIGEST, digest, 32); }

@@ -35,6 +35,9 @@ def case_queries(LN, NL, case):
     if case == "half_idle":
         n = 32 // rpq
         return [int(v) for v in rng.integers(0, top + 1, size=n)], 6
+    if case == "two_workgroups":  # of the auxiliary kernel's 64 lanes: the queries end in the second, idle rows behind them
+        n = 80 // rpq
+        return [int(v) for v in rng.integers(0, top + 1, size=n)], 7
     raise ValueError(case)
 
 
@@ -46,7 +49,7 @@ def rand_claims(LN, NL, index, seed=5):
     return betas, leaves
 
 
-@pytest.mark.parametrize("case", ["single", "duplicates", "first_and_last_index", "full", "half_idle"])
+@pytest.mark.parametrize("case", ["single", "duplicates", "first_and_last_index", "full", "half_idle", "two_workgroups"])
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_witness_equals_the_reference(ctx, vx, oracle, shape, case):
     LN, NL = SHAPES[shape]
@@ -56,7 +59,9 @@ def test_witness_equals_the_reference(ctx, vx, oracle, shape, case):
         assert n - len(index) * rpq < rpq and (shape != "NL1_FB1" or len(index) * rpq == n)
     if case == "half_idle":
         assert n // 2 - rpq < len(index) * rpq <= n // 2
-    tree0 = 3 if case == "duplicates" else 0
+    if case == "two_workgroups":
+        assert 64 < len(index) * rpq < n
+    tree0 = 3 if case in ("duplicates", "two_workgroups") else 0
     betas, leaves = rand_claims(LN, NL, index)
     ev0 = F.ev0_of(index, leaves)
     want, want_pub = F.ref_trace(index, leaves, betas, LN, log_n, tree0)

@@ -25,8 +25,10 @@ def openings(n, seed=11):
     return trees, index, rows
 
 
-# (openings, log_n): one; a wave and one more; exactly full at the smallest table and at one of two waves; idle rows behind a full wave
-WITNESS = {"one": (1, 5), "wave_64": (64, 7), "wave_65": (65, 7), "full_32": (32, 5), "full_64": (64, 6), "full_512_two_blocks": (512, 9)}
+# (openings, log_n): one; a wave and one more; exactly full at the smallest table and at one of two waves; idle rows behind a full wave;
+# two workgroups of the auxiliary kernel, full and with idle rows behind the openings in the second
+WITNESS = {"one": (1, 5), "wave_64": (64, 7), "wave_65": (65, 7), "full_32": (32, 5), "full_64": (64, 6), "full_512_two_blocks": (512, 9),
+           "idle_behind_300_two_blocks": (300, 9)}
 
 
 @pytest.mark.parametrize("name", list(WITNESS))

@@ -48,6 +48,8 @@ WITNESS = {
     "D5_L9_row_major_idle_half": (5, 9, "row_major", [30, 2], 1),
     "D5_L21_cols": (5, 21, "cols", [17], 0),
     "D5_L5_cols_bitrev": (5, 5, "cols_bitrev", [9, 22, 9, 1, 16], 0),
+    # two workgroups of the auxiliary kernel (one lane per block, 64 lanes): 69 blocks of 128, idle ones behind them
+    "D5_L21_row_major_two_workgroups": (5, 21, "row_major", [0, 31, 13, 17, 5, 9, 22, 1, 16, 30, 2, 8, 27, 3, 11, 19, 24, 6, 29, 14, 21, 10, 7], 0),
 }
 
 
@@ -57,6 +59,7 @@ def test_witness_equals_the_reference(ctx, vx, oracle, name):
     layout = layouts(vx)[lay]
     leaves, data, gtree, rtree = make(ctx, vx, oracle, D, L, layout, 0)
     log_n = R.log_rows(len(idx), L) + extra
+    assert log_n == {"D3_L5_row_major": 5, "D5_L21_row_major_two_workgroups": 12}.get(name, log_n)
     want, want_pub, digs = R.ref_trace(idx, leaves[idx], log_n)
     assert (digs == gtree.leaf_digests()[idx]).all()
     tb, pub = ctx.leaf_sponge_air_trace(data, 1 << D, L, layout, idx, log_n)

@@ -20,12 +20,17 @@ def trees(ctx, vx, oracle, D, cap_height, seed=3):
     return ctx.merkle(ctx.from_host(leaves), 1 << D, 8, vx.lib.VX_LEAVES_ROW_MAJOR, cap_height), oracle.MerkleTree(leaves, cap_height)
 
 
-@pytest.mark.parametrize("name", list(CASES))
+# ... and the ends of the auxiliary kernel's grid (one lane per block, 64 lanes): one block; 70 blocks of 128, idle ones behind them
+WITNESS = dict(CASES, D1_Q1_one_block=(1, 0, [1]), D5_Q14_two_workgroups=(5, 2, [0, 31, 31, 17, 5, 9, 22, 1, 16, 30, 2, 13, 8, 27]))
+
+
+@pytest.mark.parametrize("name", list(WITNESS))
 def test_witness_equals_the_reference(ctx, vx, oracle, name):
-    D, cap_height, idx = CASES[name]
+    D, cap_height, idx = WITNESS[name]
     gtree, rtree = trees(ctx, vx, oracle, D, cap_height)
     want, want_pub, digs = M.ref_trace(rtree, idx)
     log_n = M.log_rows(len(idx), D)
+    assert log_n == {"D1_Q1_one_block": 5, "D5_Q14_two_workgroups": 12}.get(name, log_n)
     tb, pub = ctx.merkle_open_air_trace(gtree, idx, log_n)
     assert [int(v) for v in pub] == want_pub
     got = tb.download().reshape(M.COLS, -1)

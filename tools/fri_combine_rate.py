@@ -2,7 +2,7 @@
 """FriCombineAir end to end on one GPU at the shape of the hash-chain table's query phase: 84 queries of 745 + 276 + 4 row words over
 a 2^21 LDE = 1046 rows per query in one 2^17-row table; random consistent claims (tests/fri_combine_ref.py).  One JSON line,
 milliseconds averaged over `reps` calls after a warm-up call: the witness (vx_fri_combine_air_trace: upload, the powers of alpha,
-k_fri_combine_trace, the claims digest on the host), the auxiliary columns (k_fri_combine_aux + the scan), the table's STARK with its
+k_fri_combine_trace, the claims digest on the host), the auxiliary columns (k_bus_aux<FriCombineAir> + the scan), the table's STARK with its
 auxiliary round from a ready trace (vx_stark_prove), vx_fri_combine_prove as a whole (host combination check included), the claims
 digest alone (the C oracle's hash_n_to_hash_no_pad over the same words), vx_fri_combine_verify on the host, and -- the work the table
 proves -- the host combination loop of the 84 queries: vx_fri_combine_prove's native check, timed by handing it a wrong ev_0 for the

@@ -2,7 +2,7 @@
 """FriFoldAir end to end on one GPU at the shape of one STARK proof's query phase: 84 queries of a 2^21 LDE, four fold layers, five
 index bits left = 756 rows in one 2^10-row table; the claims are cut from a FRI commit phase the reference runs on a random
 polynomial (tests/fri_fold_ref.py).  One JSON line, milliseconds averaged over `reps` calls after a warm-up call: the witness
-(vx_fri_fold_air_trace: upload, k_fri_fold_trace, the claims digest on the host), the auxiliary columns (k_fri_fold_aux + the scan),
+(vx_fri_fold_air_trace: upload, k_fri_fold_trace, the claims digest on the host), the auxiliary columns (k_bus_aux<FriFoldAir> + the scan),
 the table's STARK with its auxiliary round from a ready trace (vx_stark_prove), vx_fri_fold_prove as a whole (host fold check
 included), the claims digest alone (the C oracle's hash_n_to_hash_no_pad over the same words), vx_fri_fold_verify on the host, and
 -- the work the table proves -- the same 84 x 4 coset interpolations by the C oracle's compute_evaluation, the Lagrange loop of
