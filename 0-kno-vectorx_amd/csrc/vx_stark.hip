@@ -466,6 +466,28 @@ int32_t vx_quotient_eval(vx_ctx* ctx, int air_id, int rate_bits, const vx_buf* t
     return quotient_eval_dev(ctx, air, log_n, rate_bits, trace_lde->d, alphas, public_inputs, n_public, nullptr, nullptr, out->d, mem);
 }
 
+int32_t vx_quotient_eval_aux(vx_ctx* ctx, int air_id, int rate_bits, const vx_buf* trace_lde, int log_n, const uint64_t alphas[2],
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* challenges, size_t n_challenges,
+                             const uint64_t* aux_public, size_t n_aux_public, vx_buf* out) {
+    if (!ctx || !trace_lde || !alphas || !out) return VX_ERR_ARG;
+    const AirDesc* air = find_air(air_id);
+    VX_CHECK(air, "quotient eval: unknown AIR id %d", air_id);
+    VX_CHECK(rate_bits >= 1 && rate_bits <= 3 && log_n >= 2 && log_n >= air->period_log && log_n + rate_bits <= 27, "quotient eval: bad log_n %d / rate_bits %d", log_n, rate_bits);
+    VX_CHECK(!air->exact_log || log_n == air->period_log, "quotient eval: AIR %d has positional columns of the trace's period: log_n must be %d", air_id, air->period_log);
+    VX_CHECK((int)n_public == air->pub && (n_public == 0 || public_inputs), "quotient eval: AIR %d takes %d public inputs", air_id, air->pub);
+    VX_CHECK((int)n_challenges == air->chal && (n_challenges == 0 || challenges), "quotient eval: AIR %d takes %d challenges", air_id, air->chal);
+    VX_CHECK((int)n_aux_public == 2 * air->auxpub && (n_aux_public == 0 || aux_public), "quotient eval: AIR %d takes %d published auxiliary words", air_id, 2 * air->auxpub);
+    VX_CHECK(air->chal <= 8 && 2 * air->auxpub <= 8, "quotient eval: AIR %d has more challenges or published words than the kernel arguments hold", air_id);
+    const size_t N = (size_t)1 << (log_n + rate_bits);
+    VX_CHECK(trace_lde->n >= N * (size_t)(air->cols + air->aux) && out->n >= 2 * N, "quotient eval: buffers too small");
+    VX_CHECK(alphas[0] < glh::P && alphas[1] < glh::P, "quotient eval: non-canonical challenge");
+    for (size_t i = 0; i < n_public; ++i) VX_CHECK(public_inputs[i] < glh::P, "quotient eval: non-canonical public input");
+    for (size_t i = 0; i < n_challenges; ++i) VX_CHECK(challenges[i] < glh::P, "quotient eval: non-canonical challenge");
+    for (size_t i = 0; i < n_aux_public; ++i) VX_CHECK(aux_public[i] < glh::P, "quotient eval: non-canonical published auxiliary word");
+    DevMem mem{ctx};
+    return quotient_eval_dev(ctx, air, log_n, rate_bits, trace_lde->d, alphas, public_inputs, n_public, challenges, aux_public, out->d, mem);
+}
+
 int32_t vx_stark_aux_trace(vx_ctx* ctx, int air_id, const vx_buf* trace, int log_n, const uint64_t* public_inputs, size_t n_public,
                            const uint64_t* challenges, size_t n_challenges, vx_buf* aux_out, uint64_t* aux_public_out) {
     if (!ctx || !trace || !challenges || !aux_out) return VX_ERR_ARG;

@@ -27,7 +27,7 @@ SYMBOLS = [
     "vx_blake2b_256_batch", "vx_sha256_pairs", "vx_verify_subchain", "vx_blake_chain_trace",
     "vx_ed25519_verify_batch", "vx_verify_simple_justification", "vx_sha_chain_trace",
     "vx_verify_epoch_end_header", "vx_rotate_proof_bound", "vx_rotate_prove", "vx_rotate_verify",
-    "vx_gather_proofs", "vx_quotient_eval", "vx_decode_header_batch", "vx_decode_precommit_batch", "vx_stark_aux_trace",
+    "vx_gather_proofs", "vx_quotient_eval", "vx_quotient_eval_aux", "vx_decode_header_batch", "vx_decode_precommit_batch", "vx_stark_aux_trace",
     "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_unregister", "vx_poseidon_air_trace",
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
@@ -172,6 +172,7 @@ def load_library():
         "vx_rotate_verify": [C.POINTER(StarkConfig), vp, sz, u64, vp, vp, C.c_char_p, sz],
         "vx_gather_proofs": [vp, vp, C.c_int, vp, sz, vp],
         "vx_quotient_eval": [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, sz, vp],
+        "vx_quotient_eval_aux": [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, sz, vp, sz, vp, sz, vp],
         "vx_partial_products": [vp, vp, vp, C.c_int, sz, vp, u64, u64, sz, vp],
         "vx_decode_header_batch": [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
         "vx_decode_precommit_batch": [vp, vp, sz, vp, vp, vp, vp, vp],
@@ -1191,13 +1192,20 @@ class Context:
         self._ck(self.L.vx_partial_products(self.h, wires_buf.h, sigmas_buf.h, log_n, n_routed, _ptr(k), int(beta), int(gamma), chunk, out.h))
         return out
 
-    def quotient_eval(self, air_id, rate_bits, trace_lde_buf, log_n, alphas, public_inputs):
-        """-> [2][N] quotient values on the coset for the two challenges."""
+    def quotient_eval(self, air_id, rate_bits, trace_lde_buf, log_n, alphas, public_inputs, challenges=None, aux_public=None):
+        """-> [2][N] quotient values on the coset for the two challenges.  With challenges / aux_public (both, possibly empty) the
+        buffer holds the main columns then the auxiliary ones and any AIR is evaluated (vx_quotient_eval_aux)."""
         N = 1 << (log_n + rate_bits)
         out = self.alloc(2 * N)
         al = np.ascontiguousarray(alphas, dtype=np.uint64)
         pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
-        self._ck(self.L.vx_quotient_eval(self.h, air_id, rate_bits, trace_lde_buf.h, log_n, _ptr(al), _ptr(pub) if pub.size else None, pub.size, out.h))
+        if challenges is None and aux_public is None:
+            self._ck(self.L.vx_quotient_eval(self.h, air_id, rate_bits, trace_lde_buf.h, log_n, _ptr(al), _ptr(pub) if pub.size else None, pub.size, out.h))
+        else:
+            ch = np.ascontiguousarray(() if challenges is None else challenges, dtype=np.uint64)
+            ap = np.ascontiguousarray(() if aux_public is None else aux_public, dtype=np.uint64)
+            self._ck(self.L.vx_quotient_eval_aux(self.h, air_id, rate_bits, trace_lde_buf.h, log_n, _ptr(al), _ptr(pub) if pub.size else None, pub.size,
+                                                 _ptr(ch) if ch.size else None, ch.size, _ptr(ap) if ap.size else None, ap.size, out.h))
         v = out.download().reshape(2, N)
         out.free()
         return v

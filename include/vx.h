@@ -577,6 +577,14 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */
 int32_t vx_quotient_eval(vx_ctx* ctx, int air_id, int rate_bits, const vx_buf* trace_lde, int log_n, const uint64_t alphas[2],
                          const uint64_t* public_inputs, size_t n_public, vx_buf* out);
+/* The same evaluation for ANY AIR, an auxiliary round included -- the test surface of the compiled constraint systems: the values
+ * need not come from a trace.  trace_lde: [cols + aux cols][N], the main columns then the auxiliary ones (the layout vx_stark_prove
+ * evaluates); challenges: the AIR's CHAL lookup challenges; aux_public: the 2 * AUXPUB words published with the auxiliary cap.
+ * An AIR without an auxiliary round takes both counts 0.  Every host word must be canonical; an AIR whose row count is fixed
+ * (positional columns of the trace's period) takes that log_n only, as the prover does. */
+int32_t vx_quotient_eval_aux(vx_ctx* ctx, int air_id, int rate_bits, const vx_buf* trace_lde, int log_n, const uint64_t alphas[2],
+                             const uint64_t* public_inputs, size_t n_public, const uint64_t* challenges, size_t n_challenges,
+                             const uint64_t* aux_public, size_t n_aux_public, vx_buf* out);
 /* K9: the partial products of Plonk's permutation argument, as plonky2 computes them (plonky2 v0.2.0 plonk/prover.rs
  * wires_permutation_partial_products_and_zs, util/partial_products.rs; reached from Circuit::prove, circuits/header_range.rs:167).
  * Rows x_i = g^i of the subgroup of order 2^log_n; wires / sigmas: [n_routed][2^log_n] column-major (sigmas = the values of the

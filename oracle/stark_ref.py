@@ -396,16 +396,17 @@ def periodic_poly_coeffs(values):
     return pyref.dft([int(v) % P for v in values], inverse=True)
 
 
-def periodic_on_lde(vals, L, r):
+def periodic_on_lde(vals, L, r, points=None):
     """Values of the periodic column with one period `vals` (length p) on the LDE coset g<w_N>, natural order:
-    P(Y) with P(w_p^k) = vals[k], at Y_i = x_i^(n/p) = g^(n/p) w_{p 2^r}^i -- a coset NTT of size p 2^r, tiled."""
+    P(Y) with P(w_p^k) = vals[k], at Y_i = x_i^(n/p) = g^(n/p) w_{p 2^r}^i -- a coset NTT of size p 2^r, tiled
+    (or, with `points`, read at those indices of the coset only)."""
     p = len(vals)
     n = 1 << L
     co = O.ntt(np.array([[int(v) % P for v in vals]], dtype=np.uint64), inverse=True)[0]
     pad = np.zeros((1, p << r), dtype=np.uint64)
     pad[0, :p] = co
     ev = O.ntt(pad, shift=pow(G, n // p, P))[0]
-    return np.tile(ev, n // p)
+    return np.tile(ev, n // p) if points is None else ev[points % (p << r)]
 
 
 def poly_eval_ext(coeffs, z):
@@ -425,18 +426,27 @@ def _ext_challenge(ch):
 
 
 # ----------------------------------------------------------------------------- prover
-def quotient_values(air, lde_nat, pub, alphas, L, r, chal=None, aux_pub=None):
+def quotient_values(air, lde_nat, pub, alphas, L, r, chal=None, aux_pub=None, points=None, nxt_rows=None):
     """starky compute_quotient_polys on the coset: lde_nat [c][N] (natural order) -> [2][N] values
-    (sum_j alpha_k^(K-1-j) c_j(x)) / Z_H(x), the Horner recurrence of ConstraintConsumer."""
+    (sum_j alpha_k^(K-1-j) c_j(x)) / Z_H(x), the Horner recurrence of ConstraintConsumer.
+    points: an index array into the natural-order coset -- then lde_nat [c][len(points)] holds the rows AT those points, nxt_rows
+    the rows at their successors (i + 2^r) mod N, and x, Z_H, L_first, L_last and the periodic columns are taken at those indices
+    only: -> [2][len(points)], the corresponding entries of the full computation without the host ever holding [c][N]."""
     c = lde_nat.shape[0]
     n, LN = 1 << L, L + r
     N = n << r
     wN = O.root(LN)
-    xs = np.empty(N, dtype=np.uint64)
-    acc = G
-    for i in range(N):
-        xs[i] = acc
-        acc = acc * wN % P
+    if points is None:
+        xs = np.empty(N, dtype=np.uint64)
+        acc = G
+        for i in range(N):
+            xs[i] = acc
+            acc = acc * wN % P
+        nxt_rows = [np.roll(lde_nat[j], -(1 << r)) for j in range(c)]
+    else:
+        points = np.asarray(points, dtype=np.int64)
+        assert points.ndim == 1 and ((0 <= points) & (points < N)).all() and lde_nat.shape == (c, points.size) and np.shape(nxt_rows) == (c, points.size)
+        xs = np.array([G * pow(wN, int(i), P) % P for i in points], dtype=np.uint64)
     X = VecF(xs)
     last = pow(O.root(L), P - 2, P)
     zh = X
@@ -449,8 +459,8 @@ def quotient_values(air, lde_nat, pub, alphas, L, r, chal=None, aux_pub=None):
     l_last = zh * (ninv * last % P) * VecF(O.batch_inv((X - last).v))
     cons = Consumer([VecF.const(a, X) for a in alphas], X - last, l_first, l_last, VecF.const(0, X))
     loc = [VecF(lde_nat[j]) for j in range(c)]
-    nxt = [VecF(np.roll(lde_nat[j], -(1 << r))) for j in range(c)]
-    per = [VecF(periodic_on_lde(vals, L, r)) for vals in air.periodic_values()] if air.PERIODIC else []
+    nxt = [VecF(nxt_rows[j]) for j in range(c)]
+    per = [VecF(periodic_on_lde(vals, L, r, points)) for vals in air.periodic_values()] if air.PERIODIC else []
     air_eval(air, loc, nxt, per, [VecF.const(x, X) for x in pub], cons,
              None if chal is None else [VecF.const(x, X) for x in chal], None if aux_pub is None else [VecF.const(x, X) for x in aux_pub])
     qvals = np.stack([(cons.acc[k] * zh_inv).v for k in range(2)])

@@ -5,6 +5,7 @@ import pytest
 
 from oracle import oracle as O
 from oracle import stark_ref as S
+from quotient_arbitrary import sample_points
 
 P = 2**64 - 2**32 + 1
 
@@ -127,21 +128,6 @@ def quotient_at(air, lde, i, log_n, r, pub, alphas):
     zinv = pow(zh, P - 2, P)
     assert all(a.b == 0 for a in cons.acc)
     return [a.a * zinv % P for a in cons.acc]
-
-
-def sample_points(rng, log_N, k):
-    """0, N - 1, every 2^b - 1 and N - 2^b (runs of ones at the bottom and at the top of the index: each limb of the three-level
-    root table at its largest), runs of ones in the middle, and k random indices."""
-    N = 1 << log_N
-    pts = {0, N - 1}
-    for b in range(1, log_N + 1):
-        pts.add((1 << b) - 1)
-        pts.add(N - (1 << (b - 1)))
-    for lo, hi in ((11, 22), (22, 32), (0, 11)):
-        lo, hi = min(lo, log_N), min(hi, log_N)
-        pts.add(((1 << hi) - 1) ^ ((1 << lo) - 1))
-    pts.update(int(v) for v in rng.integers(0, N, size=k))
-    return sorted(p for p in pts if 0 <= p < N)
 
 
 @pytest.mark.parametrize("air", [S.FibAir, S.MixAir])

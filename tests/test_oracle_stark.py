@@ -129,3 +129,43 @@ def test_violating_trace_is_rejected_at_rate_3(oracle):
     tr[6, 3] += np.uint64(1)  # a multiplicity one too high: the running sum does not close
     with pytest.raises(S.VerifyError):
         S.verify(S.prove(S.LookupAir, tr, pub, cfg), cfg)
+
+
+@pytest.mark.parametrize("name,log_n,r", [("VX_AIR_MIX", 6, 2), ("VX_AIR_LOOKUP", 8, 1), ("VX_AIR_LOOKUP", 9, 3), ("VX_AIR_TRANSCRIPT", 6, 2), ("VX_AIR_FRI_FOLD", 3, 1)])
+def test_quotient_values_at_chosen_points(oracle, name, log_n, r):
+    """quotient_values(points=...) from the rows at the points and at their successors alone equals the corresponding entries of the
+    full computation: the wrap-around (N - 2^r .. N - 1), point 0, repeated and unsorted points, periodic columns shorter than the
+    trace (LookupAir at 2^9 rows: its table has period 2^8), an AIR with and without an auxiliary round."""
+    import quotient_arbitrary as QA
+
+    air, lde, pub, chal, apub, pairs = QA.arbitrary(name, log_n, r)
+    N, step = 1 << (log_n + r), 1 << r
+    rng = np.random.default_rng(9)
+    pts = np.array([N - 1, 0, N - step, step - 1, N - step - 1, 1, 0, N // 2] + [int(v) for v in rng.integers(0, N, size=40)])
+    for _, alphas in pairs:
+        full = QA.reference(air, lde, pub, chal, apub, alphas, log_n, r)
+        got = QA.reference(air, np.ascontiguousarray(lde[:, pts]), pub, chal, apub, alphas, log_n, r, points=pts, nxt_rows=np.ascontiguousarray(lde[:, (pts + step) % N]))
+        assert got.shape == (2, pts.size) and (got == full[:, pts]).all()
+    with pytest.raises(AssertionError):  # a point outside the coset
+        QA.reference(air, np.ascontiguousarray(lde[:, :1]), pub, chal, apub, alphas, log_n, r, points=np.array([N]), nxt_rows=np.ascontiguousarray(lde[:, :1]))
+
+
+def test_every_compiled_air_has_an_arbitrary_data_case(vx):
+    """every AIR id the binding names is run by test_gpu_quotient_arbitrary.py or named in its docstring as covered through its
+    template's smallest instantiation -- an AIR cannot be added without a case -- and the binding names every AIR of air_list.h"""
+    import os
+    import re
+
+    import quotient_arbitrary as QA
+    import test_gpu_quotient_arbitrary as G
+
+    ids = QA.binding_air_ids(vx.lib)
+    run = {name for name, _, _ in G.SMALL + G.FIXED + G.DEVICE}
+    same_template = set(QA.AIR_NAME.findall(G.__doc__.split("Covered through their template's smallest instantiation")[1]))
+    assert run <= set(ids) and same_template <= set(ids)
+    assert run | same_template == set(ids), "AIRs without a case: %s" % sorted(set(ids) - run - same_template)
+    assert run == set(QA.restatements()), "a restatement that no case uses, or a case without one"
+    assert len(set(ids.values())) == len(ids)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(vx.lib.__file__)), "csrc")
+    listed = re.search(r"using VxAirs = AirList<([^>]*)>", open(os.path.join(csrc, "air_list.h")).read()).group(1)
+    assert len([a for a in listed.split(",") if a.strip()]) == len(ids)
