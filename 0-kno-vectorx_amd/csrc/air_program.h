@@ -8,7 +8,9 @@
 
 #include <vector>
 
-#include "vx_internal.h"  // include/vx.h with default visibility
+#pragma GCC visibility push(default)
+#include "../../include/vx.h"  // (no HIP here: tests/host compiles this header with a host compiler)
+#pragma GCC visibility pop
 
 struct AirProgram {
     int id = 0;
@@ -20,6 +22,11 @@ struct AirProgram {
     uint32_t aux = 0, chal = 0, auxpub = 0;  // auxiliary round: columns, base-field challenges, published extension values
     vx_air_gen_aux_fn gen_aux = nullptr;     // the host's witness generator of that round (prover only)
     void* gen_aux_user = nullptr;
+    // declared bus messages (vx_air_register_bus; bus_program.h): the message program the GPU fills the auxiliary round from.  Its
+    // constraints are already part of `code`.  bus_help = 0: none
+    std::vector<uint64_t> bus_code, bus_consts;
+    uint32_t bus_regs = 0, bus_help = 0;
+    int bus_block_log = 0, bus_step = -1;
 };
 // nullptr when the id is unknown or retired; a registered program is never freed
 const AirProgram* vx_air_program_find(int id);

@@ -22,6 +22,7 @@
 
 #include "air_list.h"
 #include "air_program.h"
+#include "bus_aux_prog.cuh"
 #include "stark_proof.h"
 #include "vx_internal.h"
 
@@ -367,10 +368,11 @@ static const AirDesc* find_air(int id) {
 }
 static int air_plog(const AirDesc* air, int q) { return air->prog ? air->prog->plog[q] : air->plog(q); }
 // the auxiliary columns of an AIR: the compiled generator, or the host's callback of a registered program (which sees the
-// device arrays as buffers of the context)
-static bool air_has_gen_aux(const AirDesc* air) { return air->prog ? air->prog->gen_aux != nullptr : air->gen_aux != nullptr; }
+// device arrays as buffers of the context), or, for a program that declared its bus messages, the interpreter of bus_aux_prog.cuh
+static bool air_has_gen_aux(const AirDesc* air) { return air->prog ? air->prog->gen_aux != nullptr || air->prog->bus_help > 0 : air->gen_aux != nullptr; }
 static int32_t air_gen_aux(vx_ctx* ctx, const AirDesc* air, uint64_t* trace_d, int L, const uint64_t* chal, const uint64_t* pub, uint64_t* aux_d, uint64_t* apub) {
     if (!air->prog) return air->gen_aux(ctx, trace_d, L, chal, pub, aux_d, apub);
+    if (air->prog->bus_help > 0) return bus_prog_gen_aux(ctx, *air->prog, trace_d, L, chal, pub, aux_d, apub);
     const size_t n = (size_t)1 << L;
     vx_buf tb{trace_d, n * (size_t)air->cols}, ab{aux_d, n * (size_t)air->aux};
     const int32_t rc = air->prog->gen_aux(air->prog->gen_aux_user, ctx, &tb, L, chal, pub, &ab, apub);

@@ -22,6 +22,7 @@
 
 #include "air_list.h"
 #include "air_program.h"
+#include "bus_program.h"
 #include "stark_proof.h"
 #include "vx_bus.h"
 #include "vx_internal.h"
@@ -108,9 +109,9 @@ const AirProgram* vx_air_program_find(int id) {
     auto it = g_airp.find(id);
     return it == g_airp.end() ? nullptr : it->second.get();
 }
-extern "C" {
-int32_t vx_air_register(const vx_air_program* in, int* air_id, char* err, size_t errlen) {
-    if (!in || !air_id) return VX_ERR_ARG;
+namespace {
+// the ranges of a descriptor's fields
+int32_t airp_ranges_ok(const vx_air_program* in, char* err, size_t errlen) {
     AIRP_NEED(in->cols >= 1 && in->cols <= VX_AIRP_MAX_COLS, "air program: %u columns (1..%d)", in->cols, VX_AIRP_MAX_COLS);
     AIRP_NEED(in->n_public <= 64, "air program: %u public inputs (at most 64)", in->n_public);
     AIRP_NEED(in->n_periodic <= 256 && (in->n_periodic == 0 || (in->periodic_log && in->periodic_values)), "air program: bad periodic columns");
@@ -121,7 +122,17 @@ int32_t vx_air_register(const vx_air_program* in, int* air_id, char* err, size_t
               "air program: auxiliary round out of range (%u columns, %u challenges <= 8, %u published values <= 4)", in->aux_cols, in->n_challenges, in->n_aux_public);
     AIRP_NEED(in->aux_cols > 0 || (in->n_challenges == 0 && in->n_aux_public == 0 && !in->gen_aux), "air program: challenges / published values / a generator without auxiliary columns");
     AIRP_NEED(in->aux_cols == 0 || in->n_challenges > 0, "air program: an auxiliary round without a challenge is a second trace commitment, not a lookup round");
+    return VX_OK;
+}
+// the checks of the code and the registration; `bus`: the declaration `in` was lowered from (bus_program.h), kept for the witness kernel
+int32_t airp_register(const vx_air_program* in, const vx_air_bus* bus, uint32_t bus_help, int* air_id, char* err, size_t errlen) {
+    if (const int32_t rc = airp_ranges_ok(in, err, errlen)) return rc;
     auto pg = std::make_shared<AirProgram>();
+    if (bus) {
+        pg->bus_code.assign(bus->code, bus->code + bus->n_code);
+        pg->bus_consts.assign(bus->consts, bus->consts + bus->n_consts);
+        pg->bus_regs = bus->n_regs, pg->bus_help = bus_help, pg->bus_block_log = (int)bus->block_log, pg->bus_step = bus->step_periodic;
+    }
     pg->cols = in->cols, pg->pub = in->n_public, pg->n_regs = in->n_regs;
     pg->aux = in->aux_cols, pg->chal = in->n_challenges, pg->auxpub = in->n_aux_public, pg->gen_aux = in->gen_aux, pg->gen_aux_user = in->gen_aux_user;
     size_t n_per_values = 0;
@@ -198,6 +209,23 @@ int32_t vx_air_register(const vx_air_program* in, int* air_id, char* err, size_t
     *air_id = pg->id;
     g_airp[pg->id] = pg;
     return VX_OK;
+}
+}  // namespace
+extern "C" {
+int32_t vx_air_register(const vx_air_program* in, int* air_id, char* err, size_t errlen) {
+    if (!in || !air_id) return VX_ERR_ARG;
+    return airp_register(in, nullptr, 0, air_id, err, errlen);
+}
+int32_t vx_air_register_bus(const vx_air_program* in, const vx_air_bus* bus, int* air_id, char* err, size_t errlen) {
+    if (!in || !bus || !air_id) return VX_ERR_ARG;
+    if (const int32_t rc = airp_ranges_ok(in, err, errlen)) return rc;
+    uint32_t n_msgs = 0;
+    if (!busp::validate(*in, *bus, &n_msgs, err, errlen)) return VX_ERR_ARG;
+    busp::Lowered lo;
+    busp::lower(*in, *bus, n_msgs, &lo);
+    vx_air_program all = *in;  // the program's own constraints, then the bus block
+    all.code = lo.code.data(), all.n_code = (uint32_t)lo.code.size(), all.consts = lo.consts.data(), all.n_consts = (uint32_t)lo.consts.size(), all.n_regs = lo.n_regs;
+    return airp_register(&all, bus, lo.n_help, air_id, err, errlen);
 }
 int32_t vx_air_unregister(int air_id) {
     std::lock_guard<std::mutex> lk(g_airp_mu);

@@ -28,7 +28,7 @@ SYMBOLS = [
     "vx_ed25519_verify_batch", "vx_verify_simple_justification", "vx_sha_chain_trace",
     "vx_verify_epoch_end_header", "vx_rotate_proof_bound", "vx_rotate_prove", "vx_rotate_verify",
     "vx_gather_proofs", "vx_quotient_eval", "vx_quotient_eval_aux", "vx_decode_header_batch", "vx_decode_precommit_batch", "vx_stark_aux_trace",
-    "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_unregister", "vx_poseidon_air_trace",
+    "vx_ed_trace", "vx_sha512_trace", "vx_epoch_end_trace", "vx_partial_products", "vx_air_register", "vx_air_register_bus", "vx_air_unregister", "vx_poseidon_air_trace",
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
     "vx_fri_fold_air_trace", "vx_fri_fold_proof_bound", "vx_fri_fold_prove", "vx_fri_fold_verify", "vx_stark_fri_claims",
@@ -93,6 +93,14 @@ class AirProgramStruct(C.Structure):  # include/vx.h vx_air_program
                 ("code", C.c_void_p), ("n_code", C.c_uint32), ("aux_cols", C.c_uint32), ("n_challenges", C.c_uint32), ("n_aux_public", C.c_uint32),
                 ("gen_aux", C.c_void_p), ("gen_aux_user", C.c_void_p)]
 
+
+class AirBusStruct(C.Structure):  # include/vx.h vx_air_bus
+    _fields_ = [("code", C.c_void_p), ("n_code", C.c_uint32), ("consts", C.c_void_p), ("n_consts", C.c_uint32), ("n_regs", C.c_uint32),
+                ("block_log", C.c_uint32), ("step_periodic", C.c_int32)]
+
+
+VX_BUSP_SLOT, VX_BUSP_MSG = 64, 65
+VX_BUSP_LOWER_REGS, VX_BUSP_MAX_REGS, VX_BUSP_MAX_HELPERS, VX_BUSP_MAX_CODE = 20, 12, 19, 1 << 14
 
 # include/vx.h vx_air_gen_aux_fn: (user, ctx, trace vx_buf*, log_n, challenges, public inputs, aux_out vx_buf*, aux_public_out) -> int32
 AIR_GEN_AUX_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64))
@@ -177,7 +185,8 @@ def load_library():
         "vx_decode_header_batch": [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp],
         "vx_decode_precommit_batch": [vp, vp, sz, vp, vp, vp, vp, vp],
         "vx_stark_aux_trace": [vp, C.c_int, vp, C.c_int, vp, sz, vp, sz, vp, vp],
-        "vx_air_register": [C.POINTER(AirProgramStruct), C.POINTER(C.c_int), C.c_char_p, sz], "vx_air_unregister": [C.c_int],
+        "vx_air_register": [C.POINTER(AirProgramStruct), C.POINTER(C.c_int), C.c_char_p, sz],
+        "vx_air_register_bus": [C.POINTER(AirProgramStruct), C.POINTER(AirBusStruct), C.POINTER(C.c_int), C.c_char_p, sz], "vx_air_unregister": [C.c_int],
         "vx_poseidon_air_trace": [vp, vp, sz, vp],
         "vx_merkle_open_air_trace": [vp, vp, vp, sz, C.c_int, vp, vp],
         "vx_merkle_openings_proof_bound": [C.POINTER(StarkConfig), sz, sz, C.POINTER(sz)],
@@ -267,7 +276,7 @@ def stark_verify(proof, cfg=None, expect_air=0, expect_public=None):
     _host_verify("vx_stark_verify", cfg, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size)
 
 
-def air_register(cols, n_public, code, consts=(), periodic=(), n_regs=None, aux_cols=0, n_challenges=0, n_aux_public=0, gen_aux=None):
+def air_register(cols, n_public, code, consts=(), periodic=(), n_regs=None, aux_cols=0, n_challenges=0, n_aux_public=0, gen_aux=None, _bus=None):
     """Register a constraint program (include/vx.h vx_air_register; no GPU needed) and return its AIR id.
     code: uint64 instruction words; consts: canonical field elements; periodic: a list of columns, each 2^k values;
     n_regs: registers used (default: the highest register the code names + 1).  air_program.AirBuilder writes these.
@@ -307,10 +316,31 @@ def air_register(cols, n_public, code, consts=(), periodic=(), n_regs=None, aux_
                           _ptr(consts) if consts.size else None, consts.size, _ptr(code) if code.size else None, code.size,
                           aux_cols, n_challenges, n_aux_public, C.cast(cb, C.c_void_p) if cb is not None else None, None)
     air_id, err = C.c_int(0), C.create_string_buffer(256)
-    rc = L.vx_air_register(C.byref(st), C.byref(air_id), err, 256)
+    if _bus is None:
+        rc = L.vx_air_register(C.byref(st), C.byref(air_id), err, 256)
+    else:
+        bcode, bconsts = np.ascontiguousarray(_bus["code"], dtype=np.uint64), np.ascontiguousarray(_bus["consts"], dtype=np.uint64)
+        bregs = _bus["n_regs"]
+        if bregs is None:
+            bregs = 1 + max([int((w >> 8) & 0xFF) for w in bcode.tolist() if int(w & 0xFF) < VX_BUSP_SLOT] + [int((w >> 16) & 0xFFFF) for w in bcode.tolist() if int(w & 0xFF) >= VX_BUSP_SLOT] + [0])
+        bs = AirBusStruct(_ptr(bcode) if bcode.size else None, bcode.size, _ptr(bconsts) if bconsts.size else None, bconsts.size, bregs, _bus["block_log"], _bus["step_periodic"])
+        rc = L.vx_air_register_bus(C.byref(st), C.byref(bs), C.byref(air_id), err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
     return air_id.value
+
+
+def air_register_bus(cols, n_public, code, bus_code, consts=(), bus_consts=(), periodic=(), n_regs=None, bus_n_regs=None, block_log=0, step_periodic=-1, aux_cols=None,
+                     n_challenges=4, n_aux_public=1, gen_aux=None):
+    """Register a constraint program that DECLARES its bus messages (include/vx.h vx_air_register_bus; no GPU needed) and return its AIR
+    id.  bus_code / bus_consts: the message program (VX_BUSP_SLOT / VX_BUSP_MSG close its messages; air_program.AirBuilder.assemble_bus
+    writes it).  The library appends the helper and running-sum constraints to `code` and fills the auxiliary round on the GPU: there is
+    no callback (gen_aux is here only so that a caller sees the library refuse it).  aux_cols defaults to what the message count implies."""
+    if aux_cols is None:
+        n_msgs = sum(1 for w in np.asarray(bus_code, dtype=np.uint64).tolist() if int(w & 0xFF) == VX_BUSP_MSG)
+        aux_cols = 2 * ((n_msgs + 1) // 2) + 2
+    bus = dict(code=bus_code, consts=bus_consts, n_regs=bus_n_regs, block_log=block_log, step_periodic=step_periodic)
+    return air_register(cols, n_public, code, consts, periodic, n_regs, aux_cols, n_challenges, n_aux_public, gen_aux, _bus=bus)
 
 
 def air_unregister(air_id):

@@ -160,7 +160,8 @@ typedef struct vx_stark_config {
 } vx_stark_config;
 /* The AIRs of the statements are COMPILED INTO the library: 1 Fibonacci and 2 "cubic mixer" pin the
  * generic prover, 5 is the smallest AIR with an auxiliary (lookup / logUp) commitment round.  A host can add its own at run
- * time as a constraint PROGRAM (vx_air_register below; no auxiliary round).  The tables of the
+ * time as a constraint PROGRAM (vx_air_register below; its auxiliary round is filled by a host callback, or on the GPU from
+ * declared bus messages: vx_air_register_bus).  The tables of the
  * header_range / rotate statements, each declared with its trace generator below: 6 Blake2b header chain
  * (VX_AIR_BLAKE_CHAIN), 4 SHA-256 authority-set commitment (VX_AIR_SHA_CHAIN), 7 / 8 / 9 SHA-256 Merkle trees of 256 /
  * 512 / 16 leaves, 10 / 12 Ed25519 (2^17 / 2^16 rows), 11 / 14 / 13 SHA-512 (2^16 / 2^15 / 2^10 rows), 15 epoch-end log.
@@ -219,6 +220,39 @@ typedef struct vx_air_program {
 } vx_air_program;
 int32_t vx_air_register(const vx_air_program* program, int* air_id, char* err, size_t errlen);
 int32_t vx_air_unregister(int air_id);
+/* BUS MESSAGES of a run-time AIR: instead of writing the logUp block of its constraints by hand and filling the auxiliary round
+ * in a callback, a program may DECLARE the messages its rows send and receive, as the compiled bus tables do (csrc/air.cuh "the
+ * bus of a table").  From the one declaration vx_air_register_bus derives the helper constraints and the running-sum constraint
+ * (appended to the program's own, as ordinary instructions) and the GPU fills the auxiliary columns and the published total
+ * (k_bus_aux_prog); there is no callback.
+ * The MESSAGE PROGRAM is straight-line register code in the instruction word above, over a register file of its own (n_regs <=
+ * VX_BUSP_MAX_REGS: registration lowers it into the 32 registers of a constraint program and keeps VX_BUSP_LOWER_REGS of them for
+ * denominators and helpers), with a constant table of its own.  It admits LOC (main columns only), PER, PUB, CONST, ADD, SUB, MUL and
+ *   BUSP_SLOT d, a   slot d (0..3) of the next message = r[a]; a slot that is not set is absent (contributes 0)
+ *   BUSP_MSG a, b    closes the message: tag b (a constant below 2^16), signed multiplicity r[a] (sent m, received 0 - m); clears the slots
+ * A message (t0, t1, t2, t3, tag) has the denominator D = beta + t0 + gamma t1 + gamma^2 t2 + gamma^3 t3 + gamma^4 tag in
+ * F[X]/(X^2 - 7), beta = challenges (0, 1), gamma = challenges (2, 3).  Messages pair up in program order: messages 2e and 2e + 1
+ * share helper e = m_a / D_a + m_b / D_b (an odd count leaves the last helper with one message).  With N_HELP = ceil(messages / 2)
+ * the auxiliary layout is the compiled tables': helper e at auxiliary columns 2e, 2e + 1, the running sum at 2 N_HELP, 2 N_HELP + 1;
+ * the program must declare aux_cols = 2 N_HELP + 2, n_challenges = 4, n_aux_public = 1 (total / rows) and no gen_aux.
+ * block_log = 0: one set of helpers per row, the sum advances on every row (step_periodic < 0).  block_log = 5: one set per block of
+ * 32 rows, read from the block's first row and written to all 32, and the sum advances where periodic column step_periodic is 1
+ * (period 32; 1 at position 0, 0 elsewhere).  No other block_log is supported.
+ * The appended constraints, in order: per helper the two halves of h D_a D_b - m_a D_b - m_b D_a (h D - m for a single message),
+ * then the two halves of z' - z - sum h [* per[step]] + total, all as ASSERT.  The degree rules above apply to them: with two messages to
+ * a helper a slot has degree at most 1 and a multiplicity at most 2. */
+enum { VX_BUSP_SLOT = 64, VX_BUSP_MSG = 65 };
+enum { VX_BUSP_LOWER_REGS = 20, VX_BUSP_MAX_REGS = 12, VX_BUSP_MAX_HELPERS = 19, VX_BUSP_MAX_CODE = 1 << 14 };
+typedef struct vx_air_bus {
+    const uint64_t* code;   /* the message program */
+    uint32_t n_code;
+    const uint64_t* consts;
+    uint32_t n_consts;
+    uint32_t n_regs;
+    uint32_t block_log;     /* 0 or 5 */
+    int32_t step_periodic;  /* block_log 5: the periodic column that is 1 on a block's first row; block_log 0: negative */
+} vx_air_bus;
+int32_t vx_air_register_bus(const vx_air_program* program, const vx_air_bus* bus, int* air_id, char* err, size_t errlen);
 /* The witness of PoseidonAir -- the Poseidon permutation as a STARK table (0-kno-vectorx_amd/air_library.py poseidon_builder: 48
  * columns, one round per row, 32 rows per permutation; the constraint program ships with the library and is registered by the
  * host): states = n_perm x 12 input words, trace_out = [48][32 * n_perm] column-major with the state, x^2, x^4 and x^7 of every

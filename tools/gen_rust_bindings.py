@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 BASE = {"int32_t": "i32", "int": "c_int", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "char": "c_char",
         "float": "f32", "void": "c_void", "vx_ctx": "VxCtx", "vx_buf": "VxBuf", "vx_tree": "VxTree", "vx_stark_config": "VxStarkConfig",
-        "vx_justification": "VxJustification", "vx_hr_exchange": "VxHrExchange", "vx_air_program": "VxAirProgram"}
+        "vx_justification": "VxJustification", "vx_hr_exchange": "VxHrExchange", "vx_air_program": "VxAirProgram", "vx_air_bus": "VxAirBus"}
 
 
 def declarations():
@@ -65,6 +65,8 @@ def block():
              "    /// the host's generator of the auxiliary (lookup) columns, called between the trace cap and the constraint challenges",
              "    pub gen_aux: Option<unsafe extern \"C\" fn(user: *mut c_void, ctx: *mut VxCtx, trace: *const VxBuf, log_n: c_int, challenges: *const u64, public_inputs: *const u64, aux_out: *mut VxBuf, aux_public_out: *mut u64) -> i32>,",
              "    pub gen_aux_user: *mut c_void,", "}",
+             "/// the declared bus messages of a run-time AIR for vx_air_register_bus: the message program the library derives constraints and witness from",
+             "#[repr(C)] pub struct VxAirBus { pub code: *const u64, pub n_code: u32, pub consts: *const u64, pub n_consts: u32, pub n_regs: u32, pub block_log: u32, pub step_periodic: i32 }",
              "#[repr(C)] pub struct VxHrExchange { pub func: Option<unsafe extern \"C\" fn(user: *mut c_void, words: *mut u64, n_words: usize) -> i32>, pub user: *mut c_void }",
              '#[link(name = "vxprove")]', 'extern "C" {']
     for ret, name, args in declarations():
