@@ -359,6 +359,28 @@ int32_t vx_transcript_trace_dev(vx_ctx* ctx, const glh::TranscriptRecord* chains
 // (the query phase is walked) or its head alone (the indices are derived, no record is read)
 int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen);
 
+// ---- bus-group blob (written by vx_bus_group_prove in vx_bus_group.hip, read by vx_bus_group_verify in vx_verify.hip): magic, the
+// number of tables, one length per proof, the proofs in bus order.  No AIR id: registered ids are per process, the verifier states its own.
+static const uint64_t VX_BGRP_MAGIC = 0x3130505247425856ULL;  // "VXBGRP01"
+static constexpr size_t VX_BGRP_HDR = 2;                      // before the lengths
+// What a generic group needs to know of an AIR, compiled or registered (vx_verify.hip: the host file holds both registries)
+struct AirProgram;
+struct BusAirShape {
+    int cols = 0, pub = 0, aux = 0, chal = 0, auxpub = 0;
+    const AirProgram* prog = nullptr;  // a registered program
+};
+bool vx_air_bus_shape(int air_id, BusAirShape* out);
+// The admission rules of a generic group, stated once for bound, prover, check and verifier: 1 .. VX_BUS_GROUP_MAX_TABLES tables, every
+// one a known AIR with a logUp round of 4 challenges and one published total and at most BusMeet::MAX_PUB public inputs (n_public
+// may be nullptr: not stated).  VX_ERR_ARG with the reason, naming the table.  shapes (optional): [n]
+int32_t vx_bus_group_admit(const int32_t* air_ids, const size_t* n_public, size_t n, BusAirShape* shapes, char* err, size_t errlen);
+// the outside messages of a generic group: canonical words, tags below 2^16.  `code` is what a refusal returns (the prover's
+// VX_ERR_ARG, the verifier's VX_ERR_STATEMENT)
+int32_t vx_bus_outside_ok(const uint64_t* outside, size_t n_outside, int32_t code, char* err, size_t errlen);
+// Does the bus of these proofs close against the outside messages?  The published totals x rows under the proofs' shared challenges
+// plus sum m / D -- nothing is verified.  VX_ERR_STATEMENT with the reason when it does not (or a proof is too short to read).
+int32_t vx_bus_group_closes(const vx_stark_config* cfg, const uint64_t* const* proofs, const size_t* lens, size_t n, const uint64_t* outside, size_t n_outside, char* err, size_t errlen);
+
 static constexpr uint32_t VX_MAX_HEADER_SIZE = 35840;  // consts.rs:16
 static inline void be_limbs(const uint8_t h[32], uint64_t out[8]) {
     for (int j = 0; j < 8; ++j)

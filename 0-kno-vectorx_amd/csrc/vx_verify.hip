@@ -544,10 +544,11 @@ static bool peek_tables(const vx_stark_config* cfg, BusTable* t, size_t n) {
 using VBus = bus::Bus<X2<Fx>>;
 struct BusMessages {
     std::vector<X2<Fx>> den;
-    std::vector<uint8_t> sent;
-    void reserve(size_t n) { den.reserve(n), sent.reserve(n); }
-    void receive(const X2<Fx>& d) { den.push_back(d), sent.push_back(0); }
-    void send(const X2<Fx>& d) { den.push_back(d), sent.push_back(1); }
+    std::vector<uint64_t> mult;  // what the message adds to the right-hand side, in units of 1 / D: a canonical field word
+    void reserve(size_t n) { den.reserve(n), mult.reserve(n); }
+    void put(const X2<Fx>& d, uint64_t m) { den.push_back(d), mult.push_back(m); }
+    void receive(const X2<Fx>& d) { put(d, 1); }
+    void send(const X2<Fx>& d) { put(d, glh::P - 1); }
     // What the aggregation verifiers say about a query phase, each stated once.  The root a path ended in with the tree's depth,
     // in its two halves: the tables do not know which root belongs to which tree, the verifier does
     void receive_root(const VBus& bus, uint64_t tree, const uint64_t root[4], int depth) {
@@ -566,7 +567,7 @@ struct BusMessages {
     }
 };
 using BusOutside = std::function<void(const VBus&, BusMessages&)>;
-// sum over the messages of +- 1 / D with ONE inversion (Montgomery batch: prefix products, one inverse, walked back); false when
+// sum over the messages of mult / D (a received message counts + 1 / D, a sent one - 1 / D) with ONE inversion (Montgomery batch: prefix products, one inverse, walked back); false when
 // the product of the denominators is zero
 static bool bus_messages_sum(const BusMessages& m, X2<Fx>* sum) {
     const Fx zero{0, 0};
@@ -582,7 +583,8 @@ static bool bus_messages_sum(const BusMessages& m, X2<Fx>* sum) {
     X2<Fx> inv{prod.a * ni, (zero - prod.b) * ni};
     for (size_t k = n; k-- > 0;) {
         const X2<Fx> t = k ? inv * pre[k - 1] : inv;
-        *sum = m.sent[k] ? *sum - t : *sum + t;
+        const uint64_t mu = m.mult[k];
+        *sum = mu == 1 ? *sum + t : mu == glh::P - 1 ? *sum - t : *sum + t * Fx{mu, 0};
         inv = inv * m.den[k];
     }
     return true;
@@ -1446,4 +1448,95 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
         }
     });
 }
+}
+
+// ---- the generic bus group (include/vx.h "A generic bus group"; the prover is vx_bus_group.hip).  The verifier states its own AIR
+// ids and public inputs -- the blob carries neither -- and the outside party's messages as words (t0, t1, t2, t3, tag, m): m is the
+// party's own signed multiplicity (sent m, received 0 - m), so the right-hand side of verify_bus_group gets 0 - m per message.
+bool vx_air_bus_shape(int air_id, BusAirShape* out) {
+    for (const AirV& a : AIRS_V)
+        if (a.id == air_id) {
+            *out = {a.cols, a.pub, a.aux, a.chal, a.auxpub, nullptr};
+            return true;
+        }
+    if (air_id >= VX_AIR_USER_BASE)
+        if (const AirProgram* pg = vx_air_program_find(air_id)) {
+            *out = {(int)pg->cols, (int)pg->pub, (int)pg->aux, (int)pg->chal, (int)pg->auxpub, pg};
+            return true;
+        }
+    return false;
+}
+int32_t vx_bus_group_admit(const int32_t* air_ids, const size_t* n_public, size_t n, BusAirShape* shapes, char* err, size_t errlen) {
+    AIRP_NEED(n >= 1 && n <= (size_t)VX_BUS_GROUP_MAX_TABLES, "bus group: %zu tables (1..%d)", n, (int)VX_BUS_GROUP_MAX_TABLES);
+    for (size_t k = 0; k < n; ++k) {
+        BusAirShape sh;
+        AIRP_NEED(vx_air_bus_shape(air_ids[k], &sh), "bus group: table %zu names no AIR (%d)", k, air_ids[k]);
+        AIRP_NEED(sh.aux > 0 && sh.chal == 4 && sh.auxpub == 1, "bus group: table %zu (air %d) has no logUp round of 4 challenges and one total", k, air_ids[k]);
+        if (n_public) AIRP_NEED(n_public[k] <= (size_t)BusMeet::MAX_PUB, "bus group: table %zu has %zu public inputs (at most %d)", k, n_public[k], BusMeet::MAX_PUB);
+        if (shapes) shapes[k] = sh;
+    }
+    return VX_OK;
+}
+int32_t vx_bus_outside_ok(const uint64_t* outside, size_t n_outside, int32_t code, char* err, size_t errlen) {
+    if (n_outside && !outside) return v_fail(code, err, errlen, "bus group: %zu outside messages and no words", n_outside);
+    for (size_t i = 0; i < n_outside; ++i) {
+        const uint64_t* w = outside + i * VX_BUS_MSG_WORDS;
+        for (int j = 0; j < VX_BUS_MSG_WORDS; ++j)
+            if (w[j] >= glh::P) return v_fail(code, err, errlen, "bus group: outside message %zu has a non-canonical word at %d", i, j);
+        if (w[4] >> 16) return v_fail(code, err, errlen, "bus group: outside message %zu has a tag of 2^16 or more", i);
+    }
+    return VX_OK;
+}
+// the outside party of a generic group from its words
+static BusOutside bus_outside_words(const uint64_t* outside, size_t n_outside) {
+    return [=](const VBus& bus, BusMessages& m) {
+        m.reserve(n_outside);
+        for (size_t i = 0; i < n_outside; ++i) {
+            const uint64_t* w = outside + i * VX_BUS_MSG_WORDS;
+            if (w[5]) m.put(bus.denom(bus.beta, Fx{w[0], 0}, Fx{w[1], 0}, Fx{w[2], 0}, Fx{w[3], 0}, Fx{w[4], 0}), glh::sub(0, w[5]));
+        }
+    };
+}
+int32_t vx_bus_group_closes(const vx_stark_config* cfg, const uint64_t* const* proofs, const size_t* lens, size_t n, const uint64_t* outside, size_t n_outside, char* err, size_t errlen) {
+    std::vector<BusTable> tab(n);
+    for (size_t k = 0; k < n; ++k) tab[k].proof = proofs[k], tab[k].len = lens[k];
+    NEED(peek_tables(cfg, tab.data(), n), "bus group: a proof is too short to hold a trace cap");
+    std::vector<const uint64_t*> pubs(n), caps(n);
+    std::vector<size_t> n_pubs(n);
+    for (size_t k = 0; k < n; ++k) pubs[k] = tab[k].pub, n_pubs[k] = tab[k].n_pub, caps[k] = tab[k].cap;
+    const size_t cw = (size_t)4 << cfg->cap_height;
+    uint64_t chal[4], bus[2] = {0, 0};
+    stark_proof::shared_challenges_n(pubs.data(), n_pubs.data(), caps.data(), n, cw, chal, 4);
+    for (size_t k = 0; k < n; ++k) {  // (an admitted table has an auxiliary round: its total follows the trace cap)
+        NEED(tab[k].len >= (size_t)(tab[k].cap - tab[k].proof) + cw + 2 && tab[k].proof[2] < 64, "bus group: a proof is too short to hold its total");
+        for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(tab[k].cap[cw + q] % glh::P, ((uint64_t)1 << tab[k].proof[2]) % glh::P));
+    }
+    BusMessages msgs;
+    bus_outside_words(outside, n_outside)(VBus(Fx{chal[0], 0}, Fx{chal[1], 0}, Fx{chal[2], 0}, Fx{chal[3], 0}), msgs);
+    X2<Fx> sum;
+    NEED(bus_messages_sum(msgs, &sum), "bus group: an outside message has a zero denominator under the challenges");
+    NEED(sum.a.b == 0 && sum.b.b == 0 && bus[0] == sum.a.a && bus[1] == sum.b.a, "bus group: the bus does not close (the tables' totals and the outside messages do not cancel)");
+    return VX_OK;
+}
+extern "C" int32_t vx_bus_group_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const vx_bus_expect* expect, size_t n, const uint64_t* outside, size_t n_outside,
+                                       char* err, size_t errlen) {
+    if (!cfg || !blob || !expect) return VX_ERR_ARG;
+    int32_t ids[VX_BUS_GROUP_MAX_TABLES];
+    size_t n_pub[VX_BUS_GROUP_MAX_TABLES];
+    for (size_t k = 0; k < n && k < (size_t)VX_BUS_GROUP_MAX_TABLES; ++k) ids[k] = expect[k].air_id, n_pub[k] = expect[k].n_public;
+    BusAirShape shape[VX_BUS_GROUP_MAX_TABLES];
+    VX_TRY(vx_bus_group_admit(ids, n_pub, n, shape, err, errlen));
+    static const uint64_t no_words[1] = {0};
+    for (size_t k = 0; k < n; ++k) {  // (the public inputs are always compared: an AIR without any is compared with none)
+        if (expect[k].n_public && !expect[k].public_inputs) return VX_ERR_ARG;
+        NEED(expect[k].n_public == (size_t)shape[k].pub, "bus group: table %zu (air %d) takes %d public inputs, %zu expected", k, ids[k], shape[k].pub, expect[k].n_public);
+    }
+    VX_TRY(vx_bus_outside_ok(outside, n_outside, VX_ERR_STATEMENT, err, errlen));
+    NEED(len >= VX_BGRP_HDR && blob[0] == VX_BGRP_MAGIC, "bad bus-group blob");
+    NEED(blob[1] == n, "blob is for a different request (%llu tables, %zu expected)", (unsigned long long)blob[1], n);
+    BusTable tab[VX_BUS_GROUP_MAX_TABLES];
+    VX_TRY(read_blob(blob, len, VX_BGRP_MAGIC, "bus-group", {(uint64_t)n}, tab, n, err, errlen));
+    NEED(peek_tables(cfg, tab, n), "a proof is too short to hold a trace cap");
+    for (size_t k = 0; k < n; ++k) tab[k].expect(expect[k].air_id, expect[k].n_public ? expect[k].public_inputs : no_words, expect[k].n_public);
+    return verify_bus_group(cfg, tab, n, "the lookup bus does not balance", err, errlen, bus_outside_words(outside, n_outside));
 }

@@ -1,4 +1,5 @@
 """ctypes binding of libvxprove.so (C ABI: include/vx.h)."""
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -38,6 +39,7 @@ SYMBOLS = [
     "vx_stark_merkle_claims", "vx_merkle_paths_air_trace", "vx_leaf_sponge_rows_air_trace", "vx_stark_openings_proof_bound", "vx_stark_openings_prove", "vx_stark_openings_verify",
     "vx_leaf_noop_air_trace", "vx_stark_queries_proof_bound", "vx_stark_queries_prove", "vx_stark_queries_verify", "vx_stark_proof_head_words",
     "vx_transcript_air_trace", "vx_stark_transcript_claims", "vx_stark_transcripts_proof_bound", "vx_stark_transcripts_prove", "vx_stark_transcripts_verify",
+    "vx_bus_group_proof_bound", "vx_bus_group_prove", "vx_bus_group_verify", "vx_bus_group_check",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -99,6 +101,20 @@ class AirBusStruct(C.Structure):  # include/vx.h vx_air_bus
                 ("block_log", C.c_uint32), ("step_periodic", C.c_int32)]
 
 
+class BusTableStruct(C.Structure):  # include/vx.h vx_bus_table
+    _fields_ = [("air_id", C.c_int32), ("log_n", C.c_int32), ("trace", C.c_void_p), ("public_inputs", C.c_void_p), ("n_public", C.c_size_t)]
+
+
+class BusExpectStruct(C.Structure):  # include/vx.h vx_bus_expect
+    _fields_ = [("air_id", C.c_int32), ("public_inputs", C.c_void_p), ("n_public", C.c_size_t)]
+
+
+class BusUnmatchedStruct(C.Structure):  # include/vx.h vx_bus_unmatched
+    _fields_ = [("n_unmatched", C.c_uint64), ("table", C.c_int32), ("message", C.c_uint32), ("row", C.c_uint64), ("net", C.c_uint64)]
+
+
+VX_BUS_GROUP_MAX_TABLES, VX_BUS_MSG_WORDS = 16, 6
+BusUnmatched = collections.namedtuple("BusUnmatched", "n_unmatched table message row net")  # what Context.bus_group_check reports
 VX_BUSP_SLOT, VX_BUSP_MSG = 64, 65
 VX_BUSP_LOWER_REGS, VX_BUSP_MAX_REGS, VX_BUSP_MAX_HELPERS, VX_BUSP_MAX_CODE = 20, 12, 19, 1 << 14
 
@@ -231,6 +247,10 @@ def load_library():
         "vx_stark_transcripts_proof_bound": [C.POINTER(StarkConfig), vp, vp, sz, vp, C.POINTER(sz)],
         "vx_stark_transcripts_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, vp, vp, sz, C.POINTER(sz)],
         "vx_stark_transcripts_verify": [C.POINTER(StarkConfig), vp, sz, vp, vp, sz, vp, C.c_char_p, sz],
+        "vx_bus_group_proof_bound": [C.POINTER(StarkConfig), C.POINTER(BusTableStruct), sz, C.POINTER(sz)],
+        "vx_bus_group_prove": [vp, C.POINTER(StarkConfig), C.POINTER(BusTableStruct), sz, vp, sz, vp, sz, C.POINTER(sz)],
+        "vx_bus_group_verify": [C.POINTER(StarkConfig), vp, sz, C.POINTER(BusExpectStruct), sz, vp, sz, C.c_char_p, sz],
+        "vx_bus_group_check": [vp, C.POINTER(BusTableStruct), sz, vp, sz, C.POINTER(BusUnmatchedStruct)],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -688,6 +708,68 @@ def stark_combine_claims(proof, cfg=None):
     c, Q = cm.value + ca.value, n.value
     return dict(log_lde=log_lde.value, cm=cm.value, ca=ca.value, nq=nq.value, alpha=alpha, zeta=zeta, open_local=op[: 2 * c].reshape(c, 2), open_next=op[2 * c: 4 * c].reshape(c, 2),
                 open_quot=op[4 * c: 4 * c + 2 * nq.value].reshape(-1, 2), index=index[:Q], ev0=ev0[: 2 * Q].reshape(Q, 2), rows=rows[: Q * (c + nq.value)].reshape(Q, c + nq.value))
+
+
+BGRP_MAGIC, BGRP_HDR = 0x3130505247425856, 2  # "VXBGRP01": magic, the number of tables, one length per proof; then the proofs in bus order
+
+
+def _outside(outside):
+    """the outside messages of a generic bus group as contiguous [n][VX_BUS_MSG_WORDS] words (t0, t1, t2, t3, tag, m)"""
+    o = np.ascontiguousarray(outside, dtype=np.uint64).reshape(-1, VX_BUS_MSG_WORDS) if len(outside) else np.zeros((0, VX_BUS_MSG_WORDS), dtype=np.uint64)
+    return o
+
+
+def _bus_tables(tables):
+    """[(air_id, trace Buffer or None, log_n, public inputs)] -> (the vx_bus_table array, what it points to)"""
+    pubs = [np.ascontiguousarray(t[3], dtype=np.uint64).reshape(-1) for t in tables]
+    arr = (BusTableStruct * max(len(tables), 1))()
+    for k, (t, pub) in enumerate(zip(tables, pubs)):
+        arr[k] = BusTableStruct(int(t[0]), int(t[2]), t[1].h.value if t[1] is not None else None, pub.ctypes.data if pub.size else None, pub.size)
+    return arr, pubs
+
+
+def bus_group_proof_bound(tables, cfg=None):
+    """The words a vx_bus_group_prove blob of `tables` = [(air_id, trace or None, log_n, public inputs)] needs at most (no GPU needed;
+    only the AIR ids and the row counts are read).  A table that is not admitted is a VxError (VX_ERR_ARG) naming it."""
+    cfg = cfg or default_stark_config()
+    L = load_library()
+    arr, _keep = _bus_tables(tables)
+    need = C.c_size_t(0)
+    rc = L.vx_bus_group_proof_bound(C.byref(cfg), arr, len(tables), C.byref(need))
+    if rc != 0:
+        if not 1 <= len(tables) <= VX_BUS_GROUP_MAX_TABLES:
+            raise VxError(rc, "bus group: %d tables (1..%d)" % (len(tables), VX_BUS_GROUP_MAX_TABLES))
+        for k, t in enumerate(tables):  # the bound has no buffer for a reason: ask for every table alone
+            one, _k = _bus_tables([t])
+            if L.vx_bus_group_proof_bound(C.byref(cfg), one, 1, C.byref(need)) != 0:
+                raise VxError(rc, "bus group: table %d (air %d, 2^%d rows) is not admitted: an unknown AIR, one without a logUp round of 4 challenges and one total, or rows out of range"
+                              % (k, t[0], t[2]))
+        raise VxError(rc, "bus group: no proof bound for these tables")
+    return need.value
+
+
+def bus_group_verify(blob, expect, cfg=None, outside=()):
+    """Host-side check of a vx_bus_group_prove blob: expect = [(air_id, public inputs)] in bus order -- the verifier states its own AIR
+    ids, the blob carries none --, outside = the messages [(t0, t1, t2, t3, tag, m)] of the party that is not a table (m: sent m,
+    received P - m).  Raises VxError with the reason."""
+    b = _words(blob)
+    pubs = [np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1) for _, pub in expect]
+    arr = (BusExpectStruct * max(len(expect), 1))()
+    for k, ((air_id, _), pub) in enumerate(zip(expect, pubs)):
+        arr[k] = BusExpectStruct(int(air_id), pub.ctypes.data if pub.size else None, pub.size)
+    o = _outside(outside)
+    _host_verify("vx_bus_group_verify", cfg, b, b.size, arr, len(expect), o if o.size else None, o.shape[0])
+
+
+def split_bus_group(blob):
+    """-> the proofs of a vx_bus_group_prove blob, in bus order"""
+    n = int(blob[1])
+    out, off = [], BGRP_HDR + n
+    for k in range(n):
+        ln = int(blob[BGRP_HDR + k])
+        out.append(blob[off: off + ln])
+        off += ln
+    return tuple(out)
 
 
 ROT_HDR = 28  # words before the first proof in a rotate blob
@@ -1149,6 +1231,29 @@ class Context:
         out = np.empty(need.value, dtype=np.uint64)
         self._ck(self.L.vx_stark_prove(self.h, air_id, C.byref(cfg), trace_buf.h, log_n, _ptr(pub), pub.size, _ptr(out), out.size, C.byref(need)))
         return out[: need.value]
+
+    def bus_group_prove(self, tables, cfg=None, outside=(), out=None):
+        """Proves tables = [(air_id, trace Buffer, log_n, public inputs)] together on one logUp bus, in that order, under shared lookup
+        challenges -> blob words (lib.bus_group_verify checks it).  outside: the messages of the party that is not a table.  When every
+        table has a message list the bus balance is checked on the device first: VX_ERR_STATEMENT names what has no partner."""
+        arr, _keep = _bus_tables(tables)
+        o = _outside(outside)
+        cfg = cfg or self.stark_config()
+        if out is None:
+            need = C.c_size_t(0)  # (tables that have no bound are not admitted: the prover says why)
+            rc = self.L.vx_bus_group_proof_bound(C.byref(cfg), arr, len(tables), C.byref(need))
+            out = np.empty(need.value if rc == 0 else 1, dtype=np.uint64)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_bus_group_proof_bound(c, arr, len(tables), need), "bus group: no proof bound for these tables",
+                                lambda c, b, need: self.L.vx_bus_group_prove(self.h, c, arr, len(tables), _ptr(o) if o.size else None, o.shape[0], _ptr(b), b.size, need))
+
+    def bus_group_check(self, tables, outside=()):
+        """The bus balance of tables (as bus_group_prove takes them) and outside messages on the device, nothing proven: None when
+        the bus closes, else a BusUnmatched (n_unmatched, table, message, row, net) naming the lowest message without a partner."""
+        arr, _keep = _bus_tables(tables)
+        o = _outside(outside)
+        u = BusUnmatchedStruct()
+        self._ck(self.L.vx_bus_group_check(self.h, arr, len(tables), _ptr(o) if o.size else None, o.shape[0], C.byref(u)))
+        return None if u.n_unmatched == 0 else BusUnmatched(int(u.n_unmatched), int(u.table), int(u.message), int(u.row), int(u.net))
 
     def stark_aux_trace(self, air_id, trace_buf, log_n, challenges, n_aux_cols, public_inputs=()):
         """The auxiliary (logUp) columns of an AIR for given lookup challenges -> (Buffer [n_aux_cols][2^log_n], published values)."""

@@ -606,6 +606,58 @@ int32_t vx_stark_transcripts_prove(vx_ctx* ctx, const vx_stark_config* cfg, cons
                                    uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* const* proofs, const size_t* lens, size_t n,
                                     const uint64_t* const* ext_chals, char* err, size_t errlen);
+/* ---- A generic bus group: ANY tables on one logUp bus, proven together under shared lookup challenges (csrc/vx_bus_group.hip; the
+ * verifier in csrc/vx_verify.hip).  What the fixed group provers above are for their lists of tables, for a list the caller states:
+ * compiled tables, run-time tables (vx_air_register_bus), or both.  The traces exist already (the *_air_trace entry points, or the
+ * host's own); the group proves them in the order given, which is the order of the shared-challenge transcript.
+ * ADMITTED is any AIR id, compiled or registered, whose auxiliary round takes 4 lookup challenges and publishes 1 value (total /
+ * rows): every bus table of the library and every vx_air_register_bus program.  VX_ERR_ARG, naming the table: an unknown id, an AIR
+ * without such a round (it would never reach the rendezvous), n_public above 32, n = 0 or n > VX_BUS_GROUP_MAX_TABLES, a trace that
+ * is not cols << log_n words.  (Every table runs on a context of its own, chained behind `ctx`; the chain has no fixed length, so
+ * the limit is the one chosen here.)
+ * OUTSIDE MESSAGES: the messages of the party that is not a table -- the verifier of an aggregation proof, which holds the claims.
+ * Each is VX_BUS_MSG_WORDS canonical words (t0, t1, t2, t3, tag, m): the tag below 2^16, an absent slot 0, m the signed
+ * multiplicity as a field word with the sign of BUSP_MSG (sent m, received 0 - m).  n_outside = 0 states a closed bus.  The bus
+ * closes when   sum over the tables of total x rows  +  sum over the outside messages of m / D  =  0.
+ * vx_bus_group_check: the BALANCE CHECK on the device, before anything is proven -- which message of which table and row has no
+ *   partner.  Every table needs a message list: a vx_air_register_bus program, or a compiled AIR with ids 16 .. 23; any other
+ *   compiled AIR is VX_ERR_ARG naming the table.  *out: n_unmatched = 0 when the bus closes; otherwise the number of distinct
+ *   tuples whose multiplicities do not cancel and the lowest (table, row, message) among their messages.  It compares 128-bit
+ *   fingerprints of the tuples: a collision can hide or mis-name an imbalance, never invent one.
+ * vx_bus_group_prove: runs the check first when every table has a message list -- VX_ERR_STATEMENT naming table, AIR, row, message,
+ *   net multiplicity and the number of unmatched tuples, nothing proven; otherwise the published totals are summed with the outside
+ *   messages after the proofs exist (VX_ERR_STATEMENT "the bus does not close").  Waits for ctx's work before the group starts; the
+ *   traces are left intact.  Blob: the magic "VXBGRP01", n, one length per proof, the proofs.  AIR ids are not part of the blob's
+ *   request: registered ids are per process and the verifier states its own.  VX_ERR_BUFSZ (with *blob_len set) when the buffer is
+ *   too small.  vx_bus_group_proof_bound: the words such a blob needs at most (no GPU; only air_id and log_n of a table are read).
+ * vx_bus_group_verify (host only): every proof under the shared challenges against its expected AIR id and public inputs, and the
+ *   bus against the outside messages.  VX_ERR_STATEMENT with the reason: a non-canonical outside word, a tag of 2^16 or more, n
+ *   different from the blob's, an unexpected AIR id or public input, a zero denominator, a bus that does not balance. */
+enum { VX_BUS_GROUP_MAX_TABLES = 16, VX_BUS_MSG_WORDS = 6 };
+typedef struct vx_bus_table {   /* prover side */
+    int32_t air_id, log_n;
+    const vx_buf* trace;              /* [cols][2^log_n] on the context's device; left intact */
+    const uint64_t* public_inputs;
+    size_t n_public;
+} vx_bus_table;
+typedef struct vx_bus_expect {  /* verifier side */
+    int32_t air_id;
+    const uint64_t* public_inputs;
+    size_t n_public;
+} vx_bus_expect;
+typedef struct vx_bus_unmatched {
+    uint64_t n_unmatched;             /* distinct tuples whose multiplicities do not sum to 0; 0 = the bus closes */
+    int32_t table;                    /* of the record reported: index into tables, or n for an outside message */
+    uint32_t message;                 /* ordinal in that table's message list (program order / Air::messages order); 0 outside */
+    uint64_t row;                     /* row (first row of the block for block tables); index into `outside` for the outside party */
+    uint64_t net;                     /* the tuple's multiplicity sum over ALL parties, canonical field word */
+} vx_bus_unmatched;
+int32_t vx_bus_group_proof_bound(const vx_stark_config* cfg, const vx_bus_table* tables, size_t n, size_t* n_words);
+int32_t vx_bus_group_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_bus_table* tables, size_t n, const uint64_t* outside, size_t n_outside, uint64_t* blob_out,
+                           size_t blob_cap, size_t* blob_len);
+int32_t vx_bus_group_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const vx_bus_expect* expect, size_t n, const uint64_t* outside, size_t n_outside,
+                            char* err, size_t errlen);
+int32_t vx_bus_group_check(vx_ctx* ctx, const vx_bus_table* tables, size_t n, const uint64_t* outside, size_t n_outside, vx_bus_unmatched* out);
 /* K5: batched constraint / quotient-polynomial evaluation (starky prover.rs compute_quotient_polys) for an AIR compiled
  * into the library or registered as a program.  trace_lde: column-major [cols][N], N = 2^(log_n + rate_bits), natural order, values on the coset
  * 7 * <w_N>.  out[k*N + i] = (sum_j alpha_k^(K-1-j) c_j(x_i)) / Z_H(x_i) for the two challenges k = 0, 1. */

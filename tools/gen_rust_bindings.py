@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 BASE = {"int32_t": "i32", "int": "c_int", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "char": "c_char",
         "float": "f32", "void": "c_void", "vx_ctx": "VxCtx", "vx_buf": "VxBuf", "vx_tree": "VxTree", "vx_stark_config": "VxStarkConfig",
-        "vx_justification": "VxJustification", "vx_hr_exchange": "VxHrExchange", "vx_air_program": "VxAirProgram", "vx_air_bus": "VxAirBus"}
+        "vx_justification": "VxJustification", "vx_hr_exchange": "VxHrExchange", "vx_air_program": "VxAirProgram", "vx_air_bus": "VxAirBus",
+        "vx_bus_table": "VxBusTable", "vx_bus_expect": "VxBusExpect", "vx_bus_unmatched": "VxBusUnmatched"}
 
 
 def declarations():
@@ -67,6 +68,10 @@ def block():
              "    pub gen_aux_user: *mut c_void,", "}",
              "/// the declared bus messages of a run-time AIR for vx_air_register_bus: the message program the library derives constraints and witness from",
              "#[repr(C)] pub struct VxAirBus { pub code: *const u64, pub n_code: u32, pub consts: *const u64, pub n_consts: u32, pub n_regs: u32, pub block_log: u32, pub step_periodic: i32 }",
+             "/// a table of a generic bus group for vx_bus_group_prove / _check, what its verifier expects of one, and what the balance check reports",
+             "#[repr(C)] pub struct VxBusTable { pub air_id: i32, pub log_n: i32, pub trace: *const VxBuf, pub public_inputs: *const u64, pub n_public: usize }",
+             "#[repr(C)] pub struct VxBusExpect { pub air_id: i32, pub public_inputs: *const u64, pub n_public: usize }",
+             "#[repr(C)] #[derive(Clone, Copy, Default)] pub struct VxBusUnmatched { pub n_unmatched: u64, pub table: i32, pub message: u32, pub row: u64, pub net: u64 }",
              "#[repr(C)] pub struct VxHrExchange { pub func: Option<unsafe extern \"C\" fn(user: *mut c_void, words: *mut u64, n_words: usize) -> i32>, pub user: *mut c_void }",
              '#[link(name = "vxprove")]', 'extern "C" {']
     for ret, name, args in declarations():
