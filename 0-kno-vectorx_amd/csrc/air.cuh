@@ -226,20 +226,28 @@ struct RowViewN {  // column-major LDE, rows i[0..R) of it
     }
 };
 
-// ---- the bus of a table whose helpers hold two messages each (the Merkle-opening, leaf, FRI and transcript tables) ----
-// Such an AIR states its messages ONCE, for its constraints (bus_constraints below) and for its witness (bus_aux.cuh):
+// ---- the bus of a table whose helpers hold two messages each (the Merkle-opening, leaf, FRI and transcript tables, the SHA-256
+// Merkle tree, the epoch-end table) ----
+// Such an AIR states its messages ONCE, for its constraints (bus_constraints below), for its witness (bus_aux.cuh) and for the
+// balance check of a bus group (bus_balance.cuh):
 //   N_HELP     helpers: helper e, an extension cell at COLS + 2 e, holds m_a / D_a + m_b / D_b of message pair e; the running
 //              sum z sits behind them at COLS + 2 N_HELP and the table publishes total / rows (AUX = 2 N_HELP + 2, AUXPUB = 1)
 //   BUS_ROWS   rows that share one set of helpers: 1, or 32 (a Poseidon block)
 //   BUS_STEP   the periodic column on whose rows the sum advances (a block's first row), -1: on every row
 //   BUS_BLOCK  lanes per workgroup of the witness kernel
-//   template <class F, class Row, class Sink> static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s)
+//   BUS_PERIODIC  1: the messages read periodic columns.  The AIR then has
+//                 VX_HD static void bus_periodic(size_t row, uint64_t* per)   // per[q] of that row, for every column q the list reads
+//              which is ALSO what periodic_values() fills those columns from: the kernels compute the values from the row index
+//              (no table in memory) and cannot drift from the host's table.  0: the list gets a null `per`
+//   template <class F, class Row, class Sink>
+//   static void messages(const Row& loc, const F* per, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s)
 //              walks the pairs in helper order and hands pair e to s.put(m_a, D_a, m_b, D_b), or to s.pair(m, D_a, D_b) where
-//              both messages share a multiplicity.  A multiplicity is a signed field value: sent m, received zero - m.  Only
-//              + - * and F::from, so it instantiates for every field type of this file.  A loop over pairs is marked
-//              `#pragma unroll Sink::UNROLL`: rolled in the quotient kernel, unrolled in the witness kernel (arrays in registers)
+//              both messages share a multiplicity, or to s.single(m, D) where the helper holds one message (m / D).  A
+//              multiplicity is a signed field value: sent m, received zero - m.  Only + - * and F::from, so it instantiates
+//              for every field type of this file.  A loop over pairs is marked `#pragma unroll Sink::UNROLL`: rolled in the
+//              quotient kernel, unrolled in the witness kernel (arrays in registers)
 template <class F, class Row, class Cn>
-struct BusConstraints {  // the sink of eval: h D_a D_b - m_a D_b - m_b D_a per pair, in helper order
+struct BusConstraints {  // the sink of eval: h D_a D_b - m_a D_b - m_b D_a per pair (h D - m for a single), in helper order
     static constexpr int UNROLL = 1;
     const Row& loc;
     Cn& c;
@@ -252,6 +260,7 @@ struct BusConstraints {  // the sink of eval: h D_a D_b - m_a D_b - m_b D_a per 
     }
     VX_HD void put(const F& ma, const X2<F>& da, const F& mb, const X2<F>& db) { c.constraint_x2(helper() * da * db - db * ma - da * mb); }
     VX_HD void pair(const F& m, const X2<F>& da, const X2<F>& db) { c.constraint_x2(helper() * da * db - (da + db) * m); }
+    VX_HD void single(const F& m, const X2<F>& d) { c.constraint_x2(helper() * d - m); }
 };
 // the bus block of such an AIR's eval: the N_HELP helper constraints, then z' - z - sum h [* step] + total / rows
 template <class Air, class F, class Row, class Cn>
@@ -260,7 +269,7 @@ VX_HD void bus_constraints(const Row& loc, const Row& nxt, const F* per, const F
     constexpr int Z = Air::COLS + 2 * Air::N_HELP;
     const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
     BusConstraints<F, Row, Cn> s{loc, c, Air::COLS, X2<F>{F::from(0), F::from(0)}};
-    Air::template messages<F>(loc, pub, bus, s);
+    Air::template messages<F>(loc, per, pub, bus, s);
     const X2<F> z{loc[Z], loc[Z + 1]}, zn{nxt[Z], nxt[Z + 1]}, total{apub[0], apub[1]};
     if constexpr (Air::BUS_STEP >= 0) c.constraint_x2(zn - z - s.hsum * per[Air::BUS_STEP] + total);
     else c.constraint_x2(zn - z - s.hsum + total);

@@ -7,6 +7,8 @@
 // header bytes.  512 rows: row 0 the prefix (P = 6 + len1 + len2 bytes), rows 1..n the validators (k = P + 40 (i - 1) + j), row
 // n + 1 the delay.  44 byte cells (range: they equal message bytes the Blake2b table range-checks), row flags V / DL, six bits Q
 // of the first length byte >> 2.  Public inputs: n, bus_on, len1 one-hot (1, 2, 4, 5 bytes), len2 one-hot.
+// The bus is stated once, in `messages` (air.cuh "the bus of a table ..."): 22 helpers of two messages each, the running sum behind
+// them; the constraints (bus_constraints), the witness (bus_aux.cuh) and the balance check of a bus group read that list.
 // Constraint ORDER is protocol: oracle/epoch_air.py restates it independently.
 #pragma once
 #include <vector>
@@ -14,7 +16,7 @@
 #include "air.cuh"
 
 namespace epo {
-constexpr int LOG_N = 9, NB = 44, V = 44, DL = 45, Q0 = 46, COLS = 52, N_HELP = 23, AUX = 2 * N_HELP;
+constexpr int LOG_N = 9, NB = 44, V = 44, DL = 45, Q0 = 46, COLS = 52, N_HELP = 22, AUX = 2 * N_HELP + 2;
 VX_HD constexpr int len_of(int a) { return a == 0 ? 1 : a == 1 ? 2 : a == 2 ? 4 : 5; }
 }  // namespace epo
 
@@ -22,17 +24,61 @@ struct EpochEndAir {
     static constexpr int ID = 15, COLS = epo::COLS, PUB = 10, PERIODIC = 2, PERIOD_LOG = epo::LOG_N, QUOT_ROWS_PER_LANE = 1, AUX = epo::AUX, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int plog(int) { return epo::LOG_N; }
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
+    // the two periodic columns of a row: the prefix row, and the record index (one column, so that byte positions stay of degree 1)
+    VX_HD static void bus_periodic(size_t row, uint64_t* per) { per[0] = row == 0, per[1] = row ? row - 1 : 0; }
     static void periodic_values(std::vector<uint64_t>& v) {
         const size_t n = (size_t)1 << epo::LOG_N;
         v.assign(2 * n, 0);
-        v[0] = 1;
-        for (size_t i = 1; i < n; ++i) v[n + i] = i - 1;  // record index: one column, so that byte positions stay of degree 1
+        for (size_t i = 0; i < n; ++i) {
+            uint64_t per[2];
+            bus_periodic(i, per);
+            v[i] = per[0], v[n + i] = per[1];
+        }
+    }
+
+    static constexpr int N_HELP = epo::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 64, BUS_PERIODIC = 1;
+
+    // 40 byte receives (ordinals 0 .. 39), then 4 key sends (40 .. 43), two to a helper
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* per, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace epo;
+        const F one = F::from(1), zero = F::from(0), r0 = per[0], rec = per[1], on = pub[1], v = loc[V], dl = loc[DL];
+        const F k8 = F::from(256), k16 = F::from(65536);
+        const F* l1 = pub + 2;
+        const F* l2 = pub + 6;
+        F l1len = zero, l2len = zero;
+#pragma unroll 1
+        for (int a = 0; a < 4; ++a) l1len = l1len + l1[a] * F::from((uint64_t)len_of(a)), l2len = l2len + l2[a] * F::from((uint64_t)len_of(a));
+        const F plen = l1len + l2len + F::from(6), kbase = (one - r0) * plen + rec * F::from(40);
+        const X2<F> bbase = bus.byte_base(bus::None{}, bus::K<1>{});  // (0, k, byte, tree 1)
+        auto m_byte = [&](int j) -> F {
+            F pm = zero;  // [j < P] on the prefix row
+#pragma unroll 1
+            for (int a = 0; a < 4; ++a)
+#pragma unroll 1
+                for (int b = 0; b < 4; ++b)
+                    if (j < 6 + len_of(a) + len_of(b)) pm = pm + l1[a] * l2[b];
+            F m = v + r0 * pm;
+            if (j < 4) m = m + dl;
+            return zero - m * on;
+        };
+        auto d_byte = [&](int j) -> X2<F> { return bus.byte(bbase, kbase + F::from((uint64_t)j), loc[j]); };
+        auto d_key = [&](int q) -> X2<F> {
+            const F la = loc[8 * q] + loc[8 * q + 1] * k8 + (loc[8 * q + 2] + loc[8 * q + 3] * k8) * k16;
+            const F lb = loc[8 * q + 4] + loc[8 * q + 5] * k8 + (loc[8 * q + 6] + loc[8 * q + 7] * k8) * k16;
+            return bus.key(rec * F::from(4) + F::from((uint64_t)q), la, lb);
+        };
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 20; ++e) s.put(m_byte(2 * e), d_byte(2 * e), m_byte(2 * e + 1), d_byte(2 * e + 1));
+        const F mk = v * on;
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 2; ++e) s.pair(mk, d_key(2 * e), d_key(2 * e + 1));
     }
 
     template <class F, class Row, class Cn>
     __host__ __device__ static void eval(const Row& loc, const Row& nxt, const F* per, const F* pub, const F* chal, const F* apub, Cn& c) {
         using namespace epo;
-        const F one = F::from(1), zero = F::from(0), r0 = per[0], rec = per[1], n_auth = pub[0], on = pub[1];
+        const F one = F::from(1), zero = F::from(0), r0 = per[0], rec = per[1], n_auth = pub[0];
         const F k8 = F::from(256), k16 = F::from(65536), k24 = F::from(1ULL << 24);
         // ---- 1. row flags
         {
@@ -89,48 +135,6 @@ struct EpochEndAir {
             c.constraint(r0 * acc3);
         }
         // ---- 4. the bus: 40 byte receives, 4 key sends, two lookups per helper
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            F l1len = zero, l2len = zero;
-#pragma unroll 1
-            for (int a = 0; a < 4; ++a) l1len = l1len + l1[a] * F::from((uint64_t)len_of(a)), l2len = l2len + l2[a] * F::from((uint64_t)len_of(a));
-            const F plen = l1len + l2len + F::from(6), kbase = (one - r0) * plen + rec * F::from(40);
-            const X2<F> bbase = bus.byte_base(bus::None{}, bus::K<1>{});  // (0, k, byte, tree 1)
-            auto m_byte = [&](int j) -> F {
-                F pm = zero;  // [j < P] on the prefix row
-#pragma unroll 1
-                for (int a = 0; a < 4; ++a)
-#pragma unroll 1
-                    for (int b = 0; b < 4; ++b)
-                        if (j < 6 + len_of(a) + len_of(b)) pm = pm + l1[a] * l2[b];
-                F m = v + r0 * pm;
-                if (j < 4) m = m + dl;
-                return zero - m * on;
-            };
-            auto d_byte = [&](int j) -> X2<F> { return bus.byte(bbase, kbase + F::from((uint64_t)j), loc[j]); };
-            auto d_key = [&](int q) -> X2<F> {
-                const F la = loc[8 * q] + loc[8 * q + 1] * k8 + (loc[8 * q + 2] + loc[8 * q + 3] * k8) * k16;
-                const F lb = loc[8 * q + 4] + loc[8 * q + 5] * k8 + (loc[8 * q + 6] + loc[8 * q + 7] * k8) * k16;
-                return bus.key(rec * F::from(4) + F::from((uint64_t)q), la, lb);
-            };
-            X2<F> hsum{zero, zero};
-#pragma unroll 1
-            for (int e = 0; e < 20; ++e) {
-                const X2<F> du = d_byte(2 * e), dv = d_byte(2 * e + 1);
-                const X2<F> h{loc[COLS + 2 * e], loc[COLS + 2 * e + 1]};
-                c.constraint_x2(h * du * dv - dv * m_byte(2 * e) - du * m_byte(2 * e + 1));
-                hsum = hsum + h;
-            }
-            const F mk = v * on;
-#pragma unroll 1
-            for (int e = 0; e < 2; ++e) {
-                const X2<F> du = d_key(2 * e), dv = d_key(2 * e + 1);
-                const X2<F> h{loc[COLS + 2 * (20 + e)], loc[COLS + 2 * (20 + e) + 1]};
-                c.constraint_x2(h * du * dv - dv * mk - du * mk);
-                hsum = hsum + h;
-            }
-            const X2<F> z{loc[COLS + 2 * (N_HELP - 1)], loc[COLS + 2 * (N_HELP - 1) + 1]}, zn{nxt[COLS + 2 * (N_HELP - 1)], nxt[COLS + 2 * (N_HELP - 1) + 1]};
-            c.constraint_x2(zn - z - hsum + X2<F>{apub[0], apub[1]});
-        }
+        bus_constraints<EpochEndAir>(loc, nxt, per, pub, chal, apub, c);
     }
 };

@@ -47,11 +47,11 @@ struct FriCombineAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
-    static constexpr int N_HELP = fca::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256;
+    static constexpr int N_HELP = fca::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256, BUS_PERIODIC = 0;
 
     // a row word received on an absorb row, the entry of the fold chain sent on the last row
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         using namespace fca;
         const F ta = loc[TA], tq = loc[TQ], idx = loc[IDX];
         s.put(F::from(0) - (loc[TM] + ta + tq), bus.row_of(pub[PUB_TREE0] + ta + tq + tq, idx, loc[POS], loc[W]), loc[LAST], bus.fri(idx, loc[EV], loc[EV + 1], bus::K<0>{}));

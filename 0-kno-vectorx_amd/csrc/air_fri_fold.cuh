@@ -76,11 +76,11 @@ struct FriFoldAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
-    static constexpr int N_HELP = ffa::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 64;
+    static constexpr int N_HELP = ffa::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 64, BUS_PERIODIC = 0;
 
     // 32 leaf words received on a fold row; the entry received on the first row, the exit sent on the first bit row
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         using namespace ffa;
         const F zero = F::from(0), tree = pub[PUB_TREE0] + loc[CNT], q = loc[Q], idx = loc[IDX], received = zero - loc[FOLD];
 #pragma unroll Sink::UNROLL

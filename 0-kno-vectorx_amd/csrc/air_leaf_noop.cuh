@@ -36,11 +36,11 @@ struct LeafNoopAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { v.clear(); }
 
-    static constexpr int N_HELP = lnp::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256;
+    static constexpr int N_HELP = lnp::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256, BUS_PERIODIC = 0;
 
     // the two halves of the digest received, the words that exist sent
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
         using namespace lnp;
         const F tree = loc[TREE], idx = loc[IDX];
         s.pair(F::from(0) - loc[ACT], bus.open_of(tree, idx, loc[W], loc[W + 1], bus::K<0>{}), bus.open_of(tree, idx, loc[W + 2], loc[W + 3], bus::K<1>{}));

@@ -162,9 +162,9 @@ struct LeafSpongeAir {
         lsp::eval<LeafSpongeAir>(loc, nxt, per, pub, chal, apub, c);
     }
     static constexpr bool SET = false;
-    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64;
+    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64, BUS_PERIODIC = 0;
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         lsp::messages<SET>(loc, pub, bus, s);
     }
 };
@@ -179,9 +179,9 @@ struct LeafSpongeSetAir {
         lsp::eval<LeafSpongeSetAir>(loc, nxt, per, pub, chal, apub, c);
     }
     static constexpr bool SET = true;
-    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64;
+    static constexpr int N_HELP = lsp::N_HELP, BUS_ROWS = 32, BUS_STEP = lsp::P_FIRST, BUS_BLOCK = 64, BUS_PERIODIC = 0;
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         lsp::messages<SET>(loc, pub, bus, s);
     }
 };

@@ -155,9 +155,9 @@ struct MerkleOpenAir {
         mop::eval<MerkleOpenAir>(loc, nxt, per, pub, chal, apub, c);
     }
     static constexpr bool SET = false;
-    static constexpr int N_HELP = 1, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64;
+    static constexpr int N_HELP = 1, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64, BUS_PERIODIC = 0;
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         mop::messages<SET>(loc, pub, bus, s);
     }
 };
@@ -172,9 +172,9 @@ struct MerkleOpenSetAir {
         mop::eval<MerkleOpenSetAir>(loc, nxt, per, pub, chal, apub, c);
     }
     static constexpr bool SET = true;
-    static constexpr int N_HELP = 2, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64;
+    static constexpr int N_HELP = 2, BUS_ROWS = 32, BUS_STEP = mop::P_FIRST, BUS_BLOCK = 64, BUS_PERIODIC = 0;
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
         mop::messages<SET>(loc, pub, bus, s);
     }
 };

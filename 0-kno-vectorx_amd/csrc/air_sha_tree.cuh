@@ -16,6 +16,9 @@
 //   inner nodes:                 (tree, child id, r mod 8, word, TAG_WORD)                         from the children's PAD blocks
 //   bottom level of both trees:  (leaf, 4 (r mod 8) + q, byte q of the word, tree, TAG_BYTE), q = 0..3   from the header bytes
 // and row 63 of a PAD block sends the node's digest (tree, g, j, word_j), except for the root: its digest is public.
+// The bus is stated once, in `messages` (air.cuh "the bus of a table ..."): 13 messages in 7 helpers, the last helper holds one; the
+// constraints (bus_constraints), the witness (bus_aux.cuh) and the balance check of a bus group read that list.  What the list reads
+// of a row's position -- the 12 full-period columns -- is stated once too, in `bus_periodic`.
 // Constraint ORDER is protocol: oracle/sha_tree_air.py restates it independently.
 #pragma once
 #include <vector>
@@ -23,14 +26,11 @@
 #include "air_sha.cuh"
 
 namespace sht {
-constexpr int ENL = shc::DG0, ENR = shc::DG0 + 1, CNT = shc::DG0 + 2, COLS = shc::COLS, AUX = 16, N_PERIODIC = 17;
+constexpr int ENL = shc::DG0, ENR = shc::DG0 + 1, CNT = shc::DG0 + 2, COLS = shc::COLS, N_HELP = 7, AUX = 2 * N_HELP + 2, N_PERIODIC = 17;
 // P_NB / P_BB / P_LASTN sit on the last row of a node (row 63 of its PAD block): the next node is a bottom-level node / this
 // node and the next both are / this is the last node of its tree
 enum { P_SEL0, P_SEL63, P_SCHED, P_K, P_DATA, P_TREE, P_PWA, P_PBL, P_PBR, P_CID, P_JJ, P_PS, P_ROOT, P_GID, P_NB, P_BB, P_LASTN };
 }  // namespace sht
-
-// auxiliary columns of a tree of N leaves (vx_sha_air.hip); the table must have 256 N rows
-int32_t vx_sha_tree_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, size_t N, const uint64_t* chal, uint64_t* aux, uint64_t* aux_pub);
 
 template <int LOGN, int ID_>
 struct ShaTreeAirT {
@@ -38,8 +38,27 @@ struct ShaTreeAirT {
     static constexpr int TREE_SIZE = 1 << LOGN;
     static constexpr int plog(int q) { return q < 4 ? 6 : (q == 4 ? 7 : 8 + LOGN); }  // 4 x 64, 128, then 12 full-period columns
 
-    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t*, uint64_t* aux, uint64_t* aux_pub) {
-        return vx_sha_tree_gen_aux(ctx, trace, log_n, TREE_SIZE, chal, aux, aux_pub);
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_sha_air.hip
+
+    // the 12 full-period columns of a row (per[P_TREE .. P_LASTN]; the short-period ones are not a row's position and are left alone)
+    VX_HD static void bus_periodic(size_t row, uint64_t* per) {
+        using namespace sht;
+        const size_t N = TREE_SIZE, r = row & 63, blk = (row >> 6) & 1, pair = row >> 7, tree = pair / N, g = pair % N;
+        const bool msg = blk == 0 && r < 16, left = msg && r < 8, right = msg && r >= 8, bottom = g >= N / 2, inner = g >= 1 && g < N / 2;
+        const size_t c = r >= 8 ? 1 : 0;
+        const bool send = blk == 1 && r == 63;
+        per[P_TREE] = tree;
+        per[P_PWA] = msg && inner;
+        per[P_PBL] = left && bottom;
+        per[P_PBR] = right && bottom;
+        per[P_CID] = msg ? (bottom ? 2 * g - N + c : 2 * g + c) : 0;  // a bottom-level child is a leaf: its index; an inner child: its node id
+        per[P_JJ] = msg ? (r & 7) : 0;
+        per[P_PS] = send && g >= 2;
+        per[P_ROOT] = send && g == 1;
+        per[P_GID] = send ? g : 0;
+        per[P_NB] = send && g + 1 >= N / 2 && g + 1 < N;
+        per[P_BB] = send && g >= N / 2 && g + 1 < N;
+        per[P_LASTN] = send && g == N - 1;
     }
     // one period of every periodic column, back to back (host)
     static void periodic_values(std::vector<uint64_t>& v) {
@@ -51,25 +70,45 @@ struct ShaTreeAirT {
         for (int r = 0; r <= 47; ++r) p[128 + r] = 1;
         for (int r = 0; r < 64; ++r) p[192 + r] = shc::K_H[r];
         for (int r = 0; r < 64; ++r) p[256 + r] = 1;
-        uint64_t* q = p + 384;  // columns P_TREE .. P_GID, n values each
+        uint64_t* q = p + 384;  // columns P_TREE .. P_LASTN, n values each
         for (size_t row = 0; row < n; ++row) {
-            const size_t r = row & 63, blk = (row >> 6) & 1, pair = row >> 7, tree = pair / N, g = pair % N;
-            const bool msg = blk == 0 && r < 16, left = msg && r < 8, right = msg && r >= 8, bottom = g >= N / 2, inner = g >= 1 && g < N / 2;
-            const size_t c = r >= 8 ? 1 : 0;
-            const bool send = blk == 1 && r == 63;
-            q[(P_TREE - 5) * n + row] = tree;
-            q[(P_PWA - 5) * n + row] = msg && inner;
-            q[(P_PBL - 5) * n + row] = left && bottom;
-            q[(P_PBR - 5) * n + row] = right && bottom;
-            q[(P_CID - 5) * n + row] = msg ? (bottom ? 2 * g - N + c : 2 * g + c) : 0;  // a bottom-level child is a leaf: its index; an inner child: its node id
-            q[(P_JJ - 5) * n + row] = msg ? (r & 7) : 0;
-            q[(P_PS - 5) * n + row] = send && g >= 2;
-            q[(P_ROOT - 5) * n + row] = send && g == 1;
-            q[(P_GID - 5) * n + row] = send ? g : 0;
-            q[(P_NB - 5) * n + row] = send && g + 1 >= N / 2 && g + 1 < N;
-            q[(P_BB - 5) * n + row] = send && g >= N / 2 && g + 1 < N;
-            q[(P_LASTN - 5) * n + row] = send && g == N - 1;
+            uint64_t per[N_PERIODIC];
+            bus_periodic(row, per);
+            for (int k = P_TREE; k < N_PERIODIC; ++k) q[(k - P_TREE) * n + row] = per[k];
         }
+    }
+
+    static constexpr int N_HELP = sht::N_HELP, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256, BUS_PERIODIC = 1;
+
+    // ordinal 0 the word receive, 1 .. 4 the byte receives, 5 .. 12 the digest sends; helper e holds ordinals 2 e and 2 e + 1
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* per, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace shc;
+        using namespace sht;
+        auto val = [&](int col0, int nb) -> F {
+            F acc = loc[col0 + nb - 1];
+#pragma unroll 1
+            for (int i = nb - 2; i >= 0; --i) acc = acc + acc + loc[col0 + i];
+            return acc;
+        };
+        const F zero = F::from(0);
+        const X2<F> bword = bus.word_base(), bbyte = bus.byte_base(per[P_CID], per[P_TREE]);
+        auto mult = [&](int q) -> F {
+            if (q == 0) return zero - per[P_PWA];
+            if (q <= 4) return zero - (per[P_PBL] * loc[ENL] + per[P_PBR] * loc[ENR]);
+            return per[P_PS];
+        };
+        auto denom = [&](int q) -> X2<F> {
+            if (q >= 1 && q <= 4) return bus.byte(bbyte, per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1)), val(W0B + 24 - 8 * (q - 1), 8));
+            const bool recv = q == 0;  // message word r of a child, or word q - 5 of this node's digest
+            return bus.word(bword, per[P_TREE], recv ? per[P_CID] : per[P_GID], recv ? per[P_JJ] : F::from((uint64_t)(q - 5)), recv ? val(W0B, 32) : loc[FFV0 + q - 5]);
+        };
+        // (two loops: unrolled as one, the body with all three kinds of message is above the compiler's size limit for a `#pragma unroll` loop)
+#pragma unroll Sink::UNROLL
+        for (int e = 0; e < 3; ++e) s.put(mult(2 * e), denom(2 * e), mult(2 * e + 1), denom(2 * e + 1));
+#pragma unroll Sink::UNROLL
+        for (int e = 3; e < 6; ++e) s.put(mult(2 * e), denom(2 * e), mult(2 * e + 1), denom(2 * e + 1));
+        s.single(mult(12), denom(12));
     }
 
     template <class F, class Row, class C>
@@ -110,35 +149,7 @@ struct ShaTreeAirT {
             c.constraint(per[P_LASTN] * (loc[CNT] - pub[16]));
         }
         // ---- 9. the bus (logUp): 13 lookups in 7 helper elements of the local row, cyclic running sum
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F en_l = loc[ENL], en_r = loc[ENR], zero = F::from(0);
-            const X2<F> bword = bus.word_base(), bbyte = bus.byte_base(per[P_CID], per[P_TREE]);
-            // lookup q: 0 = word receive, 1..4 = byte receives, 5..12 = digest sends
-            auto mult = [&](int q) -> F {
-                if (q == 0) return zero - per[P_PWA];
-                if (q <= 4) return zero - (per[P_PBL] * en_l + per[P_PBR] * en_r);
-                return per[P_PS];
-            };
-            auto denom = [&](int q) -> X2<F> {
-                if (q == 0) return bus.word(bword, per[P_TREE], per[P_CID], per[P_JJ], w0);
-                if (q <= 4) return bus.byte(bbyte, per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1)), val(loc, W0B + 24 - 8 * (q - 1), 8));
-                return bus.word(bword, per[P_TREE], per[P_GID], F::from((uint64_t)(q - 5)), loc[FFV0 + q - 5]);
-            };
-            X2<F> hsum{zero, zero};
-#pragma unroll 1
-            for (int e = 0; e < 7; ++e) {
-                const X2<F> h{loc[COLS + 2 * e], loc[COLS + 2 * e + 1]};
-                const X2<F> du = denom(2 * e);
-                if (e < 6) {
-                    const X2<F> dv = denom(2 * e + 1);
-                    c.constraint_x2(h * du * dv - dv * mult(2 * e) - du * mult(2 * e + 1));
-                } else c.constraint_x2(h * du - mult(2 * e));
-                hsum = hsum + h;
-            }
-            const X2<F> z{loc[COLS + 14], loc[COLS + 15]}, zn{nxt[COLS + 14], nxt[COLS + 15]};
-            c.constraint_x2(zn - z - hsum + X2<F>{apub[0], apub[1]});
-        }
+        bus_constraints<ShaTreeAirT>(loc, nxt, per, pub, chal, apub, c);
     }
 };
 using ShaTreeAir256 = ShaTreeAirT<8, 7>;

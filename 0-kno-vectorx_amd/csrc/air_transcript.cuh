@@ -48,11 +48,11 @@ struct TranscriptAir {
     static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
     static void periodic_values(std::vector<uint64_t>& v) { lsp::periodic_values(v); }
 
-    static constexpr int N_HELP = tsc::N_HELP, BUS_ROWS = 32, BUS_STEP = tsc::P_FIRST, BUS_BLOCK = 64;
+    static constexpr int N_HELP = tsc::N_HELP, BUS_ROWS = 32, BUS_STEP = tsc::P_FIRST, BUS_BLOCK = 64, BUS_PERIODIC = 0;
 
     // eight absorbed words received with multiplicity W_i, eight outputs sent with multiplicity Q_i
     template <class F, class Row, class Sink>
-    VX_HD static void messages(const Row& loc, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
+    VX_HD static void messages(const Row& loc, const F*, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
         using namespace tsc;
         const F zero = F::from(0), chain = loc[CHAIN], nabs = loc[NABS], nch = loc[NCH];
         F sw = loc[W];  // (the sum eval has: one expression, one computation)

@@ -1,17 +1,22 @@
 // The auxiliary round of every table whose helpers hold two messages each (air.cuh "the bus of a table ..."): one witness kernel
 // and one gen_aux body for MerkleOpenAir / MerkleOpenSetAir, LeafSpongeAir / LeafSpongeSetAir, LeafNoopAir, FriFoldAir,
-// FriCombineAir and TranscriptAir.  The kernel reads the messages from the list the AIR's constraints are built from
-// (Air::messages with F = Fp), so a table states multiplicities, slots, pairing and helper order once.
+// FriCombineAir, TranscriptAir, ShaTreeAir and EpochEndAir.  The kernel reads the messages from the list the AIR's constraints are
+// built from (Air::messages with F = Fp), so a table states multiplicities, slots, pairing and helper order once.
 //   k_bus_aux<Air>  one lane per row, or per 32-row block (Air::BUS_ROWS).  A first walk of the list looks at the multiplicities
 //                   alone (the denominators are dead code in it): a row or block that sends and receives nothing -- idle, or a
 //                   row of a query that has no message -- gets zero helpers and inverts nothing.  Otherwise a second walk fills
-//                   num_e = m_a D_b + m_b D_a and den_e = D_a D_b, and ONE extension inversion yields all helpers (Montgomery
-//                   batch, gl2_batch_div).  Helper e goes to columns [2 e, 2 e + 1] of all BUS_ROWS rows; the sum of the helpers,
-//                   the increment of the running sum, to columns [2 N_HELP, 2 N_HELP + 1] of the first row, zero on the others
+//                   num_e = m_a D_b + m_b D_a and den_e = D_a D_b (num = m, den = D for a helper of one message), and ONE
+//                   extension inversion yields all helpers (Montgomery batch, gl2_batch_div).  Helper e goes to columns
+//                   [2 e, 2 e + 1] of all BUS_ROWS rows; the sum of the helpers, the increment of the running sum, to columns
+//                   [2 N_HELP, 2 N_HELP + 1] of the first row, zero on the others
+//   BusPer<Air>     the periodic values a list reads (Air::BUS_PERIODIC), computed from the row index by Air::bus_periodic -- the
+//                   function the host's periodic table is filled from -- and a null pointer for every other table
 //   bus_gen_aux     launches it and closes the sum (vx_bus_close_dev scans the increments and publishes total / rows)
 // The public inputs go to the kernel by value: at most 24 words in these tables.
-// (FriFoldAir's loop over 16 pairs is, unrolled, above the compiler's size limit for a `#pragma unroll` loop: it is unrolled in part
-// and that one kernel keeps its arrays on the stack, 1104 bytes a lane, as the kernel it replaces did -- profiles/README.md.)
+// A list's loops are unrolled up to 16 pairs, so that num[] / den[] are indexed by constants and stay in registers.  Two tables are
+// past that and keep the arrays on the stack (profiles/README.md): FriFoldAir, whose loop over 16 pairs is, unrolled, above the
+// compiler's size limit for a `#pragma unroll` loop (1104 bytes a lane, as the kernel it replaces), and EpochEndAir, whose loop has
+// 20 pairs and whose table has 512 rows.
 #pragma once
 #include <string.h>
 
@@ -24,10 +29,11 @@ struct BusPub {
 };
 
 struct BusLive {  // does the row or block have a message at all?
-    static constexpr int UNROLL = 16;  // a list's loops (at most 16 pairs) are unrolled here: num[] / den[] below want constant indices
+    static constexpr int UNROLL = 16;  // a list's loops are unrolled here: num[] / den[] below want constant indices
     bool any = false;
     __device__ __forceinline__ void put(const Fp& ma, const X2<Fp>&, const Fp& mb, const X2<Fp>&) { any |= (ma.v[0] | mb.v[0]) != 0; }
     __device__ __forceinline__ void pair(const Fp& m, const X2<Fp>&, const X2<Fp>&) { any |= m.v[0] != 0; }
+    __device__ __forceinline__ void single(const Fp& m, const X2<Fp>&) { any |= m.v[0] != 0; }
 };
 template <int N>
 struct BusFractions {  // helper e = num[e] / den[e]
@@ -40,6 +46,20 @@ struct BusFractions {  // helper e = num[e] / den[e]
     }
     __device__ __forceinline__ void put(const Fp& ma, const X2<Fp>& da, const Fp& mb, const X2<Fp>& db) { set(db * ma + da * mb, da * db); }
     __device__ __forceinline__ void pair(const Fp& m, const X2<Fp>& da, const X2<Fp>& db) { set((da + db) * m, da * db); }
+    __device__ __forceinline__ void single(const Fp& m, const X2<Fp>& d) { set(X2<Fp>{m, Fp::from(0)}, d); }
+};
+template <class Air>
+struct BusPer {  // the row's periodic values for Air::messages
+    Fp v[Air::BUS_PERIODIC ? Air::PERIODIC : 1];
+    __device__ __forceinline__ const Fp* at(size_t row) {
+        if constexpr (Air::BUS_PERIODIC) {
+            uint64_t w[Air::PERIODIC] = {};
+            Air::bus_periodic(row, w);
+#pragma unroll
+            for (int q = 0; q < Air::PERIODIC; ++q) v[q] = Fp::from(w[q]);
+            return v;
+        } else return nullptr;
+    }
 };
 
 template <class Air>
@@ -56,11 +76,13 @@ __global__ __launch_bounds__(Air::BUS_BLOCK) void k_bus_aux(const uint64_t* __re
     gl2 h[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) h[e] = gl2{0, 0};
+    BusPer<Air> pv;
+    const Fp* per = pv.at(row);
     BusLive live;
-    Air::template messages<Fp>(loc, pub, bus, live);
+    Air::template messages<Fp>(loc, per, pub, bus, live);
     if (live.any) {
         BusFractions<N> f;
-        Air::template messages<Fp>(loc, pub, bus, f);
+        Air::template messages<Fp>(loc, per, pub, bus, f);
         gl2_batch_div(f.num, f.den, h);
     }
     gl2 sum = h[0];

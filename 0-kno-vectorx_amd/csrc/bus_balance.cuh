@@ -3,7 +3,8 @@
 //   records   every message with a non-zero multiplicity becomes one record (D.a, D.b, m, origin): D the message's denominator under
 //             the CHECK CHALLENGES below, m its signed multiplicity, origin = table << 56 | row << 8 | ordinal in the table's message
 //             list.  Two kernels make them, both reading the message list the constraints and the auxiliary round are built from:
-//             k_bus_records<Air> for a compiled table (Air::messages with a third sink beside BusLive / BusFractions of bus_aux.cuh) and
+//             k_bus_records<Air> for a compiled table (Air::messages with a third sink beside BusLive / BusFractions of bus_aux.cuh: a
+//             pair is two records and two ordinals, a helper of one message one; periodic values as there, BusPer<Air>) and
 //             k_bus_records_prog for a declared run-time table (the walk of k_bus_aux_prog: busp_walk, bus_aux_prog.cuh).  No
 //             inversion, no helper storage.  Each runs twice: the count pass writes how many records a lane has, an exclusive scan over
 //             the lanes of ALL tables places them (rocPRIM), the emit pass writes them there -- never one slot per (lane, message).
@@ -14,7 +15,8 @@
 //             atomic per wave) and proposes the segment's lowest origin to a 64-bit atomicMin.  k_bus_net fetches the sum of the
 //             segment that won.  Nothing of the result depends on the order the records were written or sorted in.
 //             A segment is TWO records in the tables this is for (a sender and a receiver); one lane walking a long segment is a
-//             periodic lookup table (BlakeChainAir's XOR table, LookupAir), and those tables have no message list here.
+//             periodic lookup table (BlakeChainAir's XOR table, EdAir's range table, LookupAir), and those tables have no message
+//             list here.  The compiled tables that have one: ids 16 .. 23, ShaTreeAir (7, 8, 9) and EpochEndAir (15).
 // THE CHECK CHALLENGES (beta*, gamma*) are fixed: the check runs before anything is committed, so they cannot be a proof's.  They are
 // the first four Poseidon round constants (poseidon_constants.h VX_POSEIDON_RC_INIT[0 .. 3], canonical words of plonky2's own
 // nothing-up-my-sleeve generator) as two extension elements.  The pair (D.a, D.b) under them is a 128-bit fingerprint of the tuple
@@ -44,6 +46,7 @@ struct BusRecordCount {
     uint64_t c = 0;
     __device__ __forceinline__ void put(const Fp& ma, const X2<Fp>&, const Fp& mb, const X2<Fp>&) { c += (ma.v[0] != 0) + (mb.v[0] != 0); }
     __device__ __forceinline__ void pair(const Fp& m, const X2<Fp>&, const X2<Fp>&) { c += m.v[0] != 0 ? 2 : 0; }
+    __device__ __forceinline__ void single(const Fp& m, const X2<Fp>&) { c += m.v[0] != 0; }
 };
 struct BusRecordSink {
     static constexpr int UNROLL = 1;
@@ -57,6 +60,7 @@ struct BusRecordSink {
     }
     __device__ __forceinline__ void put(const Fp& ma, const X2<Fp>& da, const Fp& mb, const X2<Fp>& db) { one(ma, da), one(mb, db); }
     __device__ __forceinline__ void pair(const Fp& m, const X2<Fp>& da, const X2<Fp>& db) { one(m, da), one(m, db); }
+    __device__ __forceinline__ void single(const Fp& m, const X2<Fp>& d) { one(m, d); }
 };
 // One lane per row, or per BUS_ROWS-row block, as k_bus_aux<Air>.  EMIT false: cnt[lane] = its records; true: the records to
 // [offs[lane], offs[lane] + cnt[lane]), never at or behind n_rec.
@@ -71,13 +75,15 @@ __global__ __launch_bounds__(Air::BUS_BLOCK) void k_bus_records(const uint64_t* 
 #pragma unroll
     for (int q = 0; q < Air::PUB; ++q) pub[q] = Fp::from(pubw.w[q]);
     const bus::Bus<X2<Fp>> bus(Fp::from(BUS_CHECK_CHAL[0]), Fp::from(BUS_CHECK_CHAL[1]), Fp::from(BUS_CHECK_CHAL[2]), Fp::from(BUS_CHECK_CHAL[3]));
+    BusPer<Air> pv;
+    const Fp* per = pv.at(row);
     if constexpr (EMIT) {
         const uint64_t at = offs[i], end = at + cnt[i];
         BusRecordSink s{out, at, end < n_rec ? end : n_rec, bus_origin(table, row, 0)};
-        Air::template messages<Fp>(loc, pub, bus, s);
+        Air::template messages<Fp>(loc, per, pub, bus, s);
     } else {
         BusRecordCount s;
-        Air::template messages<Fp>(loc, pub, bus, s);
+        Air::template messages<Fp>(loc, per, pub, bus, s);
         cnt[i] = s.c;
     }
 }

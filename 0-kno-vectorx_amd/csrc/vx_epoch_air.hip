@@ -1,13 +1,12 @@
 // Witness of EpochEndAir (air_epoch.cuh): the ScheduledChange log of the epoch-end header, one row per authority record.
 //   k_epoch_rows  one lane per row (512): copies the row's bytes out of the header on the device, sets the row flags and the
 //                 bits of the first length byte
-//   k_epoch_aux   one lane per row: the 22 bus helpers (40 byte receives, 4 key sends, two lookups each) and the running-sum
-//                 increments
+// The auxiliary columns are bus_aux.cuh's, from the AIR's own message list: one lane per row, 22 helpers.
 // Parity: tests/test_gpu_epoch_air.py compares trace, auxiliary columns and public inputs with oracle/epoch_air.py.
 #include <string.h>
 
 #include "air_epoch.cuh"
-#include "vx_internal.h"
+#include "bus_aux.cuh"
 
 namespace {
 using namespace epo;
@@ -22,47 +21,10 @@ __global__ __launch_bounds__(64) void k_epoch_rows(const uint8_t* __restrict__ h
     tr[(size_t)V * n + row] = val, tr[(size_t)DL * n + row] = dly;
     for (int i = 0; i < 6; ++i) tr[(size_t)(Q0 + i) * n + row] = pre ? ((p[5] >> 2) >> i) & 1 : 0;
 }
-
-__global__ __launch_bounds__(64) void k_epoch_aux(const uint64_t* __restrict__ tr, uint64_t* __restrict__ aux, uint32_t plen, gl2 beta, gl2 gamma, uint64_t bus_on) {
-    const uint32_t row = blockIdx.x * blockDim.x + threadIdx.x, n = 1u << LOG_N;
-    if (row >= n) return;
-    const bool pre = row == 0, val = tr[(size_t)V * n + row] != 0, dly = tr[(size_t)DL * n + row] != 0;
-    const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-    const gl2 bbase = bus.byte_base(bus::None{}, bus::K<1>{});  // (0, k, byte, tree 1)
-    const uint64_t kbase = pre ? 0 : (uint64_t)plen + 40 * (uint64_t)(row - 1);
-    auto cell = [&](int j) -> uint64_t { return tr[(size_t)j * n + row]; };
-    gl2 hsum{0, 0};
-    auto pair = [&](int e, bool mu, bool mv, const gl2& du, const gl2& dv, bool neg) {
-        gl2 h{0, 0};
-        if (bus_on && (mu || mv)) {
-            h = gl2_mul(gl2_add(mu ? dv : gl2{0, 0}, mv ? du : gl2{0, 0}), gl2_inv(gl2_mul(du, dv)));
-            if (neg) h = gl2{gl_neg(h.a), gl_neg(h.b)};
-        }
-        aux[(size_t)(2 * e) * n + row] = h.a, aux[(size_t)(2 * e + 1) * n + row] = h.b;
-        hsum = gl2_add(hsum, h);
-    };
-    auto d_byte = [&](int j) -> gl2 { return bus.byte(bbase, gl_add(kbase, (uint64_t)j), cell(j)); };
-    auto m_byte = [&](int j) -> bool { return val || (pre && (uint32_t)j < plen) || (dly && j < 4); };
-#pragma unroll 1
-    for (int e = 0; e < 20; ++e) pair(e, m_byte(2 * e), m_byte(2 * e + 1), d_byte(2 * e), d_byte(2 * e + 1), true);
-    auto d_key = [&](int q) -> gl2 {
-        const uint64_t la = cell(8 * q) | (cell(8 * q + 1) << 8) | (cell(8 * q + 2) << 16) | (cell(8 * q + 3) << 24);
-        const uint64_t lb = cell(8 * q + 4) | (cell(8 * q + 5) << 8) | (cell(8 * q + 6) << 16) | (cell(8 * q + 7) << 24);
-        return bus.key(gl_add(gl_mul(gl_sub((uint64_t)row, 1), 4), (uint64_t)q), la, lb);  // (row - 1) * 4 + q in the field (row 0: multiplicity 0)
-    };
-#pragma unroll 1
-    for (int e = 0; e < 2; ++e) pair(20 + e, val, val, d_key(2 * e), d_key(2 * e + 1), false);
-    aux[(size_t)(2 * (N_HELP - 1)) * n + row] = hsum.a, aux[(size_t)(2 * (N_HELP - 1) + 1) * n + row] = hsum.b;  // increments; the scan makes them the running sum
-}
 }  // namespace
 
 int32_t EpochEndAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    uint32_t plen = 6;
-    for (int a = 0; a < 4; ++a) plen += (uint32_t)(pub[2 + a] + pub[6 + a]) * (uint32_t)len_of(a);
-    hipLaunchKernelGGL(k_epoch_aux, dim3((unsigned)(n / 64)), dim3(64), 0, ctx->stream, trace, aux, plen, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[1]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 2 * (N_HELP - 1) * n, log_n, aux_pub);
+    return bus_gen_aux<EpochEndAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 // header_d: the header bytes on the device (header_bytes of them readable).  The prefix is parsed here (rotate.rs:74-174: its two

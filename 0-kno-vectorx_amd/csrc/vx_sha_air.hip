@@ -1,10 +1,11 @@
 // Witness/trace generation for ShaChainAir on the GPU: one lane per trace row (block b, round r)
 // recomputes the message schedule and the r rounds it needs from the block descriptor the host
-// prepared (the 2n-1 compressions of the commitment chain are sequential and tiny: host).
+// prepared (the 2n-1 compressions of the commitment chain are sequential and tiny: host).  ShaTreeAir's rows are the same
+// kernel's; its auxiliary columns are bus_aux.cuh's, from the message list in air_sha_tree.cuh.
 #include <string.h>
 
 #include "air_sha_tree.cuh"
-#include "vx_internal.h"
+#include "bus_aux.cuh"
 
 struct ShaBlock {
     uint32_t h_in[8], block[16], dg[8], type, sgc, kc, pad;  // sgc / kc: ShaChainAir's signed flag and key counter
@@ -245,59 +246,14 @@ int32_t vx_sha_tree_trace_dev(vx_ctx* ctx, const uint8_t* state_roots, const uin
     return VX_OK;
 }
 
-// auxiliary columns of ShaTreeAir: one lane per row; the positional (periodic) quantities are recomputed from the row index
-__global__ __launch_bounds__(256) void k_sha_tree_aux(const uint64_t* tr, uint64_t* aux, size_t n, size_t N, gl2 beta, gl2 gamma) {
-    using namespace shc;
-    const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (row >= n) return;
-    const size_t r = row & 63, bk = (row >> 6) & 1, pair = row >> 7, tree = pair / N, g = pair % N;
-    const bool msg = bk == 0 && r < 16, bottom = g >= N / 2, inner = g >= 1 && g < N / 2, send = bk == 1 && r == 63 && g >= 2;
-    const uint64_t en = msg ? tr[(size_t)(r < 8 ? sht::ENL : sht::ENR) * n + row] : 0;
-    const uint64_t m_word = msg && inner ? 1 : 0, m_byte = msg && bottom && en ? 1 : 0;  // inner nodes take words, the bottom level of both trees bytes
-    auto word = [&](int col0, int nb) -> uint64_t {
-        uint64_t v = 0;
-        for (int i = 0; i < nb; ++i) v |= tr[(size_t)(col0 + i) * n + row] << i;
-        return v;
-    };
-    gl2 h[7], hsum{0, 0};
-    for (int e = 0; e < 7; ++e) h[e] = gl2{0, 0};
-    if (m_word | m_byte | (send ? 1 : 0)) {
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        const uint64_t c = r >= 8 ? 1 : 0, jj = r & 7, w0 = (msg ? word(W0B, 32) : 0);
-        const uint64_t cid = bottom ? 2 * g - N + c : 2 * g + c;  // a leaf's index / an inner child's node id
-        gl2 d[13];
-        uint64_t m[13];  // 1 = receive (-1), 2 = send (+1), 0 = inactive
-        const gl2 bword = bus.word_base(), bbyte = bus.byte_base(cid, tree);
-        d[0] = bus.word(bword, tree, cid, jj, w0);
-        m[0] = m_word;
-        for (int q = 0; q < 4; ++q) {
-            const uint64_t byte = (w0 >> (24 - 8 * q)) & 0xFF;
-            d[1 + q] = bus.byte(bbyte, 4 * jj + q, byte);
-            m[1 + q] = m_byte;
-        }
-        for (int j = 0; j < 8; ++j) {
-            const uint64_t ff = send ? tr[(size_t)(FFV0 + j) * n + row] : 0;
-            d[5 + j] = bus.word(bword, tree, g, j, ff);
-            m[5 + j] = send ? 2 : 0;
-        }
-        auto term = [&](int q) -> gl2 {  // m / D with m in {-1, 0, +1}
-            if (!m[q]) return gl2{0, 0};
-            const gl2 iv = gl2_inv(d[q]);
-            return m[q] == 2 ? iv : gl2{gl_neg(iv.a), gl_neg(iv.b)};
-        };
-        for (int e = 0; e < 7; ++e) {
-            h[e] = term(2 * e);
-            if (e < 6) h[e] = gl2_add(h[e], term(2 * e + 1));
-            hsum = gl2_add(hsum, h[e]);
-        }
-    }
-    for (int e = 0; e < 7; ++e) aux[(size_t)(2 * e) * n + row] = h[e].a, aux[(size_t)(2 * e + 1) * n + row] = h[e].b;
-    aux[(size_t)14 * n + row] = hsum.a, aux[(size_t)15 * n + row] = hsum.b;  // increments; the scan makes them the running sum
-}
-int32_t vx_sha_tree_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, size_t N, const uint64_t* chal, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
+// auxiliary columns of ShaTreeAir: bus_aux.cuh's, from the AIR's own message list (one lane per row, 7 helpers); the table of a tree
+// of N leaves must have 256 N rows
+template <int LOGN, int ID_>
+int32_t ShaTreeAirT<LOGN, ID_>::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    const size_t n = (size_t)1 << log_n, N = TREE_SIZE;
     VX_CHECK(n == 256 * N, "sha tree aux: a tree of %zu leaves has %zu rows, not 2^%d", N, 256 * N, log_n);
-    hipLaunchKernelGGL(k_sha_tree_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, aux, n, N, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]});
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 14 * n, log_n, aux_pub);
+    return bus_gen_aux<ShaTreeAirT>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
+template struct ShaTreeAirT<8, 7>;
+template struct ShaTreeAirT<9, 8>;
+template struct ShaTreeAirT<4, 9>;

@@ -319,3 +319,57 @@ def test_a_table_without_a_message_list_is_closed_on_its_published_total(ctx, vx
         ctx.bus_group_prove(tables, cfg, [[1, 2, 3, 4, 5, 1]])
     assert e.value.code == -5
     tb.free()
+
+
+TAG_BYTE, TAG_KEY = 2, 5
+
+
+def test_the_sha_tree_table_alone_closes_its_bus_against_the_root_bytes(ctx, vx):
+    """ShaTreeAir16 (2^12 rows, the list reads periodic columns and its last helper holds one message): the word messages between a
+    node and its parent close inside the table, the outside party sends the root bytes of the 5 headers; a byte left out is named by
+    the cell that would have received it, found here from the oracle's periodic columns"""
+    from oracle import sha_tree_air as T
+
+    air = T.make_air(16)
+    ch = vx.synth.Chain(5, profile="Ptiny", stride=512)
+    tr, pub = T.gen_trace(ch.state_roots, ch.data_roots, 16)
+    tb = ctx.from_host(tr)
+    tables = [(vx.lib.VX_AIR_SHA_TREE[16], tb, 12, pub)]
+    outside = [[leaf, k, bytes(root)[k], tree, TAG_BYTE, 1] for tree, roots in enumerate((ch.state_roots, ch.data_roots)) for leaf, root in enumerate(roots) for k in range(32)]
+    assert len(outside) == 5 * 2 * 32
+    assert ctx.bus_group_check(tables, outside) is None
+    per = [np.asarray(c) for c in air.periodic_values()]
+    for tree, leaf, k in ((0, 0, 0), (1, 3, 17), (1, 4, 31)):
+        at = (tree * 5 + leaf) * 32 + k
+        assert outside[at][:2] == [leaf, k] and outside[at][3] == tree
+        rows = np.flatnonzero((per[T.P_PBL] + per[T.P_PBR] == 1) & (per[T.P_TREE] == tree) & (per[T.P_CID] == leaf) & (per[T.P_JJ] == k // 4))
+        assert rows.size == 1
+        got = ctx.bus_group_check(tables, outside[:at] + outside[at + 1:])
+        assert tuple(got) == (1, 0, 1 + k % 4, int(rows[0]), P - 1)
+    tb.free()
+    tr0, pub0 = T.gen_trace([], [], 16)  # no leaf enabled: only the word messages, and nothing outside
+    tb0 = ctx.from_host(tr0)
+    assert pub0[16] == 0 and ctx.bus_group_check([(vx.lib.VX_AIR_SHA_TREE[16], tb0, 12, pub0)]) is None
+    tb0.free()
+
+
+def test_the_epoch_end_table_alone_closes_its_bus_against_bytes_and_keys(ctx, vx):
+    """EpochEndAir (2^9 rows, 22 helpers) on the header of tests/test_gpu_epoch_air.py with one new authority: the outside party sends
+    the bytes of the window and takes the four quarters of every key; a quarter left out names the validator's row and that key message"""
+    n_new = 1
+    e = vx.synth.EpochEndHeader(140000, n_new, logs_before=0)
+    hb = ctx.from_host(e.padded)
+    buf, pub, wlen = ctx.epoch_end_trace(hb, e.start_position, n_new, bus_on=1)
+    tables = [(vx.lib.VX_AIR_EPOCH_END, buf, 9, [int(x) for x in pub])]
+    window = bytes(e.bytes[e.start_position + 1: e.start_position + 1 + wlen])
+    sent = [[0, k, window[k], 1, TAG_BYTE, 1] for k in range(wlen)]
+    u32 = lambda b: int.from_bytes(b, "little")  # noqa: E731
+    taken = [[4 * i + q, u32(key[8 * q: 8 * q + 4]), u32(key[8 * q + 4: 8 * q + 8]), 0, TAG_KEY, P - 1] for i, key in enumerate(bytes(k) for k in e.new_pubkeys) for q in range(4)]
+    assert len(sent) == wlen and len(taken) == 4 * n_new
+    assert ctx.bus_group_check(tables, sent + taken) is None
+    for q in (0, 3):
+        got = ctx.bus_group_check(tables, sent + taken[:q] + taken[q + 1:])
+        assert tuple(got) == (1, 0, 40 + q, 1, 1)  # the one validator is row 1; its key quarter q is sent once
+    buf0, pub0, _ = ctx.epoch_end_trace(hb, e.start_position, n_new, bus_on=0)
+    assert ctx.bus_group_check([(vx.lib.VX_AIR_EPOCH_END, buf0, 9, [int(x) for x in pub0])]) is None
+    buf.free(), buf0.free(), hb.free()

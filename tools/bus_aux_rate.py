@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The auxiliary round alone -- vx_stark_aux_trace, HIP-event timed, milliseconds averaged over 20 calls after a warm-up call -- for
-the eight tables whose auxiliary columns come from bus_aux.cuh, each at the shape of its rate tool; the witnesses are random claims
+the ten tables whose auxiliary columns come from bus_aux.cuh, each at the shape of its rate tool; the witnesses are random claims
 of the right ranges (the auxiliary round reads flags and cells, it checks no statement).  One JSON line.  VX_LIB_PATH selects another
-libvxprove build (profiles/r11_bus_aux_refactor.json: the parent commit's and this one alternating)."""
+libvxprove build (profiles/r11_bus_aux_refactor.json, r14_bus_lists_older.json: the parent commit's and this one alternating)."""
 import json
 import os
 import sys
@@ -99,4 +99,17 @@ chains = [T.filler(650, seed=50)]
 tb, pub, _ = ctx.transcript_air_trace([ops for ops, _ in chains], [w for _, w in chains], 15)
 out["transcript_2^15"] = timed(L.VX_AIR_TRANSCRIPT, tb, 15, L.VX_TRANSCRIPT_AIR_AUX_COLS, pub)
 tb.free()
+
+# ShaTreeAir of 256 leaves, 2^16 rows: random cells (every message row of a bottom-level node receives, as in a full range)
+tb = ctx.alloc(L.VX_SHA_TREE_AIR_COLS << 16)
+ctx.fill_random(tb, L.VX_SHA_TREE_AIR_COLS << 16, 2026)
+out["sha_tree_2^16"] = timed(L.VX_AIR_SHA_TREE[256], tb, 16, 16, [0] * 17)
+tb.free()
+
+# EpochEndAir: 300 new authorities, 2^9 rows (the table of vx_rotate_prove)
+e = vx.synth.EpochEndHeader(140000, 300)
+hb = ctx.from_host(e.padded)
+tb, pub, _ = ctx.epoch_end_trace(hb, e.start_position, 300, bus_on=1)
+out["epoch_end_2^9"] = timed(L.VX_AIR_EPOCH_END, tb, 9, L.VX_EPOCH_END_AIR_AUX_COLS, pub)
+tb.free(), hb.free()
 print(json.dumps(out))
