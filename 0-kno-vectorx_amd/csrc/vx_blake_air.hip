@@ -5,6 +5,9 @@
 //             the <= 12 rounds it needs from the chunk's chaining value and writes the row
 //             packed as 96 words; k_blake_expand unpacks words into the 729 byte / limb / bit
 //             cells, a block writing 16 KB runs of one column at a time;
+//             k_blake_count: the multiplicities of the two lookup tables, counted from the packed
+//             words in block-private LDS histograms (one workgroup per part of the bins and slice
+//             of the rows); k_blake_mult adds the slices up into the M1 / M2 columns;
 //   kernel C  k_blake_aux: the logUp helper columns once the lookup challenges are known.
 // Replaces the curta Blake2b witness generation behind hash_encoded_header
 // (/root/reference circuits/builder/header.rs:14-19) for the synthetic header chain.
@@ -89,16 +92,10 @@ __global__ __launch_bounds__(64) void k_blake_chain(const uint8_t* msgs, size_t 
 // A row lane that stored its 729 cells one column at a time walked 729 columns 8n bytes apart: the walk's address
 // translation, not its bytes, set the time (7.8 ms for 3 GB).  So the row is produced in two steps:
 //   k_blake_trace   one lane per trace row (block b, r = row mod 16): recomputes the <= 12 rounds it needs from the
-//                   chunk's chaining value and stores the row PACKED as 96 words (stage[w * n + row]); the same lane knows
-//                   every XOR its row looks up and bumps the multiplicity histograms of the two tables
-//                   (hist[0 .. 2^16) for T1, hist[2^16 .. 2^17) for T2);
+//                   chunk's chaining value and stores the row PACKED as 96 words (stage[w * n + row]);
 //   k_blake_expand  one block per (2048 rows, packed word): every cell is (word >> shift) & mask, and a block writes
 //                   16 KB runs of one column at a time.
 // Packed words: 8 per G (A1 D1 C1 B1 A2 D2 C2 X; L / T are the low 7 bits / top bit of X's bytes), then
-#ifndef VX_HIST_COPIES
-#define VX_HIST_COPIES 8
-#endif
-constexpr int HIST_COPIES = VX_HIST_COPIES;
 constexpr int SW_CAR = 64, SW_MS = 65, SW_MB = 81, SW_HL = 82, SW_D = 90, SW_FLAGS = 94, SW_TN = 95, SW_WIN = 96, N_STAGE = 97;
 // SW_CAR: 32 carries x 2 bits; SW_MS: the 16 message words in this row's order; SW_D: 4 words of two limbs;
 // SW_FLAGS: ACT FIN FIRST CAP FA MDF0 MDF1 MDF3 (bits 0..7), INC (8..15), CNT (16..23), MK (24..31), E (32..39), SZ (40..63); SW_TN: T (low half),
@@ -108,15 +105,9 @@ struct ExpandEntry {
     uint8_t shift, bits;
 };
 __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const BlockDesc* descs, const uint64_t* hchain, size_t n_real,
-                                                     uint64_t* __restrict__ stage, uint32_t* __restrict__ hist, uint32_t* __restrict__ rc_part, size_t n,
-                                                     uint32_t win_off, uint32_t win_len) {
+                                                     uint64_t* __restrict__ stage, size_t n, uint32_t win_off, uint32_t win_len) {
     using namespace blk;
-    // the (byte, 0) range-check lookups of every row fall on 256 counters = 8 cache lines: as global atomics they
-    // serialise in L2 (the kernel took 7.5 ms for 0.4 GB of stores); they are counted per block in LDS instead and
-    // summed by k_blake_mult.  n is a multiple of the block size (n >= 2^16).
-    __shared__ uint32_t rc_lds[256];
-    rc_lds[threadIdx.x] = 0;
-    __syncthreads();
+    // n is a multiple of the block size (n >= 2^16)
     const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t b = row >> 4;
     const int r = (int)(row & 15);
@@ -143,17 +134,6 @@ __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const 
     }
     auto st = [&](int w) -> uint64_t& { return stage[(size_t)w * n + row]; };
     auto gw = [&](int k, int slot) -> uint64_t& { return st(8 * k + slot); };  // slot 7 = X (L / T)
-    // HIST_COPIES private copies of the two histograms, picked by block index: consecutive blocks go to different XCDs (each
-    // with its own L2), and counters shared by all of them bounce between the L2s; k_blake_mult adds the copies up
-    uint32_t* const hc = hist + (size_t)(blockIdx.x % HIST_COPIES) * 131072;
-    auto look1 = [&](uint64_t a, uint64_t bq) {  // 8 byte lookups (a_i, b_i, .) into T1
-#pragma unroll
-        for (int j = 0; j < 8; ++j) atomicAdd(&hc[((a >> (8 * j)) & 0xFF) | (((bq >> (8 * j)) & 0xFF) << 8)], 1u);
-    };
-    auto look2 = [&](uint64_t a, uint64_t bq) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) atomicAdd(&hc[65536 + (((a >> (8 * j)) & 0xFF) | (((bq >> (8 * j)) & 0xFF) << 8))], 1u);
-    };
     // ---- G area + carries
     blake_init_v(v, h, d.t, d.fin);
     uint64_t carw = 0;
@@ -169,8 +149,6 @@ __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const 
             carries(a, bq, x, car);
             carries(a1, b1, y, car + 2);
             carw |= ((uint64_t)car[0] | ((uint64_t)car[1] << 2) | ((uint64_t)car[2] << 4) | ((uint64_t)car[3] << 6)) << (8 * k);
-            // the row's lookups: (d, A1), (b, C1), (D1, A2) into T1 and (B1, C2) into T2
-            look1(dd, a1), look1(bq, c1), look1(d1, a2), look2(b1, c2);
             va = a2, vb = b2, vc = c2, vd = d2;
         };
         G(0, v[0], v[4], v[8], v[12], m[sg[0]], m[sg[1]]);
@@ -198,7 +176,6 @@ __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const 
                     const uint64_t u = v[w] ^ v[8 + w];
                     const uint64_t x = r == 13 ? v[w] : u, y = r == 13 ? v[8 + w] : h[w];
                     gw(w, S_D1) = x, gw(w, S_A2) = y, gw(w, S_D2) = b_rotr(x ^ y, 16);
-                    look1(x, y);
                 }
         }
     }
@@ -209,8 +186,6 @@ __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const 
     // ---- message schedule + bytes of natural word r (range checked as (byte, 0, byte) in T1)
     for (int s = 0; s < 16; ++s) st(SW_MS + s) = m[ORDER[r][s]];
     st(SW_MB) = m[r];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) atomicAdd(&rc_lds[(m[r] >> (8 * j)) & 0xFF], 1u);
     // ---- H register, digest register
     for (int w = 0; w < 8; ++w) st(SW_HL + w) = r <= 13 ? h[w] : (r == 14 ? h_out[w] : (d.fin ? (w == 0 ? IV[0] ^ 0x01010020ULL : IV[w]) : h_out[w]));
     const bool cap = d.act && d.fin;
@@ -236,8 +211,6 @@ __global__ __launch_bounds__(256) void k_blake_trace(const uint8_t* msgs, const 
                    (mdf << 5) | ((uint64_t)d.inc << 8) | (cnt << 16) | (mk << 24) | (eb << 32) | ((uint64_t)d.size << 40);
     st(SW_TN) = (uint64_t)d.t | ((uint64_t)d.num << 32);
     st(SW_WIN) = (uint64_t)kof | ((uint64_t)(srw ? 0 : 1) << 32);
-    __syncthreads();
-    rc_part[(size_t)blockIdx.x * 256 + threadIdx.x] = rc_lds[threadIdx.x];
 }
 constexpr int EXP_RPL = 8;  // rows per lane: a block writes 8 x 2 KB = 16 KB of a column per visit
 __global__ __launch_bounds__(256) void k_blake_expand(const uint64_t* __restrict__ stage, uint64_t* __restrict__ tr, size_t n, const ExpandEntry* __restrict__ ent,
@@ -290,15 +263,80 @@ static void blake_expand_table(std::vector<ExpandEntry>& ent, std::vector<uint32
         off.push_back((uint32_t)ent.size());
     }
 }
+// ---- multiplicities -----------------------------------------------------------------------------------------------
+// Every row looks up to 256 (a, b) byte pairs in T1 (key a | b << 8) and 64 in T2: ~100 M lookups on random bins at 2^19 rows.
+// As global atomics they held the whole chip for 4 ms while issuing next to nothing.  They are counted in LDS instead:
+//   k_blake_count  one workgroup per (part, slice).  A part is a contiguous range of 2^PART_BITS bins of one table (T1 with
+//                  b < 128, T1 with b >= 128, T2 low, T2 high at 15 bits), a slice every CNT_SLICES-th tile of 1024 rows.  The
+//                  workgroup re-derives the lookups of its rows from the packed words (the b / d operands of a G are
+//                  rotl(B1, 24) ^ C1 and rotl(D1, 32) ^ A1), counts those that fall into its part in a private 32-bit LDS
+//                  histogram, and stores it with plain stores to partial[part][slice][bin]; a slice without lookups stores zeros,
+//                  so nothing is cleared beforehand.  The (byte, 0, byte) range checks of the message bytes are T1 keys with b = 0.
+//   k_blake_mult   adds the slices of the bin that belongs to its row.
+// T1 has three lookups for every one of T2, so its parts get three quarters of the workgroups.
+#ifndef VX_PART_BITS
+#define VX_PART_BITS 15  // 128 KiB of LDS, one workgroup per CU.  14 (64 KiB, twice the parts): 226 us against 142 alone, no better in a proof (profiles/README.md)
+#endif
+constexpr int PART_BITS = VX_PART_BITS, PART = 1 << PART_BITS, PARTS = 65536 >> PART_BITS;  // PARTS per table
+constexpr int CNT_WGS = 256, CNT_THREADS = 1024;                                             // about one workgroup per CU
+constexpr int CNT_SLICES1 = 3 * CNT_WGS / (4 * PARTS), CNT_SLICES2 = CNT_WGS / (4 * PARTS);
+static_assert(PART_BITS >= 12 && PART_BITS <= 15 && CNT_SLICES2 >= 1, "a part is 16 .. 128 KiB of LDS");
+__global__ __launch_bounds__(CNT_THREADS) void k_blake_count(const uint64_t* __restrict__ stage, size_t n, uint32_t* __restrict__ partial) {
+    using namespace blk;
+    __shared__ uint32_t h[PART];
+    const bool t2 = blockIdx.x >= PARTS * CNT_SLICES1;
+    const uint32_t wg = t2 ? blockIdx.x - PARTS * CNT_SLICES1 : blockIdx.x, slices = t2 ? CNT_SLICES2 : CNT_SLICES1;
+    const uint32_t sub = wg / slices, slice = wg % slices;
+    for (int i = threadIdx.x; i < PART; i += CNT_THREADS) h[i] = 0;
+    __syncthreads();
+    auto look = [&](uint64_t a, uint64_t b) {  // 8 byte lookups (a_j, b_j, .)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t key = (uint32_t)((a >> (8 * j)) & 0xFF) | ((uint32_t)((b >> (8 * j)) & 0xFF) << 8);
+            if ((key >> PART_BITS) == sub) atomicAdd(&h[key & (PART - 1)], 1u);
+        }
+    };
+    auto rotl = [](uint64_t x, int s) -> uint64_t { return (x << s) | (x >> (64 - s)); };
+    // n is a multiple of the tile (n >= 2^16)
+    for (size_t row = (size_t)slice * CNT_THREADS + threadIdx.x; row < n; row += (size_t)slices * CNT_THREADS) {
+        const int r = (int)(row & 15);
+        auto st = [&](int w) -> uint64_t { return stage[(size_t)w * n + row]; };
+        const bool g_row = r >= 1 && r <= 12;
+        if (t2) {
+            if (g_row) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) look(st(8 * k + S_B1), st(8 * k + S_C2));
+            }
+        } else {
+            if (g_row) {  // (d, A1), (b, C1), (D1, A2)
+#pragma unroll 4
+                for (int k = 0; k < 8; ++k) {
+                    const uint64_t a1 = st(8 * k + S_A1), d1 = st(8 * k + S_D1), c1 = st(8 * k + S_C1), b1 = st(8 * k + S_B1), a2 = st(8 * k + S_A2);
+                    look(rotl(d1, 32) ^ a1, a1), look(rotl(b1, 24) ^ c1, c1), look(d1, a2);
+                }
+            } else if (r == 13 || r == 14) {  // the feed-forward XORs
+#pragma unroll
+                for (int w = 0; w < 8; ++w) look(st(8 * w + S_D1), st(8 * w + S_A2));
+            }
+            if (sub == 0) look(st(SW_MB), 0);  // the message bytes' range checks
+        }
+    }
+    __syncthreads();
+    uint32_t* out = partial + (t2 ? (size_t)65536 * CNT_SLICES1 : 0) + ((size_t)sub * slices + slice) * PART;
+    for (int i = threadIdx.x; i < PART; i += CNT_THREADS) out[i] = h[i];
+}
 // the multiplicity columns: all counts in the first copy of the periodic tables
-__global__ __launch_bounds__(256) void k_blake_mult(const uint32_t* hist, const uint32_t* rc_part, uint64_t* tr, size_t n) {
+__global__ __launch_bounds__(256) void k_blake_mult(const uint32_t* __restrict__ partial, uint64_t* tr, size_t n) {
     const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (row >= n) return;
     uint64_t m1 = 0, m2 = 0;
-    if (row < 65536)
-        for (int cpy = 0; cpy < HIST_COPIES; ++cpy) m1 += hist[(size_t)cpy * 131072 + row], m2 += hist[(size_t)cpy * 131072 + 65536 + row];
-    if (row < 256)  // table rows (a, b = 0): plus the per-block range-check counts
-        for (size_t b = 0; b < n / 256; ++b) m1 += rc_part[b * 256 + row];
+    if (row < 65536) {
+        const size_t sub = row >> PART_BITS, bin = row & (PART - 1);
+        const uint32_t* p1 = partial + sub * CNT_SLICES1 * PART + bin;
+        const uint32_t* p2 = partial + (size_t)65536 * CNT_SLICES1 + sub * CNT_SLICES2 * PART + bin;
+        for (int s = 0; s < CNT_SLICES1; ++s) m1 += p1[(size_t)s * PART];
+        for (int s = 0; s < CNT_SLICES2; ++s) m2 += p2[(size_t)s * PART];
+    }
     tr[(size_t)blk::M1 * n + row] = m1;
     tr[(size_t)blk::M2 * n + row] = m2;
 }
@@ -526,7 +564,7 @@ int32_t vx_blake_chain_trace(vx_ctx* ctx, const vx_buf* headers, size_t stride, 
     // device scratch: sizes | block_base | digests | hchain | descs
     const size_t w_sizes = (n_headers * 4 + 7) / 8, w_dig = n_headers * 4, w_hc = n_real * 8;
     const size_t w_desc = (n_blocks * sizeof(BlockDesc) + 7) / 8;
-    const size_t w_hist = (size_t)HIST_COPIES * 65536 + n / 2;  // HIST_COPIES x two tables x 2^16 uint32 counters + 256 range-check counters per 256-row block
+    const size_t w_hist = (size_t)65536 * (CNT_SLICES1 + CNT_SLICES2) / 2;  // a slice of uint32 counters per table bin: CNT_SLICES1 for T1, CNT_SLICES2 for T2
     std::vector<ExpandEntry> ent;
     std::vector<uint32_t> eoff;
     blake_expand_table(ent, eoff);
@@ -588,14 +626,15 @@ int32_t vx_blake_chain_trace(vx_ctx* ctx, const vx_buf* headers, size_t stride, 
         memcpy(d.D, D, 32);
     }
     VX_HIP(hipMemcpyAsync(d_desc, descs.data(), n_blocks * sizeof(BlockDesc), hipMemcpyHostToDevice, ctx->stream));
-    VX_HIP(hipMemsetAsync(d_hist, 0, (size_t)HIST_COPIES * 65536 * 8, ctx->stream));
     hipLaunchKernelGGL(k_blake_trace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t*)headers->d,
-                       (const BlockDesc*)d_desc, (const uint64_t*)d_hc, n_real, d_stage, d_hist, d_hist + (size_t)HIST_COPIES * 131072, n, window_offset, window_length);
+                       (const BlockDesc*)d_desc, (const uint64_t*)d_hc, n_real, d_stage, n, window_offset, window_length);
+    VX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_blake_count, dim3(PARTS * (CNT_SLICES1 + CNT_SLICES2)), dim3(CNT_THREADS), 0, ctx->stream, (const uint64_t*)d_stage, n, d_hist);
     VX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_blake_expand, dim3((unsigned)((n + 256 * EXP_RPL - 1) / (256 * EXP_RPL)), N_STAGE), dim3(256), 0, ctx->stream,
                        (const uint64_t*)d_stage, trace_out->d, n, (const ExpandEntry*)d_ent, (const uint32_t*)d_eoff);
     VX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_blake_mult, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_hist, (const uint32_t*)(d_hist + (size_t)HIST_COPIES * 131072), trace_out->d, n);
+    hipLaunchKernelGGL(k_blake_mult, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_hist, trace_out->d, n);
     VX_HIP(hipGetLastError());
     VX_HIP(hipStreamSynchronize(ctx->stream));  // descs must outlive the kernel
     for (int j = 0; j < 8; ++j) {

@@ -9,7 +9,8 @@
 //                normalisation (c = F mod 2q, r_k) which every lane runs redundantly on the 16 coefficients.  Rows go to a
 //                row-major int32 staging buffer (16 lanes write 16 neighbouring cells)
 //   k_ed_expand  staging [n][838] int32 -> trace [838][n] field elements through an LDS tile (negative limbs -> p + v)
-//   k_ed_hist    multiplicities of the 16-bit range table (global atomics on a few interleaved copies)
+//   k_ed_hist    multiplicities of the 16-bit range table, counted in block-private LDS histograms: one workgroup per (part of
+//                the bins, slice of the staged cells); k_ed_mult adds the slices up into the MULT column
 //   k_ed_aux     one lane per row: 1 / (beta_r + v) comes from a 2^16-entry table built once per proof, so the 336 range
 //                helpers of a row are gathers and additions; the six bus helpers exist on rows 0, 1, 255 of signed slots
 #include <string.h>
@@ -309,18 +310,50 @@ __global__ __launch_bounds__(256) void k_ed_expand(const int32_t* stage, uint64_
         trace[(size_t)(col0 + c) * n + row0 + tx] = v < 0 ? GL_P - (uint64_t)(-(int64_t)v) : (uint64_t)v;
     }
 }
-// one block per staged row; the rows of the idle slot count once for every idle slot of the trace
-constexpr int ED_HIST_COPIES = 32;
-__global__ __launch_bounds__(256) void k_ed_hist(const int32_t* stage, size_t k_active, uint32_t idle_weight, uint32_t* hist) {
-    const size_t row = blockIdx.x;
-    const uint32_t w = (row >> 8) < k_active ? 1u : idle_weight;
-    uint32_t* h = hist + (size_t)(blockIdx.x % ED_HIST_COPIES) * 65536;
-    for (int col = threadIdx.x; col < CELLS; col += 256) atomicAdd(&h[(uint32_t)stage[row * COLS + col] & 65535u], w);
+// Multiplicities of the range table: every staged row has CELLS 16-bit cells, 35 M of them for 201 signatures.  A third of them are
+// the high halves of carries, a handful of values around 2^15 that are the same from row to row; as global atomics they serialised.
+// One workgroup per (part, slice): a part is a contiguous range of 2^ED_PART_BITS bins, a slice every ED_SLICES-th run of
+// ED_HIST_THREADS items.  An item is one column of ED_HIST_UNROLL consecutive rows (a wave reads 64 neighbouring cells of a row): the
+// lane first adds up equal values in registers, then counts what falls into its part in the workgroup's private 32-bit LDS histogram,
+// which is stored with plain stores to partial[part][slice][bin] (nothing is cleared beforehand).  The rows of the idle slot count
+// once for every idle slot of the trace; the weight is added in LDS (totals stay below 2^32: n CELLS < 2^30).
+#ifndef VX_ED_PART_BITS
+#define VX_ED_PART_BITS 14  // 64 KiB of LDS, four parts.  15 (128 KiB, two parts) is faster alone (136 us against 247 for 201 signatures); inside a
+#endif                      // proof the launch mostly waits for a CU beside the other tables' kernels, and only 64 KiB ever waited less (profiles/README.md)
+constexpr int ED_PART_BITS = VX_ED_PART_BITS, ED_PART = 1 << ED_PART_BITS, ED_PARTS = 65536 >> ED_PART_BITS;
+constexpr int ED_HIST_WGS = 128, ED_SLICES = ED_HIST_WGS / ED_PARTS, ED_HIST_THREADS = 1024, ED_HIST_UNROLL = 8;
+static_assert(ED_PART_BITS >= 12 && ED_PART_BITS <= 15, "a part is 16 .. 128 KiB of LDS");
+__global__ __launch_bounds__(ED_HIST_THREADS) void k_ed_hist(const int32_t* __restrict__ stage, size_t k_active, uint32_t idle_weight, uint32_t* __restrict__ partial) {
+    __shared__ uint32_t h[ED_PART];
+    const uint32_t sub = blockIdx.x / ED_SLICES, slice = blockIdx.x % ED_SLICES;
+    for (int i = threadIdx.x; i < ED_PART; i += ED_HIST_THREADS) h[i] = 0;
+    __syncthreads();
+    const uint32_t items = (uint32_t)((k_active + 1) * (256 / ED_HIST_UNROLL) * CELLS);  // < 2^27: at most 2^20 rows
+    for (uint32_t item = slice * ED_HIST_THREADS + threadIdx.x; item < items; item += ED_SLICES * ED_HIST_THREADS) {
+        const uint32_t chunk = item / CELLS, col = item - chunk * CELLS;
+        const int32_t* p = stage + (size_t)chunk * ED_HIST_UNROLL * COLS + col;
+        const uint32_t w = chunk / (256 / ED_HIST_UNROLL) < k_active ? 1u : idle_weight;
+        uint32_t v[ED_HIST_UNROLL], c[ED_HIST_UNROLL];
+#pragma unroll
+        for (int u = 0; u < ED_HIST_UNROLL; ++u) v[u] = (uint32_t)p[(size_t)u * COLS] & 65535u, c[u] = w;  // (the loads are in flight together)
+#pragma unroll
+        for (int u = 1; u < ED_HIST_UNROLL; ++u)
+#pragma unroll
+            for (int t = 0; t < u; ++t)
+                if (c[t] && v[t] == v[u]) c[t] += c[u], c[u] = 0;  // the first cell of a value carries the weight of all of them
+#pragma unroll
+        for (int u = 0; u < ED_HIST_UNROLL; ++u)
+            if (c[u] && (v[u] >> ED_PART_BITS) == sub) atomicAdd(&h[v[u] & (ED_PART - 1)], c[u]);
+    }
+    __syncthreads();
+    uint32_t* out = partial + ((size_t)sub * ED_SLICES + slice) * ED_PART;
+    for (int i = threadIdx.x; i < ED_PART; i += ED_HIST_THREADS) out[i] = h[i];
 }
-__global__ __launch_bounds__(256) void k_ed_mult(const uint32_t* hist, uint64_t* mult_col) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void k_ed_mult(const uint32_t* __restrict__ partial, uint64_t* mult_col) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;  // table row = bin, 2^16 of them
+    const uint32_t* p = partial + (i >> ED_PART_BITS) * ED_SLICES * ED_PART + (i & (ED_PART - 1));
     uint64_t s = 0;
-    for (int c = 0; c < ED_HIST_COPIES; ++c) s += hist[(size_t)c * 65536 + i];
+    for (int c = 0; c < ED_SLICES; ++c) s += p[(size_t)c * ED_PART];
     mult_col[i] = s;
 }
 
@@ -411,7 +444,7 @@ int32_t vx_ed_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, const uint8_t* sigs
     VX_CHECK(k < m, "ed trace: %zu signatures do not fit the %zu slots of 2^%d rows (one slot stays idle)", k, m - 1, log_n);
     // device scratch: keys | sigs | msg | idx | bad | slots | hist, then the staging buffer from the pool
     const size_t w_keys = 4 * n_sigs + 1, w_sigs = 8 * n_sigs + 1, w_msg = 8, w_idx = (k + 1) / 2 + 1, w_slots = ((k + 1) * sizeof(EdSlot) + 7) / 8;
-    const size_t w_hist = (size_t)ED_HIST_COPIES * 65536 / 2;
+    const size_t w_hist = (size_t)ED_SLICES * 65536 / 2;  // a slice of uint32 counters per table bin
     uint64_t* sc;
     VX_TRY(vx_scratch(ctx, w_keys + w_sigs + w_msg + w_idx + 1 + w_slots + w_hist, &sc));
     uint8_t* d_keys = (uint8_t*)sc;
@@ -428,13 +461,12 @@ int32_t vx_ed_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, const uint8_t* sigs
     if (k) VX_HIP(hipMemcpyAsync(d_idx, idx.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
     VX_HIP(hipMemcpyAsync(d_msg, msg, msg_len, hipMemcpyHostToDevice, ctx->stream));
     VX_HIP(hipMemsetAsync(d_bad, 0, 8, ctx->stream));
-    VX_HIP(hipMemsetAsync(d_hist, 0, w_hist * 8, ctx->stream));
     int32_t* stage = (int32_t*)vx_pool_alloc(ctx, k4 * 256 * (size_t)COLS * 4);
     if (!stage) return vx_fail(ctx, VX_ERR_OOM, "ed trace: out of device memory");
     hipLaunchKernelGGL(k_ed_slots, dim3((unsigned)((k + 1 + 63) / 64)), dim3(64), 0, ctx->stream, d_keys, d_sigs, d_msg, msg_len, (const uint32_t*)d_idx, k, d_slots, d_bad);
     hipLaunchKernelGGL(k_ed_rows, dim3((unsigned)k4), dim3(64), 0, ctx->stream, (const EdSlot*)d_slots, stage, k, d_bad);
     hipLaunchKernelGGL(k_ed_expand, dim3((unsigned)(n / 64), (COLS + 63) / 64), dim3(256), 0, ctx->stream, (const int32_t*)stage, trace_d, n, k);
-    hipLaunchKernelGGL(k_ed_hist, dim3((unsigned)((k + 1) * 256)), dim3(256), 0, ctx->stream, (const int32_t*)stage, k, (uint32_t)(m - k), d_hist);
+    hipLaunchKernelGGL(k_ed_hist, dim3(ED_HIST_WGS), dim3(ED_HIST_THREADS), 0, ctx->stream, (const int32_t*)stage, k, (uint32_t)(m - k), d_hist);
     hipLaunchKernelGGL(k_ed_mult, dim3(256), dim3(256), 0, ctx->stream, (const uint32_t*)d_hist, trace_d + (size_t)MULT * n);
     const hipError_t e = hipGetLastError();
     vx_pool_free(ctx, stage);

@@ -2,7 +2,7 @@
 """The small kernels at the end of the kernel list (tree tops, query-phase gathers, runtime copies) in a rocprofv3 (rocpd sqlite)
 kernel trace of `bench.py --inflight 1`: launches and kernel time per proof, and for every launch how long it WAITED (from the end
 of the kernel before it on the same stream, i.e. the moment it could have started, to its own start) against how long it RAN.
-usage: rocpd_tail.py <results.db or directory> [n_proofs_in_trace]"""
+usage: rocpd_tail.py <results.db or directory> [n_proofs_in_trace] [kernel,kernel,...  (these instead of the tail kernels)]"""
 import glob
 import sqlite3
 import sys
@@ -10,6 +10,8 @@ import sys
 TAIL = ("k_merkle_top", "k_merkle_level_coop", "k_merkle_level", "k_hash_leaves_coop", "k_gather_siblings", "k_gather_rows", "k_fri_gather_leaves",
         "__amd_rocclr_copyBuffer")
 
+if len(sys.argv) > 3:
+    TAIL = tuple(sys.argv[3].split(","))
 db = sys.argv[1]
 if not db.endswith(".db"):
     db = glob.glob(db + "/**/*.db", recursive=True)[0]
