@@ -226,8 +226,8 @@ struct RowViewN {  // column-major LDE, rows i[0..R) of it
     }
 };
 
-// ---- the bus of a table whose helpers hold two messages each (the Merkle-opening, leaf, FRI and transcript tables, the SHA-256
-// Merkle tree, the epoch-end table) ----
+// ---- the bus of a table whose helpers hold two messages each, or one (the Merkle-opening, leaf, FRI and transcript tables, the
+// SHA-256 chain and Merkle tree, the SHA-512 table, the epoch-end table) ----
 // Such an AIR states its messages ONCE, for its constraints (bus_constraints below), for its witness (bus_aux.cuh) and for the
 // balance check of a bus group (bus_balance.cuh):
 //   N_HELP     helpers: helper e, an extension cell at COLS + 2 e, holds m_a / D_a + m_b / D_b of message pair e; the running

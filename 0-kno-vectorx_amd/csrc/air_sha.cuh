@@ -10,7 +10,9 @@
 // tuples (4 index + j, l0 + 2^16 l1, l2 + 2^16 l3, 0, TAG_KEY) of little-endian 16-bit limbs from the rows where its words
 // 2j / 2j+1 sit in window positions 0 / 1 (rows 0, 2, 4, 6 of FIRST, rows 8, 10, 12, 14 of DATA); index = key counter KC - 1,
 // and KC ends as the number of committed keys (public input 8; the denominator of the 2/3 threshold, justification.rs:164-186).
-// Constraint ORDER is protocol: oracle/sha_air.py restates it independently.
+// The bus is stated once, in `messages` (air.cuh "the bus of a table ..."): one message in one helper; the constraints (bus_constraints),
+// the witness (bus_aux.cuh) and the balance check of a bus group read that list, and `bus_periodic` states the three periodic columns
+// it reads.  Constraint ORDER is protocol: oracle/sha_air.py restates it independently.
 #pragma once
 #include <vector>
 
@@ -52,6 +54,14 @@ VX_HD uint32_t iv(int i) { return IV_H[i]; }
 // words 8..15 of the single block of a 32-byte message; second block of a 64-byte message
 VX_HD constexpr uint32_t tail32(int j) { return j == 0 ? 0x80000000u : (j == 7 ? 256u : 0u); }
 VX_HD constexpr uint32_t pad64(int j) { return j == 0 ? 0x80000000u : (j == 15 ? 512u : 0u); }
+// the value of the nb little-endian bit columns col0 .. col0 + nb - 1 of a row
+template <class F, class Row>
+VX_HD F val(const Row& row, int col0, int nb) {
+    F acc = row[col0 + nb - 1];
+#pragma unroll 1
+    for (int i = nb - 2; i >= 0; --i) acc = acc + acc + row[col0 + i];
+    return acc;
+}
 }  // namespace shc
 
 // Sections 1-7 shared by every SHA-256 table: the rows of a compression and the hand-over at a block boundary.
@@ -62,14 +72,8 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
     const F sel0 = per[0], sel63 = per[1], sched_on = per[2], kr = per[3];
     const F one = F::from(1), two = F::from(2), two32 = F::from(1ULL << 32);
     const F in_block = one - sel63;
-    auto val = [&](const Row& row, int col0, int nb) -> F {
-        F acc = row[col0 + nb - 1];
-#pragma unroll 1
-        for (int i = nb - 2; i >= 0; --i) acc = acc + acc + row[col0 + i];
-        return acc;
-    };
-    auto window = [&](const Row& row, int p) -> F { return p == 0 ? val(row, W0B, 32) : p == 1 ? val(row, W1B, 32) : p == 14 ? val(row, W14B, 32) : row[WV(p)]; };
-    auto state_word = [&](const Row& row, int wd) -> F { return wd == 3 ? row[DV] : wd == 7 ? row[HV] : val(row, st_bits(wd), 32); };
+    auto window = [&](const Row& row, int p) -> F { return p == 0 ? val<F>(row, W0B, 32) : p == 1 ? val<F>(row, W1B, 32) : p == 14 ? val<F>(row, W14B, 32) : row[WV(p)]; };
+    auto state_word = [&](const Row& row, int wd) -> F { return wd == 3 ? row[DV] : wd == 7 ? row[HV] : val<F>(row, st_bits(wd), 32); };
     // ---- 1. booleans
     {
         const int lo[4] = {0, NA0, CE0, FFC0}, hi[4] = {DV, WV0, FFV0, HIN0};
@@ -125,9 +129,9 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
             const F ab = a * b;
             mj = mj + mj + (ab + (a + b) * cc - two * (ab * cc));
         }
-        const F t1 = loc[HV] + x3(E_, 6, 11, 25) + ch + kr + val(loc, W0B, 32);
-        c.constraint(val(loc, NE0, 32) + two32 * val(loc, CE0, 3) - (loc[DV] + t1));
-        c.constraint(val(loc, NA0, 32) + two32 * val(loc, CA0, 3) - (t1 + x3(A_, 2, 13, 22) + mj));
+        const F t1 = loc[HV] + x3(E_, 6, 11, 25) + ch + kr + val<F>(loc, W0B, 32);
+        c.constraint(val<F>(loc, NE0, 32) + two32 * val<F>(loc, CE0, 3) - (loc[DV] + t1));
+        c.constraint(val<F>(loc, NA0, 32) + two32 * val<F>(loc, CA0, 3) - (t1 + x3(A_, 2, 13, 22) + mj));
     }
     // ---- 4. state shift inside a block
 #pragma unroll 1
@@ -139,19 +143,19 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
         c.constraint(in_block * (nxt[F_ + i] - loc[E_ + i]));
         c.constraint(in_block * (nxt[G_ + i] - loc[F_ + i]));
     }
-    c.constraint(in_block * (nxt[DV] - val(loc, C_, 32)));
-    c.constraint(in_block * (nxt[HV] - val(loc, G_, 32)));
+    c.constraint(in_block * (nxt[DV] - val<F>(loc, C_, 32)));
+    c.constraint(in_block * (nxt[HV] - val<F>(loc, G_, 32)));
     // ---- 5. message schedule: window shift, and w_{r+16} while r <= 47
 #pragma unroll 1
     for (int i = 0; i < 32; ++i) c.constraint(in_block * (nxt[W0B + i] - loc[W1B + i]));
 #pragma unroll 1
     for (int p = 1; p < 15; ++p) c.constraint(in_block * (window(nxt, p) - window(loc, p + 1)));
-    c.constraint(sched_on * (nxt[WV15] + two32 * val(loc, CW0, 2) - (loc[SV] + loc[WV(9)] + val(loc, W0B, 32))));
+    c.constraint(sched_on * (nxt[WV15] + two32 * val<F>(loc, CW0, 2) - (loc[SV] + loc[WV(9)] + val<F>(loc, W0B, 32))));
     // ---- 6. feed-forward at r = 63: FF = H_in + (NA, a, b, c, NE, e, f, g)
     {
         const int s64[8] = {NA0, A_, B_, C_, NE0, E_, F_, G_};
 #pragma unroll 1
-        for (int wd = 0; wd < 8; ++wd) c.constraint(sel63 * (loc[FFV0 + wd] + two32 * loc[FFC0 + wd] - (loc[HIN0 + wd] + val(loc, s64[wd], 32))));
+        for (int wd = 0; wd < 8; ++wd) c.constraint(sel63 * (loc[FFV0 + wd] + two32 * loc[FFC0 + wd] - (loc[HIN0 + wd] + val<F>(loc, s64[wd], 32))));
     }
     // ---- 7. block boundary: next start state = FF where data_flag, IV otherwise; H_in register
 #pragma unroll 1
@@ -160,7 +164,7 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
         if (sb >= 0) {
 #pragma unroll 1
             for (int i = 0; i < 32; ++i) c.constraint(sel63 * (one - data_flag) * (nxt[sb + i] - F::from((uint64_t)((iv(wd) >> i) & 1))));
-            c.constraint(sel63 * data_flag * (val(nxt, sb, 32) - loc[FFV0 + wd]));
+            c.constraint(sel63 * data_flag * (val<F>(nxt, sb, 32) - loc[FFV0 + wd]));
         } else {
             c.constraint(sel63 * (state_word(nxt, wd) - (data_flag * loc[FFV0 + wd] + (one - data_flag) * F::from((uint64_t)iv(wd)))));
         }
@@ -172,14 +176,43 @@ __host__ __device__ inline void sha_compression_constraints(const Row& loc, cons
 struct ShaAir {
     static constexpr int ID = 4, COLS = shc::CHAIN_COLS, PUB = 10, PERIODIC = 7, PERIOD_LOG = 6, QUOT_ROWS_PER_LANE = 1, AUX = 4, CHAL = 4, AUXPUB = 1, EXACT_LOG = 0;
     static constexpr int plog(int) { return 6; }
-    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_sha_air.hip
+    // the key-send rows of FIRST / DATA blocks and the quarter j sent there (per[4 .. 6]; the other columns are not the list's)
+    VX_HD static void bus_periodic(size_t row, uint64_t* per) {
+        const size_t r = row & 63;
+        const bool send = r < 16 && !(r & 1);
+        per[4] = send && r < 8;
+        per[5] = send && r >= 8;
+        per[6] = send ? (r & 7) >> 1 : 0;
+    }
     static void periodic_values(std::vector<uint64_t>& v) {
         v.assign(7 * 64, 0);
         v[0] = 1;                                      // sel_0
         v[64 + 63] = 1;                                // sel_63
         for (int r = 0; r <= 47; ++r) v[128 + r] = 1;  // schedule active
         for (int r = 0; r < 64; ++r) v[192 + r] = shc::K_H[r];
-        for (int r = 0; r < 16; r += 2) v[(r < 8 ? 256 : 320) + r] = 1, v[384 + r] = (r & 7) >> 1;  // key-send rows of FIRST / DATA blocks, j
+        for (int r = 0; r < 64; ++r) {
+            uint64_t per[7];
+            bus_periodic(r, per);
+            v[256 + r] = per[4], v[320 + r] = per[5], v[384 + r] = per[6];
+        }
+    }
+
+    static constexpr int N_HELP = 1, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256, BUS_PERIODIC = 1;
+
+    // the one message (ordinal 0): a key quarter, sent to EdAir under the block's flag or received from the epoch-end table
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* per, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace shc;
+        const F one = F::from(1), k8 = F::from(256), k16 = F::from(65536);
+        auto limbs = [&](int col0) -> F {  // bytes b0 b1 b2 b3 of the big-endian word: (b0 + 256 b1) + 2^16 (b2 + 256 b3)
+            return val<F>(loc, col0 + 24, 8) + val<F>(loc, col0 + 16, 8) * k8 + (val<F>(loc, col0 + 8, 8) + val<F>(loc, col0, 8) * k8) * k16;
+        };
+        // public input 9 = bus mode: 0 nothing, 1 SEND the flagged keys (to EdAir), 2 RECEIVE every key (from the epoch-end table)
+        const F mode = pub[9], inv2 = F::from(0x7FFFFFFF80000001ULL), on = mode * (F::from(3) - mode) * inv2, rcv = mode * (mode - one) * inv2;
+        const F m = on * (per[4] * loc[T_FIRST] + per[5] * loc[T_DATA]) * (loc[SGC] * (one - rcv) - rcv);
+        const X2<F> d = bus.key((loc[KC] - one) * F::from(4) + per[6], limbs(W0B), limbs(W1B));
+        s.single(m, d);
     }
 
     template <class F, class Row, class C>
@@ -188,13 +221,7 @@ struct ShaAir {
         const F sel0 = per[0], sel63 = per[1];
         const F one = F::from(1);
         const F in_block = one - sel63;
-        auto val = [&](const Row& row, int col0, int nb) -> F {
-            F acc = row[col0 + nb - 1];
-#pragma unroll 1
-            for (int i = nb - 2; i >= 0; --i) acc = acc + acc + row[col0 + i];
-            return acc;
-        };
-        auto window = [&](const Row& row, int p) -> F { return p == 0 ? val(row, W0B, 32) : p == 1 ? val(row, W1B, 32) : p == 14 ? val(row, W14B, 32) : row[WV(p)]; };
+        auto window = [&](const Row& row, int p) -> F { return p == 0 ? val<F>(row, W0B, 32) : p == 1 ? val<F>(row, W1B, 32) : p == 14 ? val<F>(row, W14B, 32) : row[WV(p)]; };
         // ---- 0. the four type flags
         const int t[4] = {T_FIRST, T_DATA, T_PAD, T_IDLE};
 #pragma unroll 1
@@ -239,20 +266,7 @@ struct ShaAir {
         c.transition(sel63 * (nxt[KC] - kc - nxt[T_DATA]));
         c.first_row(kc - one);
         c.last_row(kc - pub[8]);
-        // ---- 12. the bus: signed keys go to EdAir
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F k8 = F::from(256), k16 = F::from(65536);
-            auto limbs = [&](int col0) -> F {  // bytes b0 b1 b2 b3 of the big-endian word: (b0 + 256 b1) + 2^16 (b2 + 256 b3)
-                return val(loc, col0 + 24, 8) + val(loc, col0 + 16, 8) * k8 + (val(loc, col0 + 8, 8) + val(loc, col0, 8) * k8) * k16;
-            };
-            // public input 9 = bus mode: 0 nothing, 1 SEND the flagged keys (to EdAir), 2 RECEIVE every key (from the epoch-end table)
-            const F mode = pub[9], inv2 = F::from(0x7FFFFFFF80000001ULL), on = mode * (F::from(3) - mode) * inv2, rcv = mode * (mode - one) * inv2;
-            const F m = on * (per[4] * loc[T_FIRST] + per[5] * tdata) * (sgc * (one - rcv) - rcv);
-            const X2<F> d = bus.key((kc - one) * F::from(4) + per[6], limbs(W0B), limbs(W1B));
-            const X2<F> h{loc[CHAIN_COLS], loc[CHAIN_COLS + 1]}, z{loc[CHAIN_COLS + 2], loc[CHAIN_COLS + 3]}, zn{nxt[CHAIN_COLS + 2], nxt[CHAIN_COLS + 3]};
-            c.constraint_x2(h * d - m);
-            c.constraint_x2(zn - z - h + X2<F>{apub[0], apub[1]});
-        }
+        // ---- 12. the bus (logUp): signed keys go to EdAir, or every key comes from the epoch-end table; one helper, cyclic running sum
+        bus_constraints<ShaAir>(loc, nxt, per, pub, chal, apub, c);
     }
 };

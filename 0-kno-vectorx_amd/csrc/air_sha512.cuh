@@ -10,6 +10,9 @@
 // little-endian 16-bit limbs per tuple, cut from the bits of window positions 0 / 1); the digest goes back from rows 74..79
 // of block 2 as three 32-bit feed-forward halves per tuple (held in FFV from row 74 on; EdAir's byte cells bound them), all
 // under the slot's flag SGF.
+// The bus is stated once, in `messages` (air.cuh "the bus of a table ..."): both directions are one message in one helper; the
+// constraints (bus_constraints), the witness (bus_aux.cuh) and the balance check of a bus group read that list, and `bus_periodic`
+// states the periodic columns it reads.
 // Public inputs: message words 8..14 of block 1 as (lo, hi) halves, bus_on.  Constraint ORDER is protocol:
 // oracle/sha512_air.py restates it independently.
 #pragma once
@@ -40,14 +43,23 @@ VX_HD uint64_t iv(int i) { return IV_H[i]; }
 VX_HD constexpr uint64_t pad2(int p) { return p == 15 ? 8 * (64 + MSG_LEN) : 0; }  // block 2 of a 117-byte message
 }  // namespace s5
 
-int32_t vx_sha512_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_sha512_air.hip
-
 template <int LOGN, int ID_>
 struct Sha512AirT {
     static constexpr int ID = ID_, COLS = s5::COLS, PUB = 15, PERIODIC = s5::N_PERIODIC, PERIOD_LOG = LOGN, QUOT_ROWS_PER_LANE = 1, AUX = 4, CHAL = 4, AUXPUB = 1, EXACT_LOG = 1;
     static constexpr int plog(int) { return LOGN; }
-    static constexpr gen_aux_fn gen_aux = vx_sha512_air_gen_aux;
+    static int32_t gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub);  // vx_sha512_air.hip
     static constexpr size_t max_slots() { return ((size_t)1 << LOGN) / s5::SLOT_ROWS; }
+
+    // what the bus reads of a row's position (per[P_RCV], per[P_T0], per[P_SD0 .. P_SD0 + 5]; the other columns are not the list's):
+    // receive row j of a slot takes part 4 slot + j of R || A, send row j gives part 8 slot + j of the digest; nothing behind the last slot
+    VX_HD static void bus_periodic(size_t row, uint64_t* per) {
+        using namespace s5;
+        const size_t slot = row / SLOT_ROWS, q = row % SLOT_ROWS;
+        const bool in = row < max_slots() * SLOT_ROWS, rcv = in && q < 8 && !(q & 1), snd = in && q >= SEND0;
+        per[P_RCV] = rcv;
+        per[P_T0] = rcv ? 4 * slot + q / 2 : snd ? 8 * slot + (q - SEND0) : 0;
+        for (int j = 0; j < 6; ++j) per[P_SD0 + j] = snd && q == (size_t)(SEND0 + j);
+    }
 
     static void periodic_values(std::vector<uint64_t>& v) {
         using namespace s5;
@@ -67,11 +79,49 @@ struct Sha512AirT {
                 P(P_LAST, o + 79) = 1, P(P_HSET, o) = 1;
             }
             P(P_CONT, b + 79) = 1;
-            for (int j = 0; j < 4; ++j) P(P_RCV, b + 2 * j) = 1, P(P_T0, b + 2 * j) = 4 * s + j;
-            for (int j = 0; j < 6; ++j) P(P_SD0 + j, b + SEND0 + j) = 1, P(P_T0, b + SEND0 + j) = 8 * s + j;
             for (size_t r = b + SEND0; r < b + SEND0 + 5; ++r) P(P_FFK, r) = 1;
             for (size_t r = b; r < b + 159; ++r) P(P_SGK, r) = 1;
         }
+        for (size_t row = 0; row < n; ++row) {
+            uint64_t per[N_PERIODIC];
+            bus_periodic(row, per);
+            P(P_RCV, row) = per[P_RCV], P(P_T0, row) = per[P_T0];
+            for (int j = 0; j < 6; ++j) P(P_SD0 + j, row) = per[P_SD0 + j];
+        }
+    }
+
+    static constexpr int N_HELP = 1, BUS_ROWS = 1, BUS_STEP = -1, BUS_BLOCK = 256, BUS_PERIODIC = 1;
+
+    // the one message (ordinal 0), under the slot's flag: a receive row takes 8 limbs of the words at window positions 0 and 1 (limb j of
+    // a word = bytes 2j, 2j+1 of its big-endian byte string, little-endian); send row j gives the feed-forward halves 3j, 3j+1, 3j+2
+    template <class F, class Row, class Sink>
+    VX_HD static void messages(const Row& loc, const F* per, const F* pub, const bus::Bus<X2<F>>& bus, Sink& s) {
+        using namespace s5;
+        const F zero = F::from(0), k8 = F::from(256), k16 = F::from(65536), k32 = F::from(1ULL << 32), rcv = per[P_RCV];
+        auto val = [&](int col0, int nb) -> F {
+            F acc = loc[col0 + nb - 1];
+#pragma unroll 1
+            for (int i = nb - 2; i >= 0; --i) acc = acc + acc + loc[col0 + i];
+            return acc;
+        };
+        auto limb = [&](int q) -> F {  // q = 0..7: limbs of W0 then W1
+            const int col0 = (q < 4 ? W0B : W1B), j = q & 3;
+            return val(col0 + 56 - 16 * j, 8) + val(col0 + 48 - 16 * j, 8) * k8;
+        };
+        F t[3] = {rcv * (limb(0) + limb(1) * k16 + limb(2) * k32), rcv * (limb(3) + limb(4) * k16 + limb(5) * k32), rcv * (limb(6) + limb(7) * k16)};
+        F snd = zero;
+        // (rolled in the quotient kernel; the witness kernel unrolls them, or t[] and per[] are indexed by loop counters and go to the stack)
+#pragma unroll Sink::UNROLL
+        for (int i = 0; i < 3; ++i)
+#pragma unroll Sink::UNROLL
+            for (int j = 0; j < 6; ++j)
+                if (3 * j + i < 16) t[i] = t[i] + per[P_SD0 + j] * loc[FFV0 + 3 * j + i];
+#pragma unroll Sink::UNROLL
+        for (int j = 0; j < 6; ++j) snd = snd + per[P_SD0 + j];
+        const F m = loc[SGF] * pub[14] * (snd - rcv);
+        // a send row carries a bus.ed_digest message, a receive row a bus.ed_msg one: slots and tag are the selector-weighted sums
+        const F tag = snd * F::from(bus::TAG_EDH) + rcv * F::from(bus::TAG_EDMSG);
+        s.single(m, bus.denom(bus.beta, per[P_T0], t[0], t[1], t[2], tag));
     }
 
     template <class F, class Row, class Cn>
@@ -235,32 +285,8 @@ struct Sha512AirT {
 #pragma unroll 1
         for (int k = 0; k < 16; ++k) c.constraint(per[P_FFK] * (nxt[FFV0 + k] - loc[FFV0 + k]));
         c.constraint(per[P_SGK] * (nxt[SGF] - loc[SGF]));
-        // ---- 10. the bus: receive rows take 8 limbs of the words at window positions 0 and 1 (limb j of a word = bytes 2j, 2j+1
-        // of its big-endian byte string, little-endian); send row j gives the feed-forward halves 3j, 3j+1, 3j+2
-        {
-            const bus::Bus<X2<F>> bus(chal[0], chal[1], chal[2], chal[3]);
-            const F k8 = F::from(256), k16 = F::from(65536), k32 = F::from(1ULL << 32), rcv = per[P_RCV];
-            auto limb = [&](int q) -> F {  // q = 0..7: limbs of W0 then W1
-                const int col0 = (q < 4 ? W0B : W1B), j = q & 3;
-                return val(loc, col0 + 56 - 16 * j, 8) + val(loc, col0 + 48 - 16 * j, 8) * k8;
-            };
-            F t[3] = {rcv * (limb(0) + limb(1) * k16 + limb(2) * k32), rcv * (limb(3) + limb(4) * k16 + limb(5) * k32), rcv * (limb(6) + limb(7) * k16)};
-            F snd = zero;
-#pragma unroll 1
-            for (int i = 0; i < 3; ++i)
-#pragma unroll 1
-                for (int j = 0; j < 6; ++j)
-                    if (3 * j + i < 16) t[i] = t[i] + per[P_SD0 + j] * loc[FFV0 + 3 * j + i];
-#pragma unroll 1
-            for (int j = 0; j < 6; ++j) snd = snd + per[P_SD0 + j];
-            const F m = loc[SGF] * pub[14] * (snd - rcv);
-            // a send row carries a bus.ed_digest message, a receive row a bus.ed_msg one: slots and tag are the selector-weighted sums
-            const F tag = snd * F::from(bus::TAG_EDH) + rcv * F::from(bus::TAG_EDMSG);
-            const X2<F> d = bus.denom(bus.beta, per[P_T0], t[0], t[1], t[2], tag);
-            const X2<F> h{loc[COLS], loc[COLS + 1]}, z{loc[COLS + 2], loc[COLS + 3]}, zn{nxt[COLS + 2], nxt[COLS + 3]};
-            c.constraint_x2(h * d - m);
-            c.constraint_x2(zn - z - h + X2<F>{apub[0], apub[1]});
-        }
+        // ---- 10. the bus (logUp): R || A from EdAir, the digest back to it; one helper, cyclic running sum
+        bus_constraints<Sha512AirT>(loc, nxt, per, pub, chal, apub, c);
     }
 };
 using Sha512Air16 = Sha512AirT<16, 11>;

@@ -85,12 +85,6 @@ struct ShaTreeAirT {
     VX_HD static void messages(const Row& loc, const F* per, const F*, const bus::Bus<X2<F>>& bus, Sink& s) {
         using namespace shc;
         using namespace sht;
-        auto val = [&](int col0, int nb) -> F {
-            F acc = loc[col0 + nb - 1];
-#pragma unroll 1
-            for (int i = nb - 2; i >= 0; --i) acc = acc + acc + loc[col0 + i];
-            return acc;
-        };
         const F zero = F::from(0);
         const X2<F> bword = bus.word_base(), bbyte = bus.byte_base(per[P_CID], per[P_TREE]);
         auto mult = [&](int q) -> F {
@@ -99,9 +93,9 @@ struct ShaTreeAirT {
             return per[P_PS];
         };
         auto denom = [&](int q) -> X2<F> {
-            if (q >= 1 && q <= 4) return bus.byte(bbyte, per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1)), val(W0B + 24 - 8 * (q - 1), 8));
+            if (q >= 1 && q <= 4) return bus.byte(bbyte, per[P_JJ] * F::from(4) + F::from((uint64_t)(q - 1)), val<F>(loc, W0B + 24 - 8 * (q - 1), 8));
             const bool recv = q == 0;  // message word r of a child, or word q - 5 of this node's digest
-            return bus.word(bword, per[P_TREE], recv ? per[P_CID] : per[P_GID], recv ? per[P_JJ] : F::from((uint64_t)(q - 5)), recv ? val(W0B, 32) : loc[FFV0 + q - 5]);
+            return bus.word(bword, per[P_TREE], recv ? per[P_CID] : per[P_GID], recv ? per[P_JJ] : F::from((uint64_t)(q - 5)), recv ? val<F>(loc, W0B, 32) : loc[FFV0 + q - 5]);
         };
         // (two loops: unrolled as one, the body with all three kinds of message is above the compiler's size limit for a `#pragma unroll` loop)
 #pragma unroll Sink::UNROLL
@@ -117,13 +111,7 @@ struct ShaTreeAirT {
         using namespace sht;
         const F sel0 = per[P_SEL0], is_data = per[P_DATA];
         const F one = F::from(1);
-        auto val = [&](const Row& row, int col0, int nb) -> F {
-            F acc = row[col0 + nb - 1];
-#pragma unroll 1
-            for (int i = nb - 2; i >= 0; --i) acc = acc + acc + row[col0 + i];
-            return acc;
-        };
-        auto window = [&](const Row& row, int p) -> F { return p == 0 ? val(row, W0B, 32) : p == 1 ? val(row, W1B, 32) : p == 14 ? val(row, W14B, 32) : row[WV(p)]; };
+        auto window = [&](const Row& row, int p) -> F { return p == 0 ? val<F>(row, W0B, 32) : p == 1 ? val<F>(row, W1B, 32) : p == 14 ? val<F>(row, W14B, 32) : row[WV(p)]; };
         // ---- 1-7. the compression rows (shared with ShaChainAir); a PAD block continues from its DATA block
         sha_compression_constraints<F>(loc, nxt, per, is_data, c);
         // ---- 8. the PAD block's message, the root, zero leaves
@@ -131,7 +119,7 @@ struct ShaTreeAirT {
         for (int j = 0; j < 16; ++j) c.constraint(sel0 * (one - is_data) * (window(loc, j) - F::from(pad64(j))));
 #pragma unroll 1
         for (int j = 0; j < 8; ++j) c.constraint(per[P_ROOT] * (loc[FFV0 + j] - (pub[j] + per[P_TREE] * (pub[8 + j] - pub[j]))));
-        const F w0 = val(loc, W0B, 32);
+        const F w0 = val<F>(loc, W0B, 32);
         c.constraint(per[P_PBL] * (one - loc[ENL]) * w0);
         c.constraint(per[P_PBR] * (one - loc[ENR]) * w0);
         // ---- 8b. the leaf-enable flags are forced: leaf i of either tree is enabled exactly when i < pub[16]

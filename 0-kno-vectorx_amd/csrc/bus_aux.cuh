@@ -1,6 +1,6 @@
-// The auxiliary round of every table whose helpers hold two messages each (air.cuh "the bus of a table ..."): one witness kernel
-// and one gen_aux body for MerkleOpenAir / MerkleOpenSetAir, LeafSpongeAir / LeafSpongeSetAir, LeafNoopAir, FriFoldAir,
-// FriCombineAir, TranscriptAir, ShaTreeAir and EpochEndAir.  The kernel reads the messages from the list the AIR's constraints are
+// The auxiliary round of every table whose helpers hold two messages each, or one (air.cuh "the bus of a table ..."): one witness
+// kernel and one gen_aux body for MerkleOpenAir / MerkleOpenSetAir, LeafSpongeAir / LeafSpongeSetAir, LeafNoopAir, FriFoldAir,
+// FriCombineAir, TranscriptAir, ShaChainAir, ShaTreeAir, Sha512Air and EpochEndAir.  The kernel reads the messages from the list the AIR's constraints are
 // built from (Air::messages with F = Fp), so a table states multiplicities, slots, pairing and helper order once.
 //   k_bus_aux<Air>  one lane per row, or per 32-row block (Air::BUS_ROWS).  A first walk of the list looks at the multiplicities
 //                   alone (the denominators are dead code in it): a row or block that sends and receives nothing -- idle, or a

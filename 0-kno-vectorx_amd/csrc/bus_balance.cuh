@@ -16,7 +16,8 @@
 //             segment that won.  Nothing of the result depends on the order the records were written or sorted in.
 //             A segment is TWO records in the tables this is for (a sender and a receiver); one lane walking a long segment is a
 //             periodic lookup table (BlakeChainAir's XOR table, EdAir's range table, LookupAir), and those tables have no message
-//             list here.  The compiled tables that have one: ids 16 .. 23, ShaTreeAir (7, 8, 9) and EpochEndAir (15).
+//             list here.  The compiled tables that have one: ids 16 .. 23, ShaChainAir (4), ShaTreeAir (7, 8, 9), Sha512Air (11, 13, 14) and
+//             EpochEndAir (15).
 // THE CHECK CHALLENGES (beta*, gamma*) are fixed: the check runs before anything is committed, so they cannot be a proof's.  They are
 // the first four Poseidon round constants (poseidon_constants.h VX_POSEIDON_RC_INIT[0 .. 3], canonical words of plonky2's own
 // nothing-up-my-sleeve generator) as two extension elements.  The pair (D.a, D.b) under them is a 128-bit fingerprint of the tuple

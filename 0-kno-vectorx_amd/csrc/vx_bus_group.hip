@@ -46,7 +46,7 @@ int32_t bus_balance_dev(vx_ctx* ctx, const vx_bus_table* t, const BusAirShape* s
     size_t lane0[VX_BUS_GROUP_MAX_TABLES + 1] = {0};  // where the lanes of table k start in cnt / offs
     for (size_t k = 0; k < n; ++k) {
         const int rows = message_rows(t[k], shape[k]);
-        VX_CHECK(rows > 0, "bus group: table %zu (air %d) has no message list (a vx_air_register_bus program or a compiled AIR 7 .. 9, 15 .. 23 has one)", k, t[k].air_id);
+        VX_CHECK(rows > 0, "bus group: table %zu (air %d) has no message list (a vx_air_register_bus program or a compiled AIR 4, 7 .. 9, 11, 13 .. 23 has one)", k, t[k].air_id);
         VX_CHECK(((size_t)1 << t[k].log_n) >= (size_t)rows, "bus group: table %zu has 2^%d rows, less than one block of its bus", k, t[k].log_n);
         lane0[k + 1] = lane0[k] + (((size_t)1 << t[k].log_n) / rows);
     }

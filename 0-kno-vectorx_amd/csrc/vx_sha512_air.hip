@@ -3,10 +3,11 @@
 //   k_s512_slots  one lane per slot: both compressions of the slot, natively (mid state, digest)
 //   k_s512_rows   one lane per trace row: recomputes the message schedule and the rounds it needs from the slot record and
 //                 writes its 1055 cells (column-major: the lanes of a wave write neighbouring rows)
-//   k_s512_aux    one lane per row: the bus helper of receive / send rows, the running-sum increments
+// The auxiliary columns are bus_aux.cuh's k_bus_aux<Sha512Air*>, from the message list in air_sha512.cuh.
 #include <string.h>
 
 #include "air_sha512.cuh"
+#include "bus_aux.cuh"
 #include "vx_internal.h"
 
 namespace {
@@ -128,50 +129,16 @@ __global__ __launch_bounds__(256) void k_s512_rows(const S5Slot* slots, size_t m
         put_halves(tr, n, row, HIN0 + 2 * wd, h_in[wd]);
     }
 }
-
-__global__ __launch_bounds__(256) void k_s512_aux(const uint64_t* tr, uint64_t* aux, size_t n, size_t m, gl2 beta, gl2 gamma, uint64_t bus_on) {
-    const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (row >= n) return;
-    const size_t slot = row / SLOT_ROWS;
-    const int q = (int)(row % SLOT_ROWS);
-    const bool rcv = slot < m && q < 8 && !(q & 1), snd = slot < m && q >= SEND0;
-    gl2 h{0, 0};
-    if ((rcv || snd) && bus_on && tr[(size_t)SGF * n + row]) {
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        gl2 d;
-        if (rcv) {
-            auto word = [&](int col0) -> uint64_t {
-                uint64_t v = 0;
-                for (int i = 0; i < 64; ++i) v |= tr[(size_t)(col0 + i) * n + row] << i;
-                return v;
-            };
-            const uint64_t w[2] = {word(W0B), word(W1B)};
-            uint64_t l[8];
-            for (int j = 0; j < 8; ++j) {  // limb j of a word: bytes 2j, 2j+1 of its big-endian byte string, little-endian
-                const uint64_t x = w[j >> 2];
-                const int k = j & 3;
-                l[j] = ((x >> (56 - 16 * k)) & 0xFF) | (((x >> (48 - 16 * k)) & 0xFF) << 8);
-            }
-            d = bus.ed_msg(4 * slot + q / 2, l[0] | (l[1] << 16) | (l[2] << 32), l[3] | (l[4] << 16) | (l[5] << 32), l[6] | (l[7] << 16));
-        } else {
-            const int j = q - SEND0;
-            auto ff = [&](int k) -> uint64_t { return k < 16 ? tr[(size_t)(FFV0 + k) * n + row] : 0; };
-            d = bus.ed_digest(8 * slot + j, ff(3 * j), ff(3 * j + 1), ff(3 * j + 2));
-        }
-        h = gl2_inv(d);
-        if (rcv) h = gl2{gl_neg(h.a), gl_neg(h.b)};
-    }
-    aux[row] = h.a, aux[n + row] = h.b;
-    aux[2 * n + row] = h.a, aux[3 * n + row] = h.b;  // increments; the scan makes them the running sum
-}
 }  // namespace
 
-int32_t vx_sha512_air_gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_s512_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, aux, n, n / SLOT_ROWS, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[14]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 2 * n, log_n, aux_pub);
+// auxiliary columns: bus_aux.cuh's, from the AIR's own message list (one lane per row, one helper)
+template <int LOGN, int ID_>
+int32_t Sha512AirT<LOGN, ID_>::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
+    return bus_gen_aux<Sha512AirT>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
+template struct Sha512AirT<16, 11>;
+template struct Sha512AirT<15, 14>;
+template struct Sha512AirT<10, 13>;
 
 int32_t vx_sha512_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, const uint8_t* sigs, const uint8_t* msg, const uint8_t* flags, size_t n_sigs, int log_n, uint64_t bus_on,
                             uint64_t* trace_d, uint64_t pub_out[15]) {

@@ -1,7 +1,7 @@
 // Witness/trace generation for ShaChainAir on the GPU: one lane per trace row (block b, round r)
 // recomputes the message schedule and the r rounds it needs from the block descriptor the host
 // prepared (the 2n-1 compressions of the commitment chain are sequential and tiny: host).  ShaTreeAir's rows are the same
-// kernel's; its auxiliary columns are bus_aux.cuh's, from the message list in air_sha_tree.cuh.
+// kernel's.  Both tables' auxiliary columns are bus_aux.cuh's, from the message lists in air_sha.cuh and air_sha_tree.cuh.
 #include <string.h>
 
 #include "air_sha_tree.cuh"
@@ -94,32 +94,9 @@ __global__ __launch_bounds__(256) void k_sha_trace(const ShaBlock* blocks, uint6
     if (b.type != SB_TREE) tr[(size_t)SGC * n + row] = b.sgc, tr[(size_t)KC * n + row] = b.kc;  // (the tree table has 412 columns)
 }
 
-// auxiliary columns of ShaChainAir: the key sends of signed blocks, one lane per row
-__global__ __launch_bounds__(256) void k_sha_chain_aux(const uint64_t* tr, uint64_t* aux, size_t n, gl2 beta, gl2 gamma, uint64_t bus_on) {
-    using namespace shc;
-    const size_t row = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (row >= n) return;
-    const int r = (int)(row & 63);
-    gl2 h{0, 0};
-    // bus mode 1: the flagged keys are sent; mode 2: every key is received
-    if (bus_on && r < 16 && !(r & 1) && (bus_on == 2 || tr[(size_t)SGC * n + row]) && tr[(size_t)(r < 8 ? T_FIRST : T_DATA) * n + row]) {
-        auto limbs = [&](int col0) -> uint64_t {
-            uint32_t w = 0;
-            for (int i = 0; i < 32; ++i) w |= (uint32_t)tr[(size_t)(col0 + i) * n + row] << i;
-            return (uint64_t)((w >> 24) | ((w >> 8) & 0xFF00)) | ((uint64_t)(((w >> 8) & 0xFF) | ((w & 0xFF) << 8)) << 16);
-        };
-        const bus::Bus<gl2> bus(beta.a, beta.b, gamma.a, gamma.b);
-        h = gl2_inv(bus.key(4 * (tr[(size_t)KC * n + row] - 1) + ((r & 7) >> 1), limbs(W0B), limbs(W1B)));
-        if (bus_on == 2) h = gl2{gl_neg(h.a), gl_neg(h.b)};
-    }
-    aux[row] = h.a, aux[n + row] = h.b;
-    aux[2 * n + row] = h.a, aux[3 * n + row] = h.b;  // increments; the scan makes them the running sum
-}
+// auxiliary columns of ShaChainAir: bus_aux.cuh's, from the AIR's own message list (one lane per row, one helper)
 int32_t ShaAir::gen_aux(vx_ctx* ctx, const uint64_t* trace, int log_n, const uint64_t* chal, const uint64_t* pub, uint64_t* aux, uint64_t* aux_pub) {
-    const size_t n = (size_t)1 << log_n;
-    hipLaunchKernelGGL(k_sha_chain_aux, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, trace, aux, n, gl2{chal[0], chal[1]}, gl2{chal[2], chal[3]}, pub[9]);
-    VX_HIP(hipGetLastError());
-    return vx_bus_close_dev(ctx, aux + 2 * n, log_n, aux_pub);
+    return bus_gen_aux<ShaAir>(ctx, trace, log_n, chal, pub, aux, aux_pub);
 }
 
 int32_t vx_sha_chain_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, size_t n_keys, const uint8_t* signed_flags, uint64_t bus_on, int log_n, uint64_t* trace_d,

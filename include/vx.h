@@ -620,8 +620,9 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
  * multiplicity as a field word with the sign of BUSP_MSG (sent m, received 0 - m).  n_outside = 0 states a closed bus.  The bus
  * closes when   sum over the tables of total x rows  +  sum over the outside messages of m / D  =  0.
  * vx_bus_group_check: the BALANCE CHECK on the device, before anything is proven -- which message of which table and row has no
- *   partner.  Every table needs a message list: a vx_air_register_bus program, or a compiled AIR with ids 7 .. 9 (the SHA-256
- *   Merkle tree), 15 (the epoch-end table) or 16 .. 23; any other compiled AIR is VX_ERR_ARG naming the table.  *out: n_unmatched = 0 when the bus closes; otherwise the number of distinct
+ *   partner.  Every table needs a message list: a vx_air_register_bus program, or a compiled AIR with ids 4 (the SHA-256
+ *   chain), 7 .. 9 (the SHA-256 Merkle tree), 11 / 13 / 14 (the SHA-512 table), 15 (the epoch-end table) or 16 .. 23; any other
+ *   compiled AIR (BlakeChainAir, EdAir, LookupAir: periodic lookup tables) is VX_ERR_ARG naming the table.  *out: n_unmatched = 0 when the bus closes; otherwise the number of distinct
  *   tuples whose multiplicities do not cancel and the lowest (table, row, message) among their messages.  It compares 128-bit
  *   fingerprints of the tuples: a collision can hide or mis-name an imbalance, never invent one.
  * vx_bus_group_prove: runs the check first when every table has a message list -- VX_ERR_STATEMENT naming table, AIR, row, message,

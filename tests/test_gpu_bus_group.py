@@ -294,11 +294,11 @@ def test_argument_errors(ctx, vx, rows_case):
                 call()
             assert e.value.code == -1, why  # VX_ERR_ARG
     # a compiled table without a message list: the check refuses it by name, the prover proves and closes the bus on the totals
-    sha = ctx.alloc(vx.lib.VX_SHA_AIR_COLS << 6)
-    with pytest.raises(vx.VxError, match="table 0 .air 4. has no message list") as e:
-        ctx.bus_group_check([(vx.lib.VX_AIR_SHA_CHAIN, sha, 6, [0] * 10)])
+    blake = ctx.alloc(vx.lib.VX_BLAKE_AIR_COLS << 16)
+    with pytest.raises(vx.VxError, match="table 0 .air 6. has no message list") as e:
+        ctx.bus_group_check([(vx.lib.VX_AIR_BLAKE_CHAIN, blake, 16, [0] * 20)])
     assert e.value.code == -1
-    sha.free()
+    blake.free()
     full = ctx.bus_group_prove(good, cfg, c["outside"])
     with pytest.raises(vx.VxError) as e:
         ctx.bus_group_prove(good, cfg, c["outside"], out=np.zeros(full.size - 1, dtype=np.uint64))
@@ -308,20 +308,24 @@ def test_argument_errors(ctx, vx, rows_case):
 
 
 def test_a_table_without_a_message_list_is_closed_on_its_published_total(ctx, vx):
-    """ShaChainAir (no message list) stand-alone (bus_on = 0) publishes a zero total: the group of one proves and verifies as a closed
-    bus; with an outside message the totals do not cancel and no blob is written"""
-    tb, pub, _ = ctx.sha_chain_trace([hashlib.sha256(b"one key").digest()], 6)
+    """BlakeChainAir (a periodic lookup table, no message list) stand-alone (no tree, no window: nothing leaves the table) publishes a
+    zero total: the group of one proves and verifies as a closed bus; with an outside message the totals do not cancel and no blob is
+    written"""
+    ch = vx.synth.Chain(1, profile="Ptiny", stride=512)
+    hb = ctx.from_host(ch.headers)
+    tb, pub, _ = ctx.blake_chain_trace(hb, 512, ch.sizes, ch.trusted_hash, ch.trusted_block + 1, 16)
+    pub = [int(x) for x in pub]
     cfg = ctx.stark_config(num_queries=8)
-    tables = [(vx.lib.VX_AIR_SHA_CHAIN, tb, 6, pub)]
+    tables = [(vx.lib.VX_AIR_BLAKE_CHAIN, tb, 16, pub)]
     blob = ctx.bus_group_prove(tables, cfg)
-    vx.lib.bus_group_verify(blob, [(vx.lib.VX_AIR_SHA_CHAIN, pub)], cfg)
+    vx.lib.bus_group_verify(blob, [(vx.lib.VX_AIR_BLAKE_CHAIN, pub)], cfg)
     with pytest.raises(vx.VxError, match="the bus does not close") as e:
         ctx.bus_group_prove(tables, cfg, [[1, 2, 3, 4, 5, 1]])
     assert e.value.code == -5
-    tb.free()
+    tb.free(), hb.free()
 
 
-TAG_BYTE, TAG_KEY = 2, 5
+TAG_BYTE, TAG_KEY, TAG_EDMSG, TAG_EDH = 2, 5, 6, 7
 
 
 def test_the_sha_tree_table_alone_closes_its_bus_against_the_root_bytes(ctx, vx):
@@ -373,3 +377,97 @@ def test_the_epoch_end_table_alone_closes_its_bus_against_bytes_and_keys(ctx, vx
     buf0, pub0, _ = ctx.epoch_end_trace(hb, e.start_position, n_new, bus_on=0)
     assert ctx.bus_group_check([(vx.lib.VX_AIR_EPOCH_END, buf0, 9, [int(x) for x in pub0])]) is None
     buf.free(), buf0.free(), hb.free()
+
+
+def outside_of(trace, periodic, pub, lookup):
+    """the other side of every message a table has, from the oracle's trace and the oracle's reading of a row (m, tag, tuple):
+    -> [[t0, t1, t2, t3, tag, -m]], and the rows they belong to"""
+    out, rows = [], []
+    for row, loc in enumerate(trace.T.tolist()):
+        m, tag, tup = lookup(loc, [int(c[row % len(c)]) for c in periodic], pub)
+        if m % P:
+            out.append([int(t) % P for t in tup] + [int(tag) % P, -m % P])
+            rows.append(row)
+    return out, rows
+
+
+def test_the_sha_chain_table_alone_closes_its_bus_against_the_keys(ctx, vx):
+    """ShaChainAir (one helper of one message, the list reads three periodic columns), 3 keys in 2^9 rows -- blocks FIRST, DATA, PAD,
+    DATA, PAD and 3 IDLE -- with flags 1, 0, 1.  Mode 1: the outside party takes the four quarters of the two flagged keys; mode 2: it
+    sends those of all three, whatever the flags; mode 0: nobody says anything.  A quarter left out is named by the row it sits on"""
+    from oracle import sha_air as A
+
+    keys, flags = [hashlib.sha256(b"key %d" % i).digest() for i in range(3)], [1, 0, 1]
+    u32 = lambda b: int.from_bytes(b, "little")  # noqa: E731
+    quarters = lambda i, m: [[4 * i + j, u32(keys[i][8 * j: 8 * j + 4]), u32(keys[i][8 * j + 4: 8 * j + 8]), 0, TAG_KEY, m] for j in range(4)]  # noqa: E731
+    tb, pub, _ = ctx.sha_chain_trace(keys, 9, signed=flags, bus_on=1)
+    want, wpub, _ = A.gen_trace(keys, 9, signed=flags, bus_on=1)
+    assert (tb.download().reshape(A.CHAIN_COLS, 512) == want).all() and [int(x) for x in pub] == wpub
+    table = lambda mode: [(vx.lib.VX_AIR_SHA_CHAIN, tb, 9, wpub[:9] + [mode])]  # noqa: E731
+    # mode 1: the flagged keys are sent from rows 0, 2, 4, 6 of the FIRST block and rows 8, 10, 12, 14 of the second DATA block
+    taken, rows = outside_of(want, A.chain_periodic_values(), wpub[:9] + [1], A.key_lookup)
+    assert taken == quarters(0, P - 1) + quarters(2, P - 1) and len(taken) == 8
+    assert rows == [0, 2, 4, 6] + [64 * 3 + r for r in (8, 10, 12, 14)]
+    assert ctx.bus_group_check(table(1), taken) is None
+    assert tuple(ctx.bus_group_check(table(1), taken[:1] + taken[2:])) == (1, 0, 0, 2, 1)  # key 0, quarter 1
+    assert tuple(ctx.bus_group_check(table(1), taken[:7])) == (1, 0, 0, 64 * 3 + 14, 1)  # key 2, quarter 3
+    # mode 2: every key is received
+    sent, rows = outside_of(want, A.chain_periodic_values(), wpub[:9] + [2], A.key_lookup)
+    assert sent == quarters(0, 1) + quarters(1, 1) + quarters(2, 1) and len(sent) == 12
+    assert ctx.bus_group_check(table(2), sent) is None
+    assert rows[5] == 64 + 10 and tuple(ctx.bus_group_check(table(2), sent[:5] + sent[6:])) == (1, 0, 0, 64 + 10, P - 1)  # key 1, quarter 1
+    # mode 0
+    assert outside_of(want, A.chain_periodic_values(), wpub[:9] + [0], A.key_lookup) == ([], [])
+    assert ctx.bus_group_check(table(0)) is None
+    tb.free()
+
+
+def test_the_epoch_end_and_sha_chain_tables_close_the_key_bus_between_them(ctx, vx):
+    """the rotation's key bus as a group of two compiled lists: EpochEndAir sends the quarters of the one new key, ShaChainAir (mode 2,
+    2^6 rows, committing that key) receives them, the outside party sends the window bytes alone.  With another key in the commitment
+    table all eight key messages are without a partner and the lowest origin is named"""
+    e = vx.synth.EpochEndHeader(140000, 1, logs_before=0)
+    hb = ctx.from_host(e.padded)
+    buf, pub, wlen = ctx.epoch_end_trace(hb, e.start_position, 1, bus_on=1)
+    window = bytes(e.bytes[e.start_position + 1: e.start_position + 1 + wlen])
+    sent = [[0, k, window[k], 1, TAG_BYTE, 1] for k in range(wlen)]
+    key = bytes(e.new_pubkeys[0])
+    tb, spub, _ = ctx.sha_chain_trace([key], 6, bus_on=2)
+    epoch, chain = (vx.lib.VX_AIR_EPOCH_END, buf, 9, [int(x) for x in pub]), (vx.lib.VX_AIR_SHA_CHAIN, tb, 6, [int(x) for x in spub])
+    assert len(sent) == wlen > 0 and ctx.bus_group_check([epoch, chain], sent) is None and ctx.bus_group_check([chain, epoch], sent) is None
+    other = hashlib.sha256(key).digest()
+    assert all(other[8 * q: 8 * q + 8] != key[8 * q: 8 * q + 8] for q in range(4))
+    ob, opub, _ = ctx.sha_chain_trace([other], 6, bus_on=2)
+    wrong = (vx.lib.VX_AIR_SHA_CHAIN, ob, 6, [int(x) for x in opub])
+    assert tuple(ctx.bus_group_check([epoch, wrong], sent)) == (8, 0, 40, 1, 1)  # the validator's row of the epoch-end table, its first key message
+    assert tuple(ctx.bus_group_check([wrong, epoch], sent)) == (8, 0, 0, 0, P - 1)  # row 0 of the FIRST block takes quarter 0
+    buf.free(), tb.free(), ob.free(), hb.free()
+
+
+def test_the_sha512_table_alone_closes_its_bus_against_messages_and_digests(ctx, vx):
+    """Sha512Air10 (2^10 rows, 6 slots; one message whose tag is weighted by the row's selectors): 3 signatures with flags 1, 0, 1 fill
+    two compact slots.  The outside party sends the four parts of R || A of either slot and takes the six parts of its digest; slots
+    2 .. 5 and the rows behind the last slot say nothing"""
+    from oracle import sha512_air as H
+
+    msg = b"\x01" + bytes(range(32)) + (100000).to_bytes(4, "little") + (7).to_bytes(8, "little") + (3).to_bytes(8, "little")
+    keys, sigs, flags = [hashlib.sha256(b"A %d" % i).digest() for i in range(3)], [hashlib.sha512(b"R S %d" % i).digest() for i in range(3)], [1, 0, 1]
+    slots = [(sg[:32], k) for k, sg, f in zip(keys, sigs, flags) if f]
+    tb, pub = ctx.sha512_trace(keys, sigs, msg, flags, 10, bus_on=1)
+    want, wpub, dig = H.gen_trace(slots, msg, 10, bus_on=1)
+    assert (tb.download().reshape(H.COLS, 1024) == want).all() and [int(x) for x in pub] == wpub
+    outside, rows = outside_of(want, H.periodic_values(1024), wpub, H.bus_lookup)
+    assert len(outside) == 20 and rows == [160 * s + r for s in range(2) for r in [0, 2, 4, 6] + list(range(154, 160))]
+    assert [w[4:] for w in outside] == ([[TAG_EDMSG, 1]] * 4 + [[TAG_EDH, P - 1]] * 6) * 2
+    # two of them from the bytes: part 2 of slot 1's R || A (bytes 32 .. 47: the first half of A, three / three / two 16-bit limbs), and
+    # part 5 of slot 0's digest (the high half of word 7; halves 16 and 17 do not exist)
+    head, le = slots[1][0] + slots[1][1], lambda b: int.from_bytes(b, "little")  # noqa: E731
+    assert outside[10 + 2] == [4 * 1 + 2, le(head[32:38]), le(head[38:44]), le(head[44:48]), TAG_EDMSG, 1]
+    assert dig[0] == hashlib.sha512(slots[0][0] + slots[0][1] + msg).digest() and outside[9] == [5, int.from_bytes(dig[0][56:60], "big"), 0, 0, TAG_EDH, P - 1]
+    table = [(vx.lib.VX_AIR_SHA512[10], tb, 10, wpub)]
+    assert ctx.bus_group_check(table, outside) is None
+    assert tuple(ctx.bus_group_check(table, outside[:12] + outside[13:])) == (1, 0, 0, 164, P - 1)
+    assert tuple(ctx.bus_group_check(table, outside[:9] + outside[10:])) == (1, 0, 0, 159, 1)
+    assert outside_of(want, H.periodic_values(1024), wpub[:14] + [0], H.bus_lookup) == ([], [])
+    assert ctx.bus_group_check([(vx.lib.VX_AIR_SHA512[10], tb, 10, wpub[:14] + [0])]) is None
+    tb.free()

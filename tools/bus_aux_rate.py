@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """The auxiliary round alone -- vx_stark_aux_trace, HIP-event timed, milliseconds averaged over 20 calls after a warm-up call -- for
-the ten tables whose auxiliary columns come from bus_aux.cuh, each at the shape of its rate tool; the witnesses are random claims
+the twelve tables whose auxiliary columns come from bus_aux.cuh, each at the shape of its rate tool; the witnesses are random claims
 of the right ranges (the auxiliary round reads flags and cells, it checks no statement).  One JSON line.  VX_LIB_PATH selects another
-libvxprove build (profiles/r11_bus_aux_refactor.json, r14_bus_lists_older.json: the parent commit's and this one alternating)."""
+libvxprove build (profiles/r11_bus_aux_refactor.json, r14_bus_lists_older.json, r16_bus_lists_sha.json: the parent commit's and this
+one alternating)."""
+import hashlib
 import json
 import os
 import sys
@@ -112,4 +114,16 @@ hb = ctx.from_host(e.padded)
 tb, pub, _ = ctx.epoch_end_trace(hb, e.start_position, 300, bus_on=1)
 out["epoch_end_2^9"] = timed(L.VX_AIR_EPOCH_END, tb, 9, L.VX_EPOCH_END_AIR_AUX_COLS, pub)
 tb.free(), hb.free()
+
+# ShaChainAir: 300 keys, all flagged and sent (mode 1), 2^16 rows (the commitment table of a header_range proof with a justification)
+keys = [hashlib.sha256(b"authority %d" % i).digest() for i in range(300)]
+tb, pub, _ = ctx.sha_chain_trace(keys, 16, signed=[1] * 300, bus_on=1)
+out["sha_chain_2^16"] = timed(L.VX_AIR_SHA_CHAIN, tb, 16, L.VX_SHA_AIR_AUX_COLS, pub)
+tb.free()
+
+# Sha512Air15: 201 of the 300 flagged, 2^15 rows (the table hashes R || A || message: the signatures need not verify)
+sigs = [hashlib.sha512(b"signature %d" % i).digest() for i in range(300)]
+tb, pub = ctx.sha512_trace(keys, sigs, bytes(range(53)), [1] * 201 + [0] * 99, 15, bus_on=1)
+out["sha512_2^15"] = timed(L.VX_AIR_SHA512[15], tb, 15, L.VX_SHA512_AIR_AUX_COLS, pub)
+tb.free()
 print(json.dumps(out))
