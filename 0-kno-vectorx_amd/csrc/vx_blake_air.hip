@@ -590,7 +590,7 @@ int32_t vx_blake_chain_trace(vx_ctx* ctx, const vx_buf* headers, size_t stride, 
     VX_HIP(hipGetLastError());
     std::vector<uint8_t> dig(32 * n_headers);
     VX_HIP(hipMemcpyAsync(dig.data(), d_dig, dig.size(), hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     // block descriptors (host): the link rule is checked here too, so a broken chain fails loudly
     std::vector<BlockDesc> descs(n_blocks);
     uint8_t D[32];
@@ -636,7 +636,7 @@ int32_t vx_blake_chain_trace(vx_ctx* ctx, const vx_buf* headers, size_t stride, 
     VX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_blake_mult, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)d_hist, trace_out->d, n);
     VX_HIP(hipGetLastError());
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // descs must outlive the kernel
+    VX_HIP(vx_wait(ctx));  // descs must outlive the kernel
     for (int j = 0; j < 8; ++j) {
         uint32_t a, b;
         memcpy(&a, trusted_hash + 4 * j, 4);

@@ -180,7 +180,7 @@ int32_t vx_bus_group_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_bus
             return vx_fail(ctx, VX_ERR_STATEMENT, "bus group: the bus does not close: message %u of table %d (air %d) at row %llu has no partner (net multiplicity %llu; %llu unmatched tuples)",
                            u.message, u.table, tables[u.table].air_id, (unsigned long long)u.row, (unsigned long long)u.net, (unsigned long long)u.n_unmatched);
     }
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // the traces were written on ctx's stream; the side contexts have streams of their own
+    VX_HIP(vx_wait(ctx));  // the traces were written on ctx's stream; the side contexts may have streams of their own
     char names[VX_BUS_GROUP_MAX_TABLES][24];
     TableGroup g(ctx, cfg, WHAT);
     for (size_t k = 0; k < n; ++k) {

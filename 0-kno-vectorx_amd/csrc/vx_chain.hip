@@ -340,7 +340,7 @@ int32_t vx_blake2b_256_batch(vx_ctx* ctx, const vx_buf* msgs, size_t stride, con
                        (const uint32_t*)sc, n, (uint8_t*)(sc + sz_words));
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(digests_out, sc + sz_words, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -354,7 +354,7 @@ int32_t vx_sha256_pairs(vx_ctx* ctx, const uint8_t* pairs64, size_t n, uint8_t* 
                        (uint8_t*)(sc + n * 8));
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(out32, sc + n * 8, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -384,7 +384,7 @@ int32_t vx_decode_header_batch(vx_ctx* ctx, const vx_buf* headers, size_t stride
     VX_HIP(hipMemcpyAsync(parent_out, d_par, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipMemcpyAsync(state_root_out, d_sr, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipMemcpyAsync(data_root_out, d_dr, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -409,7 +409,7 @@ int32_t vx_decode_precommit_batch(vx_ctx* ctx, const uint8_t* precommits, size_t
     VX_HIP(hipMemcpyAsync(block_number_out, d_bn, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipMemcpyAsync(round_out, d_round, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipMemcpyAsync(set_id_out, d_sid, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -445,7 +445,7 @@ int32_t vx_verify_subchain(vx_ctx* ctx, const vx_buf* headers, size_t stride, co
     uint32_t status = 0;
     VX_HIP(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
     VX_HIP(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     memcpy(out96, res.end_header_hash, 32);
     memcpy(out96 + 32, res.state_root, 32);
     memcpy(out96 + 64, res.data_root, 32);

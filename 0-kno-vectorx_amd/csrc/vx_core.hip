@@ -2,6 +2,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "gl.cuh"
 #include <dlfcn.h>
@@ -14,6 +15,43 @@
 // when the library is loaded, unless the host has chosen a value itself.  A host that touches HIP before loading the library
 // exports it on its own.
 __attribute__((constructor)) static void vx_runtime_env() { setenv("GPU_MAX_HW_QUEUES", "16", /*overwrite=*/0); }
+
+// Table streams.  A proof runs each of its tables on a context of its own (the host's context and the chain of side contexts behind
+// it, one host thread each), and these contexts reach the GPU in one of two ways:
+//   own     every context has a stream of its own.  A proof's tables overlap on the chip and one proof alone is fastest.  With
+//           several proofs in flight the 5-6 streams of each are spread over the hardware queues, which are in order: where queues
+//           are few, a 36 ms leaf hash of proof A sits in front of the 20 us kernels of proof B's small tables, and B's hash-chain
+//           table waits for those at the challenge rendezvous (bus_meet.cpp).
+//   shared  a side context enqueues on its parent's stream: one stream, hence one hardware queue, per proof.  Blocking stays inside
+//           a proof, and N proofs in flight offer the chip N independent kernels; the tables of one proof no longer overlap, so the
+//           latency of a proof alone rises.  Everything else of a context stays its own (pool, scratch, pinned block, tables,
+//           error text).  The tables of a group exchange host data only (public inputs and caps, bus_meet.cpp) or read device
+//           buffers their parent finished before it started them, so one in-order stream orders no less than several did.
+// VX_TABLE_STREAMS = own | shared | auto is read when the HOST's context is created (not when the library is loaded: one process can
+// hold both kinds) and inherited by its side contexts.  auto, the default: shared when the process's GPU_MAX_HW_QUEUES -- read
+// here, after the constructor above -- is 4 or less, own otherwise (4 is the only low setting with measurements,
+// profiles/README.md).  In shared mode a table's thread must not wait for what the OTHER tables' threads enqueue after it: every
+// internal wait is vx_wait (an event recorded at the call); the public vx_sync and vx_ctx_destroy still drain the stream.
+// One queue per proof holds only if the host contexts' streams land on different queues: the runtime gives a new stream the
+// least-used queue, and the null stream, once anything has used it, counts as a user of one -- so nothing in this library runs on
+// the null stream (with the context tables copied by hipMemcpy, four host contexts sat on queues 1, 3, 4, 4; profiles/README.md).
+extern "C" int32_t vx_table_streams_mode(const char* table_streams, const char* hw_queues) {
+    if (table_streams && strcmp(table_streams, "own") == 0) return VX_TABLE_STREAMS_OWN;
+    if (table_streams && strcmp(table_streams, "shared") == 0) return VX_TABLE_STREAMS_SHARED;
+    // auto (also: unset, empty, anything else).  An unset queue count is the runtime's default of 4; one that is no positive number
+    // is left to the runtime and keeps today's streams.
+    if (!hw_queues) return VX_TABLE_STREAMS_SHARED;
+    char* end = nullptr;
+    const long q = strtol(hw_queues, &end, 10);
+    if (end == hw_queues || *end || q < 1) return VX_TABLE_STREAMS_OWN;
+    return q <= 4 ? VX_TABLE_STREAMS_SHARED : VX_TABLE_STREAMS_OWN;
+}
+
+hipError_t vx_wait(vx_ctx* ctx) {
+    if (ctx->table_streams != VX_TABLE_STREAMS_SHARED) return hipStreamSynchronize(ctx->stream);
+    const hipError_t e = hipEventRecord(ctx->ev_wait, ctx->stream);
+    return e != hipSuccess ? e : hipEventSynchronize(ctx->ev_wait);
+}
 
 int32_t vx_fail(vx_ctx* ctx, int32_t code, const char* fmt, ...) {
     char buf[512];
@@ -38,7 +76,7 @@ static int32_t make_powtab(vx_ctx* ctx, uint64_t base, PowTab* out) {
     }
     VX_HIP(hipMalloc(&out->d, h.size() * 8));
     VX_HIP(hipMemcpyAsync(out->d, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -76,7 +114,7 @@ int32_t vx_get_tw2(vx_ctx* ctx, int log_s, int inverse, Tw2* out) {
         uint64_t* d = nullptr;
         VX_HIP(hipMalloc(&d, h.size() * 8));
         VX_HIP(hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        VX_HIP(hipStreamSynchronize(ctx->stream));
+        VX_HIP(vx_wait(ctx));
         it = ctx->tw2.emplace(key, d).first;
     }
     out->lo = it->second;
@@ -86,7 +124,7 @@ int32_t vx_get_tw2(vx_ctx* ctx, int log_s, int inverse, Tw2* out) {
 }
 
 void vx_pool_trim(vx_ctx* ctx) {
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)vx_wait(ctx);
     for (auto& kv : ctx->pool_free)
         for (void* p : kv.second) (void)hipFree(p);
     ctx->pool_free.clear();
@@ -142,9 +180,10 @@ const char* vx_backend_name(void) { return "hip-gfx950"; }
 
 // Stream priorities (VX_STREAM_PRIO=1; off by default, see profiles/README.md): a context made by the host gets the device's
 // highest priority, the side contexts a proof chains behind it (one per further table) the lowest -- the hash-chain table,
-// which is the critical path of a proof, runs on the host's context.
-static thread_local int g_side_ctx = 0;
-int32_t vx_ctx_create(int device, vx_ctx** out) {
+// which is the critical path of a proof, runs on the host's context.  With shared table streams a side context has no stream of
+// its own, so there is nothing for the low priority to apply to: the proof's one stream has the host context's priority.
+// parent: the context this one is a side context of (nullptr: a context made by the host).
+static int32_t ctx_create(int device, vx_ctx* parent, vx_ctx** out) {
     if (!out) return VX_ERR_ARG;
     *out = nullptr;
     int n_dev = 0;
@@ -155,26 +194,29 @@ int32_t vx_ctx_create(int device, vx_ctx** out) {
     ctx->scratch_n = 0;
     ctx->pinned = nullptr;
     ctx->pinned_n = 0;
-    {
-        // A proof's host threads (one per table, several proofs in flight) mostly wait in hipStreamSynchronize.  The runtime's default
-        // spins: 35.6 s of CPU for a 10 s bench run, 9.3 s with blocking waits, at the same 7.95 proofs/s (profiles/README.md) -- and
-        // eight ranks share the cores of one node.  VX_SYNC_MODE = s (spin) / y (yield) / b (blocking, the default) overrides.
-        const char* sm = getenv("VX_SYNC_MODE");
-        const char m = sm ? sm[0] : 'b';
-        (void)hipSetDevice(device);
-        (void)hipSetDeviceFlags(m == 's' ? hipDeviceScheduleSpin : m == 'y' ? hipDeviceScheduleYield : hipDeviceScheduleBlockingSync);
-        (void)hipGetLastError();  // (a host that has fixed the flags already keeps them)
-    }
+    ctx->table_streams = parent ? parent->table_streams : vx_table_streams_mode(getenv("VX_TABLE_STREAMS"), getenv("GPU_MAX_HW_QUEUES"));
+    ctx->stream_owned = !(parent && ctx->table_streams == VX_TABLE_STREAMS_SHARED);
+    // A proof's host threads (one per table, several proofs in flight) mostly wait in hipStreamSynchronize (vx_wait).  The runtime's
+    // default spins: 35.6 s of CPU for a 10 s bench run, 9.3 s with blocking waits, at the same 7.95 proofs/s (profiles/README.md) -- and
+    // eight ranks share the cores of one node.  VX_SYNC_MODE = s (spin) / y (yield) / b (blocking, the default) overrides.
+    const char* sm = getenv("VX_SYNC_MODE");
+    const char m = sm ? sm[0] : 'b';
+    (void)hipSetDevice(device);
+    (void)hipSetDeviceFlags(m == 's' ? hipDeviceScheduleSpin : m == 'y' ? hipDeviceScheduleYield : hipDeviceScheduleBlockingSync);
+    (void)hipGetLastError();  // (a host that has fixed the flags already keeps them)
     hipError_t se = hipSetDevice(device);
-    if (se == hipSuccess) {
+    if (se == hipSuccess && !ctx->stream_owned) ctx->stream = parent->stream;
+    else if (se == hipSuccess) {
         const char* sp = getenv("VX_STREAM_PRIO");
         int least = 0, greatest = 0;
         if (sp && sp[0] == '1' && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            se = hipStreamCreateWithPriority(&ctx->stream, hipStreamDefault, g_side_ctx ? least : greatest);
+            se = hipStreamCreateWithPriority(&ctx->stream, hipStreamDefault, parent ? least : greatest);
         else se = hipStreamCreate(&ctx->stream);
     }
-    if (se != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+    // the event of vx_wait carries no timestamp, and its wait blocks or spins as the stream waits of this mode do (an event made
+    // without the blocking flag waits as the device flags say)
+    if (se != hipSuccess || hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
+        hipEventCreateWithFlags(&ctx->ev_wait, hipEventDisableTiming | (m == 's' || m == 'y' ? 0 : hipEventBlockingSync)) != hipSuccess) {
         delete ctx;
         return VX_ERR_DEVICE;
     }
@@ -189,9 +231,11 @@ int32_t vx_ctx_create(int device, vx_ctx** out) {
             a = glh::mul(a, w);
             c = glh::mul(c, wi);
         }
+        // (on the context's stream, not with hipMemcpy: that runs on the NULL stream, which the runtime creates at its first use and
+        // which then holds a hardware queue of its own -- with 4 queues the streams of four host contexts came out on THREE of them)
         if (hipMalloc(&ctx->w12_fwd, 2048 * 8) != hipSuccess || hipMalloc(&ctx->w12_inv, 2048 * 8) != hipSuccess ||
-            hipMemcpy(ctx->w12_fwd, f.data(), 2048 * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ctx->w12_inv, b.data(), 2048 * 8, hipMemcpyHostToDevice) != hipSuccess)
+            hipMemcpyAsync(ctx->w12_fwd, f.data(), 2048 * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(ctx->w12_inv, b.data(), 2048 * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess || vx_wait(ctx) != hipSuccess)
             rc = VX_ERR_DEVICE;
     }
     if (rc == VX_OK) {
@@ -205,6 +249,7 @@ int32_t vx_ctx_create(int device, vx_ctx** out) {
     *out = ctx;
     return VX_OK;
 }
+int32_t vx_ctx_create(int device, vx_ctx** out) { return ctx_create(device, nullptr, out); }
 
 int32_t vx_ctx_destroy(vx_ctx* ctx) {
     if (!ctx) return VX_ERR_ARG;
@@ -213,7 +258,7 @@ int32_t vx_ctx_destroy(vx_ctx* ctx) {
         ctx->side = nullptr;
     }
     hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
+    hipStreamSynchronize(ctx->stream);  // (the whole stream, in either mode)
     for (auto& kv : ctx->shift_tabs) hipFree(kv.second.d);
     for (auto& kv : ctx->periodic_cache) hipFree(kv.second);
     for (auto& kv : ctx->tw2) hipFree(kv.second);
@@ -227,18 +272,21 @@ int32_t vx_ctx_destroy(vx_ctx* ctx) {
     if (ctx->pinned) hipHostFree(ctx->pinned);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
-    hipStreamDestroy(ctx->stream);
+    hipEventDestroy(ctx->ev_wait);
+    if (ctx->stream_owned) hipStreamDestroy(ctx->stream);  // (a shared stream goes with the host's context: the side contexts went first, above)
     delete ctx;
     return VX_OK;
 }
 
 int32_t vx_sync(vx_ctx* ctx) {
     if (!ctx) return VX_ERR_ARG;
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(hipStreamSynchronize(ctx->stream));  // everything enqueued on the stream, in shared mode the side contexts' work too
     return VX_OK;
 }
 const char* vx_last_error(const vx_ctx* ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
 
+// (the two events are recorded on ctx->stream: with shared table streams they also see what the other tables of the proof enqueue
+// on it between them)
 int32_t vx_timer_start(vx_ctx* ctx) {
     if (!ctx) return VX_ERR_ARG;
     VX_HIP(hipEventRecord(ctx->ev0, ctx->stream));
@@ -274,14 +322,14 @@ int32_t vx_upload(vx_ctx* ctx, vx_buf* dst, size_t off, const uint64_t* src, siz
     if (!ctx || !dst || !src) return VX_ERR_ARG;
     VX_CHECK(off + n <= dst->n, "vx_upload: range [%zu,%zu) exceeds buffer of %zu", off, off + n, dst->n);
     VX_HIP(hipMemcpyAsync(dst->d + off, src, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // caller may reuse src immediately
+    VX_HIP(vx_wait(ctx));  // caller may reuse src immediately
     return VX_OK;
 }
 int32_t vx_download(vx_ctx* ctx, const vx_buf* src, size_t off, uint64_t* dst, size_t n) {
     if (!ctx || !dst || !src) return VX_ERR_ARG;
     VX_CHECK(off + n <= src->n, "vx_download: range [%zu,%zu) exceeds buffer of %zu", off, off + n, src->n);
     VX_HIP(hipMemcpyAsync(dst, src->d + off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 int32_t vx_copy(vx_ctx* ctx, vx_buf* dst, size_t doff, const vx_buf* src, size_t soff, size_t n) {
@@ -385,16 +433,12 @@ int32_t vx_gather_proofs(vx_ctx* ctx, void* nccl_comm, int world, const uint64_t
     const int rc = all_gather(sc, sc + n_words, n_words, /*ncclUint64=*/5, nccl_comm, ctx->stream);
     if (rc != 0) return vx_fail(ctx, VX_ERR_DEVICE, "gather: ncclAllGather failed (%d)", rc);
     VX_HIP(hipMemcpyAsync(out, sc + n_words, n_words * 8 * (size_t)world, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 }
 
 vx_ctx* vx_side_ctx(vx_ctx* ctx) {
-    if (!ctx->side) {
-        g_side_ctx = 1;
-        if (vx_ctx_create(ctx->device, &ctx->side) != VX_OK) ctx->side = nullptr;
-        g_side_ctx = 0;
-    }
+    if (!ctx->side && ctx_create(ctx->device, ctx, &ctx->side) != VX_OK) ctx->side = nullptr;
     return ctx->side;
 }

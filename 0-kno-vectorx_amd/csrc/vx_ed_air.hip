@@ -473,7 +473,7 @@ int32_t vx_ed_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, const uint8_t* sigs
     if (e != hipSuccess) return vx_fail(ctx, VX_ERR_DEVICE, "ed trace: %s", hipGetErrorString(e));
     uint32_t bad = 0;
     VX_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // idx (host vector) must outlive the copy; bad is read below
+    VX_HIP(vx_wait(ctx));  // idx (host vector) must outlive the copy; bad is read below
     if (bad) return vx_fail(ctx, VX_ERR_STATEMENT, "ed trace: a signed slot does not verify (undecodable key / R, or [S]B != R + [h]A)");
     pub_out[0] = k, pub_out[1] = bus_on;
     return VX_OK;

@@ -37,7 +37,7 @@ int32_t vx_epoch_end_trace_dev(vx_ctx* ctx, const uint8_t* header_d, size_t head
     VX_CHECK((uint64_t)start_position + 1 + 17 <= header_bytes, "epoch-end trace: start position %u leaves no room for the 17-byte prefix", start_position);
     uint8_t p[17];
     VX_HIP(hipMemcpyAsync(p, header_d + start_position + 1, 17, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     if (p[0] != 4 || memcmp(p + 1, "FRNK", 4) != 0) return vx_fail(ctx, VX_ERR_STATEMENT, "epoch-end trace: consensus flag / engine id");
     const int m1 = p[5] & 3, len1 = len_of(m1);
     if (m1 == 3 && p[5] != 3) return vx_fail(ctx, VX_ERR_STATEMENT, "epoch-end trace: compact int (length)");

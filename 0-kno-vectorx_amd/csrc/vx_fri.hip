@@ -256,7 +256,7 @@ int32_t vx_fri_leaves_dev(vx_ctx* ctx, const uint64_t* evals_d, int log_n, int a
     vx_fri_leaves_enqueue(ctx, evals_d, log_n, arity_bits, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(out, sc + n_idx, 2 * tot * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 
@@ -278,7 +278,7 @@ int32_t vx_fri_pow(vx_ctx* ctx, const uint64_t state[12], int pos, int bits, uin
         hipLaunchKernelGGL(k_fri_pow, dim3(blocks), dim3(256), 0, ctx->stream, sc, pos, bits, base, chunk, best);
         VX_HIP(hipGetLastError());
         VX_HIP(hipMemcpyAsync(&h, best, 8, hipMemcpyDeviceToHost, ctx->stream));
-        VX_HIP(hipStreamSynchronize(ctx->stream));
+        VX_HIP(vx_wait(ctx));
         if (h != ~0ULL) {
             *nonce = h;
             return VX_OK;

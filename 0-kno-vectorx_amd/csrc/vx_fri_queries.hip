@@ -80,7 +80,7 @@ int32_t vx_fri_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, int log_ld
         const size_t n_cap = (size_t)1 << trees[l]->cap_height;
         std::vector<uint64_t> cap(4 * n_cap);
         VX_HIP(hipMemcpyAsync(cap.data(), trees[l]->levels + trees[l]->total - 4 * n_cap, 4 * n_cap * 8, hipMemcpyDeviceToHost, ctx->stream));
-        VX_HIP(hipStreamSynchronize(ctx->stream));  // also: the trees and the layers are this stream's work, the side contexts read them
+        VX_HIP(vx_wait(ctx));  // also: the trees and the layers are this stream's work, the side contexts read them
         for (uint64_t& w : cap) w = w >= glh::P ? w - glh::P : w;
         vx_cap_fold(cap.data(), trees[l]->cap_height, roots.data() + 4 * l);
     }

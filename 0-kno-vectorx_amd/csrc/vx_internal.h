@@ -33,10 +33,17 @@ struct PowTab {
     uint64_t* d;  // 3*2048 on device
 };
 
+// How the tables of one proof (a context and the chain of side contexts behind it) reach the GPU; chosen when the host's context
+// is made (VX_TABLE_STREAMS, vx_core.hip) and inherited by its side contexts.
+enum { VX_TABLE_STREAMS_OWN = 0, VX_TABLE_STREAMS_SHARED = 1 };
+
 struct vx_ctx {
     int device;
     hipStream_t stream;
+    bool stream_owned;  // false: a side context in shared mode, `stream` is its parent's and is not destroyed with it
+    int table_streams;  // VX_TABLE_STREAMS_*
     hipEvent_t ev0, ev1;
+    hipEvent_t ev_wait;  // shared mode: what vx_wait records and waits for (no timing)
     std::string err;
     PowTab tw_fwd, tw_inv;       // base = omega_{2^32}, omega_{2^32}^-1
     uint64_t *w12_fwd, *w12_inv;  // omega_4096^e, e < 2048
@@ -48,16 +55,21 @@ struct vx_ctx {
     size_t pinned_n;
     // device memory pool: blocks are recycled by exact (rounded) size instead of hipFree'd -- a
     // proof allocates tens of GB and hipMalloc/hipFree of such blocks costs far more than the kernels.
-    // All work is on ctx->stream, so a recycled block is safe to hand out again immediately.
+    // All work is on ctx->stream, so a recycled block is safe to hand out again immediately (in shared mode too: the contexts of a
+    // proof then enqueue on ONE in-order stream, and a block never leaves the pool of the context that allocated it).
     std::map<size_t, std::vector<void*>> pool_free;
     std::map<void*, size_t> pool_live;
-    // a second context on the same device (own stream, scratch and pool), made on first use: independent small proofs
+    // a second context on the same device (own scratch and pool; own stream unless table_streams is shared), made on first use: independent small proofs
     // (the authority-set commitment STARKs) run on it from a host thread while this context proves the hash chain
     vx_ctx* side = nullptr;
     // periodic columns of an AIR on the LDE coset, by (air id, degree bits, rate bits): identical for every proof of a shape
     std::map<uint64_t, uint64_t*> periodic_cache;
 };
 vx_ctx* vx_side_ctx(vx_ctx* ctx);  // nullptr if it cannot be created
+// Every internal "wait for this context's work".  Own mode: hipStreamSynchronize(ctx->stream).  Shared mode: an event recorded on the
+// stream now and waited for -- what THIS context has enqueued (and whatever the proof's other tables enqueued before the record),
+// not the kernels another table's thread enqueues afterwards.  Called from the one host thread that drives ctx.
+hipError_t vx_wait(vx_ctx* ctx);
 void* vx_pool_alloc(vx_ctx* ctx, size_t bytes);
 void vx_pool_free(vx_ctx* ctx, void* p);
 void vx_pool_trim(vx_ctx* ctx);
@@ -100,7 +112,7 @@ struct Scratch {
     }
     void launched() { keep(hipGetLastError()); }  // after a kernel launch
     void sync() {
-        if (ok()) err = hipStreamSynchronize(ctx->stream);
+        if (ok()) err = vx_wait(ctx);
     }
     int32_t status(const char* what) const {
         if (!base) return vx_fail(ctx, VX_ERR_OOM, "%s: out of device memory", what);

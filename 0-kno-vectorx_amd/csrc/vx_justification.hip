@@ -112,7 +112,7 @@ int32_t vx_ed25519_verify_batch(vx_ctx* ctx, const uint8_t* pubkeys, const uint8
                        (const uint8_t*)d_msg, msg_len, (const uint8_t*)d_en, n, d_ok);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(ok_out, d_ok, n, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 

@@ -367,7 +367,7 @@ int32_t vx_merkle_rows_prove(vx_ctx* ctx, const vx_stark_config* cfg, const vx_t
                                   return leaf_sponge_trace_dev(c, data->d + off, n_leaves, leaf_len, layout, tree->levels, leaf_idx, n_idx, log_sponge, trace->d, pub);
                               }});
     // the tree and the leaf data are the work of this context's stream; the openings table reads the tree from another one
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     VX_TRY(g.prove(sponge));
     return pack_blob(ctx, "merkle rows", VX_MROWS_MAGIC, {(uint64_t)depth, leaf_len, n_idx}, {&g.job[0], &g.job[1]}, blob_out, blob_cap, blob_len);
 }

@@ -77,7 +77,7 @@ int32_t vx_scan_cols_dev(vx_ctx* ctx, uint64_t* data, int log_n, size_t n_cols, 
     if (totals_host) {  // column total = sum of its tile sums: take them before the scan overwrites the array
         std::vector<uint64_t> h(tiles * n_cols);
         VX_HIP(hipMemcpyAsync(h.data(), sums, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        VX_HIP(hipStreamSynchronize(ctx->stream));
+        VX_HIP(vx_wait(ctx));
         for (size_t c = 0; c < n_cols; ++c) {
             uint64_t t = 0;
             for (size_t k = 0; k < tiles; ++k) t = glh::add(t, h[c * tiles + k]);

@@ -689,7 +689,7 @@ int32_t vx_gather_rows_dev(vx_ctx* ctx, const uint64_t* lde, int log_N, size_t n
     vx_gather_rows_enqueue(ctx, lde, log_N, n_cols, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(out, sc + n_idx, tot * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 

@@ -293,13 +293,13 @@ int32_t vx_merkle_cap(vx_ctx* ctx, const vx_tree* tree, uint64_t* cap_out) {
     if (!ctx || !tree || !cap_out) return VX_ERR_ARG;
     size_t cap = (size_t)4 << tree->cap_height;
     VX_HIP(hipMemcpyAsync(cap_out, tree->levels + tree->total - cap, cap * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 int32_t vx_merkle_leaf_digests(vx_ctx* ctx, const vx_tree* tree, uint64_t* out) {
     if (!ctx || !tree || !out) return VX_ERR_ARG;
     VX_HIP(hipMemcpyAsync(out, tree->levels, tree->n_leaves * 32, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 int32_t vx_merkle_open(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_idx, size_t n_idx, uint64_t* siblings_out) {
@@ -316,7 +316,7 @@ int32_t vx_merkle_open(vx_ctx* ctx, const vx_tree* tree, const uint64_t* leaf_id
     vx_merkle_open_enqueue(ctx, tree, sc, n_idx, sc + n_idx);
     VX_HIP(hipGetLastError());
     VX_HIP(hipMemcpyAsync(siblings_out, sc + n_idx, 4 * tot * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     return VX_OK;
 }
 }

@@ -93,7 +93,7 @@ int32_t vx_verify_epoch_end_header(vx_ctx* ctx, const vx_buf* header, uint32_t n
     VX_HIP(hipGetLastError());
     uint32_t res = 0;
     VX_HIP(hipMemcpyAsync(&res, sc + key_words, 4, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     if (res == EE_OK) return VX_OK;
     static const char* WHY[] = {"", "subarray out of the header buffer", "consensus flag", "engine id", "compact int", "scheduled change flag",
                                 "authority count", "pubkey", "weight", "delay"};
@@ -125,7 +125,7 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
     uint8_t head[40], header_hash[32], new_commit[32];
     const uint8_t* parent = head;
     VX_HIP(hipMemcpyAsync(head, header->d, 40, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     {
         // The hash AIR pins the header's own SCALE number (4-byte compact at bytes 32..36) to its public input.  The
         // reference binds number and hash only through the signed precommit; for any header GRANDPA finalised the

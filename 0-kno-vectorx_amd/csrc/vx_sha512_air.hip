@@ -166,7 +166,7 @@ int32_t vx_sha512_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, const uint8_t* 
     hipLaunchKernelGGL(k_s512_slots, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, d_keys, d_sigs, d_msg, (const uint32_t*)d_idx, k, m, d_slots);
     hipLaunchKernelGGL(k_s512_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const S5Slot*)d_slots, m, trace_d, n);
     VX_HIP(hipGetLastError());
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // idx (host vector) must outlive the copy
+    VX_HIP(vx_wait(ctx));  // idx (host vector) must outlive the copy
     uint8_t tail[64];
     memset(tail, 0, sizeof tail);
     memcpy(tail, msg, MSG_LEN);

@@ -151,7 +151,7 @@ int32_t vx_sha_chain_trace_dev(vx_ctx* ctx, const uint8_t* pubkeys, size_t n_key
     VX_HIP(hipMemcpyAsync(sc, blocks.data(), n_blocks * sizeof(ShaBlock), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_sha_trace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const ShaBlock*)sc, trace_d, n);
     VX_HIP(hipGetLastError());
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     for (int j = 0; j < 8; ++j) {
         public_inputs_out[j] = dig[j];
         if (commitment_out)
@@ -219,7 +219,7 @@ int32_t vx_sha_tree_trace_dev(vx_ctx* ctx, const uint8_t* state_roots, const uin
     VX_HIP(hipMemcpyAsync(sc, blocks.data(), n_blocks * sizeof(ShaBlock), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_sha_trace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const ShaBlock*)sc, trace_d, n);
     VX_HIP(hipGetLastError());
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // blocks (host vector) must outlive the copy
+    VX_HIP(vx_wait(ctx));  // blocks (host vector) must outlive the copy
     return VX_OK;
 }
 

@@ -425,7 +425,7 @@ struct DevMem {  // RAII for the prover's temporaries (recycled through the ctx 
 static void read_cap(vx_ctx* ctx, const vx_tree* t, uint64_t* out) {
     size_t cap = (size_t)4 << t->cap_height;
     (void)hipMemcpyAsync(out, t->levels + t->total - cap, cap * 8, hipMemcpyDeviceToHost, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)vx_wait(ctx);
 }
 
 struct DevMem;
@@ -553,7 +553,7 @@ static int32_t periodic_table_dev(vx_ctx* ctx, const AirDesc* air, int L, int r,
             }
             VX_HIP(hipMemcpyAsync(tmp, pv.data() + in_off, p * 8, hipMemcpyHostToDevice, ctx->stream));
             int32_t rc = vx_lde_dev(ctx, tmp, pl, 1, r, shift_pow, VX_LDE_SRC_VALUES, d + off, nullptr);
-            VX_HIP(hipStreamSynchronize(ctx->stream));
+            VX_HIP(vx_wait(ctx));
             vx_pool_free(ctx, tmp);
             if (rc != VX_OK) {
                 (void)hipFree(d);
@@ -562,7 +562,7 @@ static int32_t periodic_table_dev(vx_ctx* ctx, const AirDesc* air, int L, int r,
         }
         off += m, in_off += p;
     }
-    VX_HIP(hipStreamSynchronize(ctx->stream));  // tab / pv (host vectors) must outlive the copies
+    VX_HIP(vx_wait(ctx));  // tab / pv (host vectors) must outlive the copies
     ctx->periodic_cache[key] = d;
     *out = d;
     return VX_OK;
@@ -624,7 +624,8 @@ static int32_t quotient_eval_dev(vx_ctx* ctx, const AirDesc* air, int L, int r, 
                 std::vector<uint64_t> blob(pg.code);
                 blob.insert(blob.end(), pg.consts.begin(), pg.consts.end());
                 VX_HIP(hipMalloc((void**)&d_code, blob.size() * 8));
-                VX_HIP(hipMemcpy(d_code, blob.data(), blob.size() * 8, hipMemcpyHostToDevice));
+                VX_HIP(hipMemcpyAsync(d_code, blob.data(), blob.size() * 8, hipMemcpyHostToDevice, ctx->stream));  // (never the null stream: vx_core.hip)
+                VX_HIP(vx_wait(ctx));  // blob must outlive the copy
                 ctx->periodic_cache[key] = d_code;
             }
             size_t off = 0;
@@ -640,7 +641,7 @@ static int32_t quotient_eval_dev(vx_ctx* ctx, const AirDesc* air, int L, int r, 
             const size_t N = (size_t)1 << LN;
             hipLaunchKernelGGL(k_quotient_prog, dim3((unsigned)((N + QB - 1) / QB)), dim3(QB), pg.n_regs * QB * sizeof(uint64_t), ctx->stream, qa, pa);
         } else air->launch(qa, ctx->stream);
-        VX_HIP(hipStreamSynchronize(ctx->stream));  // apow / per_tab (host vectors) must outlive the copies
+        VX_HIP(vx_wait(ctx));  // apow / per_tab (host vectors) must outlive the copies
         VX_HIP(hipGetLastError());
     }
     return VX_OK;
@@ -793,7 +794,7 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     VX_HIP(hipGetLastError());
     std::vector<uint64_t> h_open(BARY_SPLIT * open_words);
     VX_HIP(hipMemcpyAsync(h_open.data(), d_open, h_open.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     for (int sp = 1; sp < BARY_SPLIT; ++sp)  // the partial sums of the split blocks
         for (size_t j = 0; j < open_words; ++j) h_open[j] = glh::add(h_open[j], h_open[sp * open_words + j]);
     const uint64_t gn_ = glh::pow(g, n), fsc = glh::inv(glh::mul(n % glh::P, gn_));
@@ -864,7 +865,7 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     const size_t fm = (size_t)1 << cur_log;
     std::vector<uint64_t> fv(2 * fm), fc(2 * fm);
     VX_HIP(hipMemcpyAsync(fv.data(), layers.back(), 2 * fm * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     {
         const uint64_t wi = glh::inv(glh::root(cur_log)), minv = glh::inv(fm % glh::P), sinv = glh::inv(shift);
         uint64_t sk = 1;
@@ -944,7 +945,7 @@ int32_t vx_stark_prove_impl(vx_ctx* ctx, int air_id, const vx_stark_config* cfg_
     VX_HIP(hipGetLastError());
     std::vector<uint64_t> q(words);
     VX_HIP(hipMemcpyAsync(q.data(), gat, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-    VX_HIP(hipStreamSynchronize(ctx->stream));
+    VX_HIP(vx_wait(ctx));
     const uint64_t *rows_t = q.data() + o_rows_t, *rows_a = q.data() + o_rows_a, *rows_q = q.data() + o_rows_q;
     const uint64_t *sib_t = q.data() + o_sib_t, *sib_a = q.data() + o_sib_a, *sib_q = q.data() + o_sib_q;
     for (size_t k = 0; k < nqr; ++k) {

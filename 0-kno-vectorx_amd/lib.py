@@ -17,7 +17,7 @@ ERR_NAMES = {-1: "VX_ERR_ARG", -2: "VX_ERR_DEVICE", -3: "VX_ERR_OOM", -4: "VX_ER
 
 # every symbol include/vx.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "vx_ctx_create", "vx_ctx_destroy", "vx_sync", "vx_last_error", "vx_backend_name", "vx_timer_start", "vx_timer_stop",
+    "vx_ctx_create", "vx_ctx_destroy", "vx_sync", "vx_last_error", "vx_backend_name", "vx_timer_start", "vx_timer_stop", "vx_table_streams_mode",
     "vx_alloc", "vx_free", "vx_upload", "vx_download", "vx_copy", "vx_fill_random", "vx_buf_devptr", "vx_buf_len",
     "vx_field_batch_add", "vx_field_batch_sub", "vx_field_batch_mul", "vx_field_batch_inv", "vx_ext_batch_mul",
     "vx_ntt", "vx_lde", "vx_lde_rows",
@@ -847,8 +847,19 @@ class Tree:
             self.h = None
 
 
+def table_streams_mode(table_streams, hw_queues):
+    """The library's choice between a stream per table ("own") and one stream per proof ("shared") for the values of VX_TABLE_STREAMS and
+    GPU_MAX_HW_QUEUES (strings, None = unset).  Host only.  (Bound here and not in load_library: an A/B library of an older build,
+    VX_LIB_PATH, does not have it.)"""
+    f = load_library().vx_table_streams_mode
+    f.argtypes, f.restype = [C.c_char_p, C.c_char_p], C.c_int32
+    a, b = (None if v is None else str(v).encode() for v in (table_streams, hw_queues))
+    return ("own", "shared")[f(a, b)]
+
+
 class Context:
-    """One device + one stream (vx_ctx).  Raises VxError on any failure."""
+    """One device + one stream (vx_ctx).  Raises VxError on any failure.  The circuit provers run their tables on side contexts behind it:
+    with streams of their own or on this one's, as VX_TABLE_STREAMS says when the context is made (include/vx.h)."""
 
     def __init__(self, device=0):
         self.L = load_library()

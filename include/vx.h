@@ -55,6 +55,12 @@ const char* vx_backend_name(void); /* "hip-gfx950" */
  * vx_timer_start records, vx_timer_stop records + synchronises and returns ms. */
 int32_t vx_timer_start(vx_ctx* ctx);
 int32_t vx_timer_stop(vx_ctx* ctx, float* ms);
+/* How the circuit provers' tables reach the GPU (environment, read by vx_ctx_create and inherited by the side contexts a prover
+ * makes behind the ctx): VX_TABLE_STREAMS = own (a stream per table), shared (the tables of one proof on the ctx's one stream:
+ * for several proofs in flight where hardware queues are few; the latency of one proof alone rises) or auto (the default: shared
+ * when GPU_MAX_HW_QUEUES is 4 or less).  The decision itself, host only: the two strings as getenv returns them (NULL = unset)
+ * -> 0 own, 1 shared.  Results are the same bytes in either mode. */
+int32_t vx_table_streams_mode(const char* table_streams, const char* hw_queues);
 
 /* ---- memory --------------------------------------------------------------- */
 int32_t vx_alloc(vx_ctx* ctx, size_t n_u64, vx_buf** out);
