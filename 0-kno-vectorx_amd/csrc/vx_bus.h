@@ -359,6 +359,21 @@ int32_t vx_transcript_trace_dev(vx_ctx* ctx, const glh::TranscriptRecord* chains
 // (the query phase is walked) or its head alone (the indices are derived, no record is read)
 int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen);
 
+// ---- STARK-inner blob (written by vx_stark_inner_prove in vx_stark_inner.hip, read by vx_stark_inner_verify in vx_verify.hip): magic,
+// the 7 shape words of the inner proof (as VXSQRY01), the number of tables, n_obs, n_chal, the n_chal claimed challenges as
+// (absorbed, value), one length per table, the proofs in bus order: the tables of VXSQRY01, then TranscriptAir (one chain, id 0)
+static const uint64_t VX_SINR_MAGIC = 0x3130524e49535856ULL;  // "VXSINR01"
+static constexpr size_t VX_SINR_HDR = 11;                     // before the claims
+// The ONE replay of the prover's side: the verifier's code over the recording challenger with the paths delegated -> the claims of
+// the query phase and what the transcript did.  head_ok: a proof that ends at its head is read query-free (the proof bound).
+int32_t vx_stark_inner_replay(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, bool head_ok, StarkQueries* sq, glh::TranscriptRecord* rec, char* err,
+                              size_t errlen);
+// the statement of an inner proof, the four digest words of every table of its group, prover and verifier alike:
+// hash_n_to_hash_no_pad(the 7 shape words, n_obs, n_chal, the observed words, (absorbed, value) of every challenge).  Everything the
+// query-phase digest held is a function of these words: alpha, zeta, betas and indices are claimed challenges, the openings, the
+// final polynomial and the caps (hence the folded roots) are observed words.
+void vx_stark_inner_statement(const std::array<uint64_t, 7>& shape, const TranscriptClaim& chain, uint64_t digest[4]);
+
 // ---- bus-group blob (written by vx_bus_group_prove in vx_bus_group.hip, read by vx_bus_group_verify in vx_verify.hip): magic, the
 // number of tables, one length per proof, the proofs in bus order.  No AIR id: registered ids are per process, the verifier states its own.
 static const uint64_t VX_BGRP_MAGIC = 0x3130505247425856ULL;  // "VXBGRP01"

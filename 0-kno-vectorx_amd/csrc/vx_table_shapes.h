@@ -78,11 +78,12 @@ static inline int leaf_noop_log_n(size_t n_idx) {
 // its own digest: the quotient rows, and any other tree that short, have no sponge).  Rows: 32 per level of every path, 32 per 8
 // words of every leaf, each table at the smallest log_n >= 5.  false: a tree without a level, more than 8 layers, or a table of
 // more than 2^26 rows.
-// The tables of either group: the openings table, n_sponge sponge tables and, in the query-phase group, three more.
+// The tables of such a group: the openings table, n_sponge sponge tables and, in the query-phase group, three more; the inner-proof
+// group (stark_inner_tables below) has the transcript table behind them.
 struct StarkGroupTables {
     int n = 0, n_sponge = 0;
-    int air[7], log_n[7];
-    size_t leaf_len[7];  // of the sponge tables, 0 elsewhere
+    int air[8], log_n[8];
+    size_t leaf_len[8];  // of the sponge tables, 0 elsewhere
     size_t noop_per_query = 0;  // query-phase group
 };
 static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, StarkGroupTables* t) {
@@ -146,4 +147,14 @@ static inline int transcript_log_n(size_t blocks, const vx_stark_config& cfg) {
     if (l < 5) l = 5;
     while (l <= 26 && !fri_plan_ok(l, cfg)) ++l;
     return l;
+}
+// The tables of a STARK proof's query phase AND transcript on one bus (vx_stark_inner_prove / vx_stark_inner_verify), in bus order: the
+// tables of stark_queries_tables, then TranscriptAir with the one chain of `blocks` duplexes.  false: what stark_queries_tables
+// refuses, or a transcript table of more than 2^26 rows.
+static inline bool stark_inner_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, size_t blocks, const vx_stark_config& cfg, StarkGroupTables* t) {
+    if (!stark_queries_tables(LN, cm, ca, a, NL, n_queries, cfg, t)) return false;
+    const int log_n = transcript_log_n(blocks, cfg);
+    if (log_n > 26) return false;
+    t->air[t->n] = VX_AIR_TRANSCRIPT, t->log_n[t->n] = log_n, t->leaf_len[t->n] = 0, ++t->n;
+    return true;
 }

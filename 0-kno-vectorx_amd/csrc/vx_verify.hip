@@ -521,6 +521,14 @@ int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* p
     *out = static_cast<const glh::TranscriptRecord&>(ch);
     return VX_OK;
 }
+// ... and with the claims of the query phase from the same run (vx_bus.h): the one replay of vx_stark_inner_prove
+int32_t vx_stark_inner_replay(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, bool head_ok, StarkQueries* sq, glh::TranscriptRecord* rec, char* err,
+                              size_t errlen) {
+    sp::TranscriptOf<glh::RecordingChallenger> ch;
+    VX_TRY(stark_verify_over(ch, head_ok, cfg, proof, len, 0, nullptr, 0, ext_chal, nullptr, nullptr, QueryPhase::Delegated, sq, err, errlen));
+    *rec = static_cast<const glh::TranscriptRecord&>(ch);
+    return VX_OK;
+}
 
 // One table of a bus group: its serialised proof, what peek_tables reads from it (public inputs, trace cap), and what the
 // request implies for it (AIR id, public inputs).
@@ -1447,6 +1455,100 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
             for (size_t j = 0; j < claims[c].n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claims[c].chal[2 * j], 0}, Fx{claims[c].chal[2 * j + 1], 0}));
         }
     });
+}
+}
+
+void vx_stark_inner_statement(const std::array<uint64_t, 7>& shape, const TranscriptClaim& chain, uint64_t digest[4]) {
+    std::vector<uint64_t> w(shape.begin(), shape.end());
+    w.reserve(9 + chain.n_obs + 2 * chain.n_chal);
+    w.push_back(chain.n_obs), w.push_back(chain.n_chal);
+    w.insert(w.end(), chain.words, chain.words + chain.n_obs);
+    w.insert(w.end(), chain.chal, chain.chal + 2 * chain.n_chal);
+    glh::hash_no_pad(w.data(), w.size(), digest);
+}
+
+extern "C" {
+// An inner proof's query phase AND transcript on one bus (the prover is vx_stark_inner.hip): the tables of vx_stark_queries_verify,
+// then TranscriptAir with the one chain 0.  The inner proof -- whole, or its head alone -- is verified QUERY-FREE over the CLAIMED
+// challenger: every challenge is the blob's claim, every absorbed word is noted, no Poseidon permutation runs for the inner
+// transcript.  Proof of work, the constraint identity at zeta, reduce_openings and the indices (value mod N) use the claimed values.
+// The verifier is the outside party of both halves: per query it RECEIVES root(tree, lo / hi) for every tree of the record and
+// fri(index, final_poly(x_NL), 1); it SENDS obs(0, i, w_i) for every observed word and RECEIVES chal(0, j, A_j, v_j):
+//     sum over the tables of total x rows = sum over the queries of sum over the trees (1 / D_root(lo) + 1 / D_root(hi)) + 1 / D_fri(exit)
+//                                           + sum_j 1 / D_chal(0, j, A_j, v_j) - sum_i 1 / D_obs(0, i, w_i).
+// EVERY public input of every table is rebuilt from the head, the claims and the ONE statement digest (vx_bus.h), the only hashing
+// of the head.  What forces what: DESIGN.md 5o.
+int32_t vx_stark_inner_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                              size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    if (!cfg || !blob || !proof) return VX_ERR_ARG;
+    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "stark inner: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
+    // ---- the claims inside the blob: bounds first, then canonical values drawn after at most n_obs words
+    NEED(len >= VX_SINR_HDR && blob[0] == VX_SINR_MAGIC, "bad stark-inner blob");
+    NEED(blob[10] <= (len - VX_SINR_HDR) / 2, "blob truncated (the claims)");
+    TranscriptClaim claim{nullptr, (size_t)blob[9], blob + VX_SINR_HDR, (size_t)blob[10]};
+    for (size_t j = 0; j < claim.n_chal; ++j) {
+        NEED(claim.chal[2 * j + 1] < glh::P, "claimed challenge %zu is not canonical", j);
+        NEED(claim.chal[2 * j] <= claim.n_obs, "challenge %zu claims %llu absorbed words of %zu", j, (unsigned long long)claim.chal[2 * j], claim.n_obs);
+    }
+    // ---- the inner proof under its claimed transcript, query-free
+    sp::TranscriptOf<glh::ClaimedChallenger> ch;
+    ch.claims = claim.chal, ch.n_claims = claim.n_chal;
+    StarkQueries sq;
+    char inner[200] = "";
+    const int32_t rc = stark_verify_over(ch, true, cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, QueryPhase::QueryFree, &sq, inner, sizeof inner);
+    // what the claims got wrong comes first: a run on too few claims was answered with zeros
+    NEED(!ch.short_of, "the blob claims %zu challenges, the proof's shape draws more", claim.n_chal);
+    if (rc != VX_OK) return v_fail(rc, err, errlen, "%s", inner);
+    NEED(ch.next == claim.n_chal, "the blob claims %zu challenges, the proof's shape draws %zu", claim.n_chal, ch.next);
+    NEED(ch.words.size() == claim.n_obs, "the blob claims %zu absorbed words, the proof's shape absorbs %zu", claim.n_obs, ch.words.size());
+    for (size_t j = 0; j < claim.n_chal; ++j)
+        NEED(claim.chal[2 * j] == ch.absorbed[j], "challenge %zu is claimed after %llu absorbed words, the proof's shape draws it after %llu", j, (unsigned long long)claim.chal[2 * j],
+             (unsigned long long)ch.absorbed[j]);
+    claim.words = ch.words.data();
+    // ---- the tables: the blob must be for this shape and these claims.  The table list gives the count and the leaf lengths; every
+    // table's rows are read from its proof, so no block count is stated here
+    const StarkOpenings& so = sq.so;
+    StarkGroupTables ts;
+    if (so.cap_h > 16 || !stark_inner_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, 0, *cfg, &ts))
+        return v_fail(VX_ERR_ARG, err, errlen, "stark inner: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
+    BusTable tab[8];
+    const std::array<uint64_t, 7> sw = so.shape_words();
+    std::vector<uint64_t> request(sw.begin(), sw.end());
+    request.push_back((uint64_t)ts.n), request.push_back(claim.n_obs), request.push_back(claim.n_chal);
+    request.insert(request.end(), claim.chal, claim.chal + 2 * claim.n_chal);
+    VX_TRY(read_blob(blob, len, VX_SINR_MAGIC, "stark-inner", request.data(), request.size(), tab, (size_t)ts.n, err, errlen));
+    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
+    const size_t n_trees = so.tree.size(), final_len = sq.final_poly.size() / 2;
+    std::vector<uint64_t> roots(4 * n_trees);
+    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
+    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB], npub[lnp::PUB], cpub[fca::PUB], fpub[ffa::PUB], tpub[tsc::PUB];
+    vx_stark_inner_statement(sw, claim, stmt);
+    vx_merkle_open_set_public(stmt, opub);
+    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
+    int k = 1;
+    for (; k <= ts.n_sponge; ++k) {
+        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
+        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
+    }
+    vx_leaf_noop_public(stmt, npub);
+    tab[k].expect(VX_AIR_LEAF_NOOP, npub, lnp::PUB), ++k;
+    vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, cpub);
+    tab[k].expect(VX_AIR_FRI_COMBINE, cpub, fca::PUB), ++k;
+    vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, fpub);
+    tab[k].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB), ++k;
+    vx_transcript_public(stmt, tpub);
+    tab[k].expect(VX_AIR_TRANSCRIPT, tpub, tsc::PUB);
+    return verify_bus_group(cfg, tab, (size_t)ts.n, "the query phase and the transcript the tables prove are not the ones of this proof and these claims (the lookup bus does not balance)", err,
+                            errlen, [&](const VBus& bus, BusMessages& m) {
+                                m.reserve(so.n_queries * (2 * n_trees + 1) + claim.n_obs + claim.n_chal);
+                                for (size_t i = 0; i < so.n_queries; ++i) {
+                                    for (size_t t = 0; t < n_trees; ++t) m.receive_root(bus, so.tree[t], roots.data() + 4 * t, so.log_leaves(so.tree[t]));
+                                    m.receive_exit(bus, so.index[i], so.LN, so.NL, sq.final_poly.data(), final_len);
+                                }
+                                const Fx chain{0, 0};
+                                for (size_t i = 0; i < claim.n_obs; ++i) m.send(bus.obs(chain, Fx{(uint64_t)i, 0}, Fx{claim.words[i], 0}));
+                                for (size_t j = 0; j < claim.n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claim.chal[2 * j], 0}, Fx{claim.chal[2 * j + 1], 0}));
+                            });
 }
 }
 

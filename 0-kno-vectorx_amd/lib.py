@@ -39,6 +39,7 @@ SYMBOLS = [
     "vx_stark_merkle_claims", "vx_merkle_paths_air_trace", "vx_leaf_sponge_rows_air_trace", "vx_stark_openings_proof_bound", "vx_stark_openings_prove", "vx_stark_openings_verify",
     "vx_leaf_noop_air_trace", "vx_stark_queries_proof_bound", "vx_stark_queries_prove", "vx_stark_queries_verify", "vx_stark_proof_head_words",
     "vx_transcript_air_trace", "vx_stark_transcript_claims", "vx_stark_transcripts_proof_bound", "vx_stark_transcripts_prove", "vx_stark_transcripts_verify",
+    "vx_stark_inner_proof_bound", "vx_stark_inner_prove", "vx_stark_inner_verify",
     "vx_bus_group_proof_bound", "vx_bus_group_prove", "vx_bus_group_verify", "vx_bus_group_check",
 ]
 
@@ -247,6 +248,9 @@ def load_library():
         "vx_stark_transcripts_proof_bound": [C.POINTER(StarkConfig), vp, vp, sz, vp, C.POINTER(sz)],
         "vx_stark_transcripts_prove": [vp, C.POINTER(StarkConfig), vp, vp, sz, vp, vp, sz, C.POINTER(sz)],
         "vx_stark_transcripts_verify": [C.POINTER(StarkConfig), vp, sz, vp, vp, sz, vp, C.c_char_p, sz],
+        "vx_stark_inner_proof_bound": [C.POINTER(StarkConfig), vp, sz, vp, C.POINTER(sz)],
+        "vx_stark_inner_prove": [vp, C.POINTER(StarkConfig), vp, sz, vp, vp, sz, C.POINTER(sz)],
+        "vx_stark_inner_verify": [C.POINTER(StarkConfig), vp, sz, vp, sz, C.c_int, vp, sz, vp, C.c_char_p, sz],
         "vx_bus_group_proof_bound": [C.POINTER(StarkConfig), C.POINTER(BusTableStruct), sz, C.POINTER(sz)],
         "vx_bus_group_prove": [vp, C.POINTER(StarkConfig), C.POINTER(BusTableStruct), sz, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_bus_group_verify": [C.POINTER(StarkConfig), vp, sz, C.POINTER(BusExpectStruct), sz, vp, sz, C.c_char_p, sz],
@@ -645,6 +649,30 @@ def stark_transcripts_verify(blob, proofs, cfg=None, ext_chals=None):
     transcript -- and the TranscriptAir table proves the claims.  Raises VxError with the reason; it names the chain."""
     b, pl = _words(blob), _ProofList(proofs, ext_chals)
     _host_verify("vx_stark_transcripts_verify", cfg, b, b.size, pl.ptrs, pl.lens, pl.n, pl.exts)
+
+
+SINR_MAGIC, SINR_HDR = 0x3130524E49535856, 11  # "VXSINR01": magic, the 7 shape words, the table count, n_obs, n_chal; then the claims as (absorbed, value), one length per table, the proofs
+
+
+def split_stark_inner(blob):
+    """-> (the 7 shape words, n_obs, the claimed challenges [n_chal][2] as (absorbed, value), the table proofs in bus order) of a
+    vx_stark_inner_prove blob"""
+    n, n_chal = int(blob[8]), int(blob[10])
+    at = SINR_HDR + 2 * n_chal
+    out, off = [], at + n
+    for k in range(n):
+        ln = int(blob[at + k])
+        out.append(blob[off: off + ln])
+        off += ln
+    return [int(v) for v in blob[1:8]], int(blob[9]), np.asarray(blob[SINR_HDR: at], dtype=np.uint64).reshape(-1, 2), tuple(out)
+
+
+def stark_inner_verify(blob, proof, cfg=None, expect_air=0, expect_public=None, ext_chal=None):
+    """Host-side check of a vx_stark_inner_prove blob together with the inner proof it belongs to -- the whole proof or its HEAD alone
+    (lib.stark_proof_head cuts it): the proof is verified query-free with its transcript answered from the blob's claims -- no Poseidon
+    permutation runs for the inner transcript -- and the group proves the query phase and the claims.  Raises VxError with the reason."""
+    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
+    _host_verify("vx_stark_inner_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
 
 
 FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
@@ -1198,6 +1226,18 @@ class Context:
         return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_transcripts_proof_bound(c, pl.ptrs, pl.lens, pl.n, pl.exts, need),
                                 "stark transcripts: 1..64 proofs of known AIRs under this configuration, every one acceptable, in a table of at most 2^26 rows",
                                 lambda c, o, need: self.L.vx_stark_transcripts_prove(self.h, c, pl.ptrs, pl.lens, pl.n, pl.exts, _ptr(o), o.size, need))
+
+    def stark_inner_prove(self, proof, cfg=None, ext_chal=None, out=None):
+        """Proves the query phase AND the Fiat-Shamir transcript of the vx_stark_prove proof `proof` on one bus -> blob words
+        (lib.stark_inner_verify checks blob and the proof's head together).  Six to eight tables: those of stark_queries_prove, then
+        the transcript.  The proof is verified on the way, by one replay, and paths, combinations and folds are checked natively first:
+        VxError(VX_ERR_STATEMENT) names query and tree or layer.  out: a caller's uint64 buffer; when it is too small the VxError
+        (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
+        pr = np.ascontiguousarray(proof, dtype=np.uint64)
+        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
+        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_inner_proof_bound(c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), need),
+                                "stark inner: not a proof of a known AIR under this configuration, its head is not acceptable, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)",
+                                lambda c, o, need: self.L.vx_stark_inner_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

@@ -456,7 +456,7 @@ int32_t vx_fri_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, 
  *   no sibling: the siblings are dead weight in a proof verified this way.  The statement digest costs about as many permutations as
  *   hashing the rows would; what disappears is everything per tree level.
  * The query arithmetic on this same bus: vx_stark_queries_prove (below), where FriCombineAir / FriFoldAir take the verifier's place.
- * STILL OUTSIDE: the constraint identity at zeta and the transcript. */
+ * STILL OUTSIDE: the constraint identity at zeta; the transcript joins this bus in vx_stark_inner_prove (below). */
 int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t shape_out[7], size_t* n_trees,
                                uint64_t cap_tree_out[11], uint64_t* caps_out, size_t caps_cap, size_t* n_claims, uint64_t* tree_out, uint64_t* index_out, uint64_t* leaf_len_out,
                                size_t claims_cap, size_t* leaves_len, uint64_t* leaves_out, size_t leaves_cap, size_t* siblings_len, uint64_t* siblings_out, size_t siblings_cap,
@@ -568,8 +568,8 @@ int32_t vx_leaf_noop_air_trace(vx_ctx* ctx, const uint64_t* tree_of, const uint6
  *   query one exponentiation and one Horner evaluation remain; the query records (over 90 % of a proof) are dead weight.
  * vx_stark_proof_head_words: where the query records of a proof start -- the length of the head vx_stark_queries_verify accepts --
  *   from the proof's header and the configuration alone; nothing is verified.
- * STILL OUTSIDE: the transcript (proven on a bus of its own by vx_stark_transcripts_prove below; joining the two groups is not built),
- * the constraint identity at zeta and the final-polynomial evaluation. */
+ * STILL OUTSIDE here: the transcript (vx_stark_inner_prove below puts TranscriptAir on this same bus), the constraint identity at
+ * zeta and the final-polynomial evaluation. */
 int32_t vx_stark_proof_head_words(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* head_words);
 int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words);
 int32_t vx_stark_queries_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t* blob_out, size_t blob_cap,
@@ -601,7 +601,8 @@ int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob
  *   Poseidon permutation runs for an inner transcript; proof of work, query indices, the constraint identity at zeta and (for a whole
  *   proof) the walked query phase use the claimed values; a head alone is read query-free.  Then it is the outside party of the bus:
  *   per chain it SENDS obs(c, i, w_i) for the words it absorbed and RECEIVES chal(c, j, A_j, v_j).  Error texts name the chain.
- * Stand-alone this does not lower the verifier's permutation count: the statement digest hashes the same words. */
+ * Stand-alone this does not lower the verifier's permutation count: the statement digest hashes the same words; on the
+ * bus of the query phase (vx_stark_inner_prove below) it does. */
 enum { VX_AIR_TRANSCRIPT = 23, VX_TRANSCRIPT_AIR_COLS = 93, VX_TRANSCRIPT_AIR_AUX_COLS = 18, VX_TRANSCRIPT_MAX_CHAINS = 64 };
 int32_t vx_transcript_air_trace(vx_ctx* ctx, size_t n_chains, const size_t* n_ops, const uint64_t* ops, const uint64_t* words, size_t n_words, int log_n, vx_buf* trace_out,
                                 uint64_t public_out[4], uint64_t* chal_out);
@@ -612,6 +613,30 @@ int32_t vx_stark_transcripts_prove(vx_ctx* ctx, const vx_stark_config* cfg, cons
                                    uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* const* proofs, const size_t* lens, size_t n,
                                     const uint64_t* const* ext_chals, char* err, size_t errlen);
+/* ---- An inner proof's query phase AND transcript on ONE bus (csrc/vx_stark_inner.hip): the tables of
+ * vx_stark_queries_prove in their order, then TranscriptAir with one chain (id 0) -- six to eight tables.  The tags of the two halves
+ * do not meet.  Argument conventions as vx_stark_queries_*; the bound takes ext_chal because the transcript's block count depends on it.
+ * vx_stark_inner_prove: claims and chain come from ONE replay of the verifier's code over the recording challenger; the native checks
+ *   and the refusals are those of vx_stark_queries_prove (texts under "stark inner:").  The four digest words of every table are ONE
+ *   statement digest: hash_n_to_hash_no_pad(the 7 shape words, n_obs, n_chal, the observed words in order, (absorbed, value) of every
+ *   challenge in order) -- alpha, zeta, betas and indices are claimed challenges, the openings, the final polynomial and the caps are
+ *   observed words: nothing is hashed twice.
+ *   Blob: "VXSINR01", the 7 shape words, the table count, n_obs, n_chal, the n_chal claimed challenges as (absorbed, value), one
+ *   length per table, the proofs in bus order.
+ * vx_stark_inner_verify (host only): `proof` is the whole inner proof or its head alone, any other length is refused.  The claims are
+ *   parsed as vx_stark_transcripts_verify does; the inner proof is verified QUERY-FREE with its transcript answered from the claims --
+ *   NO Poseidon permutation runs for the inner transcript, the only hashing of the head is the statement digest; proof of work, the
+ *   constraint identity at zeta, reduce_openings and the indices (value mod N) use the claimed values.  It rebuilds every public input
+ *   of every table from the head, the claims and the digest, and is the outside party of both halves: per query it RECEIVES
+ *   root(tree, lo / hi) for every tree of the record and fri(index, final_poly(x_NL), 1); it SENDS obs(0, i, w_i) for every observed
+ *   word and RECEIVES chal(0, j, A_j, v_j).
+ * STILL OUTSIDE: the constraint identity at zeta (next: it receives alpha and zeta from the transcript table on this bus), the index
+ * and proof-of-work checks, the final-polynomial evaluation, more than one inner proof per group. */
+int32_t vx_stark_inner_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, size_t* n_words);
+int32_t vx_stark_inner_prove(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, uint64_t* blob_out, size_t blob_cap,
+                             size_t* blob_len);
+int32_t vx_stark_inner_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* proof, size_t proof_len, int expect_air,
+                              const uint64_t* expect_public, size_t n_public, const uint64_t* ext_chal, char* err, size_t errlen);
 /* ---- A generic bus group: ANY tables on one logUp bus, proven together under shared lookup challenges (csrc/vx_bus_group.hip; the
  * verifier in csrc/vx_verify.hip).  What the fixed group provers above are for their lists of tables, for a list the caller states:
  * compiled tables, run-time tables (vx_air_register_bus), or both.  The traces exist already (the *_air_trace entry points, or the
