@@ -14,6 +14,7 @@
 #include "bus_meet.h"
 #include "glh_poseidon.h"
 #include "vx_internal.h"
+#include "vx_table_shapes.h"
 
 // the hook of a table that is alone on its bus (the other party is the verifier): the lookup challenges are the shared-challenge
 // transcript of this one table's (public inputs, trace cap); `party` is unused
@@ -156,12 +157,14 @@ int32_t vx_fri_fold_trace_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, s
 int32_t vx_fri_fold_check_dev(vx_ctx* ctx, int log_lde, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index, const uint64_t* ev0,
                               const uint64_t* leaves, size_t n_queries);
 
-// ---- STARK-openings blob (written by vx_stark_openings_prove in vx_stark_openings.hip, read by vx_stark_openings_verify in
+// ---- STARK-openings blob (written by vx_stark_openings_prove in vx_stark_groups.hip, read by vx_stark_openings_verify in
 // vx_verify.hip): magic, the shape words of the inner proof (log_lde, cm, ca, arity_bits, fold layers, cap_height, queries), the
-// number of tables, one length per table, the proofs: MerkleOpenSetAir, then one LeafSpongeSetAir per leaf length above 4
+// number of tables, one length per table, the proofs in bus order (stark_openings_tables, vx_table_shapes.h)
 static const uint64_t VX_SOPEN_MAGIC = 0x314e45504f535856ULL;  // "VXSOPEN1"
 static constexpr size_t VX_SOPEN_HDR = 9;                       // before the lengths
 static constexpr uint64_t VX_SOPEN_TREE0 = 8;                   // main / auxiliary / quotient = TREE0 + 0 / 1 / 2; layer l = l
+// the two-to-one fold of a cap of canonical words down to one digest: the root the openings table proves paths to
+void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]);
 // The Merkle side of a vx_stark_prove proof as claims: one per (query, tree), queries outermost in proof order, inside a query the
 // order of the query record -- main, auxiliary (ca > 0), quotient, layers 0..NL-1.  Filled by the verifier's own query phase
 // (vx_verify.hip) whenever it has a sink (StarkQueries below).
@@ -180,9 +183,13 @@ struct StarkOpenings {
     std::vector<uint64_t> leaves;
     int log_leaves(uint64_t t) const { return t >= VX_SOPEN_TREE0 ? LN : LN - a * ((int)t + 1); }
     std::array<uint64_t, 7> shape_words() const { return {{(uint64_t)LN, cm, ca, (uint64_t)a, NL, (uint64_t)cap_h, n_queries}}; }
+    // the folded root of every tree, [tree.size()][4] in record order: what prover and verifier both call "the roots"
+    std::vector<uint64_t> roots() const {
+        std::vector<uint64_t> r(4 * tree.size());
+        for (size_t k = 0; k < tree.size(); ++k) vx_cap_fold(caps.data() + k * ((size_t)4 << cap_h), cap_h, r.data() + 4 * k);
+        return r;
+    }
 };
-// the two-to-one fold of a cap of canonical words down to one digest: the root the openings table proves paths to
-void vx_cap_fold(const uint64_t* cap, int cap_height, uint64_t root[4]);
 // the statement of a proof's openings, the four digest words of every table: hash_n_to_hash_no_pad(the shape words, the folded
 // root of every tree in record order, per query the index and the leaf words of every tree in record order).  roots: [tree.size()][4]
 void vx_stark_openings_statement(const StarkOpenings& so, const uint64_t* roots, uint64_t digest[4]);
@@ -265,9 +272,9 @@ int32_t vx_fri_combine_host(vx_ctx* ctx, const FriCombineStmt& st, const uint64_
 void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* betas, size_t n_layers, const uint64_t* final_poly, size_t final_len, const uint64_t* index,
                                    const uint64_t* rows, const uint64_t* leaves, size_t n_queries, uint64_t digest[4]);
 
-// ---- STARK-queries blob (written by vx_stark_queries_prove in vx_stark_queries.hip, read by vx_stark_queries_verify in
+// ---- STARK-queries blob (written by vx_stark_queries_prove in vx_stark_groups.hip, read by vx_stark_queries_verify in
 // vx_verify.hip): magic, the 7 shape words of the inner proof (as VXSOPEN1), the number of tables, one length per table, the proofs
-// in bus order: MerkleOpenSetAir, one LeafSpongeSetAir per leaf length above 4, LeafNoopAir, FriCombineAir, FriFoldAir
+// in bus order (stark_queries_tables, vx_table_shapes.h)
 static const uint64_t VX_SQRY_MAGIC = 0x3130595251535856ULL;  // "VXSQRY01"
 static constexpr size_t VX_SQRY_HDR = 9;                      // before the lengths
 // What the verifier's query phase does with the openings of a proof.  Walked: it walks every path itself (vx_stark_verify).
@@ -302,22 +309,22 @@ int32_t vx_stark_openings_claims(const vx_stark_config* cfg, const uint64_t* pro
 // every query).  No row word and no leaf word: they are in committed traces.  roots: [so.tree.size()][4]
 void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, uint64_t digest[4]);
 
-// The Merkle side of the two proof-sourced group provers (vx_stark_openings_prove, vx_stark_queries_prove; defined in
-// vx_stark_openings.hip): everything their tables read, gathered from the claims and the proof that carries the paths.  It holds
-// pool blocks of `ctx` until the group has proven, so it is declared before the TableGroup.
+// The Merkle side of the proof-sourced group prover (every level; defined in vx_stark_groups.hip): everything its first
+// 1 + n_sponge tables read, gathered from the claims and the proof that carries the paths.  It holds pool blocks of `ctx` until the
+// group has proven, so it is declared before the TableGroup.
 struct StarkMerkleSide {
     static constexpr int N_TREE_IDS = (int)VX_SOPEN_TREE0 + 3;
     // sponge_len: the leaf lengths of the n_sponge (<= 3) sponge tables, in table order (vx_table_shapes.h)
-    StarkMerkleSide(vx_ctx* ctx, const char* prefix, const StarkOpenings& so, const uint64_t* proof, const size_t* sponge_len, int n_sponge);
+    StarkMerkleSide(vx_ctx* ctx, const char* what, const StarkOpenings& so, const uint64_t* proof, const size_t* sponge_len, int n_sponge);
     // the sponge chains of every leaf longer than 4 words, one launch per length (their digests enter the paths on the device),
-    // then every path walked once: "<prefix> query Q: the path of ... does not reach the root of its tree" (VX_ERR_STATEMENT) otherwise
+    // then every path walked once: "<what>: query Q: the path of ... does not reach the root of its tree" (VX_ERR_STATEMENT) otherwise
     int32_t launch();
-    // the openings table and the sponge tables as the next 1 + n_sponge tables of `g`, with log_n[k] rows (log2) and the statement
-    // digest in their public inputs (stmt outlives the group); returns the index of the openings table
-    int add_tables(TableGroup& g, const int* log_n, const uint64_t* stmt);
+    // the openings table and the sponge tables as the next 1 + n_sponge tables of `g`, with ts.log_n[k] rows (log2) and the public
+    // inputs of stark_table_public (ts, sq and stmt outlive the group); returns the index of the openings table
+    int add_tables(TableGroup& g, const StarkGroupTables& ts, const StarkQueries& sq, const uint64_t* stmt);
 
     vx_ctx* ctx;
-    const char* prefix;
+    const char* what;  // the group's name in messages
     const StarkOpenings& so;
     int n_sponge;
     size_t sponge_len[3] = {0, 0, 0};
@@ -331,8 +338,6 @@ struct StarkMerkleSide {
     std::vector<size_t> s_who[3];                                 // ... and which claims they are
     std::vector<uint64_t> n_tree, n_idx, n_len, n_rows;           // the openings of the leaves of at most 4 words, rows [.][4] (LeafNoopAir's)
 };
-// the blob of such a group: magic, the 7 shape words, the number of tables, one length per table, the proofs of g.job[0 .. n_tables)
-int32_t vx_stark_group_blob(TableGroup& g, int n_tables, uint64_t magic, const StarkOpenings& so, uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 
 // ---- STARK-transcripts blob (written by vx_stark_transcripts_prove in vx_transcript_air.hip, read by vx_stark_transcripts_verify in
 // vx_verify.hip): magic, the request -- n chains, then per chain n_obs, n_chal and the n_chal claimed challenges as (absorbed, value)
@@ -359,9 +364,9 @@ int32_t vx_transcript_trace_dev(vx_ctx* ctx, const glh::TranscriptRecord* chains
 // (the query phase is walked) or its head alone (the indices are derived, no record is read)
 int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen);
 
-// ---- STARK-inner blob (written by vx_stark_inner_prove in vx_stark_inner.hip, read by vx_stark_inner_verify in vx_verify.hip): magic,
+// ---- STARK-inner blob (written by vx_stark_inner_prove in vx_stark_groups.hip, read by vx_stark_inner_verify in vx_verify.hip): magic,
 // the 7 shape words of the inner proof (as VXSQRY01), the number of tables, n_obs, n_chal, the n_chal claimed challenges as
-// (absorbed, value), one length per table, the proofs in bus order: the tables of VXSQRY01, then TranscriptAir (one chain, id 0)
+// (absorbed, value), one length per table, the proofs in bus order (stark_inner_tables, vx_table_shapes.h)
 static const uint64_t VX_SINR_MAGIC = 0x3130524e49535856ULL;  // "VXSINR01"
 static constexpr size_t VX_SINR_HDR = 11;                     // before the claims
 // The ONE replay of the prover's side: the verifier's code over the recording challenger with the paths delegated -> the claims of
@@ -373,6 +378,50 @@ int32_t vx_stark_inner_replay(const vx_stark_config* cfg, const uint64_t* proof,
 // query-phase digest held is a function of these words: alpha, zeta, betas and indices are claimed challenges, the openings, the
 // final polynomial and the caps (hence the folded roots) are observed words.
 void vx_stark_inner_statement(const std::array<uint64_t, 7>& shape, const TranscriptClaim& chain, uint64_t digest[4]);
+
+// ---- The three proof-sourced groups as LEVELS of one group (StarkLevel, vx_table_shapes.h): what a level fixes besides its table
+// list, stated once for the one prover body (vx_stark_groups.hip) and the one verifier body (vx_verify.hip).
+struct StarkLevelInfo {
+    uint64_t magic;
+    size_t hdr;              // words before the claims (Inner) or the lengths
+    const char* name;        // "<name>: ..." in messages
+    const char* blob_name;   // "bad <blob_name> blob"
+    const char* no_group;    // the proof's shape has no group of this level
+    const char* unbalanced;  // the bus of the group does not close against the verifier's messages
+};
+static inline const StarkLevelInfo& stark_level(StarkLevel level) {
+    static const StarkLevelInfo LEVELS[3] = {
+        {VX_SOPEN_MAGIC, VX_SOPEN_HDR, "stark openings", "stark-openings",
+         "stark openings: the proof's shape has no openings group (cap height above 16, a tree without a level, or a table of more than 2^26 rows)",
+         "the openings the tables prove are not the ones of this proof (the lookup bus does not balance)"},
+        {VX_SQRY_MAGIC, VX_SQRY_HDR, "stark queries", "stark-queries",
+         "stark queries: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)",
+         "the query phase the tables prove is not the one of this proof (the lookup bus does not balance)"},
+        {VX_SINR_MAGIC, VX_SINR_HDR, "stark inner", "stark-inner",
+         "stark inner: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)",
+         "the query phase and the transcript the tables prove are not the ones of this proof and these claims (the lookup bus does not balance)"},
+    };
+    return LEVELS[(int)level];
+}
+// The request words of a level's blob, between the magic and the per-table lengths, for the writer (pack_blob) and the reader
+// (read_blob): the 7 shape words and the table count; Inner: then n_obs, n_chal and the claims of its one chain.
+static inline std::vector<uint64_t> stark_group_request(StarkLevel level, const StarkOpenings& so, int n_tables, const TranscriptClaim& chain) {
+    const std::array<uint64_t, 7> sw = so.shape_words();
+    std::vector<uint64_t> r(sw.begin(), sw.end());
+    r.push_back((uint64_t)n_tables);
+    if (level == StarkLevel::Inner) {
+        r.push_back(chain.n_obs), r.push_back(chain.n_chal);
+        r.insert(r.end(), chain.chal, chain.chal + 2 * chain.n_chal);
+    }
+    return r;
+}
+// The statement digest of a level, the four digest words of every table (the three functions above: their word lists are protocol).
+// roots: so.roots(); chain: Inner only.
+void stark_group_statement(StarkLevel level, const StarkQueries& sq, const uint64_t* roots, const TranscriptClaim& chain, uint64_t digest[4]);
+// The public inputs of table k of a group, prover (after its trace) and verifier (what it expects) alike: writes them to `pub` and
+// returns their count, at most VX_STARK_TABLE_MAX_PUB.
+static constexpr size_t VX_STARK_TABLE_MAX_PUB = 24;
+size_t stark_table_public(const StarkGroupTables& ts, int k, const StarkQueries& sq, const uint64_t stmt[4], uint64_t* pub);
 
 // ---- bus-group blob (written by vx_bus_group_prove in vx_bus_group.hip, read by vx_bus_group_verify in vx_verify.hip): magic, the
 // number of tables, one length per proof, the proofs in bus order.  No AIR id: registered ids are per process, the verifier states its own.

@@ -81,9 +81,10 @@ static inline int leaf_noop_log_n(size_t n_idx) {
 // The tables of such a group: the openings table, n_sponge sponge tables and, in the query-phase group, three more; the inner-proof
 // group (stark_inner_tables below) has the transcript table behind them.
 struct StarkGroupTables {
+    static constexpr int MAX = 8, MAX_SPONGE = 3;  // Inner with three leaf lengths above 4
     int n = 0, n_sponge = 0;
-    int air[8], log_n[8];
-    size_t leaf_len[8];  // of the sponge tables, 0 elsewhere
+    int air[MAX], log_n[MAX];
+    size_t leaf_len[MAX];  // of the sponge tables, 0 elsewhere
     size_t noop_per_query = 0;  // query-phase group
 };
 static inline bool stark_openings_tables(int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, StarkGroupTables* t) {
@@ -157,4 +158,13 @@ static inline bool stark_inner_tables(int LN, size_t cm, size_t ca, int a, size_
     if (log_n > 26) return false;
     t->air[t->n] = VX_AIR_TRANSCRIPT, t->log_n[t->n] = log_n, t->leaf_len[t->n] = 0, ++t->n;
     return true;
+}
+// The three groups nest, and so do their table lists: a LEVEL names how much of a proof one bus proves.  Everything else a level
+// fixes -- magic, header, names, refusal texts -- is stark_level in vx_bus.h; callers reach the lists above through here.  `blocks`:
+// the duplexes of the transcript chain (Inner; the verifier states 0: it reads a table's rows from its proof).
+enum class StarkLevel { Openings, Queries, Inner };
+static inline bool stark_level_tables(StarkLevel level, int LN, size_t cm, size_t ca, int a, size_t NL, size_t n_queries, size_t blocks, const vx_stark_config& cfg, StarkGroupTables* t) {
+    return level == StarkLevel::Openings  ? stark_openings_tables(LN, cm, ca, a, NL, n_queries, t)
+           : level == StarkLevel::Queries ? stark_queries_tables(LN, cm, ca, a, NL, n_queries, cfg, t)
+                                          : stark_inner_tables(LN, cm, ca, a, NL, n_queries, blocks, cfg, t);
 }

@@ -17,6 +17,7 @@
 #include <memory>
 #include <mutex>
 #include <optional>
+#include <string>
 
 #include <array>
 
@@ -1112,81 +1113,50 @@ int32_t vx_stark_merkle_claims(const vx_stark_config* cfg, const uint64_t* proof
     return VX_OK;
 }
 
-// What vx_stark_openings_prove / vx_stark_queries_prove write for this inner proof at most: read from the proof's head alone (AIR id
-// and degree bits -> the columns of the three trees, the fold layers), nothing is verified.
-static int32_t stark_group_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, bool queries, size_t* n_words) {
-    if (!cfg || !proof || !n_words || !sp::config_ok(*cfg)) return VX_ERR_ARG;
+// What the prover of a level (vx_stark_groups.hip) writes for this inner proof.  Openings and Queries: AT MOST -- read from the
+// proof's head alone (AIR id and degree bits -> the columns of the three trees, the fold layers), nothing is verified, every table
+// at its bound_words().  Inner: TO THE WORD -- the transcript table's rows and the claims need the block count, so the head is
+// replayed (no query record is read), and a table's proof has the one length its AIR, its rows and the configuration imply
+// (Shape::words()).  Callers see the difference (the `needed` of a refused buffer); the two numbers are not unified.
+static int32_t stark_group_proof_bound(StarkLevel level, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, size_t* n_words) {
+    if (!cfg || !proof || !n_words) return VX_ERR_ARG;
+    const StarkLevelInfo& lv = stark_level(level);
+    StarkGroupTables ts;
+    if (level == StarkLevel::Inner) {
+        size_t head = 0;
+        if (vx_stark_proof_head_words(cfg, proof, proof_len, &head) != VX_OK || proof_len < head) return VX_ERR_ARG;
+        StarkQueries sq;
+        glh::TranscriptRecord rec;
+        if (vx_stark_inner_replay(cfg, proof, head, ext_chal, true, &sq, &rec, nullptr, 0) != VX_OK) return VX_ERR_ARG;
+        const StarkOpenings& so = sq.so;
+        if (so.cap_h > 16 || !stark_level_tables(level, so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, rec.n_blocks(), *cfg, &ts)) return VX_ERR_ARG;
+        size_t total = lv.hdr + rec.chal.size() + (size_t)ts.n;
+        for (int k = 0; k < ts.n; ++k) {
+            BusAirShape a;
+            if (!vx_air_bus_shape(ts.air[k], &a)) return VX_ERR_ARG;
+            total += sp::Shape(ts.air[k], a.cols, a.aux, a.pub, a.auxpub, ts.log_n[k], *cfg).words();
+        }
+        *n_words = total;
+        return VX_OK;
+    }
+    if (!sp::config_ok(*cfg)) return VX_ERR_ARG;
     ProofHead head;
     if (proof_head(*cfg, proof, proof_len, 0, &head, nullptr, 0) != VX_OK) return VX_ERR_ARG;
     const sp::Shape& shape = *head.shape;
-    const size_t NL = shape.arities.size(), n_q = (size_t)shape.num_queries;
-    StarkGroupTables ts;
     if (shape.LN < shape.cap_h || shape.cap_h > 16) return VX_ERR_ARG;
-    if (!(queries ? stark_queries_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, NL, n_q, *cfg, &ts) : stark_openings_tables(shape.LN, shape.cm, shape.ca, cfg->arity_bits, NL, n_q, &ts)))
-        return VX_ERR_ARG;
-    TableShape sh[7];
+    if (!stark_level_tables(level, shape.LN, shape.cm, shape.ca, cfg->arity_bits, shape.arities.size(), (size_t)shape.num_queries, 0, *cfg, &ts)) return VX_ERR_ARG;
+    TableShape sh[StarkGroupTables::MAX];
     for (int k = 0; k < ts.n; ++k) sh[k] = {ts.air[k], ts.log_n[k]};
-    return vx_tables_proof_bound(cfg, (queries ? VX_SQRY_HDR : VX_SOPEN_HDR) + (size_t)ts.n, sh, (size_t)ts.n, n_words);
+    return vx_tables_proof_bound(cfg, lv.hdr + (size_t)ts.n, sh, (size_t)ts.n, n_words);
 }
 int32_t vx_stark_openings_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
-    return stark_group_proof_bound(cfg, proof, proof_len, false, n_words);
+    return stark_group_proof_bound(StarkLevel::Openings, cfg, proof, proof_len, nullptr, n_words);
 }
 int32_t vx_stark_queries_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, size_t* n_words) {
-    return stark_group_proof_bound(cfg, proof, proof_len, true, n_words);
+    return stark_group_proof_bound(StarkLevel::Queries, cfg, proof, proof_len, nullptr, n_words);
 }
-
-// STARK openings (the prover is vx_stark_openings.hip): the Merkle side of one inner vx_stark_prove proof on one bus -- the
-// openings table (MerkleOpenSetAir, one path per (query, tree)) and one LeafSpongeSetAir table per leaf length above 4, which
-// receive the openings of their trees (TAG_OPEN closes between them).  The inner proof is verified here in the delegated mode:
-// every check except the paths.  The verifier is the outside party: per (query, tree) it receives the root the path ended in with
-// the tree's depth -- the tables do not know which root belongs to which tree, the verifier does (vx_cap_fold of the proof's cap)
-// --, every word of a row longer than 4 words, and the opening itself of a row that is its own digest:
-//     sum over the tables of total x rows = sum over the claims of 1 / D_root(tree, lo) + 1 / D_root(tree, hi)
-//         + [leaf_len > 4] sum over j of 1 / D_row(tree, index, j, word_j)  +  [leaf_len <= 4] (1 / D_open(lo) + 1 / D_open(hi)).
-// EVERY public input of every table is rebuilt from the inner proof (the digest words are the statement digest, vx_bus.h).
-// No path is walked, no leaf hashed, no sibling read; the statement digest costs about what hashing the rows would.
-int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
-                                 size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
-    if (!cfg || !blob || !proof) return VX_ERR_ARG;
-    StarkQueries sq;
-    VX_TRY(vx_stark_openings_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, &sq, err, errlen));
-    const StarkOpenings& so = sq.so;
-    StarkGroupTables ts;
-    NEED(stark_openings_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, &ts), "stark openings: the proof's shape has no openings group (a tree without a level, or a table of more than 2^26 rows)");
-    NEED(so.cap_h <= 16, "stark openings: cap height %d (at most 16)", so.cap_h);
-    BusTable tab[4];
-    const std::array<uint64_t, 7> sw = so.shape_words();
-    VX_TRY(read_blob(blob, len, VX_SOPEN_MAGIC, "stark-openings", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen));
-    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
-    const size_t n_trees = so.tree.size();
-    std::vector<uint64_t> roots(4 * n_trees);
-    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
-    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB];
-    vx_stark_openings_statement(so, roots.data(), stmt);
-    vx_merkle_open_set_public(stmt, opub);
-    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
-    for (int k = 1; k < ts.n; ++k) {
-        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
-        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
-    }
-    return verify_bus_group(cfg, tab, (size_t)ts.n, "the openings the tables prove are not the ones of this proof (the lookup bus does not balance)", err, errlen,
-                            [&](const VBus& bus, BusMessages& m) {
-                                m.reserve(2 * so.claims.size() + so.leaves.size());
-                                for (size_t i = 0; i < so.claims.size(); ++i) {
-                                    const StarkOpenings::Claim& c = so.claims[i];
-                                    const uint64_t* leaf = so.leaves.data() + c.leaf;
-                                    const Fx tree{c.tree, 0}, idx{c.index, 0};
-                                    m.receive_root(bus, c.tree, roots.data() + 4 * (i % n_trees), so.log_leaves(c.tree));
-                                    if (c.leaf_len > 4) {
-                                        for (size_t j = 0; j < c.leaf_len; ++j) m.receive(bus.row_of(tree, idx, Fx{(uint64_t)j, 0}, Fx{leaf[j], 0}));
-                                    } else {
-                                        uint64_t d[4] = {0, 0, 0, 0};
-                                        memcpy(d, leaf, c.leaf_len * 8);
-                                        m.receive(bus.open_of(tree, idx, Fx{d[0], 0}, Fx{d[1], 0}, bus::K<0>{}));
-                                        m.receive(bus.open_of(tree, idx, Fx{d[2], 0}, Fx{d[3], 0}, bus::K<1>{}));
-                                    }
-                                }
-                            });
+int32_t vx_stark_inner_proof_bound(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, const uint64_t* ext_chal, size_t* n_words) {
+    return stark_group_proof_bound(StarkLevel::Inner, cfg, proof, proof_len, ext_chal, n_words);
 }
 
 // FRI combine (the prover is vx_fri_combine_air.hip), the fourth aggregation verifier: the claims are what a STARK verifier holds
@@ -1315,57 +1285,42 @@ void vx_stark_queries_statement(const StarkQueries& sq, const uint64_t* roots, u
     glh::hash_no_pad(w.data(), w.size(), digest);
 }
 
-extern "C" {
-// The whole query phase of a proof (the prover is vx_stark_queries.hip): MerkleOpenSetAir, the sponge tables, LeafNoopAir,
-// FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0) on one bus.  TAG_OPEN closes between the openings and the leaf tables,
-// TAG_ROW between the leaf tables and the arithmetic, TAG_FRI end 0 between combination and fold.  The inner proof is verified in
-// the QUERY-FREE mode: transcript, proof of work, the constraint identity at zeta, reduce_openings and the query indices, from the
-// head of the proof alone -- it may be handed over whole or without its query records.  The verifier is the outside party: per query
-// it receives root(tree, lo / hi) with the tree's depth for every tree of the record and fri(index, final_poly(x_NL), 1), and sends
-// nothing:
-//     sum over the tables of total x rows = sum over the queries of sum over the trees (1 / D_root(lo) + 1 / D_root(hi)) + 1 / D_fri(exit).
-// EVERY public input of every table is rebuilt from the head; per query one exponentiation and one Horner evaluation remain.
-int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
-                                size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
-    if (!cfg || !blob || !proof) return VX_ERR_ARG;
-    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "stark queries: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
-    StarkQueries sq;
-    VX_TRY(vx_stark_queries_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, QueryPhase::QueryFree, &sq, err, errlen));
-    const StarkOpenings& so = sq.so;
-    StarkGroupTables ts;
-    if (so.cap_h > 16 || !stark_queries_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, *cfg, &ts))
-        return v_fail(VX_ERR_ARG, err, errlen, "stark queries: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
-    BusTable tab[7];
-    const std::array<uint64_t, 7> sw = so.shape_words();
-    VX_TRY(read_blob(blob, len, VX_SQRY_MAGIC, "stark-queries", {sw[0], sw[1], sw[2], sw[3], sw[4], sw[5], sw[6], (uint64_t)ts.n}, tab, (size_t)ts.n, err, errlen));
-    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
-    const size_t n_trees = so.tree.size(), final_len = sq.final_poly.size() / 2;
-    std::vector<uint64_t> roots(4 * n_trees);
-    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
-    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB], npub[lnp::PUB], cpub[fca::PUB], fpub[ffa::PUB];
-    vx_stark_queries_statement(sq, roots.data(), stmt);
-    vx_merkle_open_set_public(stmt, opub);
-    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
-    int k = 1;
-    for (; k <= ts.n_sponge; ++k) {
-        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
-        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
+// ---- a proof under a CLAIMED transcript, for the verifiers of TranscriptAir's chains (vx_stark_transcripts_verify: one per proof;
+// stark_group_verify at Inner: the one chain 0).  `prefix` opens every message ("chain 3: " or "").
+using ClaimedTranscript = sp::TranscriptOf<glh::ClaimedChallenger>;
+static std::string chain_prefix(size_t c) { return "chain " + std::to_string(c) + ": "; }
+// the claims of a chain as the blob states them: canonical values, each drawn after at most n_obs words
+static int32_t transcript_claims_ok(const TranscriptClaim& claim, const char* prefix, char* err, size_t errlen) {
+    for (size_t j = 0; j < claim.n_chal; ++j) {
+        NEED(claim.chal[2 * j + 1] < glh::P, "%sclaimed challenge %zu is not canonical", prefix, j);
+        NEED(claim.chal[2 * j] <= claim.n_obs, "%schallenge %zu claims %llu absorbed words of %zu", prefix, j, (unsigned long long)claim.chal[2 * j], claim.n_obs);
     }
-    vx_leaf_noop_public(stmt, npub);
-    tab[k].expect(VX_AIR_LEAF_NOOP, npub, lnp::PUB), ++k;
-    vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, cpub);
-    tab[k].expect(VX_AIR_FRI_COMBINE, cpub, fca::PUB), ++k;
-    vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, fpub);
-    tab[k].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB);
-    return verify_bus_group(cfg, tab, (size_t)ts.n, "the query phase the tables prove is not the one of this proof (the lookup bus does not balance)", err, errlen,
-                            [&](const VBus& bus, BusMessages& m) {
-                                m.reserve(so.n_queries * (2 * n_trees + 1));
-                                for (size_t i = 0; i < so.n_queries; ++i) {
-                                    for (size_t t = 0; t < n_trees; ++t) m.receive_root(bus, so.tree[t], roots.data() + 4 * t, so.log_leaves(so.tree[t]));
-                                    m.receive_exit(bus, so.index[i], so.LN, so.NL, sq.final_poly.data(), final_len);
-                                }
-                            });
+    return VX_OK;
 }
+// The verifier's own code over the claimed challenger `ch`, which hashes nothing: every challenge is the blob's claim, every absorbed
+// word is noted.  Then the claims against what the run did: as many as the shape draws, each drawn after as many words as the blob
+// says.  Leaves claim->words at the absorbed words (they live in `ch`).  A head alone is read query-free whatever `mode` says.
+static int32_t claimed_transcript_check(TranscriptClaim* claim, const char* prefix, ClaimedTranscript& ch, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int expect_air,
+                                        const uint64_t* expect_public, size_t n_expect_public, const uint64_t* ext_chal, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
+    ch.claims = claim->chal, ch.n_claims = claim->n_chal;
+    char inner[200] = "";
+    const int32_t rc = stark_verify_over(ch, true, cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, mode, sink, inner, sizeof inner);
+    // what the claims got wrong comes first: a run on too few claims was answered with zeros
+    NEED(!ch.short_of, "%sthe blob claims %zu challenges, the proof's shape draws more", prefix, claim->n_chal);
+    if (rc != VX_OK) return v_fail(rc, err, errlen, "%s%s", prefix, inner);
+    NEED(ch.next == claim->n_chal, "%sthe blob claims %zu challenges, the proof's shape draws %zu", prefix, claim->n_chal, ch.next);
+    NEED(ch.words.size() == claim->n_obs, "%sthe blob claims %zu absorbed words, the proof's shape absorbs %zu", prefix, claim->n_obs, ch.words.size());
+    for (size_t j = 0; j < claim->n_chal; ++j)
+        NEED(claim->chal[2 * j] == ch.absorbed[j], "%schallenge %zu is claimed after %llu absorbed words, the proof's shape draws it after %llu", prefix, j,
+             (unsigned long long)claim->chal[2 * j], (unsigned long long)ch.absorbed[j]);
+    claim->words = ch.words.data();
+    return VX_OK;
+}
+// what the outside party says about chain `c`: it SENDS obs(c, i, w_i) for every observed word and RECEIVES chal(c, j, A_j, v_j)
+static void transcript_messages(const VBus& bus, BusMessages& m, size_t c, const TranscriptClaim& claim) {
+    const Fx chain{(uint64_t)c, 0};
+    for (size_t i = 0; i < claim.n_obs; ++i) m.send(bus.obs(chain, Fx{(uint64_t)i, 0}, Fx{claim.words[i], 0}));
+    for (size_t j = 0; j < claim.n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claim.chal[2 * j], 0}, Fx{claim.chal[2 * j + 1], 0}));
 }
 
 extern "C" {
@@ -1417,28 +1372,16 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
         NEED(len - at >= 2 && blob[at + 1] <= (len - at - 2) / 2, "blob truncated (the claims of chain %zu)", c);
         claims[c] = {nullptr, (size_t)blob[at], blob + at + 2, (size_t)blob[at + 1]};
         at += 2 + 2 * claims[c].n_chal;
-        for (size_t j = 0; j < claims[c].n_chal; ++j) {
-            NEED(claims[c].chal[2 * j + 1] < glh::P, "chain %zu: claimed challenge %zu is not canonical", c, j);
-            NEED(claims[c].chal[2 * j] <= claims[c].n_obs, "chain %zu: challenge %zu claims %llu absorbed words of %zu", c, j, (unsigned long long)claims[c].chal[2 * j], claims[c].n_obs);
-        }
+        VX_TRY(transcript_claims_ok(claims[c], chain_prefix(c).c_str(), err, errlen));
     }
     const size_t n_request = at - 1;
-    // ---- every inner proof under its claimed transcript
-    std::vector<sp::TranscriptOf<glh::ClaimedChallenger>> ch(n);
+    // ---- every inner proof under its claimed transcript (the claims of EVERY chain were read first: a bad claim of a later chain
+    // is reported before an earlier proof's own failure)
+    std::vector<ClaimedTranscript> ch(n);
     for (size_t c = 0; c < n; ++c) {
         if (!proofs[c]) return VX_ERR_ARG;
-        ch[c].claims = claims[c].chal, ch[c].n_claims = claims[c].n_chal;
-        char inner[200] = "";
-        const int32_t rc = stark_verify_over(ch[c], true, cfg, proofs[c], lens[c], 0, nullptr, 0, ext_chals ? ext_chals[c] : nullptr, nullptr, nullptr, QueryPhase::Walked, nullptr, inner, sizeof inner);
-        // what the claims got wrong comes first: a run on too few claims was answered with zeros
-        NEED(!ch[c].short_of, "chain %zu: the blob claims %zu challenges, the proof's shape draws more", c, claims[c].n_chal);
-        if (rc != VX_OK) return v_fail(rc, err, errlen, "chain %zu: %s", c, inner);
-        NEED(ch[c].next == claims[c].n_chal, "chain %zu: the blob claims %zu challenges, the proof's shape draws %zu", c, claims[c].n_chal, ch[c].next);
-        NEED(ch[c].words.size() == claims[c].n_obs, "chain %zu: the blob claims %zu absorbed words, the proof's shape absorbs %zu", c, claims[c].n_obs, ch[c].words.size());
-        for (size_t j = 0; j < claims[c].n_chal; ++j)
-            NEED(claims[c].chal[2 * j] == ch[c].absorbed[j], "chain %zu: challenge %zu is claimed after %llu absorbed words, the proof's shape draws it after %llu", c, j,
-                 (unsigned long long)claims[c].chal[2 * j], (unsigned long long)ch[c].absorbed[j]);
-        claims[c].words = ch[c].words.data();
+        VX_TRY(claimed_transcript_check(&claims[c], chain_prefix(c).c_str(), ch[c], cfg, proofs[c], lens[c], 0, nullptr, 0, ext_chals ? ext_chals[c] : nullptr, QueryPhase::Walked, nullptr, err,
+                                        errlen));
     }
     // ---- the table, and the verifier as the outside party of its bus
     BusTable tab[1];
@@ -1449,11 +1392,7 @@ int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* 
     vx_transcript_public(stmt, pub);
     tab[0].expect(VX_AIR_TRANSCRIPT, pub, tsc::PUB);
     return verify_bus_group(cfg, tab, 1, "the transcripts the table proves are not the claimed ones (the lookup bus does not balance)", err, errlen, [&](const VBus& bus, BusMessages& m) {
-        for (size_t c = 0; c < n; ++c) {
-            const Fx chain{(uint64_t)c, 0};
-            for (size_t i = 0; i < claims[c].n_obs; ++i) m.send(bus.obs(chain, Fx{(uint64_t)i, 0}, Fx{claims[c].words[i], 0}));
-            for (size_t j = 0; j < claims[c].n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claims[c].chal[2 * j], 0}, Fx{claims[c].chal[2 * j + 1], 0}));
-        }
+        for (size_t c = 0; c < n; ++c) transcript_messages(bus, m, c, claims[c]);
     });
 }
 }
@@ -1467,88 +1406,124 @@ void vx_stark_inner_statement(const std::array<uint64_t, 7>& shape, const Transc
     glh::hash_no_pad(w.data(), w.size(), digest);
 }
 
-extern "C" {
-// An inner proof's query phase AND transcript on one bus (the prover is vx_stark_inner.hip): the tables of vx_stark_queries_verify,
-// then TranscriptAir with the one chain 0.  The inner proof -- whole, or its head alone -- is verified QUERY-FREE over the CLAIMED
-// challenger: every challenge is the blob's claim, every absorbed word is noted, no Poseidon permutation runs for the inner
-// transcript.  Proof of work, the constraint identity at zeta, reduce_openings and the indices (value mod N) use the claimed values.
-// The verifier is the outside party of both halves: per query it RECEIVES root(tree, lo / hi) for every tree of the record and
-// fri(index, final_poly(x_NL), 1); it SENDS obs(0, i, w_i) for every observed word and RECEIVES chal(0, j, A_j, v_j):
-//     sum over the tables of total x rows = sum over the queries of sum over the trees (1 / D_root(lo) + 1 / D_root(hi)) + 1 / D_fri(exit)
-//                                           + sum_j 1 / D_chal(0, j, A_j, v_j) - sum_i 1 / D_obs(0, i, w_i).
-// EVERY public input of every table is rebuilt from the head, the claims and the ONE statement digest (vx_bus.h), the only hashing
-// of the head.  What forces what: DESIGN.md 5o.
-int32_t vx_stark_inner_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
-                              size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
-    if (!cfg || !blob || !proof) return VX_ERR_ARG;
-    if (sp::config_ok(*cfg) && cfg->arity_bits != 4) return v_fail(VX_ERR_ARG, err, errlen, "stark inner: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", cfg->arity_bits);
-    // ---- the claims inside the blob: bounds first, then canonical values drawn after at most n_obs words
-    NEED(len >= VX_SINR_HDR && blob[0] == VX_SINR_MAGIC, "bad stark-inner blob");
-    NEED(blob[10] <= (len - VX_SINR_HDR) / 2, "blob truncated (the claims)");
-    TranscriptClaim claim{nullptr, (size_t)blob[9], blob + VX_SINR_HDR, (size_t)blob[10]};
-    for (size_t j = 0; j < claim.n_chal; ++j) {
-        NEED(claim.chal[2 * j + 1] < glh::P, "claimed challenge %zu is not canonical", j);
-        NEED(claim.chal[2 * j] <= claim.n_obs, "challenge %zu claims %llu absorbed words of %zu", j, (unsigned long long)claim.chal[2 * j], claim.n_obs);
+// ---- the three proof-sourced groups (the prover is vx_stark_groups.hip), levels of ONE group: statement digest, public inputs and
+// verifier body are stated once, for every level
+void stark_group_statement(StarkLevel level, const StarkQueries& sq, const uint64_t* roots, const TranscriptClaim& chain, uint64_t digest[4]) {
+    if (level == StarkLevel::Openings) vx_stark_openings_statement(sq.so, roots, digest);
+    else if (level == StarkLevel::Queries) vx_stark_queries_statement(sq, roots, digest);
+    else vx_stark_inner_statement(sq.so.shape_words(), chain, digest);
+}
+static_assert(mop::SET_PUB <= VX_STARK_TABLE_MAX_PUB && lsp::PUB <= VX_STARK_TABLE_MAX_PUB && lnp::PUB <= VX_STARK_TABLE_MAX_PUB && fca::PUB <= VX_STARK_TABLE_MAX_PUB &&
+                  ffa::PUB <= VX_STARK_TABLE_MAX_PUB && tsc::PUB <= VX_STARK_TABLE_MAX_PUB,
+              "vx_bus.h: VX_STARK_TABLE_MAX_PUB is smaller than a table's public inputs");
+size_t stark_table_public(const StarkGroupTables& ts, int k, const StarkQueries& sq, const uint64_t stmt[4], uint64_t* pub) {
+    const StarkOpenings& so = sq.so;
+    switch (ts.air[k]) {
+        case VX_AIR_MERKLE_OPEN_SET: vx_merkle_open_set_public(stmt, pub); return mop::SET_PUB;
+        case VX_AIR_LEAF_SPONGE_SET: vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, pub); return lsp::PUB;
+        case VX_AIR_LEAF_NOOP: vx_leaf_noop_public(stmt, pub); return lnp::PUB;
+        case VX_AIR_FRI_COMBINE: vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, pub); return fca::PUB;
+        case VX_AIR_FRI_FOLD: vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, pub); return ffa::PUB;
+        default: vx_transcript_public(stmt, pub); return tsc::PUB;  // VX_AIR_TRANSCRIPT: the table lists hold no other AIR
     }
-    // ---- the inner proof under its claimed transcript, query-free
-    sp::TranscriptOf<glh::ClaimedChallenger> ch;
-    ch.claims = claim.chal, ch.n_claims = claim.n_chal;
+}
+
+// The ONE verifier body.  What a level's tables are: vx_table_shapes.h.  How the inner proof is replayed:
+//   Openings  delegated: every check except the paths (no path is walked, no leaf hashed, no sibling read);
+//   Queries   QUERY-FREE: transcript, proof of work, the constraint identity at zeta, reduce_openings and the query indices, from the
+//             head of the proof alone -- it may be handed over whole or without its query records;
+//   Inner     query-free over the CLAIMED challenger (claimed_transcript_check): no Poseidon permutation runs for the inner transcript.
+// The verifier is the party outside the tables.  Openings: per claim (query, tree) it receives the root the path ended in with the
+// tree's depth -- the tables do not know which root belongs to which tree, the verifier does --, every word of a row longer than 4
+// words, and the opening itself of a row that is its own digest:
+//     sum over the tables of total x rows = sum over the claims of 1 / D_root(tree, lo) + 1 / D_root(tree, hi)
+//         + [leaf_len > 4] sum over j of 1 / D_row(tree, index, j, word_j)  +  [leaf_len <= 4] (1 / D_open(lo) + 1 / D_open(hi)).
+// Queries and Inner: per query the roots of every tree of the record and the exit of the fold chain, fri(index, final_poly(x_NL), 1);
+// Inner adds the messages of chain 0 (transcript_messages):
+//     sum over the tables of total x rows = sum over the queries of sum over the trees (1 / D_root(lo) + 1 / D_root(hi)) + 1 / D_fri(exit)
+//                                           [+ sum_j 1 / D_chal(0, j, A_j, v_j) - sum_i 1 / D_obs(0, i, w_i)].
+// EVERY public input of every table is rebuilt from the inner proof (stark_table_public over the level's statement digest).  What
+// forces what: DESIGN.md 5k / 5l / 5o.
+static int32_t stark_group_verify(StarkLevel level, const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air,
+                                  const uint64_t* expect_public, size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    if (!cfg || !blob || !proof) return VX_ERR_ARG;
+    const StarkLevelInfo& lv = stark_level(level);
+    if (level != StarkLevel::Openings && sp::config_ok(*cfg) && cfg->arity_bits != 4)
+        return v_fail(VX_ERR_ARG, err, errlen, "%s: FriFoldAir is compiled for arity_bits 4 (16 values per leaf), the configuration says %d", lv.name, cfg->arity_bits);
+    // ---- the inner proof, replayed as the level says; Inner reads its claims from the blob first, bounds before values
     StarkQueries sq;
-    char inner[200] = "";
-    const int32_t rc = stark_verify_over(ch, true, cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, nullptr, nullptr, QueryPhase::QueryFree, &sq, inner, sizeof inner);
-    // what the claims got wrong comes first: a run on too few claims was answered with zeros
-    NEED(!ch.short_of, "the blob claims %zu challenges, the proof's shape draws more", claim.n_chal);
-    if (rc != VX_OK) return v_fail(rc, err, errlen, "%s", inner);
-    NEED(ch.next == claim.n_chal, "the blob claims %zu challenges, the proof's shape draws %zu", claim.n_chal, ch.next);
-    NEED(ch.words.size() == claim.n_obs, "the blob claims %zu absorbed words, the proof's shape absorbs %zu", claim.n_obs, ch.words.size());
-    for (size_t j = 0; j < claim.n_chal; ++j)
-        NEED(claim.chal[2 * j] == ch.absorbed[j], "challenge %zu is claimed after %llu absorbed words, the proof's shape draws it after %llu", j, (unsigned long long)claim.chal[2 * j],
-             (unsigned long long)ch.absorbed[j]);
-    claim.words = ch.words.data();
-    // ---- the tables: the blob must be for this shape and these claims.  The table list gives the count and the leaf lengths; every
+    TranscriptClaim claim{nullptr, 0, nullptr, 0};
+    ClaimedTranscript ch;
+    if (level == StarkLevel::Inner) {
+        NEED(len >= lv.hdr && blob[0] == lv.magic, "bad %s blob", lv.blob_name);
+        NEED(blob[10] <= (len - lv.hdr) / 2, "blob truncated (the claims)");
+        claim = {nullptr, (size_t)blob[9], blob + lv.hdr, (size_t)blob[10]};
+        VX_TRY(transcript_claims_ok(claim, "", err, errlen));
+        VX_TRY(claimed_transcript_check(&claim, "", ch, cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, QueryPhase::QueryFree, &sq, err, errlen));
+    } else if (level == StarkLevel::Queries) {
+        VX_TRY(vx_stark_queries_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, QueryPhase::QueryFree, &sq, err, errlen));
+    } else {
+        VX_TRY(vx_stark_openings_claims(cfg, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, &sq, err, errlen));
+    }
+    // ---- the tables: the blob must be for this shape (and these claims).  The table list gives the count and the leaf lengths; every
     // table's rows are read from its proof, so no block count is stated here
     const StarkOpenings& so = sq.so;
     StarkGroupTables ts;
-    if (so.cap_h > 16 || !stark_inner_tables(so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, 0, *cfg, &ts))
-        return v_fail(VX_ERR_ARG, err, errlen, "stark inner: the proof's shape has no query-phase group (no fold layer or more than 8, no index bit left, cap height above 16, or a table of more than 2^26 rows)");
-    BusTable tab[8];
-    const std::array<uint64_t, 7> sw = so.shape_words();
-    std::vector<uint64_t> request(sw.begin(), sw.end());
-    request.push_back((uint64_t)ts.n), request.push_back(claim.n_obs), request.push_back(claim.n_chal);
-    request.insert(request.end(), claim.chal, claim.chal + 2 * claim.n_chal);
-    VX_TRY(read_blob(blob, len, VX_SINR_MAGIC, "stark-inner", request.data(), request.size(), tab, (size_t)ts.n, err, errlen));
-    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
-    const size_t n_trees = so.tree.size(), final_len = sq.final_poly.size() / 2;
-    std::vector<uint64_t> roots(4 * n_trees);
-    for (size_t k = 0; k < n_trees; ++k) vx_cap_fold(so.caps.data() + k * ((size_t)4 << so.cap_h), so.cap_h, roots.data() + 4 * k);
-    uint64_t stmt[4], opub[mop::SET_PUB], spub[3][lsp::PUB], npub[lnp::PUB], cpub[fca::PUB], fpub[ffa::PUB], tpub[tsc::PUB];
-    vx_stark_inner_statement(sw, claim, stmt);
-    vx_merkle_open_set_public(stmt, opub);
-    tab[0].expect(VX_AIR_MERKLE_OPEN_SET, opub, mop::SET_PUB);
-    int k = 1;
-    for (; k <= ts.n_sponge; ++k) {
-        vx_leaf_sponge_set_public(ts.leaf_len[k], stmt, spub[k - 1]);
-        tab[k].expect(VX_AIR_LEAF_SPONGE_SET, spub[k - 1], lsp::PUB);
+    const bool has_group = stark_level_tables(level, so.LN, so.cm, so.ca, so.a, so.NL, so.n_queries, 0, *cfg, &ts);
+    if (level == StarkLevel::Openings) {  // this level's verifier words the two refusals apart, as statement errors
+        NEED(has_group, "stark openings: the proof's shape has no openings group (a tree without a level, or a table of more than 2^26 rows)");
+        NEED(so.cap_h <= 16, "stark openings: cap height %d (at most 16)", so.cap_h);
+    } else if (so.cap_h > 16 || !has_group) {
+        return v_fail(VX_ERR_ARG, err, errlen, "%s", lv.no_group);
     }
-    vx_leaf_noop_public(stmt, npub);
-    tab[k].expect(VX_AIR_LEAF_NOOP, npub, lnp::PUB), ++k;
-    vx_fri_combine_public_digest(sq.stmt(), fca::TREE0, stmt, cpub);
-    tab[k].expect(VX_AIR_FRI_COMBINE, cpub, fca::PUB), ++k;
-    vx_fri_fold_public_digest(so.LN, sq.betas.data(), so.NL, 0, stmt, fpub);
-    tab[k].expect(VX_AIR_FRI_FOLD, fpub, ffa::PUB), ++k;
-    vx_transcript_public(stmt, tpub);
-    tab[k].expect(VX_AIR_TRANSCRIPT, tpub, tsc::PUB);
-    return verify_bus_group(cfg, tab, (size_t)ts.n, "the query phase and the transcript the tables prove are not the ones of this proof and these claims (the lookup bus does not balance)", err,
-                            errlen, [&](const VBus& bus, BusMessages& m) {
-                                m.reserve(so.n_queries * (2 * n_trees + 1) + claim.n_obs + claim.n_chal);
-                                for (size_t i = 0; i < so.n_queries; ++i) {
-                                    for (size_t t = 0; t < n_trees; ++t) m.receive_root(bus, so.tree[t], roots.data() + 4 * t, so.log_leaves(so.tree[t]));
-                                    m.receive_exit(bus, so.index[i], so.LN, so.NL, sq.final_poly.data(), final_len);
-                                }
-                                const Fx chain{0, 0};
-                                for (size_t i = 0; i < claim.n_obs; ++i) m.send(bus.obs(chain, Fx{(uint64_t)i, 0}, Fx{claim.words[i], 0}));
-                                for (size_t j = 0; j < claim.n_chal; ++j) m.receive(bus.chal(chain, Fx{(uint64_t)j, 0}, Fx{claim.chal[2 * j], 0}, Fx{claim.chal[2 * j + 1], 0}));
-                            });
+    BusTable tab[StarkGroupTables::MAX];
+    const std::vector<uint64_t> request = stark_group_request(level, so, ts.n, claim);
+    VX_TRY(read_blob(blob, len, lv.magic, lv.blob_name, request.data(), request.size(), tab, (size_t)ts.n, err, errlen));
+    NEED(peek_tables(cfg, tab, (size_t)ts.n), "a proof is too short to hold a trace cap");
+    const std::vector<uint64_t> roots = so.roots();
+    uint64_t stmt[4], pub[StarkGroupTables::MAX][VX_STARK_TABLE_MAX_PUB];
+    stark_group_statement(level, sq, roots.data(), claim, stmt);
+    for (int k = 0; k < ts.n; ++k) tab[k].expect(ts.air[k], pub[k], stark_table_public(ts, k, sq, stmt, pub[k]));
+    const size_t n_trees = so.tree.size();
+    return verify_bus_group(cfg, tab, (size_t)ts.n, lv.unbalanced, err, errlen, [&](const VBus& bus, BusMessages& m) {
+        if (level == StarkLevel::Openings) {
+            m.reserve(2 * so.claims.size() + so.leaves.size());
+            for (size_t i = 0; i < so.claims.size(); ++i) {
+                const StarkOpenings::Claim& c = so.claims[i];
+                const uint64_t* leaf = so.leaves.data() + c.leaf;
+                const Fx tree{c.tree, 0}, idx{c.index, 0};
+                m.receive_root(bus, c.tree, roots.data() + 4 * (i % n_trees), so.log_leaves(c.tree));
+                if (c.leaf_len > 4) {
+                    for (size_t j = 0; j < c.leaf_len; ++j) m.receive(bus.row_of(tree, idx, Fx{(uint64_t)j, 0}, Fx{leaf[j], 0}));
+                } else {
+                    uint64_t d[4] = {0, 0, 0, 0};
+                    memcpy(d, leaf, c.leaf_len * 8);
+                    m.receive(bus.open_of(tree, idx, Fx{d[0], 0}, Fx{d[1], 0}, bus::K<0>{}));
+                    m.receive(bus.open_of(tree, idx, Fx{d[2], 0}, Fx{d[3], 0}, bus::K<1>{}));
+                }
+            }
+            return;
+        }
+        m.reserve(so.n_queries * (2 * n_trees + 1) + claim.n_obs + claim.n_chal);
+        for (size_t i = 0; i < so.n_queries; ++i) {
+            for (size_t t = 0; t < n_trees; ++t) m.receive_root(bus, so.tree[t], roots.data() + 4 * t, so.log_leaves(so.tree[t]));
+            m.receive_exit(bus, so.index[i], so.LN, so.NL, sq.final_poly.data(), sq.final_poly.size() / 2);
+        }
+        if (level == StarkLevel::Inner) transcript_messages(bus, m, 0, claim);
+    });
+}
+extern "C" {
+int32_t vx_stark_openings_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                                 size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    return stark_group_verify(StarkLevel::Openings, cfg, blob, len, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, err, errlen);
+}
+int32_t vx_stark_queries_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                                size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    return stark_group_verify(StarkLevel::Queries, cfg, blob, len, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, err, errlen);
+}
+int32_t vx_stark_inner_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public,
+                              size_t n_expect_public, const uint64_t* ext_chal, char* err, size_t errlen) {
+    return stark_group_verify(StarkLevel::Inner, cfg, blob, len, proof, proof_len, expect_air, expect_public, n_expect_public, ext_chal, err, errlen);
 }
 }
 

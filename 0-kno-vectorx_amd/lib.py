@@ -579,12 +579,17 @@ def stark_merkle_claims(proof, cfg=None, ext_chal=None):
                 leaves=[leaves[lcut[i]: lcut[i + 1]] for i in range(tree.size)], siblings=[sibs[scut[i]: scut[i + 1]].reshape(-1, 4) for i in range(tree.size)])
 
 
+def _stark_group_verify(symbol, blob, proof, cfg, expect_air, expect_public, ext_chal):
+    """the three levels of a proof's bus group (stark_openings / _queries / _inner) share one verifier signature"""
+    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
+    _host_verify(symbol, cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
+
+
 def stark_openings_verify(blob, proof, cfg=None, expect_air=0, expect_public=None, ext_chal=None):
     """Host-side check of a vx_stark_openings_prove blob together with the inner proof it belongs to: the proof is verified in
     the delegated mode (every check except the Merkle paths) and the group proves the paths.  Walks no path, hashes no leaf,
     reads no sibling; raises VxError with the reason."""
-    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
-    _host_verify("vx_stark_openings_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
+    _stark_group_verify("vx_stark_openings_verify", blob, proof, cfg, expect_air, expect_public, ext_chal)
 
 
 def stark_proof_head(proof, cfg=None):
@@ -604,8 +609,7 @@ def stark_queries_verify(blob, proof, cfg=None, expect_air=0, expect_public=None
     alone (everything before the first query record; lib.stark_proof_head cuts it): the proof's transcript, proof of work and
     constraint identity at zeta are checked in the query-free mode, which reads no query record, and the group proves the query phase.
     Raises VxError with the reason."""
-    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
-    _host_verify("vx_stark_queries_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
+    _stark_group_verify("vx_stark_queries_verify", blob, proof, cfg, expect_air, expect_public, ext_chal)
 
 
 class _ProofList:
@@ -671,8 +675,7 @@ def stark_inner_verify(blob, proof, cfg=None, expect_air=0, expect_public=None, 
     """Host-side check of a vx_stark_inner_prove blob together with the inner proof it belongs to -- the whole proof or its HEAD alone
     (lib.stark_proof_head cuts it): the proof is verified query-free with its transcript answered from the blob's claims -- no Poseidon
     permutation runs for the inner transcript -- and the group proves the query phase and the claims.  Raises VxError with the reason."""
-    b, pr, pub = _words(blob), _words(proof), _words(expect_public)
-    _host_verify("vx_stark_inner_verify", cfg, b, b.size, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, _words(ext_chal))
+    _stark_group_verify("vx_stark_inner_verify", blob, proof, cfg, expect_air, expect_public, ext_chal)
 
 
 FCOMB_MAGIC, FCOMB_HDR = 0x31424D4F43465856, 7  # "VXFCOMB1": magic, log2 of the inner LDE, cm, ca, nq, queries, proof length; then the FriCombineAir proof
@@ -1177,16 +1180,20 @@ class Context:
         self._ck(self.L.vx_leaf_noop_air_trace(self.h, _ptr(to), _ptr(idx), _ptr(ln), _ptr(rw), idx.size, log_n, out.h, _ptr(pub)))
         return out, pub
 
+    def _stark_group_prove(self, level, proof, cfg, ext_chal, out, refusal, bound_takes_chal=False):
+        """the three levels of a proof's bus group share one prover signature; only the inner level's bound replays the head and takes ext_chal"""
+        pr, ext = _words(proof), _words(ext_chal)
+        ch = None if ext is None else _ptr(ext)
+        bound, prove = getattr(self.L, f"vx_stark_{level}_proof_bound"), getattr(self.L, f"vx_stark_{level}_prove")
+        return self._prove_blob(cfg, out, lambda c, need: bound(c, _ptr(pr), pr.size, ch, need) if bound_takes_chal else bound(c, _ptr(pr), pr.size, need),
+                                f"stark {level}: {refusal}", lambda c, o, need: prove(self.h, c, _ptr(pr), pr.size, ch, _ptr(o), o.size, need))
+
     def stark_openings_prove(self, proof, cfg=None, ext_chal=None, out=None):
         """Proves the Merkle openings of the vx_stark_prove proof `proof` from the paths it carries -> blob words
         (lib.stark_openings_verify checks blob and proof together).  One openings table and one sponge table per leaf length above 4.
         The proof is verified on the way and every path walked natively first: VxError(VX_ERR_STATEMENT) names query and tree.
         out: a caller's uint64 buffer; when it is too small the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
-        pr = np.ascontiguousarray(proof, dtype=np.uint64)
-        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
-        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_openings_proof_bound(c, _ptr(pr), pr.size, need),
-                                "stark openings: not a proof of a known AIR under this configuration, or a shape without an openings group (more than 8 fold layers, a table above 2^26 rows)",
-                                lambda c, o, need: self.L.vx_stark_openings_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
+        return self._stark_group_prove("openings", proof, cfg, ext_chal, out, "not a proof of a known AIR under this configuration, or a shape without an openings group (more than 8 fold layers, a table above 2^26 rows)")
 
     def stark_queries_prove(self, proof, cfg=None, ext_chal=None, out=None):
         """Proves the whole query phase of the vx_stark_prove proof `proof` on one bus -> blob words (lib.stark_queries_verify checks
@@ -1194,11 +1201,7 @@ class Context:
         leaves, the FRI combination, the fold chains.  The proof is verified on the way and paths, combinations and folds are checked
         natively first: VxError(VX_ERR_STATEMENT) names query and tree or layer.  out: a caller's uint64 buffer; when it is too small
         the VxError (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
-        pr = np.ascontiguousarray(proof, dtype=np.uint64)
-        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
-        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_queries_proof_bound(c, _ptr(pr), pr.size, need),
-                                "stark queries: not a proof of a known AIR under this configuration, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)",
-                                lambda c, o, need: self.L.vx_stark_queries_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
+        return self._stark_group_prove("queries", proof, cfg, ext_chal, out, "not a proof of a known AIR under this configuration, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)")
 
     def transcript_air_trace(self, ops, words, log_n, out=None):
         """The witness of TranscriptAir: chain c has the run lengths ops[c] = [observe count, challenge count, observe count, ...] and
@@ -1233,11 +1236,7 @@ class Context:
         the transcript.  The proof is verified on the way, by one replay, and paths, combinations and folds are checked natively first:
         VxError(VX_ERR_STATEMENT) names query and tree or layer.  out: a caller's uint64 buffer; when it is too small the VxError
         (VX_ERR_BUFSZ) carries the needed length as `.needed`."""
-        pr = np.ascontiguousarray(proof, dtype=np.uint64)
-        ch = None if ext_chal is None else np.ascontiguousarray(ext_chal, dtype=np.uint64)
-        return self._prove_blob(cfg, out, lambda c, need: self.L.vx_stark_inner_proof_bound(c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), need),
-                                "stark inner: not a proof of a known AIR under this configuration, its head is not acceptable, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)",
-                                lambda c, o, need: self.L.vx_stark_inner_prove(self.h, c, _ptr(pr), pr.size, None if ch is None else _ptr(ch), _ptr(o), o.size, need))
+        return self._stark_group_prove("inner", proof, cfg, ext_chal, out, "not a proof of a known AIR under this configuration, its head is not acceptable, or a shape without a query-phase group (arity_bits other than 4, no fold layer or more than 8, a table above 2^26 rows)", True)
 
     def merkle(self, data, n_leaves, leaf_len, layout, cap_height, off=0):
         t = C.c_void_p()

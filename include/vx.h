@@ -548,7 +548,7 @@ int32_t vx_fri_combine_fold_verify(const vx_stark_config* cfg, const uint64_t* b
 enum { VX_AIR_LEAF_NOOP = 22, VX_LEAF_NOOP_AIR_COLS = 11, VX_LEAF_NOOP_AIR_AUX_COLS = 8 };
 int32_t vx_leaf_noop_air_trace(vx_ctx* ctx, const uint64_t* tree_of, const uint64_t* leaf_idx, const uint64_t* leaf_len, const uint64_t* rows, size_t n_idx, int log_n,
                                vx_buf* trace_out, uint64_t public_out[4]);
-/* ---- The whole query phase of a vx_stark_prove proof on ONE bus (csrc/vx_stark_queries.hip): the group of
+/* ---- The whole query phase of a vx_stark_prove proof on ONE bus (csrc/vx_stark_groups.hip): the group of
  * vx_stark_openings_prove with LeafNoopAir, FriCombineAir (TREE0 = 8) and FriFoldAir (TREE0 = 0) in the verifier's place on the row
  * bus, five to seven tables in this order: MerkleOpenSetAir (one path per claim), one LeafSpongeSetAir per distinct leaf length above
  * 4 among {cm, ca, 32} ascending, LeafNoopAir (one row per claim of a leaf of at most 4 words: the quotient tree always),
@@ -613,7 +613,7 @@ int32_t vx_stark_transcripts_prove(vx_ctx* ctx, const vx_stark_config* cfg, cons
                                    uint64_t* blob_out, size_t blob_cap, size_t* blob_len);
 int32_t vx_stark_transcripts_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, const uint64_t* const* proofs, const size_t* lens, size_t n,
                                     const uint64_t* const* ext_chals, char* err, size_t errlen);
-/* ---- An inner proof's query phase AND transcript on ONE bus (csrc/vx_stark_inner.hip): the tables of
+/* ---- An inner proof's query phase AND transcript on ONE bus (csrc/vx_stark_groups.hip): the tables of
  * vx_stark_queries_prove in their order, then TranscriptAir with one chain (id 0) -- six to eight tables.  The tags of the two halves
  * do not meet.  Argument conventions as vx_stark_queries_*; the bound takes ext_chal because the transcript's block count depends on it.
  * vx_stark_inner_prove: claims and chain come from ONE replay of the verifier's code over the recording challenger; the native checks

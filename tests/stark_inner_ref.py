@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE for an inner proof's query phase AND transcript on one bus (csrc/vx_stark_inner.hip): nothing is restated
+"""TEST INFRASTRUCTURE for an inner proof's query phase AND transcript on one bus (csrc/vx_stark_groups.hip): nothing is restated
 here that tests/ already has.  The claims, rows, leaves and the five to seven query-phase tables are stark_queries_ref's, the chain,
 its plan and the transcript table are transcript_ref's (recorded from oracle/stark_ref.py's own verifier); new are the ONE statement
 digest, the group's table list with forge hooks, the blob's wrap and unwrap, and the outside party's sum -- the sum of the two

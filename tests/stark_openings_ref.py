@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE for a STARK proof's Merkle openings proven from the paths it carries (csrc/vx_stark_openings.hip): the claims
+"""TEST INFRASTRUCTURE for a STARK proof's Merkle openings proven from the paths it carries (csrc/vx_stark_groups.hip): the claims
 of a proof restated INDEPENDENTLY (the proof walked word by word, the transcript replayed for the query indices and the running
 evaluation that fills a layer leaf's `within` slot), path -> blocks from the leaf digest, the siblings and the fold of the cap with
 oracle.two_to_one, the statement digest, the group's tables and reference prover, the blob wrapper and the verifier's side of the

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE for the whole query phase of a STARK proof on one bus (csrc/vx_stark_queries.hip): the head of a proof walked
+"""TEST INFRASTRUCTURE for the whole query phase of a STARK proof on one bus (csrc/vx_stark_groups.hip): the head of a proof walked
 word by word with its transcript replayed (alpha, zeta, the openings, betas, the final polynomial, where the query records start),
 the claims of the group (the Merkle side is stark_openings_ref.extract; the rows the combination reads and the leaves the folds
 read are taken from it), the statement digest, the five to seven tables and the group's reference prover, blob wrap and unwrap, the

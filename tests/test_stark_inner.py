@@ -183,6 +183,21 @@ def test_every_change_to_the_head_and_every_other_length_is_refused(vx, oracle):
     refused(vx, g, bad, match="truncated")
 
 
+def test_both_verifiers_of_a_claimed_transcript_refuse_bad_claims_in_the_same_words(vx, oracle):
+    """the claimed-transcript check is ONE check with two callers: vx_stark_inner_verify (the one chain, bare messages) and
+    vx_stark_transcripts_verify (per chain, `chain c: ` in front).  Both refuse before they read a table, so the same table proofs serve."""
+    g = I.group("fib8_two_layers_cap0")
+    cfg, words, chals = pcfg(vx, g["cfg"]), g["chain"][1], list(g["chals"])
+    cases = [([(chals[0][0], P)] + chals[1:], "claimed challenge 0 is not canonical"),
+             (chals[:-1], f"the blob claims {len(chals) - 1} challenges, the proof's shape draws more")]
+    for forged, text in cases:
+        inner = refused(vx, g, I.wrap(g["proofs"], g["cl"]["shape"], len(words), forged), code=ERR_STATEMENT)
+        with pytest.raises(vx.VxError) as e:
+            vx.lib.stark_transcripts_verify(T.wrap(g["proofs"][-1], [(words, forged)]), [g["proof"]], cfg, [g["ext"]])
+        assert e.value.code == ERR_STATEMENT
+        assert str(inner).endswith(": " + text) and "chain 0: " in str(e.value) and str(e.value).replace("chain 0: ", "", 1) == str(inner)
+
+
 # ---- forged groups on fib8: the reference prover proves them, the product verifier must refuse them
 def _forged_blob(g, chals=None, hd=None, forge=None):
     """-> (blob, the first (table, constraint, row) a row check refuses or None, whether the tables balance against the outside party)"""

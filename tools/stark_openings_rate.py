@@ -8,30 +8,11 @@ vx_stark_merkle_claims alone (the host share of it), vx_stark_openings_verify an
 same proof as the header_range verifier does it (every path walked on the host): the inner proof's claims extraction is that
 verifier minus the paths."""
 import json
-import os
-import sys
-import time
 
-import numpy as np
+import stark_rate_common as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import vx_import  # noqa: E402
-from oracle import oracle as O  # noqa: E402
-
-O.build()
-from oracle import stark_ref as S  # noqa: E402
-
-vx = vx_import.load()
-ctx = vx.Context(0)
-reps, N = 5, 256
-ch = vx.synth.Chain(N, profile="P15k")
-cfg = ctx.stark_config()
-out96, blob = ctx.header_range_prove(ctx.from_host(ch.headers), ch.stride, ch.sizes, N, ch.trusted_block, ch.trusted_hash, ch.target_block, cfg)
-segs, p_sha, p_tree, p_ed, p_h = vx.lib.split_blob_segments(blob)
-assert len(segs) == 1 and p_sha.size == 0
-proof = np.array(segs[0], dtype=np.uint64)
-chal = S.shared_challenges_n([S.proof_peek(p, cfg.cap_height) for p in (proof, p_tree)], 4)  # bus order: segments, Merkle
+r = R.setup()
+vx, ctx, cfg, ch, out96, blob, proof, chal, N = r.vx, r.ctx, r.cfg, r.ch, r.out96, r.blob, r.proof, r.chal, R.N
 out = ctx.stark_openings_prove(proof, cfg, ext_chal=chal)  # warm-up (pool, side contexts)
 vx.lib.stark_openings_verify(out, proof, cfg, ext_chal=chal)
 mc = vx.lib.stark_merkle_claims(proof, cfg, ext_chal=chal)
@@ -41,19 +22,10 @@ for k in range(n_tab):
     logs.append(int(out[at + 2]))
     at += int(out[vx.lib.SOPEN_HDR + k])
 
-
-def timed_wall(fn):
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        fn()
-    ctx.sync()
-    return round(1e3 * (time.perf_counter() - t0) / reps, 2)
-
-
 res = {"shape_LN_cm_ca_a_NL_cap_queries": mc["shape"], "claims": int(mc["tree"].size), "tables_log2_rows": logs, "inner_proof_KB": round(proof.size * 8 / 1024, 1),
        "sibling_KB": round(sum(s.size for s in mc["siblings"]) * 8 / 1024, 1), "blob_KB": round(out.size * 8 / 1024, 1)}
-res["prove_wall_ms"] = timed_wall(lambda: ctx.stark_openings_prove(proof, cfg, ext_chal=chal, out=out))
-res["claims_host_ms"] = timed_wall(lambda: vx.lib.stark_merkle_claims(proof, cfg, ext_chal=chal))
-res["verify_host_ms"] = timed_wall(lambda: vx.lib.stark_openings_verify(out, proof, cfg, ext_chal=chal))
-res["header_range_verify_host_ms"] = timed_wall(lambda: vx.lib.header_range_verify(blob, N, ch.trusted_block, ch.trusted_hash, ch.target_block, out96, cfg))
+res["prove_wall_ms"] = R.timed_wall(ctx, lambda: ctx.stark_openings_prove(proof, cfg, ext_chal=chal, out=out))
+res["claims_host_ms"] = R.timed_wall(ctx, lambda: vx.lib.stark_merkle_claims(proof, cfg, ext_chal=chal))
+res["verify_host_ms"] = R.timed_wall(ctx, lambda: vx.lib.stark_openings_verify(out, proof, cfg, ext_chal=chal))
+res["header_range_verify_host_ms"] = R.timed_wall(ctx, lambda: vx.lib.header_range_verify(blob, N, ch.trusted_block, ch.trusted_hash, ch.target_block, out96, cfg))
 print(json.dumps(res))
