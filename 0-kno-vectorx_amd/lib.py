@@ -1305,11 +1305,12 @@ class Context:
         self._ck(self.L.vx_bus_group_check(self.h, arr, len(tables), _ptr(o) if o.size else None, o.shape[0], C.byref(u)))
         return None if u.n_unmatched == 0 else BusUnmatched(int(u.n_unmatched), int(u.table), int(u.message), int(u.row), int(u.net))
 
-    def stark_aux_trace(self, air_id, trace_buf, log_n, challenges, n_aux_cols, public_inputs=()):
-        """The auxiliary (logUp) columns of an AIR for given lookup challenges -> (Buffer [n_aux_cols][2^log_n], published values)."""
+    def stark_aux_trace(self, air_id, trace_buf, log_n, challenges, n_aux_cols, public_inputs=(), out=None):
+        """The auxiliary (logUp) columns of an AIR for given lookup challenges -> (Buffer [n_aux_cols][2^log_n], published values).
+        out: a caller's Buffer of at least n_aux_cols << log_n words (the columns go to its start)."""
         ch = np.ascontiguousarray(challenges, dtype=np.uint64)
         pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
-        out = self.alloc(n_aux_cols << log_n)
+        out = out or self.alloc(n_aux_cols << log_n)
         apub = np.zeros(8, dtype=np.uint64)
         self._ck(self.L.vx_stark_aux_trace(self.h, air_id, trace_buf.h, log_n, _ptr(pub) if pub.size else None, pub.size, _ptr(ch), ch.size, out.h, _ptr(apub)))
         return out, apub
@@ -1377,11 +1378,13 @@ class Context:
         self._ck(self.L.vx_partial_products(self.h, wires_buf.h, sigmas_buf.h, log_n, n_routed, _ptr(k), int(beta), int(gamma), chunk, out.h))
         return out
 
-    def quotient_eval(self, air_id, rate_bits, trace_lde_buf, log_n, alphas, public_inputs, challenges=None, aux_public=None):
+    def quotient_eval(self, air_id, rate_bits, trace_lde_buf, log_n, alphas, public_inputs, challenges=None, aux_public=None, out=None):
         """-> [2][N] quotient values on the coset for the two challenges.  With challenges / aux_public (both, possibly empty) the
-        buffer holds the main columns then the auxiliary ones and any AIR is evaluated (vx_quotient_eval_aux)."""
+        buffer holds the main columns then the auxiliary ones and any AIR is evaluated (vx_quotient_eval_aux).
+        out: a caller's Buffer of at least 2 N words (the values go to its start; it is not freed)."""
         N = 1 << (log_n + rate_bits)
-        out = self.alloc(2 * N)
+        own = out is None
+        out = out or self.alloc(2 * N)
         al = np.ascontiguousarray(alphas, dtype=np.uint64)
         pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
         if challenges is None and aux_public is None:
@@ -1391,8 +1394,9 @@ class Context:
             ap = np.ascontiguousarray(() if aux_public is None else aux_public, dtype=np.uint64)
             self._ck(self.L.vx_quotient_eval_aux(self.h, air_id, rate_bits, trace_lde_buf.h, log_n, _ptr(al), _ptr(pub) if pub.size else None, pub.size,
                                                  _ptr(ch) if ch.size else None, ch.size, _ptr(ap) if ap.size else None, ap.size, out.h))
-        v = out.download().reshape(2, N)
-        out.free()
+        v = out.download(2 * N).reshape(2, N)
+        if own:
+            out.free()
         return v
 
     def gather_proofs(self, nccl_comm, world, blob_words):

@@ -18,6 +18,13 @@
  *   - matrices are COLUMN-MAJOR: one polynomial / trace column is contiguous.
  *   - the caller owns host buffers; vx_buf are device (HBM) buffers owned by
  *     the ctx that allocated them.
+ *   - EXTENTS: a vx_buf may be longer than the extent a call documents (the one
+ *     exception: a vx_bus_table's trace).  An output's extent starts at the
+ *     buffer's first word, or at the offset argument where there is one.  EVERY
+ *     word of it is written -- the idle rows, idle slots and padding blocks of a
+ *     trace included, whatever the buffer held before -- and NO word outside it.
+ *     A `const vx_buf*` input is left intact, as is every word around it.
+ *     (tests/test_gpu_extents.py holds every entry point to this.)
  *   - a vx_ctx is bound to one device and one HIP stream; calls are
  *     asynchronous on that stream; vx_sync / vx_download block.  Not
  *     thread-safe: one ctx per host thread.
@@ -83,7 +90,9 @@ int32_t vx_ext_batch_mul(vx_ctx* ctx, const vx_buf* a, const vx_buf* b, vx_buf* 
 
 /* ---- K2: batched radix-2 NTT (plonky2_field::fft::{fft,ifft}, polynomial::{coset_fft,coset_ifft})
  * buf holds n_cols columns of n = 2^log_n elements at column stride `col_stride`
- * (elements).  Natural order in and out, in place.
+ * (elements), the first at element `off`.  Natural order in and out, in place: the n words of
+ * every column are written; the col_stride - n words between two columns, and everything
+ * before `off` and behind the last column, are not touched.
  *   inverse = 0: values[i] = sum_k coeff[k] * (shift * w^i)^k        (coset_fft; shift 0/1 = plain fft)
  *   inverse = 1: the inverse map, including the 1/n factor           (coset_ifft / ifft)
  * order: VX_ORDER_NATURAL, or VX_ORDER_BITREV to leave a FORWARD result (or take an
