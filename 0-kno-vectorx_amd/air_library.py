@@ -4,9 +4,11 @@ the two tables a recursive STARK verifier is mostly made of (plonky
   poseidon_builder()        PoseidonAir   -- the Poseidon-Goldilocks permutation (width 12, x^7, 4 + 22 + 4 rounds), one round per row
   merkle_path_builder(d)    MerklePathAir -- verify_merkle_proof_to_cap for a cap of height 0: d levels, one PoseidonAir block each
   sponge_builder(k)         SpongeAir     -- hash_n_to_hash_no_pad of 8 k words (the leaf hash of a Merkle tree): k blocks, overwrite mode
+  fri_exit_builder()        FriExitAir    -- an inner proof's query indices, proof of work and FRI exits; on a bus, with declared messages
 
 Each returns an AirBuilder (`.register()` gives the AIR id; `.assemble()` the code).  The witness (trace) of these tables is the
-host's to fill: tests/air_programs.py has reference generators; tests/test_gpu_air_program.py proves a path of a GPU-built tree."""
+host's to fill: tests/air_programs.py has reference generators; tests/test_gpu_air_program.py proves a path of a GPU-built tree.
+FriExitAir's witness is the library's (Context.fri_exit_air_trace)."""
 import importlib.util
 import os
 
@@ -171,4 +173,96 @@ def sponge_builder(blocks):
         b.assert_first(b.loc(i))
     for i in range(4):
         b.assert_last(b.loc(i) - b.pub(8 * blocks + i))
+    return b
+
+
+# ---- FriExitAir.  The numbers below are csrc/fri_exit_layout.h's (tests/test_fri_exit.py compares the two).
+FRI_EXIT_BLOCK, FRI_EXIT_HORNER_ROW, FRI_EXIT_MAX_FINAL_LEN = 128, 63, 64
+(FRI_EXIT_BIT, FRI_EXIT_V, FRI_EXIT_F, FRI_EXIT_C, FRI_EXIT_EF, FRI_EXIT_C2, FRI_EXIT_G, FRI_EXIT_EB, FRI_EXIT_W, FRI_EXIT_X, FRI_EXIT_IDX, FRI_EXIT_T, FRI_EXIT_HF, FRI_EXIT_K,
+ FRI_EXIT_CA, FRI_EXIT_CB, FRI_EXIT_ACC) = range(17)
+FRI_EXIT_ACT, FRI_EXIT_ISPOW, FRI_EXIT_ORD, FRI_EXIT_COLS = 18, 19, 20, 21
+(FRI_EXIT_P_FIRST, FRI_EXIT_P_LAST, FRI_EXIT_P_BIT, FRI_EXIT_P_WEIGHT, FRI_EXIT_P_HIGH, FRI_EXIT_P_HOLD, FRI_EXIT_P_LOW, FRI_EXIT_P_PRE, FRI_EXIT_P_R62,
+ FRI_EXIT_PERIODIC) = range(10)
+(FRI_EXIT_PUB_ORD_POW, FRI_EXIT_PUB_ABSORBED, FRI_EXIT_PUB_POW_BITS, FRI_EXIT_PUB_SKIP, FRI_EXIT_PUB_FB, FRI_EXIT_PUB_W, FRI_EXIT_PUB_G, FRI_EXIT_PUB_FINAL_LEN,
+ FRI_EXIT_PUB_DIGEST) = range(9)
+FRI_EXIT_PUB, FRI_EXIT_N_HELP, FRI_EXIT_AUX_COLS = 12, 2, 6
+TAG_FRI, TAG_CHAL, TAG_FIN = 10, 13, 14  # csrc/air_bus.cuh
+
+
+def fri_exit_periodic():
+    """the nine position columns of a 128-row block, in the order of the FRI_EXIT_P_* indices"""
+    rows = range(FRI_EXIT_BLOCK)
+    return [[int(r == 0) for r in rows], [int(r == 127) for r in rows], [int(r < 64) for r in rows], [1 << (63 - r) if r < 64 else 0 for r in rows],
+            [int(1 <= r < 32) for r in rows], [int(32 <= r < 63) for r in rows], [int(32 <= r < 64) for r in rows], [int(r < 63) for r in rows], [int(r == 62) for r in rows]]
+
+
+def fri_exit_builder():
+    """FriExitAir: what a verifier does with the challenges an inner proof's transcript yields behind the final polynomial.  One block
+    of 128 rows per challenge value v of chain 0, received as chal(0, ordinal, absorbed, v) on the block's last row: block 0 the
+    proof-of-work response (ordinal ORD_POW), block 1 + q the index challenge of query q.  Rows 0 .. 63 hold the bits of v, MSB first,
+    boolean, their weighted sum v, and the integer they spell is below p (T: if the top 32 are all ones the low 32 are zero).  F is a
+    prefix flag of a length the counter C forces exactly: the top pow_bits bits of the PoW response, which are zero, or the top 64 - LN
+    bits of an index challenge, which the index (the weighted sum of the other bits) leaves out.  The FB rows behind F (EF, counter
+    C2) are the exponent bits of the query's point behind the folds, x_NL = 7^(16^NL) w_FB^brev(index >> 4 NL, FB): the step of weight
+    2^s comes s-th, so W is squared on every row and X takes it where the bit is set.  Rows 63 .. 62 + final_len (HF, counter K) are
+    the Horner steps ACC' = ACC x + c_k of the final polynomial, every coefficient received as fin(k, c_k); the last row receives the
+    exit fri(index, ACC, 1) of the query's fold chain.  Positional: nine periodic columns of period 128 (csrc/fri_exit_layout.h).
+    Public inputs: ORD_POW, ABSORBED, pow_bits, 64 - LN, FB, w_FB, 7^(16^NL), final_len, four statement-digest words."""
+    b = ap.AirBuilder(FRI_EXIT_COLS, FRI_EXIT_PUB, periodic=fri_exit_periodic())
+    loc, nxt, pub = b.loc, b.nxt, b.pub
+    first, last, pbit, weight, high, hold, low, pre, r62 = (b.per(q) for q in range(FRI_EXIT_PERIODIC))
+    bit, v, f, c, ef, c2, g, eb, w, x, idx, t, hf, k, ca, cb = (loc(j) for j in range(16))
+    acc, act, ispow, ordinal = [loc(FRI_EXIT_ACC), loc(FRI_EXIT_ACC + 1)], loc(FRI_EXIT_ACT), loc(FRI_EXIT_ISPOW), loc(FRI_EXIT_ORD)
+    idxb, h, h_n = act - ispow, f + ef, nxt(FRI_EXIT_F) + nxt(FRI_EXIT_EF)
+    inside = 1 - last
+    # 1. boolean cells; no bit behind row 63
+    for e in (bit, f, ef, h, hf, act, ispow):
+        b.assert_zero(e * (e - 1))
+    b.assert_zero(ispow * (1 - act))
+    b.assert_zero((1 - pbit) * bit)
+    # 2. the blocks: flags constant over a block, ordinals by position from ORD_POW, block 0 alone is the PoW block
+    b.assert_zero(inside * (nxt(FRI_EXIT_ACT) - act))
+    b.assert_zero(inside * (nxt(FRI_EXIT_ISPOW) - ispow))
+    b.assert_transition(nxt(FRI_EXIT_ORD) - ordinal - last)
+    b.assert_first(ordinal - pub(FRI_EXIT_PUB_ORD_POW))
+    b.assert_first(ispow - act)
+    b.assert_transition(last * nxt(FRI_EXIT_ISPOW))
+    # 3. the value, and that its bits spell an integer below p
+    b.assert_zero(nxt(FRI_EXIT_V) - inside * v - bit * weight)
+    b.assert_zero(nxt(FRI_EXIT_T) - first * bit - t * (high * bit + hold))
+    b.assert_zero(low * t * bit)
+    # 4. the prefix flag of a public length
+    b.assert_zero(last * f)
+    b.assert_zero(nxt(FRI_EXIT_F) * (1 - f - last))
+    b.assert_zero(first * (c - ispow * pub(FRI_EXIT_PUB_POW_BITS) - idxb * pub(FRI_EXIT_PUB_SKIP)))
+    b.assert_zero(inside * (nxt(FRI_EXIT_C) - c + f))
+    b.assert_zero(last * c)
+    # 5. the exponent flag: FB rows behind it
+    b.assert_zero(last * ef)
+    b.assert_zero(h_n * (1 - h - last))
+    b.assert_zero(first * (c2 - idxb * pub(FRI_EXIT_PUB_FB)))
+    b.assert_zero(inside * (nxt(FRI_EXIT_C2) - c2 + ef))
+    b.assert_zero(last * c2)
+    # 6. the products flag x bit; the PoW response has no bit under its flag
+    b.assert_zero(g - bit + f * bit)
+    b.assert_zero(eb - ef * bit)
+    b.assert_zero(ispow * (bit - g))
+    # 7. the index: the bits the flag leaves
+    b.assert_zero(nxt(FRI_EXIT_IDX) - inside * idx - g * weight)
+    # 8. the point
+    b.assert_zero(nxt(FRI_EXIT_W) - f * pub(FRI_EXIT_PUB_W) - ef * w * w)
+    b.assert_zero(nxt(FRI_EXIT_X) - f * pub(FRI_EXIT_PUB_G) - (1 - f - last) * x - x * eb * (w - 1))
+    # 9. the Horner steps
+    b.assert_zero(pre * hf)
+    b.assert_zero(last * hf)
+    b.assert_zero(nxt(FRI_EXIT_HF) * (1 - hf - r62))
+    b.assert_zero(first * (k - idxb * pub(FRI_EXIT_PUB_FINAL_LEN)))
+    b.assert_zero(inside * (nxt(FRI_EXIT_K) - k + hf))
+    b.assert_zero(last * k)
+    for j, cj in enumerate((ca, cb)):
+        b.assert_zero(nxt(FRI_EXIT_ACC + j) - inside * acc[j] - hf * (acc[j] * (x - 1) + cj))
+    # the bus: the challenge (TranscriptAir sends it), the step's coefficient (the holder of the proof head), the exit (FriFoldAir)
+    b.receive(TAG_CHAL, [None, ordinal, pub(FRI_EXIT_PUB_ABSORBED), v], last * act)
+    b.receive(TAG_FIN, [k - 1, ca, cb], hf)
+    b.receive(TAG_FRI, [idx, acc[0], acc[1], b.const(1)], last * idxb)
     return b

@@ -12,7 +12,7 @@
 #include "gl.cuh"
 
 namespace bus {
-enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10, TAG_ROOT = 11, TAG_OBS = 12, TAG_CHAL = 13 };
+enum Tag : uint64_t { TAG_T1 = 0, TAG_T2 = 1, TAG_BYTE = 2, TAG_WORD = 3, TAG_R16 = 4, TAG_KEY = 5, TAG_EDMSG = 6, TAG_EDH = 7, TAG_OPEN = 8, TAG_ROW = 9, TAG_FRI = 10, TAG_ROOT = 11, TAG_OBS = 12, TAG_CHAL = 13, TAG_FIN = 14 };
 
 // a slot known at compile time: 0 leaves its term out, 1 adds the bare power of gamma, so a kind that does not use a slot
 // (or whose tag is 0 or 1) costs what the hand-written sum cost
@@ -111,5 +111,8 @@ struct Bus {
     // a challenge a transcript yields (chain, ordinal among the chain's challenges, words absorbed when it was drawn, value):
     // TranscriptAir -> whoever uses the challenges (the verifier).  `absorbed` binds WHEN: without it the absorptions could be regrouped
     VX_HD X chal(const S& chain, const S& ordinal, const S& absorbed, const S& word) const { return denom(beta, chain, ordinal, absorbed, word, K<TAG_CHAL>{}); }
+    // a coefficient of an inner proof's final polynomial (k, c_k.a, c_k.b): whoever holds the proof head (the verifier of
+    // fri_exits_verify, once per query) -> FriExitAir, which evaluates the polynomial at every query's point
+    VX_HD X fin(const S& k, const S& ca, const S& cb) const { return denom(beta, k, ca, cb, None{}, K<TAG_FIN>{}); }
 };
 }  // namespace bus

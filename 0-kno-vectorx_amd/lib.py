@@ -33,6 +33,7 @@ SYMBOLS = [
     "vx_merkle_open_air_trace", "vx_merkle_openings_proof_bound", "vx_merkle_openings_prove", "vx_merkle_openings_verify",
     "vx_leaf_sponge_air_trace", "vx_merkle_rows_proof_bound", "vx_merkle_rows_prove", "vx_merkle_rows_verify",
     "vx_fri_fold_air_trace", "vx_fri_fold_proof_bound", "vx_fri_fold_prove", "vx_fri_fold_verify", "vx_stark_fri_claims",
+    "vx_fri_exit_air_trace", "vx_fri_exit_public", "vx_fri_exit_log_n", "vx_fri_exit_statement",
     "vx_merkle_open_set_air_trace", "vx_leaf_sponge_set_air_trace", "vx_fri_queries_proof_bound", "vx_fri_queries_prove", "vx_fri_queries_verify",
     "vx_fri_combine_air_trace", "vx_fri_combine_proof_bound", "vx_fri_combine_prove", "vx_fri_combine_verify", "vx_stark_combine_claims",
     "vx_fri_combine_fold_proof_bound", "vx_fri_combine_fold_prove", "vx_fri_combine_fold_verify",
@@ -60,6 +61,8 @@ VX_AIR_LEAF_SPONGE_SET, VX_LEAF_SPONGE_SET_AIR_COLS, VX_LEAF_SPONGE_SET_AIR_AUX_
 VX_AIR_FRI_COMBINE, VX_FRI_COMBINE_AIR_COLS, VX_FRI_COMBINE_AIR_AUX_COLS = 21, 28, 4
 VX_AIR_LEAF_NOOP, VX_LEAF_NOOP_AIR_COLS, VX_LEAF_NOOP_AIR_AUX_COLS = 22, 11, 8
 VX_AIR_TRANSCRIPT, VX_TRANSCRIPT_AIR_COLS, VX_TRANSCRIPT_AIR_AUX_COLS, VX_TRANSCRIPT_MAX_CHAINS = 23, 93, 18, 64
+FRI_EXIT_AIR_COLS, FRI_EXIT_AIR_AUX_COLS, FRI_EXIT_PUBLIC, FRI_EXIT_BLOCK, FRI_EXIT_MAX_FINAL_LEN = 21, 6, 12, 128, 64  # csrc/fri_exit_layout.h: a shipped program, no compiled AIR
+TAG_ROW, TAG_FRI, TAG_OBS, TAG_CHAL, TAG_FIN = 9, 10, 12, 13, 14  # csrc/air_bus.cuh: the tags an exit group's outside party uses
 
 
 class JustificationStruct(C.Structure):
@@ -215,6 +218,8 @@ def load_library():
         "vx_merkle_rows_verify": [C.POINTER(StarkConfig), vp, sz, vp, C.c_int, C.c_int, sz, vp, vp, sz, C.c_char_p, sz],
         "vx_fri_fold_air_trace": [vp, C.c_int, vp, sz, C.c_uint64, vp, vp, vp, sz, C.c_int, vp, vp],
         "vx_fri_fold_proof_bound": [C.POINTER(StarkConfig), C.c_int, sz, sz, C.POINTER(sz)],
+        "vx_fri_exit_air_trace": [vp, C.c_int, sz, C.c_int, C.c_uint64, C.c_uint64, vp, sz, vp, sz, C.c_int, vp, vp],
+        "vx_fri_exit_public": [C.c_int, sz, C.c_int, C.c_uint64, C.c_uint64, vp, sz, vp], "vx_fri_exit_log_n": [sz], "vx_fri_exit_statement": [vp, sz, vp],
         "vx_fri_fold_prove": [vp, C.POINTER(StarkConfig), C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_fri_fold_verify": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, vp, sz, vp, vp, vp, sz, C.c_char_p, sz],
         "vx_merkle_open_set_air_trace": [vp, vp, sz, vp, vp, sz, C.c_int, vp, vp],
@@ -502,6 +507,156 @@ def fri_fold_verify(blob, log_lde, betas, final_poly, index, ev0, leaves, cfg=No
     b = _words(blob)
     be, fp, idx, ev, lv = _fri_claims(betas, final_poly, index, ev0, leaves)
     _host_verify("vx_fri_fold_verify", cfg, b, b.size, log_lde, be, be.shape[0], fp, fp.shape[0], idx, ev, lv, idx.size)
+
+
+def fri_exit_log_n(n_queries):
+    """The smallest log_n whose rows hold FriExitAir's 1 + n_queries blocks of 128; the caller raises it to a size with a FRI plan."""
+    return int(load_library().vx_fri_exit_log_n(int(n_queries)))
+
+
+def fri_exit_public(log_lde, n_layers, pow_bits, ord_pow, absorbed, final_poly):
+    """FriExitAir's 12 public inputs from what a verifier knows (host only): ord_pow, absorbed, pow_bits, 64 - log_lde, FB, w_FB,
+    7^(16^NL), final_len, and the digest of these with the final polynomial's words.  VxError (VX_ERR_ARG) says which limit a shape
+    misses."""
+    fp = np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
+    pub = np.zeros(FRI_EXIT_PUBLIC, dtype=np.uint64)
+    rc = load_library().vx_fri_exit_public(int(log_lde), int(n_layers), int(pow_bits), int(ord_pow), int(absorbed), _ptr(fp) if fp.size else None, fp.shape[0], _ptr(pub))
+    if rc != 0:  # the entry point has no buffer for a reason: the binding names the limit that was missed
+        n, fb = fp.shape[0], log_lde - 4 * n_layers
+        why = ("%d fold layers (1..8)" % n_layers if not 1 <= n_layers <= 8 else "log_lde %d (5..32)" % log_lde if not 5 <= log_lde <= 32 else
+               "%d index bits behind the fold layers (FB, at least 1)" % fb if fb < 1 else "pow_bits %d (0..64)" % pow_bits if not 0 <= pow_bits <= 64 else
+               "a final polynomial of %d coefficients (1..%d): more do not fit the Horner rows of a block" % (n, FRI_EXIT_MAX_FINAL_LEN) if not 1 <= n <= FRI_EXIT_MAX_FINAL_LEN else
+               "ord_pow or absorbed is 2^32 or more" if max(int(ord_pow), int(absorbed)) >> 32 else "a non-canonical final-polynomial word")
+        raise VxError(rc, "fri exit: " + why)
+    return pub
+
+
+_fri_exit_air = None
+
+
+def fri_exit_air_id():
+    """The AIR id of the shipped FriExitAir program (air_library.fri_exit_builder()) in this process: registered on first use, prover
+    and verifier alike (a proof does not carry its program)."""
+    global _fri_exit_air
+    if _fri_exit_air is None:
+        from . import air_library
+
+        _fri_exit_air = air_library.fri_exit_builder().register()
+    return _fri_exit_air
+
+
+def _table_log_n(log_n, cfg=None):
+    """The rows (log2) a table of at least 2^log_n rows is proven at: the next size whose FRI plan under cfg leaves a final polynomial."""
+    cfg = cfg or default_stark_config()
+    while True:
+        d = log_n
+        while d > cfg.final_poly_bits and d + cfg.rate_bits - cfg.arity_bits >= cfg.cap_height:
+            d -= cfg.arity_bits
+        if d >= 0:
+            return log_n
+        log_n += 1
+
+
+def _transcript_ops(n_obs, chal):
+    """A chain's run lengths [observe count, challenge count, ...] (what transcript_air_trace takes) from its claims: the challenges
+    [n][2] as (words absorbed when it was drawn, value).  -> (ops, the number of duplexes: a counter machine, nothing is hashed)"""
+    ops, at = [], 0
+    for a, _ in np.asarray(chal, dtype=np.uint64).reshape(-1, 2).tolist():
+        if not ops or a != at:
+            ops += [a - at, 0]
+            at = a
+        ops[-1] += 1
+    if at != n_obs:
+        raise ValueError("the chain ends on observed words that no challenge follows")
+    n_in, n_out, blocks = 0, 0, 0
+    for j, count in enumerate(ops):
+        for _ in range(count):
+            if j % 2 == 0:
+                n_out, n_in = 0, n_in + 1
+                if n_in == 8:
+                    blocks, n_in, n_out = blocks + 1, 0, 8
+            else:
+                if n_in > 0 or n_out == 0:
+                    blocks, n_in, n_out = blocks + 1, 0, 8
+                n_out -= 1
+    return ops, blocks
+
+
+def fri_exit_statement_words(log_lde, pow_bits, ord_pow, obs, chal, index, ev0, leaves):
+    """The words of an exit group's ONE statement digest, everything its outside party states, fixed before the shared lookup
+    challenges are drawn: log_lde, pow_bits, ord_pow, n_obs, n_queries, the fold layers; the observed words (the final polynomial
+    and the nonce among them); (absorbed, value) of every challenge BELOW ord_pow (the betas among them); per query (index, ev_0,
+    leaves).  The challenges from ord_pow on are NOT in it: FriExitAir's trace cap commits them."""
+    idx, lv = np.asarray(index, dtype=np.uint64).reshape(-1), np.asarray(leaves, dtype=np.uint64)
+    lv = lv.reshape(idx.size, -1)
+    claims = np.concatenate([idx.reshape(-1, 1), np.asarray(ev0, dtype=np.uint64).reshape(-1, 2), lv], axis=1)
+    head = [int(log_lde), int(pow_bits), int(ord_pow), len(obs), idx.size, lv.shape[1] // 32]
+    return np.concatenate([np.array(head, dtype=np.uint64), np.asarray(obs, dtype=np.uint64).reshape(-1), np.asarray(chal, dtype=np.uint64).reshape(-1, 2)[:ord_pow].reshape(-1),
+                           claims.reshape(-1)])
+
+
+def fri_exit_statement(words):
+    """hash_n_to_hash_no_pad of an exit group's statement words (host only) -> the four digest words"""
+    w, d = _words(words), np.zeros(4, dtype=np.uint64)
+    rc = load_library().vx_fri_exit_statement(_ptr(w), w.size, _ptr(d))
+    if rc != 0:
+        raise VxError(rc, "fri exit: the statement has no words, or a non-canonical one")
+    return d
+
+
+def fri_exits_outside(log_lde, ord_pow, obs, chal, final_poly, index, ev0, leaves):
+    """The messages of an exit group's outside party, the verifier: per query the 32 words of every layer's leaf and the entry (index,
+    ev_0) of the fold chain SENT; every observed word SENT; the challenges below ord_pow RECEIVED; every coefficient of the final
+    polynomial SENT n_queries times.  -> [n][6] words (t0, t1, t2, t3, tag, m)"""
+    idx = [int(i) for i in np.asarray(index, dtype=np.uint64).reshape(-1)]
+    lv = np.asarray(leaves, dtype=np.uint64).reshape(len(idx), -1, 32)
+    ev = np.asarray(ev0, dtype=np.uint64).reshape(-1, 2)
+    out = []
+    for q, i in enumerate(idx):
+        for l in range(lv.shape[1]):
+            out += [[i >> (4 * (l + 1)), j, int(lv[q, l, j]), l, TAG_ROW, 1] for j in range(32)]
+        out.append([i, int(ev[q, 0]), int(ev[q, 1]), 0, TAG_FRI, 1])
+    out += [[0, j, int(w), 0, TAG_OBS, 1] for j, w in enumerate(np.asarray(obs, dtype=np.uint64).reshape(-1))]
+    out += [[0, j, int(a), int(v), TAG_CHAL, P - 1] for j, (a, v) in enumerate(np.asarray(chal, dtype=np.uint64).reshape(-1, 2)[:ord_pow].tolist())]
+    out += [[k, int(c[0]), int(c[1]), 0, TAG_FIN, len(idx)] for k, c in enumerate(np.asarray(final_poly, dtype=np.uint64).reshape(-1, 2))]
+    return np.array(out, dtype=np.uint64)
+
+
+def _fri_exits_statement(proof, cfg, ext_chal):
+    """what prover and verifier of an exit group both derive from the inner proof with the exported claim functions"""
+    cfg = cfg or default_stark_config()
+    fc = stark_fri_claims(proof, cfg)
+    obs, chal = stark_transcript_claims(proof, cfg, ext_chal)
+    n_q, NL = fc["index"].size, fc["betas"].shape[0]
+    ord_pow = chal.shape[0] - 1 - n_q
+    if cfg.arity_bits != 4 or ord_pow < 0:
+        raise VxError(-1, "fri exits: the exit group is stated for arity_bits 4 and a transcript that ends on the proof-of-work response and one challenge per query")
+    stmt = fri_exit_statement(fri_exit_statement_words(fc["log_lde"], cfg.pow_bits, ord_pow, obs, chal, fc["index"], fc["ev0"], fc["leaves"]))
+    ops, blocks = _transcript_ops(obs.size, chal)
+    logs = (_table_log_n(max(5, (n_q * (fc["log_lde"] - 3 * NL) - 1).bit_length()), cfg), _table_log_n(max(5, (32 * blocks - 1).bit_length()), cfg), _table_log_n(fri_exit_log_n(n_q), cfg))
+    return cfg, fc, obs, chal, ord_pow, stmt, ops, logs
+
+
+def fri_exits_verify(blob, proof, cfg=None, ext_chal=None):
+    """Host-side check of a Context.fri_exits_prove blob against the inner proof it belongs to: three tables on one bus -- FriFoldAir,
+    TranscriptAir, FriExitAir -- with the verifier outside (fri_exits_outside).  The verifier holds the fold claims of the proof
+    (lib.stark_fri_claims, as vx_fri_fold_verify's caller does) and the challenges below the proof-of-work response; it computes no
+    value mod N, no proof-of-work shift, no x^(16^NL) and no Horner evaluation of the final polynomial: the bus forces the claims'
+    indices to be the transcript's.  This composition OBTAINS the claims with the exported replays (stark_fri_claims,
+    stark_transcript_claims), which run the inner verifier; an aggregation verifier is handed them instead, and nothing here but
+    bus_group_verify judges them.  ext_chal reaches the transcript claims; the fold claims come from a proof with drawn lookup
+    challenges.  Raises VxError with the reason."""
+    cfg, fc, obs, chal, ord_pow, stmt, _, _ = _fri_exits_statement(proof, cfg, ext_chal)
+    NL = fc["betas"].shape[0]
+    fold_pub = [NL, fc["log_lde"] - 3 * NL, pow(_root(fc["log_lde"]), P - 2, P), 0] + [int(v) for v in fc["betas"].reshape(-1)] + [0] * (16 - 2 * NL) + [int(v) for v in stmt]
+    exit_pub = [int(v) for v in fri_exit_public(fc["log_lde"], NL, cfg.pow_bits, ord_pow, obs.size, fc["final_poly"])[:8]] + [int(v) for v in stmt]
+    expect = [(VX_AIR_FRI_FOLD, fold_pub), (VX_AIR_TRANSCRIPT, [int(v) for v in stmt]), (fri_exit_air_id(), exit_pub)]
+    bus_group_verify(blob, expect, cfg, fri_exits_outside(fc["log_lde"], ord_pow, obs, chal, fc["final_poly"], fc["index"], fc["ev0"], fc["leaves"]))
+
+
+def _root(log_n):
+    """the 2^log_n-th root of unity the library uses (Goldilocks: 7^((p - 1) / 2^32) squared down)"""
+    return pow(pow(7, (P - 1) >> 32, P), 1 << (32 - log_n), P)
 
 
 FQRY_MAGIC, FQRY_HDR = 0x3130595251465856, 7  # "VXFQRY01": magic, log2 of the inner LDE, fold layers, queries, three proof lengths; then the proofs
@@ -1043,6 +1198,55 @@ class Context:
         pub = np.zeros(24, dtype=np.uint64)
         self._ck(self.L.vx_fri_fold_air_trace(self.h, log_lde, _ptr(be), be.shape[0], tree0, _ptr(idx), _ptr(ev), _ptr(lv), idx.size, log_n, out.h, _ptr(pub)))
         return out, pub
+
+    def fri_exit_air_trace(self, log_lde, n_layers, pow_bits, ord_pow, absorbed, values, final_poly, log_n, out=None):
+        """The witness of FriExitAir (air_library.fri_exit_builder()): values = the proof-of-work response, then one index challenge
+        per query -> (Buffer [21][2^log_n], the 12 public inputs).  VxError: VX_ERR_STATEMENT "proof of work invalid", VX_ERR_ARG
+        for a non-canonical value or a shape the table does not hold."""
+        vals, fp = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1), np.ascontiguousarray(final_poly, dtype=np.uint64).reshape(-1, 2)
+        if vals.size < 2:
+            raise ValueError("the proof-of-work response and at least one index challenge")
+        own = out is None
+        out = out or self.alloc(FRI_EXIT_AIR_COLS << log_n)
+        pub = np.zeros(FRI_EXIT_PUBLIC, dtype=np.uint64)
+        try:
+            self._ck(self.L.vx_fri_exit_air_trace(self.h, log_lde, n_layers, pow_bits, int(ord_pow), int(absorbed), _ptr(vals), vals.size - 1, _ptr(fp), fp.shape[0], log_n, out.h, _ptr(pub)))
+        except VxError:
+            if own:
+                out.free()
+            raise
+        return out, pub
+
+    def fri_exits_tables(self, proof, cfg=None, ext_chal=None):
+        """The three tables of an inner proof's exit group as bus_group_prove takes them, [(air_id, trace Buffer, log_n, public inputs)]
+        for FriFoldAir, TranscriptAir, FriExitAir, every one with the group's statement digest as its last four public inputs, and
+        the outside party's messages.  The three Buffers are the caller's to free."""
+        cfg, fc, obs, chal, ord_pow, stmt, ops, logs = _fri_exits_statement(proof, cfg, ext_chal)
+        NL = fc["betas"].shape[0]
+        made = []  # allocated here and handed to the witness calls, so that a call that raises leaves nothing behind
+        try:
+            for cols, log_n in zip((VX_FRI_FOLD_AIR_COLS, VX_TRANSCRIPT_AIR_COLS, FRI_EXIT_AIR_COLS), logs):
+                made.append(self.alloc(cols << log_n))
+            ftr, fpub = self.fri_fold_air_trace(fc["log_lde"], fc["betas"], fc["index"], fc["ev0"], fc["leaves"], logs[0], out=made[0])
+            ttr, _, _ = self.transcript_air_trace([ops], [obs], logs[1], out=made[1])
+            etr, epub = self.fri_exit_air_trace(fc["log_lde"], NL, cfg.pow_bits, ord_pow, obs.size, chal[ord_pow:, 1], fc["final_poly"], logs[2], out=made[2])
+        except Exception:
+            for buf in made:
+                buf.free()
+            raise
+        tables = [(VX_AIR_FRI_FOLD, ftr, logs[0], np.concatenate([fpub[:-4], stmt])), (VX_AIR_TRANSCRIPT, ttr, logs[1], stmt), (fri_exit_air_id(), etr, logs[2], np.concatenate([epub[:-4], stmt]))]
+        return tables, fri_exits_outside(fc["log_lde"], ord_pow, obs, chal, fc["final_poly"], fc["index"], fc["ev0"], fc["leaves"]), cfg
+
+    def fri_exits_prove(self, proof, cfg=None, ext_chal=None):
+        """Proves the exit group of a vx_stark_prove proof: its fold chains (FriFoldAir), its transcript (TranscriptAir) and, between
+        them on one bus, FriExitAir -- query indices, proof of work and the final polynomial at every query's point -> a bus-group
+        blob (lib.fri_exits_verify checks it).  Composed from the exported claims, witnesses and the generic bus group."""
+        tables, outside, cfg = self.fri_exits_tables(proof, cfg, ext_chal)
+        try:
+            return self.bus_group_prove(tables, cfg, outside)
+        finally:
+            for t in tables:
+                t[1].free()
 
     def fri_fold_prove(self, log_lde, betas, final_poly, index, ev0, leaves, cfg=None, out=None):
         """Proves the fold chains of the claims in one FriFoldAir table -> blob words (lib.fri_fold_verify checks it).  The chains are

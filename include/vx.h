@@ -386,6 +386,35 @@ int32_t vx_fri_fold_verify(const vx_stark_config* cfg, const uint64_t* blob, siz
 int32_t vx_stark_fri_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int* log_lde, size_t* n_layers, size_t* final_len, size_t* n_queries,
                             uint64_t betas_out[16], uint64_t* final_poly_out, size_t final_cap, uint64_t* index_out, uint64_t* ev0_out, uint64_t* ev_last_out, size_t query_cap,
                             uint64_t* leaves_out, size_t leaves_cap, char* err, size_t errlen);
+/* ---- FriExitAir: an inner proof's query indices, proof of work and FRI exits in one STARK table.  NOT a compiled AIR: the
+ * constraint program ships with the library (0-kno-vectorx_amd/air_library.py fri_exit_builder(), registered by the host with
+ * vx_air_register_bus; columns and public inputs: csrc/fri_exit_layout.h) and is proven together with the compiled tables by the
+ * generic bus group (vx_bus_group_prove); its witness is the library's, as PoseidonAir's is.
+ * The statement, for one inner proof: an LDE of 2^log_lde points, n_layers (1..8) fold layers of arity 16, FB = log_lde - 4 n_layers
+ * >= 1, pow_bits, n_queries, a final polynomial of final_len (1..64) extension coefficients.  The table holds 1 + n_queries blocks
+ * of 128 rows, one per challenge value v of chain 0 behind the final polynomial: the proof-of-work response (ordinal ord_pow), then
+ * the index challenges (ordinals ord_pow + 1 + q), all drawn with `absorbed` words absorbed.  PROVEN per block: the 64 bits of v,
+ * MSB first, are boolean, spell an integer below p = 2^64 - 2^32 + 1 and sum to the value the block RECEIVES as (0, ordinal,
+ * absorbed, v) under tag 13 (TranscriptAir sends it); the PoW response has its top pow_bits bits zero; a query's index is the low
+ * log_lde bits of v, its point behind the folds x_NL = 7^(16^NL) w_FB^brev(index >> 4 NL, FB), and the final polynomial's value
+ * there -- every coefficient RECEIVED as (k, c_k.a, c_k.b) under tag 14, which whoever holds the proof head sends n_queries times
+ * -- is RECEIVED as (index, value, 1) under tag 10, the exit FriFoldAir sends.  A verifier with this table on its bus computes no
+ * value mod N, no proof-of-work shift, no x^(16^NL) and no Horner evaluation.  Public inputs (12): ord_pow, absorbed, pow_bits,
+ * 64 - log_lde, FB, w_FB, 7^(16^NL), final_len and four statement-digest words the table does not constrain.
+ * vx_fri_exit_air_trace: the witness -- values: the 1 + n_queries challenge values (host); trace_out: [21][2^log_n] with 2^log_n
+ *   >= 128 (1 + n_queries); blocks behind the values are idle (all zero but the ordinal column, which goes by position).
+ *   public_out[12]: as vx_fri_exit_public.  VX_ERR_ARG: a non-canonical value, a log_n too small or above 26, n_layers outside
+ *   1..8, FB < 1, final_len outside 1..64; VX_ERR_STATEMENT ("proof of work invalid"): a response with a bit among its top pow_bits.
+ * vx_fri_exit_public (host only, the verifier's side): the 12 public inputs, the digest being hash_n_to_hash_no_pad(the other
+ *   eight, the final polynomial's words).  VX_ERR_ARG for the same shapes.
+ * vx_fri_exit_log_n: the smallest log_n that holds the blocks; the caller raises it to a size with a FRI plan.
+ * vx_fri_exit_statement (host only): hash_n_to_hash_no_pad of the canonical words the caller lays out -- the ONE statement digest
+ *   that the tables of an exit group carry as their last four public inputs (lib.py fri_exit_statement_words states the layout). */
+int32_t vx_fri_exit_air_trace(vx_ctx* ctx, int log_lde, size_t n_layers, int pow_bits, uint64_t ord_pow, uint64_t absorbed, const uint64_t* values, size_t n_queries,
+                              const uint64_t* final_poly, size_t final_len, int log_n, vx_buf* trace_out, uint64_t* public_out);
+int32_t vx_fri_exit_public(int log_lde, size_t n_layers, int pow_bits, uint64_t ord_pow, uint64_t absorbed, const uint64_t* final_poly, size_t final_len, uint64_t* public_out);
+int vx_fri_exit_log_n(size_t n_queries);
+int32_t vx_fri_exit_statement(const uint64_t* words, size_t n_words, uint64_t digest_out[4]);
 /* ---- The FRI query phase on one bus: the layer leaves opened, hashed and folded (vx_fri_queries_prove).  An inner proof's FRI
  * has n_layers layer trees with different roots and depths (log_lde - 4 (l + 1)), every leaf 32 words.  Two SET tables carry
  * several trees in one table:
