@@ -178,6 +178,7 @@ struct StarkOpenings {
         uint64_t tree, index;  // index: x_index for the commitment trees, x_index >> a (l + 1) for layer l
         size_t leaf, leaf_len;  // the leaf words: leaves[leaf .. leaf + leaf_len), a layer leaf with its `within` slot filled
         size_t sib;             // where the path's 4 (log_leaves - cap_h) sibling words start in the proof
+        int n_sib;              // log_leaves - cap_h of its tree: the levels of the path
     };
     std::vector<Claim> claims;
     std::vector<uint64_t> leaves;
@@ -278,10 +279,11 @@ void vx_fri_combine_fold_statement(const FriCombineStmt& st, const uint64_t* bet
 static const uint64_t VX_SQRY_MAGIC = 0x3130595251535856ULL;  // "VXSQRY01"
 static constexpr size_t VX_SQRY_HDR = 9;                      // before the lengths
 // What the verifier's query phase does with the openings of a proof.  Walked: it walks every path itself (vx_stark_verify).
-// Delegated: the paths are left to the tables of a bus group -- none is walked and no sibling word is read.  QueryFree: the whole
-// query phase is left to them -- only the indices are derived, no word at or behind the query records is read, and the proof may
-// end there.
-enum class QueryPhase { Walked, Delegated, QueryFree };
+// Delegated: the paths are left to the tables of a bus group -- none is walked and no sibling word is read.  Deferred: the paths
+// are left to a check that runs once the pass has ended (DeferredPaths below) -- none is walked here, but every word of the proof is
+// scanned as in Walked: the check will read the siblings.  QueryFree: the whole query phase is left to the tables -- only the
+// indices are derived, no word at or behind the query records is read, and the proof may end there.
+enum class QueryPhase { Walked, Delegated, Deferred, QueryFree };
 // The whole query phase of a vx_stark_prove proof as claims, the ONE sink of the verifier's query phase: the Merkle side (`so`: trees
 // 0..7 the layers, 8 / 9 / 10 main / auxiliary / quotient) and the arithmetic side, from one replay of the verifier's code.  Query-free
 // only the head is filled: so.claims / so.leaves / rows / leaves / ev0 / ev_last stay empty, so.index holds the derived indices.
@@ -298,6 +300,41 @@ struct StarkQueries {
         return FriCombineStmt{so.LN, rate_bits, so.cm, so.ca, nq, alpha, zeta, openings.data(), openings.data() + 2 * c, openings.data() + 4 * c};
     }
 };
+// The openings that passes in the Deferred mode recorded, of one proof or of every table of a blob, as ONE batch: the arguments of
+// vx_merkle_check (include/vx.h), every array in the order the walked verifier would have met the openings.
+struct MerkleBatch {
+    int cap_height = 0;
+    std::vector<uint64_t> caps;  // [log_leaves.size()][4 << cap_height]
+    std::vector<int> log_leaves;
+    std::vector<uint64_t> tree_of, leaf_idx, leaf_len, leaves, siblings;
+};
+// Checks every opening of a batch: VX_OK with *first_bad = the first one that misses its cap (SIZE_MAX: none), or the code of a
+// failure of its own with the reason in err.  glh::merkle_path_ok one after the other (vx_stark_verify_deferred), or one launch of
+// k_merkle_check (vx_merkle_check.hip: the _dev verifiers).
+using PathChecker = std::function<int32_t(const MerkleBatch&, size_t* first_bad, char* err, size_t errlen)>;
+// The deferred form of the host verifiers (vx_verify.hip): a verifier runs in its own order with every proof read in the Deferred
+// mode through pass(), which keeps the openings the proof's query phase recorded -- of a pass that stopped inside its query phase,
+// those it had met by then.  settle() then has them checked together and gives the answer of the walked verifier: the first
+// opening that fails, in the order they were met, wins over the verdict the verifier itself came to -- the walked verifier would
+// have stopped there first.
+struct DeferredPaths {
+    explicit DeferredPaths(PathChecker check) : check(std::move(check)) {}
+    // vx_stark_verify_ext's arguments and answer
+    int32_t pass(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public, const uint64_t* ext_chal,
+                 const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen);
+    int32_t settle(int32_t verdict, char* err, size_t errlen);
+
+    PathChecker check;
+    MerkleBatch batch;
+    enum { TRACE, AUX, QUOT, LAYER };
+    struct Opening {
+        int kind;  // which tree of its proof
+        size_t layer, query;
+    };
+    std::vector<Opening> opening;  // of every claim of the batch
+};
+// the checker of the _dev verifiers: the batch through vx_merkle_check, one launch on `ctx` (vx_merkle_check.hip)
+PathChecker vx_merkle_check_paths(vx_ctx* ctx);
 // verifies `proof` as vx_stark_verify_ext does with its query phase in `mode`, and fills *out
 int32_t vx_stark_queries_claims(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
                                 const uint64_t* ext_chal, QueryPhase mode, StarkQueries* out, char* err, size_t errlen);

@@ -2,8 +2,9 @@
 // the reference's library seam (/root/reference circuits/header_range.rs:170).  Mirrors starky
 // v0.2.0 verify_stark_proof_with_challenges + plonky2 v0.2.0 verify_fri_proof
 // (fri_combine_initial, compute_evaluation, verify_merkle_proof_to_cap); crates pinned at
-// Cargo.lock:4848-4905, not vendored.  Verification is cheap scalar work (a few thousand
-// Poseidon permutations) and stays on the host, as in the reference.
+// Cargo.lock:4848-4905, not vendored.  Verification is scalar work and stays on the host, as in the
+// reference -- except, in the _dev forms, its Merkle openings (most of its Poseidon permutations),
+// which one launch of k_merkle_check takes (vx_merkle_check.hip; this file still holds no GPU code).
 // Every host verifier of a statement lives here too, and all of them end in ONE sequence, verify_bus_group: the tables of a logUp
 // bus under their shared challenges, and the balance of the bus against the messages of a party outside the tables -- nobody (the
 // circuit verifiers) or the verifier itself (the aggregation verifiers: argument checks, read_blob, their tables, their messages).
@@ -330,6 +331,11 @@ static int32_t constraints_at_zeta(const AirV& air, const sp::View& v, const uin
     }
     return VX_OK;
 }
+// the refusal of an opening, for the walked check and the deferred one (kind: DeferredPaths::Opening, vx_bus.h)
+static int32_t opening_invalid(int kind, size_t layer, size_t qi, char* err, size_t errlen) {
+    if (kind == DeferredPaths::LAYER) return v_fail(VX_ERR_STATEMENT, err, errlen, "FRI layer %zu Merkle proof invalid (query %zu)", layer, qi);
+    return v_fail(VX_ERR_STATEMENT, err, errlen, "%s Merkle proof invalid (query %zu)", kind == DeferredPaths::TRACE ? "trace" : kind == DeferredPaths::AUX ? "auxiliary" : "quotient", qi);
+}
 // The FRI query phase (verify_fri_proof): per query the three rows under their caps, the combination of their words
 // (fri_combine_initial), and per layer the coset's leaf under its cap and its fold at beta (compute_evaluation), down to the
 // final polynomial.  The arithmetic of a query is stated once; the modes differ in what happens to an OPENING: walked here,
@@ -344,7 +350,7 @@ static int32_t fri_queries(const sp::View& v, T& ch, Fx alpha, Fx zeta, const st
     auto opening = [&](uint64_t tree, size_t index, const uint64_t* leaf, size_t leaf_len, const uint64_t* sib, int depth, const uint64_t* cap) {
         if (sink) {
             StarkOpenings& so = sink->so;
-            so.claims.push_back({tree, index, so.leaves.size(), leaf_len, (size_t)(sib - v.pr)});
+            so.claims.push_back({tree, index, so.leaves.size(), leaf_len, (size_t)(sib - v.pr), depth});
             so.leaves.insert(so.leaves.end(), leaf, leaf + leaf_len);
         }
         return mode != QueryPhase::Walked || glh::merkle_path_ok(leaf, leaf_len, index, sib, depth, cap);
@@ -354,9 +360,9 @@ static int32_t fri_queries(const sp::View& v, T& ch, Fx alpha, Fx zeta, const st
         if (sink) sink->so.index.push_back(x_index);
         if (mode == QueryPhase::QueryFree) continue;  // every other step of a query is proven by the tables of vx_stark_queries_prove
         const sp::Query<const uint64_t> q = v.query(qi);
-        NEED(opening(VX_SOPEN_TREE0, x_index, q.row_t(), s.cm, q.sib_t(), s.depth0, v.cap_trace()), "trace Merkle proof invalid (query %zu)", qi);
-        if (s.ca) NEED(opening(VX_SOPEN_TREE0 + 1, x_index, q.row_a(), s.ca, q.sib_a(), s.depth0, v.cap_aux()), "auxiliary Merkle proof invalid (query %zu)", qi);
-        NEED(opening(VX_SOPEN_TREE0 + 2, x_index, q.row_q(), nq, q.sib_q(), s.depth0, v.cap_quot()), "quotient Merkle proof invalid (query %zu)", qi);
+        if (!opening(VX_SOPEN_TREE0, x_index, q.row_t(), s.cm, q.sib_t(), s.depth0, v.cap_trace())) return opening_invalid(DeferredPaths::TRACE, 0, qi, err, errlen);
+        if (s.ca && !opening(VX_SOPEN_TREE0 + 1, x_index, q.row_a(), s.ca, q.sib_a(), s.depth0, v.cap_aux())) return opening_invalid(DeferredPaths::AUX, 0, qi, err, errlen);
+        if (!opening(VX_SOPEN_TREE0 + 2, x_index, q.row_q(), nq, q.sib_q(), s.depth0, v.cap_quot())) return opening_invalid(DeferredPaths::QUOT, 0, qi, err, errlen);
         uint64_t x = sp::query_point(x_index, s.LN);
         Fx s1{0, 0}, ap{1, 0};
         for (size_t j = 0; j < c; ++j) {
@@ -388,7 +394,7 @@ static int32_t fri_queries(const sp::View& v, T& ch, Fx alpha, Fx zeta, const st
                 }
             }
             if (sink) sink->leaves.insert(sink->leaves.end(), leaf.begin(), leaf.end());
-            NEED(opening(l, x_index >> a, leaf.data(), 2 * arity, q.sibs(l), s.depth[l], v.layer_cap(l)), "FRI layer %zu Merkle proof invalid (query %zu)", l, qi);
+            if (!opening(l, x_index >> a, leaf.data(), 2 * arity, q.sibs(l), s.depth[l], v.layer_cap(l))) return opening_invalid(DeferredPaths::LAYER, l, qi, err, errlen);
             // compute_evaluation: interpolate the coset {x g^i} and evaluate at beta
             const uint64_t g = glh::root(a);
             std::vector<Fx> evn(arity);
@@ -443,7 +449,7 @@ static int32_t stark_verify_over(T& ch, bool head_ok, const vx_stark_config* cfg
     // every word that is read is canonical -- the whole proof, everything but the siblings, or the head alone
     if (head_ok && len == shape.o_queries) mode = QueryPhase::QueryFree;
     const bool query_free = mode == QueryPhase::QueryFree;
-    if (mode == QueryPhase::Walked)
+    if (mode == QueryPhase::Walked || mode == QueryPhase::Deferred)
         for (size_t i = hdr.size(); i < len; ++i) NEED(pr[i] < glh::P, "non-canonical element at word %zu", i);
     sp::View v;
     const char* bad_length = query_free ? sp::View::parse_head(pr, len, shape, &v) : sp::View::parse(pr, len, shape, &v);
@@ -514,6 +520,39 @@ static int32_t stark_verify_impl(const vx_stark_config* cfg, const uint64_t* pr,
                                  const uint64_t* ext_chal, const uint64_t** apub_out, int* log_n_out, QueryPhase mode, StarkQueries* sink, char* err, size_t errlen) {
     sp::Transcript ch;
     return stark_verify_over(ch, false, cfg, pr, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, mode, sink, err, errlen);
+}
+// The deferred form (vx_bus.h): the pass of one proof keeps what its query phase recorded ...
+int32_t DeferredPaths::pass(const vx_stark_config* cfg, const uint64_t* proof, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public, const uint64_t* ext_chal,
+                            const uint64_t** apub_out, int* log_n_out, char* err, size_t errlen) {
+    StarkQueries sq;
+    const int32_t rc = stark_verify_impl(cfg, proof, len, expect_air, expect_public, n_expect_public, ext_chal, apub_out, log_n_out, QueryPhase::Deferred, &sq, err, errlen);
+    // a query records all its openings before its one check that can fail (the final polynomial): whole queries, in record order
+    const StarkOpenings& so = sq.so;
+    const size_t per_query = so.tree.size(), tree0 = batch.log_leaves.size();
+    if (so.claims.empty()) return rc;
+    const size_t first_layer = per_query - so.NL;
+    batch.cap_height = so.cap_h;
+    batch.caps.insert(batch.caps.end(), so.caps.begin(), so.caps.end());
+    for (size_t pos = 0; pos < per_query; ++pos) batch.log_leaves.push_back(so.claims[pos].n_sib + so.cap_h);
+    for (size_t k = 0; k < so.claims.size(); ++k) {
+        const StarkOpenings::Claim& c = so.claims[k];
+        const size_t pos = k % per_query;
+        batch.tree_of.push_back(tree0 + pos), batch.leaf_idx.push_back(c.index), batch.leaf_len.push_back(c.leaf_len);
+        batch.siblings.insert(batch.siblings.end(), proof + c.sib, proof + c.sib + 4 * (size_t)c.n_sib);
+        opening.push_back({pos >= first_layer ? LAYER : pos == 0 ? TRACE : pos + 1 == first_layer ? QUOT : AUX, pos >= first_layer ? pos - first_layer : 0, k / per_query});
+    }
+    batch.leaves.insert(batch.leaves.end(), so.leaves.begin(), so.leaves.end());
+    return rc;
+}
+// ... and the openings of every pass are checked together: the first that fails is what the walked verifier would have said
+int32_t DeferredPaths::settle(int32_t verdict, char* err, size_t errlen) {
+    if (opening.empty()) return verdict;
+    size_t bad = SIZE_MAX;
+    char own[256] = "";
+    const int32_t rc = check(batch, &bad, own, sizeof own);
+    if (rc != VX_OK) return v_fail(rc, err, errlen, "%s", own);
+    if (bad == SIZE_MAX) return verdict;
+    return opening_invalid(opening[bad].kind, opening[bad].layer, opening[bad].query, err, errlen);
 }
 // ... over the recording challenger (vx_bus.h): what the transcript of a valid proof did, as TranscriptAir's chain
 int32_t vx_stark_transcript_record(const vx_stark_config* cfg, const uint64_t* proof, size_t len, const uint64_t* ext_chal, glh::TranscriptRecord* out, char* err, size_t errlen) {
@@ -604,7 +643,9 @@ static bool bus_messages_sum(const BusMessages& m, X2<Fx>* sum) {
 // tables must be what the messages of the party `outside` them sum to: zero when the tables are a closed statement
 // (vx_header_range_verify, vx_rotate_verify), the verifier's own claims when it is the last party of the bus (the aggregation
 // verifiers vx_merkle_openings_verify, vx_merkle_rows_verify, vx_fri_fold_verify).
-static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, size_t n, const char* unbalanced, char* err, size_t errlen, const BusOutside& outside = nullptr) {
+// With `paths` every table is read in the deferred form: its openings are kept for the caller's settle(), none is walked here.
+static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, size_t n, const char* unbalanced, char* err, size_t errlen, const BusOutside& outside = nullptr,
+                                DeferredPaths* paths = nullptr) {
     std::vector<const uint64_t*> pubs(n), caps(n);
     std::vector<size_t> n_pubs(n);
     for (size_t i = 0; i < n; ++i) pubs[i] = t[i].pub, n_pubs[i] = t[i].n_pub, caps[i] = t[i].cap;
@@ -614,7 +655,8 @@ static int32_t verify_bus_group(const vx_stark_config* cfg, const BusTable* t, s
     for (size_t i = 0; i < n; ++i) {
         const uint64_t* apub = nullptr;
         int L = 0;
-        const int32_t rc = vx_stark_verify_ext(cfg, t[i].proof, t[i].len, t[i].air, t[i].want, t[i].n_want, chal, &apub, &L, err, errlen);
+        const int32_t rc = paths ? paths->pass(cfg, t[i].proof, t[i].len, t[i].air, t[i].want, t[i].n_want, chal, &apub, &L, err, errlen)
+                                 : vx_stark_verify_ext(cfg, t[i].proof, t[i].len, t[i].air, t[i].want, t[i].n_want, chal, &apub, &L, err, errlen);
         if (rc != VX_OK) return rc;
         for (int q = 0; q < 2; ++q) bus[q] = glh::add(bus[q], glh::mul(apub[q], ((uint64_t)1 << L) % glh::P));
     }
@@ -687,11 +729,10 @@ int32_t vx_justification_expect(const uint64_t* ppub_chain, size_t n_chain, cons
     return VX_OK;
 }
 
-extern "C" {
-
-int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint32_t max_headers,
-                               uint32_t trusted_block, const uint8_t trusted_hash[32], uint64_t authority_set_id, const uint8_t* authority_set_hash,
-                               uint32_t target_block, const uint8_t out96[96], char* err, size_t errlen) {
+// The two circuit verifiers, each stated once: walked (paths == nullptr) or in the deferred form, which the caller settles.
+static int32_t header_range_verify_over(DeferredPaths* paths, const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint32_t max_headers, uint32_t trusted_block,
+                                        const uint8_t trusted_hash[32], uint64_t authority_set_id, const uint8_t* authority_set_hash, uint32_t target_block, const uint8_t out96[96],
+                                        char* err, size_t errlen) {
     if (!cfg || !blob || !trusted_hash || !out96) return VX_ERR_ARG;
     NEED(len > VX_HR_BLOB_FIXED_WORDS + 1 && blob[0] == VX_HR_BLOB_MAGIC, "bad header_range blob");
     NEED(blob[1] == max_headers && blob[2] == trusted_block && blob[3] == target_block, "blob is for a different request");
@@ -770,7 +811,15 @@ int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob,
     }
     // the bus closes: state roots and data roots of the hashed headers = the leaves of the Merkle trees; the keys of the signed
     // authorities = the keys the signatures verify under; R || A and H between the curve table and the SHA-512 table
-    return verify_bus_group(cfg, tab.data(), n_tab, "the lookup bus between the tables does not balance", err, errlen);
+    return verify_bus_group(cfg, tab.data(), n_tab, "the lookup bus between the tables does not balance", err, errlen, nullptr, paths);
+}
+
+extern "C" {
+
+int32_t vx_header_range_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint32_t max_headers,
+                               uint32_t trusted_block, const uint8_t trusted_hash[32], uint64_t authority_set_id, const uint8_t* authority_set_hash,
+                               uint32_t target_block, const uint8_t out96[96], char* err, size_t errlen) {
+    return header_range_verify_over(nullptr, cfg, blob, len, max_headers, trusted_block, trusted_hash, authority_set_id, authority_set_hash, target_block, out96, err, errlen);
 }
 
 // The aggregation verifiers: the verifier holds claims and is the LAST PARTY of a logUp bus whose other parties are tables.  Each
@@ -866,8 +915,8 @@ int32_t vx_merkle_rows_verify(const vx_stark_config* cfg, const uint64_t* blob, 
 // in this file, which holds no GPU code): the blob must be for this (authority_set_id, authority_set_hash) request and claim out32;
 // then its six STARKs are verified in their two shared-challenge groups against the public inputs those values imply, and both
 // buses must balance.
-int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint64_t authority_set_id,
-                         const uint8_t authority_set_hash[32], const uint8_t out32[32], char* err, size_t errlen) {
+static int32_t rotate_verify_over(DeferredPaths* paths, const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint64_t authority_set_id, const uint8_t authority_set_hash[32],
+                                  const uint8_t out32[32], char* err, size_t errlen) {
     if (!cfg || !blob || !authority_set_hash || !out32) return VX_ERR_ARG;
     NEED(len > VX_ROT_HDR && blob[0] == VX_ROT_MAGIC, "bad rotate blob");
     NEED(blob[1] == authority_set_id && memcmp(blob + 8, authority_set_hash, 32) == 0, "blob is for a different request");
@@ -910,7 +959,7 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
         }
         be_limbs(out32, spub);
         spub[8] = blob[3], spub[9] = 2;  // receives every key
-        const int32_t rc = verify_bus_group(cfg, tab, 3, "the lookup bus between the header hash, the epoch-end table and the new set does not balance", err, errlen);
+        const int32_t rc = verify_bus_group(cfg, tab, 3, "the lookup bus between the header hash, the epoch-end table and the new set does not balance", err, errlen, nullptr, paths);
         if (rc != VX_OK) return rc;
     }
     // the justification by the current set: commitment, Ed25519 and SHA-512 tables under shared lookup challenges; the signed
@@ -925,7 +974,50 @@ int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_
     tab[0].expect(air[0], spub, 10);
     tab[1].expect(air[1], epub, 2);
     tab[2].expect(air[2], hpub, 15);
-    return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen);
+    return verify_bus_group(cfg, tab, 3, "the lookup bus between the justification tables does not balance", err, errlen, nullptr, paths);
+}
+int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint64_t authority_set_id,
+                         const uint8_t authority_set_hash[32], const uint8_t out32[32], char* err, size_t errlen) {
+    return rotate_verify_over(nullptr, cfg, blob, len, authority_set_id, authority_set_hash, out32, err, errlen);
+}
+
+// The deferred forms (include/vx.h).  On the device: the host pass of every proof, then ONE launch of k_merkle_check over the openings
+// they recorded (vx_merkle_check.hip); vx_stark_verify_deferred runs the same code over glh::merkle_path_ok, one opening after
+// the other, so that the order of the answers can be tested without a GPU.
+static int32_t paths_on_host(const MerkleBatch& b, size_t* first_bad, char*, size_t) {
+    const size_t cap_words = (size_t)4 << b.cap_height;
+    const uint64_t *leaf = b.leaves.data(), *sib = b.siblings.data();
+    for (size_t i = 0; i < b.tree_of.size() && *first_bad == SIZE_MAX; ++i) {
+        const size_t t = b.tree_of[i], n_sib = (size_t)(b.log_leaves[t] - b.cap_height);
+        if (!glh::merkle_path_ok(leaf, b.leaf_len[i], b.leaf_idx[i], sib, n_sib, b.caps.data() + t * cap_words)) *first_bad = i;
+        leaf += b.leaf_len[i], sib += 4 * n_sib;
+    }
+    return VX_OK;
+}
+int32_t vx_stark_verify_deferred(const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public, char* err,
+                                 size_t errlen) {
+    DeferredPaths paths(paths_on_host);
+    return paths.settle(paths.pass(cfg, pr, len, expect_air, expect_public, n_expect_public, nullptr, nullptr, nullptr, err, errlen), err, errlen);
+}
+int32_t vx_stark_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* pr, size_t len, int expect_air, const uint64_t* expect_public, size_t n_expect_public, char* err,
+                            size_t errlen) {
+    if (!ctx) return VX_ERR_ARG;
+    DeferredPaths paths(vx_merkle_check_paths(ctx));
+    return paths.settle(paths.pass(cfg, pr, len, expect_air, expect_public, n_expect_public, nullptr, nullptr, nullptr, err, errlen), err, errlen);
+}
+int32_t vx_header_range_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint32_t max_headers, uint32_t trusted_block,
+                                   const uint8_t trusted_hash[32], uint64_t authority_set_id, const uint8_t* authority_set_hash, uint32_t target_block, const uint8_t out96[96],
+                                   char* err, size_t errlen) {
+    if (!ctx) return VX_ERR_ARG;
+    DeferredPaths paths(vx_merkle_check_paths(ctx));
+    return paths.settle(header_range_verify_over(&paths, cfg, blob, len, max_headers, trusted_block, trusted_hash, authority_set_id, authority_set_hash, target_block, out96, err, errlen),
+                        err, errlen);
+}
+int32_t vx_rotate_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* blob, size_t len, uint64_t authority_set_id, const uint8_t authority_set_hash[32],
+                             const uint8_t out32[32], char* err, size_t errlen) {
+    if (!ctx) return VX_ERR_ARG;
+    DeferredPaths paths(vx_merkle_check_paths(ctx));
+    return paths.settle(rotate_verify_over(&paths, cfg, blob, len, authority_set_id, authority_set_hash, out32, err, errlen), err, errlen);
 }
 
 // FRI fold (the prover is vx_fri_fold_air.hip), the third aggregation verifier: the claims are what a STARK verifier holds when it

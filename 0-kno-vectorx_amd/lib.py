@@ -42,6 +42,7 @@ SYMBOLS = [
     "vx_transcript_air_trace", "vx_stark_transcript_claims", "vx_stark_transcripts_proof_bound", "vx_stark_transcripts_prove", "vx_stark_transcripts_verify",
     "vx_stark_inner_proof_bound", "vx_stark_inner_prove", "vx_stark_inner_verify",
     "vx_bus_group_proof_bound", "vx_bus_group_prove", "vx_bus_group_verify", "vx_bus_group_check",
+    "vx_merkle_check", "vx_stark_verify_dev", "vx_header_range_verify_dev", "vx_rotate_verify_dev", "vx_stark_verify_deferred",
 ]
 
 VX_AIR_FIBONACCI, VX_AIR_MIX, VX_AIR_BLAKE_CHAIN, VX_AIR_LOOKUP = 1, 2, 6, 5
@@ -260,6 +261,11 @@ def load_library():
         "vx_bus_group_prove": [vp, C.POINTER(StarkConfig), C.POINTER(BusTableStruct), sz, vp, sz, vp, sz, C.POINTER(sz)],
         "vx_bus_group_verify": [C.POINTER(StarkConfig), vp, sz, C.POINTER(BusExpectStruct), sz, vp, sz, C.c_char_p, sz],
         "vx_bus_group_check": [vp, C.POINTER(BusTableStruct), sz, vp, sz, C.POINTER(BusUnmatchedStruct)],
+        "vx_merkle_check": [vp, vp, C.c_int, vp, sz, vp, vp, vp, vp, sz, vp, sz, sz, C.POINTER(sz)],
+        "vx_stark_verify_dev": [vp, C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, C.c_char_p, sz],
+        "vx_header_range_verify_dev": [vp, C.POINTER(StarkConfig), vp, sz, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_char_p, sz],
+        "vx_rotate_verify_dev": [vp, C.POINTER(StarkConfig), vp, sz, u64, vp, vp, C.c_char_p, sz],
+        "vx_stark_verify_deferred": [C.POINTER(StarkConfig), vp, sz, C.c_int, vp, sz, C.c_char_p, sz],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -289,20 +295,27 @@ def _words(x):
     return None if x is None else np.ascontiguousarray(x, dtype=np.uint64)
 
 
-def _host_verify(name, cfg, *args):
+def _host_verify(name, cfg, *args, ctx=None):
     """One call of a host `vx_*_verify`: the configuration (None: the default), then `args` -- an array goes as its pointer, None as
-    NULL --, then a 256-byte buffer for the reason.  Raises VxError(rc, reason) unless it returns VX_OK."""
+    NULL --, then a 256-byte buffer for the reason.  Raises VxError(rc, reason) unless it returns VX_OK.
+    ctx: the handle a `_dev` form takes in front (its Merkle openings are checked on that context's device)."""
     cfg = cfg or default_stark_config()
     err = C.create_string_buffer(256)
-    rc = getattr(load_library(), name)(C.byref(cfg), *[_ptr(a) if isinstance(a, np.ndarray) else a for a in args], err, 256)
+    rc = getattr(load_library(), name)(*([] if ctx is None else [ctx]), C.byref(cfg), *[_ptr(a) if isinstance(a, np.ndarray) else a for a in args], err, 256)
     if rc != 0:
         raise VxError(rc, err.value.decode())
 
 
-def stark_verify(proof, cfg=None, expect_air=0, expect_public=None):
+def stark_verify(proof, cfg=None, expect_air=0, expect_public=None, _symbol="vx_stark_verify", _ctx=None):
     """Host-side verification (no GPU needed).  Raises VxError(VX_ERR_STATEMENT) with the reason."""
     pr, pub = _words(proof), _words(expect_public)
-    _host_verify("vx_stark_verify", cfg, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size)
+    _host_verify(_symbol, cfg, pr, pr.size, expect_air, pub, 0 if pub is None else pub.size, ctx=_ctx)
+
+
+def stark_verify_deferred(proof, cfg=None, expect_air=0, expect_public=None):
+    """stark_verify with the Merkle openings recorded during the host pass and checked after it, in the order and with the answers of
+    stark_verify: the code Context.stark_verify runs, with the host's path check in place of the kernel (no GPU needed)."""
+    stark_verify(proof, cfg, expect_air, expect_public, _symbol="vx_stark_verify_deferred")
 
 
 def air_register(cols, n_public, code, consts=(), periodic=(), n_regs=None, aux_cols=0, n_challenges=0, n_aux_public=0, gen_aux=None, _bus=None):
@@ -431,19 +444,19 @@ def merge_blobs(blobs):
     return out[: n.value]
 
 
-def header_range_verify(blob, max_headers, trusted_block, trusted_hash, target_block, out96, cfg=None, authority_set_hash=None, authority_set_id=0):
+def header_range_verify(blob, max_headers, trusted_block, trusted_hash, target_block, out96, cfg=None, authority_set_hash=None, authority_set_id=0, _ctx=None):
     b = _words(blob)
     th = np.frombuffer(bytes(trusted_hash), dtype=np.uint8).copy()
     o = np.frombuffer(bytes(out96), dtype=np.uint8).copy()
     ah = None if authority_set_hash is None else np.frombuffer(bytes(authority_set_hash), dtype=np.uint8).copy()
-    _host_verify("vx_header_range_verify", cfg, b, b.size, max_headers, trusted_block, th, authority_set_id, ah, target_block, o)
+    _host_verify("vx_header_range_verify" if _ctx is None else "vx_header_range_verify_dev", cfg, b, b.size, max_headers, trusted_block, th, authority_set_id, ah, target_block, o, ctx=_ctx)
 
 
-def rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg=None):
+def rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg=None, _ctx=None):
     b = _words(blob)
     ah = np.frombuffer(bytes(authority_set_hash), dtype=np.uint8).copy()
     o = np.frombuffer(bytes(out32), dtype=np.uint8).copy()
-    _host_verify("vx_rotate_verify", cfg, b, b.size, authority_set_id, ah, o)
+    _host_verify("vx_rotate_verify" if _ctx is None else "vx_rotate_verify_dev", cfg, b, b.size, authority_set_id, ah, o, ctx=_ctx)
 
 
 MOPEN_MAGIC, MOPEN_HDR = 0x314E45504F4D5856, 4  # "VXMOPEN1": magic, log2(n_leaves), number of openings, proof length; then the MerkleOpenAir proof
@@ -1090,6 +1103,39 @@ class Context:
 
     def alloc(self, n):
         return Buffer(self, n)
+
+    # verifying on the GPU: the host verifiers with every Merkle opening checked in one launch (include/vx.h)
+    def merkle_check(self, caps, log_leaves, tree_of, leaf_idx, leaves, siblings):
+        """Checks a batch of Merkle openings on the device.  caps [n_trees][2^cap_height][4]; log_leaves [n_trees]; per claim its tree,
+        its leaf index, its leaf row (any length >= 1) and its siblings [log_leaves - cap_height][4], leaf level first -- the layout
+        of lib.stark_merkle_claims.  Returns None when every claim reaches its cap, else the smallest failing claim; VxError
+        (VX_ERR_ARG) for claims out of range or non-canonical words."""
+        cp = np.ascontiguousarray(caps, dtype=np.uint64)
+        n_trees = len(log_leaves)
+        cap_height = (cp.size // max(n_trees, 1) // 4).bit_length() - 1
+        ll = np.ascontiguousarray(log_leaves, dtype=np.int32)
+        tr, ix = _words(tree_of), _words(leaf_idx)
+        ln = np.array([np.asarray(r).size for r in leaves], dtype=np.uint64)
+        cat = lambda rows: np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint64).reshape(-1) for r in rows] + [np.zeros(0, np.uint64)]))
+        lv, sb = cat(leaves), cat(siblings)
+        bad = C.c_size_t(0)
+        rc = self.L.vx_merkle_check(self.h, _ptr(cp), cap_height, _ptr(ll), n_trees, _ptr(tr), _ptr(ix), _ptr(ln), _ptr(lv), lv.size, _ptr(sb), sb.size, tr.size, C.byref(bad))
+        if rc == -5:
+            return bad.value
+        self._ck(rc)
+        return None
+
+    def stark_verify(self, proof, cfg=None, expect_air=0, expect_public=None):
+        """lib.stark_verify with the openings checked on this context's device: the same VxError, code and text."""
+        stark_verify(proof, cfg, expect_air, expect_public, _symbol="vx_stark_verify_dev", _ctx=self.h)
+
+    def header_range_verify(self, blob, max_headers, trusted_block, trusted_hash, target_block, out96, cfg=None, authority_set_hash=None, authority_set_id=0):
+        """lib.header_range_verify with the openings of every table checked in one launch on this context's device."""
+        header_range_verify(blob, max_headers, trusted_block, trusted_hash, target_block, out96, cfg, authority_set_hash, authority_set_id, _ctx=self.h)
+
+    def rotate_verify(self, blob, authority_set_id, authority_set_hash, out32, cfg=None):
+        """lib.rotate_verify with the openings of its six tables checked in one launch on this context's device."""
+        rotate_verify(blob, authority_set_id, authority_set_hash, out32, cfg, _ctx=self.h)
 
     def from_host(self, arr):
         a = np.ascontiguousarray(arr)

@@ -976,6 +976,42 @@ int32_t vx_rotate_prove(vx_ctx* ctx, const vx_buf* header, uint32_t header_size,
 int32_t vx_rotate_verify(const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, uint64_t authority_set_id,
                          const uint8_t authority_set_hash[32], const uint8_t out32[32], char* err, size_t errlen);
 
+/* ---- Verifying on the GPU: every Merkle opening of a verification checked in one launch (csrc/vx_merkle_check.hip) ----
+ * A proof's verification on the host is mostly its Merkle openings, walked one after the other (per opening: one permutation per 8
+ * leaf words, one per tree level).  The verifiers below run everything else on the host as before and leave the openings to ONE
+ * launch of k_merkle_check: 16 lanes per opening, the row absorbed as hash_or_noop does, the path walked with two_to_one, the cap
+ * entry compared; the kernel stores one word, the first opening that fails.
+ * vx_merkle_check: the check on its own.  All pointers are host pointers and the layout is what vx_stark_merkle_claims hands out:
+ *   tree t (< n_trees) has 2^log_leaves[t] leaves under the cap caps[t][4 << cap_height]; claim i opens leaf leaf_idx[i] of tree
+ *   tree_of[i] with a row of leaf_len[i] >= 1 words; the rows lie one after the other in `leaves` (leaves_len words in all), the
+ *   4 (log_leaves - cap_height) sibling words of every claim, leaf level first, one after the other in `siblings`.
+ *   VX_OK with *first_bad = SIZE_MAX when every claim reaches its cap entry (index >> (log_leaves - cap_height)); VX_ERR_STATEMENT
+ *   with *first_bad = the smallest failing claim; VX_ERR_ARG for a non-canonical word, an index outside its tree, a tree with
+ *   log_leaves < cap_height (or above 40), cap_height above 16, lengths that do not add up.  n_claims = 0: VX_OK, nothing is launched.
+ *   The words are staged through a pool block of `ctx` on its stream and the call waits before it returns; the ctx stays usable
+ *   after a refusal.
+ * vx_stark_verify_dev / vx_header_range_verify_dev / vx_rotate_verify_dev: the arguments of their host namesakes behind a ctx, and
+ *   for every input the same code and the same reason in err -- the query and tree a failing opening names included.  The host
+ *   verifier checks in sequence; to answer as it does, the proof is scanned for non-canonical words whole (siblings included), the
+ *   host pass runs with the openings recorded instead of walked, and the openings recorded up to the point where the pass ended --
+ *   at its end, or at a refusal of its own -- are checked on the device: the first that fails wins over the pass's own refusal,
+ *   the host verifier would have met it first.  A blob's tables are read in the host verifier's order, tables behind the first
+ *   refused one are not read, and the openings of all tables read go to the device in one launch.  A failure of the device
+ *   itself: VX_ERR_DEVICE / VX_ERR_OOM with the reason in err.
+ * vx_stark_verify_deferred (host only, test surface): the same deferred-order code with the host's own path check in place of the
+ *   kernel; answers as vx_stark_verify does. */
+int32_t vx_merkle_check(vx_ctx* ctx, const uint64_t* caps, int cap_height, const int* log_leaves, size_t n_trees, const uint64_t* tree_of, const uint64_t* leaf_idx,
+                        const uint64_t* leaf_len, const uint64_t* leaves, size_t leaves_len, const uint64_t* siblings, size_t siblings_len, size_t n_claims, size_t* first_bad);
+int32_t vx_stark_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public, size_t n_expect_public,
+                            char* err, size_t errlen);
+int32_t vx_header_range_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, uint32_t max_headers, uint32_t trusted_block,
+                                   const uint8_t trusted_hash[32], uint64_t authority_set_id, const uint8_t* authority_set_hash /* 32 B or NULL */, uint32_t target_block,
+                                   const uint8_t out96[96], char* err, size_t errlen);
+int32_t vx_rotate_verify_dev(vx_ctx* ctx, const vx_stark_config* cfg, const uint64_t* blob, size_t blob_len, uint64_t authority_set_id, const uint8_t authority_set_hash[32],
+                             const uint8_t out32[32], char* err, size_t errlen);
+int32_t vx_stark_verify_deferred(const vx_stark_config* cfg, const uint64_t* proof, size_t proof_len, int expect_air, const uint64_t* expect_public, size_t n_expect_public, char* err,
+                                 size_t errlen);
+
 /* ---- multi-GPU: proofs are independent, one per rank; the only exchange is this gather ----
  * All-gathers `n_words` u64 words per rank over RCCL on the ctx stream: out (host, world * n_words words, rank
  * order) is filled on EVERY rank; blobs must have the same length on all ranks (pad to the proof bound).
