@@ -187,7 +187,7 @@ __device__ __forceinline__ void poseidon_mds(uint64_t* s, int rc_next) {
 
 #endif
 
-// ---- partial rounds on a SPLIT state (VX_POSEIDON_SPLIT_PARTIAL, default; tools/ab_poseidon_split.sh: permutation 62.3 k -> 58.8 k
+// ---- partial rounds on a SPLIT state (VX_POSEIDON_SPLIT_PARTIAL, the default before VX_POSEIDON_FREQ_PARTIAL below; tools/ab_poseidon_split.sh: permutation 62.3 k -> 58.8 k
 // cycles per wave, 2.60 -> 2.75 G permutations/s, header_range_256 8.59 -> 8.84 proofs/s, same outputs): in a partial round only element 0 meets the s-box, so only
 // element 0 has to be a 64-bit word; the other eleven go from one linear layer straight into the next and stay in the layer's
 // own representation, low part + high part 2^52.  Between two layers they are merely NORMALISED -- the bits of the low part
@@ -250,22 +250,46 @@ __device__ __forceinline__ void poseidon_mds_split_out(uint64_t s0, uint64_t* xl
     }
 }
 
-// CANON = false leaves the output as any 64-bit representative: for a sponge's inner permutations, whose output only meets
-// gl_add_nc (the next permutation's first constant add) or is overwritten by the next absorb
-template <bool CANON = true>
-__device__ __forceinline__ void poseidon_permute(uint64_t* s) {
-    int rc = 12;  // constants of round k+1 are added by the MDS layer of round k
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s[i] = gl_add_nc(s[i], POSEIDON_RC[i]);
+// ---- partial rounds in the TRANSFORM DOMAIN of the layer (VX_POSEIDON_FREQ_PARTIAL, default; poseidon_freq.h has the algebra and the
+// bounds): the state of a partial round is the twelve FFT components the network above computes as u0 / u2 / ur / ui, a round runs the
+// block products only (no FFT stage in or out), and nine of the twelve components are normalised every second round.  The layer after
+// round 3 becomes pfreq::enter + the first round; the layer before round 26 is pfreq::leave.  tools/ab_poseidon_freq.sh,
+// profiles/r21_ab_poseidon_freq.txt: a partial round 328 -> 277 vector instructions, 1316 -> 1093 cycles per wave; the permutation
+// 57.1 k -> 52.6 k cycles per wave at 8 waves per SIMD; header_range_256 8.99 -> 9.39 proofs/s against the parent's library; same
+// outputs.  -DVX_POSEIDON_FREQ_PARTIAL=0 brings the split state above back.
+#ifndef VX_POSEIDON_FREQ_PARTIAL
+#define VX_POSEIDON_FREQ_PARTIAL 1
+#endif
+#if VX_POSEIDON_FREQ_PARTIAL
+#include "poseidon_freq.h"
+// s = the state after the s-boxes of round 3; on return the state after the layer of round 25 with round 26's constants added.
+// rc = index of round 4's constants.
+__device__ __forceinline__ void poseidon_partial_freq(uint64_t* s, int rc) {
+    pfreq::State u;
+    pfreq::enter(s, u);
+    uint64_t x0 = s[0];
 #pragma unroll 1
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s[i] = poseidon_sbox(s[i]);
-        poseidon_mds<12>(s, rc);
-        rc += 12;
+    for (int r = 0; r < 11; ++r) {
+        uint64_t y0 = pfreq::round_y0(u, x0);
+        uint64_t t = poseidon_sbox(gl_add_nc(y0, POSEIDON_RC[rc]));
+        pfreq::round_put<false>(u, x0, y0, t);
+        x0 = t;
+        y0 = pfreq::round_y0(u, x0);
+        t = poseidon_sbox(gl_add_nc(y0, POSEIDON_RC[rc + 12]));
+        pfreq::round_put<true>(u, x0, y0, t);
+        x0 = t;
+        rc += 24;
     }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) s[i] = poseidon_sbox(s[i]);
+    pfreq::leave(u, x0, &POSEIDON_RC[rc], s);
+}
+#endif
+
+// The middle of the permutation: s = the state after the s-boxes of round 3, rc = index of round 4's constants; on return s is the
+// state after the layer of round 25 with round 26's constants added (23 layers, 22 s-boxes on element 0).
+__device__ __forceinline__ void poseidon_partial_rounds(uint64_t* s, int rc) {
+#if VX_POSEIDON_FREQ_PARTIAL
+    poseidon_partial_freq(s, rc);
+#else
     poseidon_mds<1>(s, rc);  // round 4 is partial
     rc += 12;
 #if VX_POSEIDON_SPLIT_PARTIAL && !VX_POSEIDON_FP64
@@ -285,7 +309,6 @@ __device__ __forceinline__ void poseidon_permute(uint64_t* s) {
             rc += 12;
         }
         poseidon_mds_split_out(poseidon_sbox(s0), xl, xh, s, rc);  // round 26 is full again
-        rc += 12;
     }
 #else
 #pragma unroll 1
@@ -296,8 +319,28 @@ __device__ __forceinline__ void poseidon_permute(uint64_t* s) {
     }
     s[0] = poseidon_sbox(s[0]);
     poseidon_mds<12>(s, rc);  // round 26 is full again (its constants absorbed what the partial rounds pushed forward)
-    rc += 12;
 #endif
+#endif
+}
+
+// CANON = false leaves the output as any 64-bit representative: for a sponge's inner permutations, whose output only meets
+// gl_add_nc (the next permutation's first constant add) or is overwritten by the next absorb
+template <bool CANON = true>
+__device__ __forceinline__ void poseidon_permute(uint64_t* s) {
+    int rc = 12;  // constants of round k+1 are added by the MDS layer of round k
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = gl_add_nc(s[i], POSEIDON_RC[i]);
+#pragma unroll 1
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) s[i] = poseidon_sbox(s[i]);
+        poseidon_mds<12>(s, rc);
+        rc += 12;
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) s[i] = poseidon_sbox(s[i]);
+    poseidon_partial_rounds(s, rc);  // the layer of round 3, the partial rounds 4..25, round 26's constants
+    rc += 12 * 23;
 #pragma unroll 1
     for (int r = 0; r < 3; ++r) {
 #pragma unroll

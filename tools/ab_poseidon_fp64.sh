@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; C=$R/0-kno-vectorx_amd/
 if [ "$1" = build ]; then
   mkdir -p $R/build_ab
   for v in 0 1; do
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -DVX_POSEIDON_FP64=$v -I$R/include -o $R/build_ab/poseidon_rate_$v $R/tools/poseidon_rate.hip
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -DVX_POSEIDON_FP64=$v -DVX_POSEIDON_FREQ_PARTIAL=0 -I$R/include -o $R/build_ab/poseidon_rate_$v $R/tools/poseidon_rate.hip
     for f in vx_poseidon vx_fri; do
-      /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wno-unused-value -Wno-pass-failed -DVX_POSEIDON_FP64=$v -I$R/include -c $C/$f.hip -o $R/build_ab/${f}_pfp$v.o
+      /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wno-unused-value -Wno-pass-failed -DVX_POSEIDON_FP64=$v -DVX_POSEIDON_FREQ_PARTIAL=0 -I$R/include -c $C/$f.hip -o $R/build_ab/${f}_pfp$v.o
     done
     objs=""
     for o in $C/*.o; do b=$(basename $o .o); if [ -f $R/build_ab/${b}_pfp$v.o ]; then objs="$objs $R/build_ab/${b}_pfp$v.o"; else objs="$objs $o"; fi; done

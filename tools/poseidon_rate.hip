@@ -1,7 +1,8 @@
 // Poseidon permutation / MDS-layer cost on gfx950 for one build of csrc/poseidon.cuh, plus the issue cost of the
 // double-precision instructions the exact-fp64 MDS low part is made of.  Built twice by tools/ab_poseidon_fp64.sh
-// (-DVX_POSEIDON_FP64=0 / 1); prints cycles per wave-permutation, per MDS layer, and a checksum of fixed permutations that
-// must be the same for every build.
+// (-DVX_POSEIDON_FP64=0 / 1), tools/ab_poseidon_split.sh and tools/ab_poseidon_freq.sh (-DVX_POSEIDON_FREQ_PARTIAL=0 / 1); prints cycles
+// per wave-permutation, per MDS layer, per partial round (the middle of the permutation, 23 layers and 22 s-boxes, divided by 22), and a
+// checksum of fixed permutations that must be the same for every build.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -31,6 +32,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     for (int j = 0; j < 12; ++j) s[j] = 0x9E3779B97F4A7C15ULL * (threadIdx.x + seed + j) | 1;
 #pragma unroll 1
     for (int i = 0; i < PITER; ++i) poseidon_permute(s);
+    uint64_t x = 0;
+    for (int j = 0; j < 12; ++j) x ^= s[j];
+    out[blockIdx.x * 256 + threadIdx.x] = x;
+}
+// the middle of the permutation alone (poseidon_partial_rounds: the layer of round 3, the 22 partial rounds, round 26's constants)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_partial(uint64_t* out, uint32_t seed) {
+    uint64_t s[12];
+    for (int j = 0; j < 12; ++j) s[j] = 0x9E3779B97F4A7C15ULL * (threadIdx.x + seed + j) | 1;
+#pragma unroll 1
+    for (int i = 0; i < PITER; ++i) poseidon_partial_rounds(s, 48);
     uint64_t x = 0;
     for (int j = 0; j < 12; ++j) x ^= s[j];
     out[blockIdx.x * 256 + threadIdx.x] = x;
@@ -80,9 +91,9 @@ int main() {
     hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
     uint64_t cx = 0, cy = 0;
     for (size_t i = 0; i < 64 * 256; ++i) cx ^= h[2 * i] + i, cy += h[2 * i + 1] % 0xFFFFFFFF00000001ULL;
-    printf("{\"fp64\": %d, \"split_partial\": %d, \"checksum\": \"%016llx%016llx\"", VX_POSEIDON_FP64, VX_POSEIDON_SPLIT_PARTIAL, (unsigned long long)cx, (unsigned long long)cy);
+    printf("{\"fp64\": %d, \"split_partial\": %d, \"freq_partial\": %d, \"checksum\": \"%016llx%016llx\"", VX_POSEIDON_FP64, VX_POSEIDON_SPLIT_PARTIAL, VX_POSEIDON_FREQ_PARTIAL, (unsigned long long)cx, (unsigned long long)cy);
     struct { const char* n; kern k; double scale; } ks[] = {
-        {"perm_cycles_per_wave", k_perm, (double)ITER * 64 / PITER}, {"mds12_cycles_per_layer", k_mds, (double)ITER * 64 / (PITER * 30)},
+        {"perm_cycles_per_wave", k_perm, (double)ITER * 64 / PITER}, {"partial_round_cycles_per_wave", k_partial, (double)ITER * 64 / (PITER * 22)}, {"mds12_cycles_per_layer", k_mds, (double)ITER * 64 / (PITER * 30)},
         {"mds1_cycles_per_layer", k_mds1, (double)ITER * 64 / (PITER * 30)}, {"v_add_f64", k_add_f64, 1}, {"v_fma_f64", k_fma_f64, 1}, {"v_mul_f64", k_mul_f64, 1}};
     for (auto& e : ks)
         for (int wps : {4, 6, 8}) {
